@@ -12,14 +12,19 @@ pre_model ~ U[0,1) -> mask = pre >= 0.5, target ~ U[0,1), actions ~ U{0..CH*N^2-
 The headline `value` is the FFT mode (the reference's algorithm: the whole
 touched colour group is re-propagated every step).  The incremental-field
 mode (SURVEY 8d "reported separately") is measured afterwards on the same
-workload and reported under `incremental_psf_mode`.
+workload and reported under `incremental_psf_mode` (a `--full` side line).
 
 N GPUs: one process per GPU (torchrun), 128 envs per rank (weak scaling), the
 per-step rewards / psnr / done flags gathered to rank 0 over RCCL.
 
-Prints ONE JSON line on rank 0 (driver contract), plus `roofline` for the
-dominant kernel (live hipEvent timing) and `cpu_baseline` (the float64
-numpy oracle timed on this host, rank 0, N=1 only).
+Prints ONE JSON line on rank 0 (driver contract) with `roofline` for the
+dominant kernel (live hipEvent timing sampled inside the timed loop).
+
+A plain run measures the headline only: set-up, warm-up, the `--steps` timed
+steps, the optional `--dump-outputs DIR`, the result line.  `--full` adds every
+side line (incremental / plane-cached / crop / mono / drop-in modes, the DBS
+walks, probe and precision sweeps, the PSNR check against the numpy oracle and
+the CPU baselines, rank 0, N=1 only); the `--no-*` switches trim a `--full` run.
 """
 from __future__ import annotations
 
@@ -41,6 +46,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--envs", type=int, default=128, help="envs per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure every side line and check (other modes, sizes and precisions, DBS walks, "
+                         "SB3-facing steps, drop-in env, numpy-oracle PSNR check, CPU baselines); off: headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned (reward, psnr, accepted, "
+                         "terminated, truncated, one value per env) as DIR/<name>.npy (float64)")
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--cpu-sample", type=int, default=20,
                     help="env-steps of the numpy oracle timed for cpu_baseline, after 2 warm-ups "
@@ -73,7 +84,13 @@ def parse():
                          "the step kernel writes into the gather rows, one dist.gather per K steps)")
     ap.add_argument("--timing-every", type=int, default=4,
                     help="pass-timing hipEvent pairs on every K-th launch of each pass in the timed loop")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:
+        # headline only: everything else the bench measures or checks is a side line of --full
+        args.cpu_sample = args.dbs_flips = 0
+        for k in ("dropin", "psnr_check", "psf", "planes", "scipy", "probe", "ppo", "crop", "obs", "precision"):
+            setattr(args, "no_" + k, True)
+    return args
 
 
 def _free_port() -> int:
@@ -905,6 +922,22 @@ def vecenv_step_sharded(mcfg, B, steps, warmup, tsrc, psrc, every, dev, world):
                     "barrier-bracketed, max over ranks"}
 
 
+STEP_OUT_NAMES = ("reward", "psnr", "accepted", "terminated", "truncated")
+
+
+def dump_outputs(path: str, step_out, rank: int = 0):
+    """--dump-outputs: the five [B] arrays HologramVecEnv.step_device returned for the last timed
+    step, as float64 DIR/<name>.npy (rank r > 0 of a multi-GPU run: DIR/<name>.rank<r>.npy).
+    Targets, pre-models and actions are seeded, so equal arguments give equal inputs."""
+    import numpy as np
+    if step_out is None:
+        raise SystemExit("bench.py: --dump-outputs needs at least one timed step (--steps >= 1)")
+    os.makedirs(path, exist_ok=True)
+    for name, t in zip(STEP_OUT_NAMES, step_out):
+        np.save(os.path.join(path, name + (f".rank{rank}" if rank else "") + ".npy"),
+                t.cpu().numpy().astype(np.float64))
+
+
 def psnr_check(vec, N):
     """PSNR delta vs the numpy oracle for env 0's initial state (full 24-plane propagate)."""
     import numpy as np
@@ -1017,11 +1050,13 @@ def main():
         mg = hd.StepMetricGather(B, args.gather_every, dev) if gather else None
 
         def one_step(k):
-            if mg is not None:
-                mg.add(*vec.step_device(actions[k], out=mg.slot()))
-            else:
-                vec.step_device(actions[k])
+            if mg is None:
+                return vec.step_device(actions[k])
+            res = vec.step_device(actions[k], out=mg.slot())
+            mg.add(*res)
+            return res
 
+        last = None
         for k in range(warmup):
             one_step(k)
         if mg is not None:
@@ -1034,12 +1069,14 @@ def main():
         acc0 = int(vec.state.flip_count.sum().item())
         t0 = time.perf_counter()
         for k in range(warmup, total):
-            one_step(k)
+            last = one_step(k)
         if mg is not None:
             mg.flush()
         torch.cuda.synchronize()
         hd.barrier()
         dt = hd.max_over_ranks(time.perf_counter() - t0, dev)
+        # what the last timed step returned (its gather row is not rewritten after the loop)
+        vec.last_step_out = None if last is None else tuple(t.clone() for t in last)
         timing = vec.plan.read_timing()
         vec.state.check_error()
         # accepted steps in the timed region (flip_count counts accepted flips, no resets here)
@@ -1052,6 +1089,8 @@ def main():
     vec, dt, timing, acc_rate = measure("fft", args.steps, args.warmup)
     value = B * world * args.steps / dt
     ms_per_step = dt / args.steps * 1e3
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, vec.last_step_out, rank)
     abytes = algorithmic_bytes(N, P)
     passes = pass_table(timing, abytes)
     out = None

@@ -6,7 +6,7 @@ set -o pipefail
 T=$1; shift
 L=binary-hologram-reinforcement-learning_amd/hbx
 mkdir -p gpurun_out/$T
-Q="--steps 20 --warmup 3 --no-psf --no-ppo --no-probe --no-precision --no-obs --dbs-flips 0 --cpu-sample 0 --no-psnr-check"
+Q="--full --steps 20 --warmup 3 --no-psf --no-ppo --no-probe --no-precision --no-obs --dbs-flips 0 --cpu-sample 0 --no-psnr-check"
 i=0
 for lib in "$@"; do
   i=$((i + 1))

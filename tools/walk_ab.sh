@@ -4,7 +4,7 @@
 set -o pipefail
 T=${1:-wab}
 mkdir -p gpurun_out/$T
-Q="--steps 2 --warmup 1 --no-psf --no-probe --no-precision --no-ppo --no-obs --cpu-sample 0 --no-psnr-check"
+Q="--full --steps 2 --warmup 1 --no-psf --no-probe --no-precision --no-ppo --no-obs --cpu-sample 0 --no-psnr-check"
 for p in 0 1 0 1; do
   HBX_WALK_PERSIST=$p timeout -k 10 300 python bench.py $Q > gpurun_out/$T/p$p.json 2> gpurun_out/$T/p$p.err || exit 1
   python -c "

@@ -5,7 +5,7 @@ set -o pipefail
 T=${1:-wlab}; shift
 L=binary-hologram-reinforcement-learning_amd/hbx
 mkdir -p gpurun_out/$T
-Q="--steps 2 --warmup 1 --no-psf --no-probe --no-precision --no-ppo --no-obs --cpu-sample 0 --no-psnr-check"
+Q="--full --steps 2 --warmup 1 --no-psf --no-probe --no-precision --no-ppo --no-obs --cpu-sample 0 --no-psnr-check"
 i=0
 for lib in "$@"; do
   i=$((i + 1))
