@@ -423,7 +423,9 @@ int check_obs_buffers(const hbx_env_buffers_t* e) {
 int propagate_full(hbx_plan_t p, const uint64_t* mask, const float* target, const int32_t* env_ids,
                    int n_ids, float* intensity, double* chan_stats, double* psnr, const EnvDev* env,
                    float2* field, hipStream_t st, float* plane_pool = nullptr, int32_t* plane_slot = nullptr,
-                   int spares = 1) {
+                   int spares = 1, const float* values = nullptr) {
+  // values (ABI v15, with mask, env_ids and plane_pool null): [n_ids][G*P][N][N] f32 samples of a
+  // real-valued field, read by the first pass in place of the mask bits
   const PlanDev& pd = p->pd;
   const int CHs = pd.G * pd.P + 2 * spares;   // plane-cache slots per env
   if (plane_pool) {                           // identity slots, then every plane's |U|^2 into its slot
@@ -447,10 +449,11 @@ int propagate_full(hbx_plan_t p, const uint64_t* mask, const float* target, cons
     JobDesc* jobs = env_ids ? p->jobs : p->full_jobs;
     if (env_ids) HBX_HIP(hbx::launch_jobs_full(env_ids + i0, n, G, jobs, st));
     const size_t mwords = (size_t)G * pd.P * pd.N * (pd.N / 64);
-    const uint64_t* m = env_ids ? mask : mask + (size_t)i0 * mwords;
+    const uint64_t* m = (env_ids || !mask) ? mask : mask + (size_t)i0 * mwords;
     const float* tg = (env_ids || !target) ? target : target + (size_t)i0 * G * pd.N * pd.N;
     float2* fo = field ? (env_ids ? field : field + (size_t)i0 * G * pd.P * pd.N * pd.N) : nullptr;
     PlanDev pdx = pd;
+    if (values) pdx.real_values = values + (size_t)i0 * G * pd.P * pd.N * pd.N;
     if (plane_pool) {
       pdx.plane_mode = hbx::kPlanesFill;
       pdx.plane_spares = spares;
@@ -499,6 +502,38 @@ int hbx_simulate(hbx_plan_t p, const uint64_t* mask, int32_t n_env, float* field
   HBX_HIP(hipSetDevice(p->device));
   return propagate_full(p, mask, nullptr, nullptr, n_env, intensity, nullptr, nullptr, nullptr,
                         reinterpret_cast<float2*>(field), (hipStream_t)stream);
+}
+
+namespace {
+int check_real_plan(hbx_plan_t p) {
+  if (p->pd.store_kind != HBX_PRECISION_F32)
+    return fail(HBX_ERR_UNSUPPORTED, "real-valued fields: HBX_PRECISION_F32 only (the plan stores reduced-precision intermediates)");
+  return HBX_OK;
+}
+}  // namespace
+
+int hbx_propagate_real(hbx_plan_t p, const float* values, const float* target, int32_t n_env,
+                       float* intensity, double* chan_stats, double* psnr, void* stream) {
+  int rc = check_plan(p);
+  if (rc) return rc;
+  if (n_env <= 0) return n_env == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "n_env");  // empty: null buffers allowed
+  if (!values || !target || !chan_stats) return fail(HBX_ERR_INVALID, "null buffer");
+  if ((rc = check_real_plan(p))) return rc;
+  HBX_HIP(hipSetDevice(p->device));
+  return propagate_full(p, nullptr, target, nullptr, n_env, intensity, chan_stats, psnr, nullptr,
+                        nullptr, (hipStream_t)stream, nullptr, nullptr, 1, values);
+}
+
+int hbx_simulate_real(hbx_plan_t p, const float* values, int32_t n_env, float* field, float* intensity,
+                      void* stream) {
+  int rc = check_plan(p);
+  if (rc) return rc;
+  if (n_env <= 0) return n_env == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "n_env");
+  if (!values || !field) return fail(HBX_ERR_INVALID, "null buffer");
+  if ((rc = check_real_plan(p))) return rc;
+  HBX_HIP(hipSetDevice(p->device));
+  return propagate_full(p, nullptr, nullptr, nullptr, n_env, intensity, nullptr, nullptr, nullptr,
+                        reinterpret_cast<float2*>(field), (hipStream_t)stream, nullptr, nullptr, 1, values);
 }
 
 int hbx_psnr(hbx_plan_t p, const double* chan_stats, int32_t n_env, double* psnr, void* stream) {

@@ -205,6 +205,10 @@ struct PlanDev {
   // launch) and one of its workgroups per job writes the JobDesc the later passes read
   const int64_t* actions = nullptr;
   int32_t* act_err = nullptr;
+  // (ABI v15) full propagation of a real-valued field: [env][G*P][N][N] f32 samples the first
+  // pass reads instead of the mask bits (u = value; va / vb are not applied).  f32 intermediates,
+  // no plane cache, no actions, no walk
+  const float* real_values = nullptr;
 };
 constexpr int kPlanesOff = 0, kPlanesFill = 1, kPlanesStep = 2;
 

@@ -402,6 +402,186 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd32(const JobDesc* jobs,
 }
 
 // ---------------------------------------------------------------------------
+// Pass 1 on real-valued fields (hbx_simulate_real / hbx_propagate_real, ABI v15)
+// ---------------------------------------------------------------------------
+// values[env][CH][N][N] f32: lane t of a row's group loads pixel x = t + R jj of planes pa, pb
+// straight into the (re, im) of v[jj] -- one coalesced 4 R-byte run per lane group and jj,
+// read once (non-temporal) -- and from there on the code is k_rowfwd's / k_rowfwd32's: row
+// FFT, Hermitian split, LDS tile, panel stores.  Full propagations only (no flip, no action
+// decode, no pair step, no walk phase), f32 intermediates only.
+// One row block per workgroup: the samples land in v itself, so a prefetch of the next row
+// block would be a second v (64 VGPRs at N = 1024), which does not fit three workgroups per
+// CU; the co-resident workgroups cover each other's loads instead.  This is the
+// bit kernels' RIT = 1 form with another load, at every launch size (no small / large switch).
+template <int R>
+__device__ __forceinline__ void real_load_row(pk2 (&v)[R], const float* __restrict__ rowa, size_t plane, int t) {
+  const float* rowb = rowa + plane;
+  float a[R], b[R];
+#pragma unroll
+  for (int jj = 0; jj < R; ++jj) a[jj] = __builtin_nontemporal_load(rowa + t + R * jj);
+#pragma unroll
+  for (int jj = 0; jj < R; ++jj) b[jj] = __builtin_nontemporal_load(rowb + t + R * jj);
+#pragma unroll
+  for (int jj = 0; jj < R; ++jj) v[jj] = (pk2){a[jj], b[jj]};
+}
+
+template <int R, int NT>
+__global__ __launch_bounds__(NT, 512 / NT) void k_rowfwd_real(const JobDesc* __restrict__ jobs,
+                                                        const float* __restrict__ values,
+                                                        float2* __restrict__ ws_a,
+                                                        const float2* __restrict__ tw_glob, int P, int CH) {
+  constexpr int N = R * R;
+  constexpr int GPB = NT / R;          // rows per row block
+  constexpr int SCR = GPB * R * (R + 1);
+  static_assert(N * GPB <= SCR, "tile must fit in the scratch area");
+  __shared__ float2 tw[N];
+  __shared__ __attribute__((aligned(16))) float2 lds[SCR];
+
+  for (int i = threadIdx.x; i < N; i += NT) tw[i] = tw_glob[i];
+
+  const int grp = threadIdx.x / R;
+  const int t = threadIdx.x % R;
+  const int lane_base = (threadIdx.x & 63) - t;
+  constexpr int RB = N / GPB;
+  int bid = xcd_pair<RB>(blockIdx.x);
+  const int rbw = bid % RB;
+  bid /= RB;
+  const int npair = P / 2;
+  const int j = bid / npair;
+  const JobDesc jb = jobs[j];
+  if (jb.env < 0) return;  // uniform per block
+  const int pa = 2 * (bid % npair);
+  const int y0 = rbw * GPB;
+  const int y = y0 + grp;
+  pk2 v[R];
+  real_load_row<R>(v, values + (((size_t)jb.env * CH + jb.group * P + pa) * N + y) * N, (size_t)N * N, t);
+  __syncthreads();  // tw visible
+
+  constexpr size_t PLA = plane_a_elems(R);
+  float2* base = ws_a + ((size_t)j * P + pa) * PLA;
+  fft_group<R, false>(v, t, PaddedScratch<R>{lds + grp * R * (R + 1)}, tw);
+  lds_barrier();    // every group is done with its scratch: reuse as the tile
+
+  // Hermitian split -> tile[plane][kx][row]
+  float2* tile = lds;
+  const float2 zny = from_pk(v[R / 2]);  // Z[N/2] on lane 0
+#pragma unroll
+  for (int k2 = 0; k2 < R / 2; ++k2) {
+    const float2 z = from_pk(v[k2]);
+    const float2 m = mirror_conj<R>(v, k2, t, lane_base);
+    float2 fa = make_float2(z.x + m.x, z.y + m.y);       // 2 A (htab holds H / 2)
+    float2 fb = make_float2(z.y - m.y, m.x - z.x);
+    if (k2 == 0 && t == 0) {  // DC and Nyquist of a real row are real
+      fa = make_float2(z.x + z.x, zny.x + zny.x);
+      fb = make_float2(z.y + z.y, zny.y + zny.y);
+    }
+    const int kx = t + R * k2;
+    tile[tile_pos<R, GPB>(kx, grp)] = fa;
+    tile[tile_pos<R, GPB>(N / 2 + kx, grp)] = fb;
+  }
+  lds_barrier();
+  // store tile lines: A[pa|pb][kx][y0 .. y0+GPB), 16 B per thread per chunk
+  constexpr int CHUNKS = N * GPB / 2;
+  static_assert(CHUNKS % NT == 0, "chunking");
+#pragma unroll
+  for (int i = 0; i < CHUNKS / NT; ++i) {
+    const int c = threadIdx.x + NT * i;
+    const int r2 = (c % (GPB / 2)) * 2;
+    const int line = c / (GPB / 2);  // pl * N/2 + kx : A planes pa, pb are adjacent
+    float2 a, b;
+    if constexpr (GPB == 16) {   // one ds_read_b128 per chunk, as k_rowfwd
+      const int p0 = tile_pos<R, GPB>(line, r2);
+      const float4 ab = *reinterpret_cast<const float4*>(tile + (p0 & ~1));
+      const bool sw = (p0 & 1) != 0;
+      a = sw ? make_float2(ab.z, ab.w) : make_float2(ab.x, ab.y);
+      b = sw ? make_float2(ab.x, ab.y) : make_float2(ab.z, ab.w);
+    } else {
+      a = tile[tile_pos<R, GPB>(line, r2)];
+      b = tile[tile_pos<R, GPB>(line, r2 + 1)];
+    }
+    const int pl = line / (N / 2);
+    st_stream4(base + (size_t)pl * PLA + LayoutA<R>::at(line - pl * (N / 2), y0 + r2),
+               make_float4(a.x, a.y, b.x, b.y));
+  }
+}
+
+// N = 1024: k_rowfwd32's three workgroups per CU (split FFT tiles, one plane's tile at a time)
+__global__ __launch_bounds__(256, 3) void k_rowfwd32_real(const JobDesc* __restrict__ jobs,
+                                                          const float* __restrict__ values,
+                                                          float2* __restrict__ ws_a,
+                                                          const float2* __restrict__ tw_glob, int P, int CH) {
+  constexpr int R = 32, NT = 256, N = R * R;
+  constexpr int GPB = NT / R;          // 8 rows per row block
+  constexpr int SCRF = GPB * R * (R + 1);               // floats: 8 FFT tiles
+  static_assert((N / 2) * GPB * 2 <= SCRF, "one plane's tile must fit in the FFT tiles");
+  __shared__ float2 tw[N];
+  __shared__ __attribute__((aligned(16))) float lds[SCRF];
+
+  for (int i = threadIdx.x; i < N; i += NT) tw[i] = tw_glob[i];
+
+  const int grp = threadIdx.x / R;
+  const int t = threadIdx.x % R;
+  const int k1 = mirror_k1(t);         // the second FFT stage in mirror-paired lane order
+  constexpr int RB = N / GPB;
+  int bid = xcd_pair<RB>(blockIdx.x);
+  const int rbw = bid % RB;
+  bid /= RB;
+  const int npair = P / 2;
+  const int j = bid / npair;
+  const JobDesc jb = jobs[j];
+  if (jb.env < 0) return;  // uniform per block
+  const int pa = 2 * (bid % npair);
+  const int y0 = rbw * GPB;
+  const int y = y0 + grp;
+  pk2 v[R];
+  real_load_row<R>(v, values + (((size_t)jb.env * CH + jb.group * P + pa) * N + y) * N, (size_t)N * N, t);
+  __syncthreads();  // tw visible
+
+  constexpr size_t PLA = plane_a_elems(R);
+  float2* base = ws_a + ((size_t)j * P + pa) * PLA;
+  float2* tile = reinterpret_cast<float2*>(lds);
+  // lane t now holds Z[k1 + 32 k2] (k1 = mirror_k1(t)): the mirror partner is lane t ^ 1
+  fft_group_split_mirror<false>(v, t, k1, lds + grp * R * (R + 1), tw);
+
+  // Hermitian split: plane a now, plane b kept in registers for the second tile
+  float2 fb[R / 2];
+  lds_barrier();    // every group is done with its FFT tile: reuse as the plane tile
+  const float2 zny = from_pk(v[R / 2]);  // Z[N/2] on lane 0 (k1 = 0)
+#pragma unroll
+  for (int k2 = 0; k2 < R / 2; ++k2) {
+    const float2 z = from_pk(v[k2]);
+    const float2 m = mirror_conj_paired(v, k2, t);
+    float2 fa = make_float2(z.x + m.x, z.y + m.y);       // 2 A (htab holds H / 2)
+    fb[k2] = make_float2(z.y - m.y, m.x - z.x);
+    if (k2 == 0 && t == 0) {  // DC and Nyquist of a real row are real
+      fa = make_float2(z.x + z.x, zny.x + zny.x);
+      fb[k2] = make_float2(z.y + z.y, zny.y + zny.y);
+    }
+    tile[tile_pos<R, GPB>(k1 + R * k2, grp)] = fa;
+  }
+  constexpr int CHUNKS = (N / 2) * GPB / 2;   // 16-B chunks of one plane's panel
+  static_assert(CHUNKS % NT == 0, "chunking");
+#pragma unroll
+  for (int pl = 0; pl < 2; ++pl) {
+    if (pl == 1) {
+      lds_barrier();   // plane a's tile has been read
+#pragma unroll
+      for (int k2 = 0; k2 < R / 2; ++k2) tile[tile_pos<R, GPB>(k1 + R * k2, grp)] = fb[k2];
+    }
+    lds_barrier();
+#pragma unroll
+    for (int i = 0; i < CHUNKS / NT; ++i) {
+      const int c = threadIdx.x + NT * i;
+      const int r2 = (c % (GPB / 2)) * 2;
+      const int line = c / (GPB / 2);
+      const float2 a = tile[tile_pos<R, GPB>(line, r2)];
+      const float2 b = tile[tile_pos<R, GPB>(line, r2 + 1)];
+      st_stream4(base + (size_t)pl * PLA + LayoutA<R>::at(line, y0 + r2), make_float4(a.x, a.y, b.x, b.y));
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Pass 2
 // ---------------------------------------------------------------------------
 // Column pass, one lane group per input line and both of its output lines:
@@ -1110,7 +1290,16 @@ static hipError_t launch_passes(const PlanDev& pd, const JobDesc* jobs, int n_jo
   const bool small = kTiledB<R> && rf_blocks < kSmallBlocks && col_blocks < kSmallBlocks;
   {
     if (tm) tm->begin(0, st);
-    if constexpr (R == 32) {
+    if (pd.real_values) {   // real-valued field: one row block per workgroup at every launch size
+      if (SK != HBX_PRECISION_F32 || pair || pd.actions || pd.walk_phase) return hipErrorInvalidValue;
+      const unsigned blocks = (unsigned)n_jobs * (P / 2) * (N / (kRowNT<R> / R));
+      if constexpr (R == 32)
+        hipLaunchKernelGGL(k_rowfwd32_real, dim3(blocks), dim3(256), 0, st, jobs, pd.real_values, pd.ws_a, pd.tw, P,
+                           CH);
+      else
+        hipLaunchKernelGGL((k_rowfwd_real<R, kRowNT<R>>), dim3(blocks), dim3(kRowNT<R>), 0, st, jobs,
+                           pd.real_values, pd.ws_a, pd.tw, P, CH);
+    } else if constexpr (R == 32) {
       if (small)
         hipLaunchKernelGGL((k_rowfwd32<SK, 1>), dim3(rf_blocks * rowfwd_iters<R>()), dim3(256), 0, st, jobs, mask,
                            pd.ws_a, pd.tw, P, CH, pd.va, pd.vb, pair, pd.actions, pd.act_err, pd.walk_phase);

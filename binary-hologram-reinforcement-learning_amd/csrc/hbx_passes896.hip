@@ -202,6 +202,97 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd896(const JobDesc* __restrict_
   }
 }
 
+// Pass 1 on real-valued fields (hbx_simulate_real / hbx_propagate_real, ABI v15):
+// values[env][CH][896][896] f32.  Lane t loads pixel x = t + 32 jj (jj < 28) of planes pa, pb
+// into the (re, im) of v[jj] (one coalesced 128-B run per lane group and jj, non-temporal);
+// the FFT, the split, the tile and the panel stores are k_rowfwd896's.  One row block per
+// workgroup (no register room for a second row's samples at three workgroups per CU); full
+// propagations only.
+__global__ __launch_bounds__(256, 3) void k_rowfwd896_real(const JobDesc* __restrict__ jobs,
+                                                           const float* __restrict__ values,
+                                                           float2* __restrict__ ws_a,
+                                                           const float2* __restrict__ tw_glob, int P, int CH) {
+  constexpr int SCRF = kGPB * kR * (kR + 1);      // floats: 8 FFT tiles (33.8 KB)
+  static_assert(kHalf * kGPB * 2 <= SCRF, "one plane's tile must fit in the FFT tiles");
+  __shared__ float2 tw[kN];
+  __shared__ __attribute__((aligned(16))) float lds[SCRF];
+  for (int i = threadIdx.x; i < kN; i += 256) tw[i] = tw_glob[i];
+
+  const int grp = threadIdx.x / kR;
+  const int t = threadIdx.x % kR;
+  const int lane_base = (threadIdx.x & 63) - t;
+  int bid = blockIdx.x;
+  const int rbw = bid % kRB;
+  bid /= kRB;
+  const int npair = P / 2;
+  const int j = bid / npair;
+  const JobDesc jb = jobs[j];
+  if (jb.env < 0) return;  // uniform per block
+  const int pa = 2 * (bid % npair);
+  const int y0 = rbw * kGPB;
+  const int y = y0 + grp;
+  const float* rowa = values + (((size_t)jb.env * CH + jb.group * P + pa) * kN + y) * kN + t;
+  const float* rowb = rowa + (size_t)kN * kN;
+  float2 v[32];
+  {
+    float a[kL], b[kL];
+#pragma unroll
+    for (int jj = 0; jj < kL; ++jj) a[jj] = __builtin_nontemporal_load(rowa + kR * jj);
+#pragma unroll
+    for (int jj = 0; jj < kL; ++jj) b[jj] = __builtin_nontemporal_load(rowb + kR * jj);
+#pragma unroll
+    for (int jj = 0; jj < kL; ++jj) v[jj] = make_float2(a[jj], b[jj]);
+  }
+#pragma unroll
+  for (int jj = kL; jj < 32; ++jj) v[jj] = make_float2(0.f, 0.f);
+  __syncthreads();  // tw visible
+
+  float2* base = ws_a + ((size_t)j * P + pa) * kPlaneA;
+  float2* tile = reinterpret_cast<float2*>(lds);
+  constexpr int CHUNKS = kHalf * kGPB / 2;      // 16-B chunks of one plane's panel (1792)
+  static_assert(CHUNKS % 256 == 0, "chunking");
+  fft896_ns_split<false>(v, t, lds + grp * kR * (kR + 1), tw);
+
+  // Hermitian split of the slot-layout spectrum (kx = t + 28 k2 < 448: k2 < 16): plane a
+  // now, plane b kept in registers for the second tile
+  float2 fb[16];
+  lds_barrier();    // every group is done with its FFT tile: reuse as the plane tile
+  const float2 zny = v[16];  // Z[448] on lane 0
+#pragma unroll
+  for (int k2 = 0; k2 < 16; ++k2) {
+    const float2 z = v[k2];
+    const float2 m = mirror_conj896(v, k2, t, lane_base);
+    float2 fa = make_float2(z.x + m.x, z.y + m.y);       // 2 A (htab holds H / 2)
+    fb[k2] = make_float2(z.y - m.y, m.x - z.x);
+    if (k2 == 0 && t == 0) {  // DC and Nyquist of a real row are real
+      fa = make_float2(z.x + z.x, zny.x + zny.x);
+      fb[k2] = make_float2(z.y + z.y, zny.y + zny.y);
+    }
+    if (t < kL) tile[tile896_pos(t + kL * k2, grp)] = fa;
+  }
+#pragma unroll
+  for (int pl = 0; pl < 2; ++pl) {
+    if (pl == 1) {
+      lds_barrier();   // plane a's tile has been read
+#pragma unroll
+      for (int k2 = 0; k2 < 16; ++k2)
+        if (t < kL) tile[tile896_pos(t + kL * k2, grp)] = fb[k2];
+    }
+    lds_barrier();
+    float2* panel = base + (size_t)pl * kPlaneA + a896_at(0, y0);
+#pragma unroll
+    for (int i = 0; i < CHUNKS / 256; ++i) {
+      const int c = threadIdx.x + 256 * i;
+      const int r2 = (c % (kGPB / 2)) * 2;
+      const int line = c / (kGPB / 2);
+      const int p0 = tile896_pos(line, r2);
+      const float4 ab = *reinterpret_cast<const float4*>(tile + (p0 & ~1));
+      const bool sw = (p0 & 1) != 0;
+      st_stream4(panel + 2 * c, sw ? make_float4(ab.z, ab.w, ab.x, ab.y) : ab);   // = a896_at(line, y0 + r2)
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Pass 2 (r04: k_col2's scheme at 896): one lane group per input line and both of its
 // output lines.  FFT over y -> Z (slot layout); H(kx, ky) for ky <= 448 only (17 of 32
@@ -513,8 +604,13 @@ hipError_t run_jobs_896(const PlanDev& pd, const JobDesc* jobs, int n_jobs, cons
   // flipped plane's pair only (the walk's decision runs in a launch of its own at 896)
   const int pair = pd.plane_mode == kPlanesStep ? 1 : 0;
   if (pd.plane_mode != kPlanesOff && (!pd.plane_pool || !pd.plane_slot)) return hipErrorInvalidValue;
+  if (pd.real_values && (pair || pd.store_kind != HBX_PRECISION_F32)) return hipErrorInvalidValue;
   if (tm) tm->begin(0, st);
-  hipLaunchKernelGGL(k_rowfwd896, dim3((unsigned)n_jobs * (pair ? 1 : P / 2) * (kRB / kRit896)), dim3(256), 0, st,
+  if (pd.real_values)
+    hipLaunchKernelGGL(k_rowfwd896_real, dim3((unsigned)n_jobs * (P / 2) * kRB), dim3(256), 0, st, jobs,
+                       pd.real_values, pd.ws_a, pd.tw, P, CH);
+  else
+    hipLaunchKernelGGL(k_rowfwd896, dim3((unsigned)n_jobs * (pair ? 1 : P / 2) * (kRB / kRit896)), dim3(256), 0, st,
                      jobs, mask, pd.ws_a, pd.tw, P, CH, pd.va, pd.vb, pair);
   if (tm) tm->end(0, n_jobs, st);
   if (tm) tm->begin(1, st);

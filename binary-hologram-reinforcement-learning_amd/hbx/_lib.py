@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HBX_LIB", os.path.join(_HERE, "libhbx.so"))
 
 # constants mirrored from include/hbx.h
-ABI_VERSION = 14
+ABI_VERSION = 15
 OK = 0
 ERR_INVALID, ERR_HIP, ERR_UNSUPPORTED, ERR_NOMEM = -1, -2, -3, -4
 TF_ASM, TF_FRESNEL = 0, 1
@@ -39,6 +39,7 @@ EXPORTED_SYMBOLS = (
     "hbx_plan_set_precision", "hbx_plan_precision", "hbx_env_obs_sync",
     "hbx_planes_fill", "hbx_eval_flips_planes", "hbx_commit_flip_planes", "hbx_dbs_walk_planes",
     "hbx_dbs_walk_planes_fill", "hbx_host_alloc", "hbx_host_free", "hbx_pack_mask", "hbx_rel_stats",
+    "hbx_simulate_real", "hbx_propagate_real",
 )
 NUM_PASSES = 5
 PASS_NAMES = ("k_rowfwd", "k_col", "k_rowinv", "k_psf_eval", "k_psf_commit")
@@ -125,6 +126,8 @@ def _declare(lib):
                                      VP, VP, VP, VP]
     lib.hbx_field_refresh.argtypes = [VP, C.POINTER(EnvBuffers), I32, VP, I32, VP]
     lib.hbx_simulate.argtypes = [VP, VP, I32, VP, VP, VP]
+    lib.hbx_simulate_real.argtypes = [VP, VP, I32, VP, VP, VP]
+    lib.hbx_propagate_real.argtypes = [VP, VP, VP, I32, VP, VP, VP, VP]
     lib.hbx_flip_map.argtypes = [VP, VP, VP, VP, VP, VP]
     lib.hbx_eval_flips_psf.argtypes = [VP, VP, VP, VP, VP, VP, VP, I32, VP, VP, VP]
     lib.hbx_commit_flip_psf.argtypes = [VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, I32, VP]

@@ -295,6 +295,40 @@ class Plan:
                    "hbx_simulate")
         return torch.view_as_complex(field), inten
 
+    def values_shape(self, n: int):
+        c = self.cfg
+        return (n, c.channels, c.height, c.width)
+
+    def simulate_real(self, values: torch.Tensor, want_intensity: bool = False, stream=None):
+        """`simulate` on a real-valued field (hbx_simulate_real, ABI v15): `values` float32
+        [B, CH, H, W] are the field samples themselves (u = value; the plan's field_kind is not
+        applied).  Returns (field complex64 [B, CH, H, W], intensity [B, G, H, W] | None)."""
+        n = values.shape[0] if isinstance(values, torch.Tensor) and values.dim() else 0
+        c = self.cfg
+        _need(values, "values", torch.float32, self.values_shape(n), self.device)
+        field = torch.empty((n, c.channels, c.height, c.width, 2), dtype=torch.float32, device=self.device)
+        inten = torch.empty((n, c.groups, c.height, c.width), dtype=torch.float32,
+                            device=self.device) if want_intensity else None
+        _lib.check(self.lib.hbx_simulate_real(self._h, _ptr(values), n, _ptr(field), _ptr(inten),
+                                              _stream(stream)), "hbx_simulate_real")
+        return torch.view_as_complex(field), inten
+
+    def propagate_real(self, values: torch.Tensor, target: torch.Tensor, want_intensity: bool = True,
+                       stream=None):
+        """`propagate` on a real-valued field (hbx_propagate_real, ABI v15): returns
+        (intensity|None, chan_stats, psnr)."""
+        n = values.shape[0] if isinstance(values, torch.Tensor) and values.dim() else 0
+        c = self.cfg
+        _need(values, "values", torch.float32, self.values_shape(n), self.device)
+        _need(target, "target", torch.float32, self.target_shape(n), self.device)
+        inten = torch.empty((n, c.groups, c.height, c.width), dtype=torch.float32,
+                            device=self.device) if want_intensity else None
+        stats = torch.empty((n, c.groups, 3), dtype=torch.float64, device=self.device)
+        psnr = torch.empty((n,), dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.hbx_propagate_real(self._h, _ptr(values), _ptr(target), n, _ptr(inten),
+                                               _ptr(stats), _ptr(psnr), _stream(stream)), "hbx_propagate_real")
+        return inten, stats, psnr
+
     def psnr(self, chan_stats: torch.Tensor, stream=None) -> torch.Tensor:
         n = chan_stats.shape[0]
         _need(chan_stats, "chan_stats", torch.float64, (n, self.cfg.groups, 3), self.device)

@@ -8,20 +8,30 @@ DBS_1024_24.py:244-257,326-352; range.py:225-309):
     psnr = tt.relativeLoss(mean_intensity, target, tm.get_PSNR)
     mse = tt.relativeLoss(mean_intensity, target, F.mse_loss)
 
-``simulate`` runs on the MI355X through libhbx.so: one hbx_pack_mask launch turns the mask
-into bits (ABI v14), then hbx_simulate's three HIP FFT passes with the transfer function fused
-in.  The reference only ever propagates binary masks, and so does this shim: a non-binary
-field raises ValueError (there is no CPU / float fallback).  The binary check is part of the
-pack kernel and costs no host sync: the kernel flags a value other than 0 / 1 in host-mapped
-memory, and the shim raises at the first point the host has waited for that work -- inside
-the tt.relativeLoss(.., tm.get_PSNR) that consumes the result (it waits for its PSNR anyway,
-env.py:174 / DBS.py:270 compare it at once), at the next tt.simulate, or at check_binary().
-``simulate(x, z, strict=True)`` waits and raises before returning.
-The physics follows the assumptions documented in DESIGN.md (the original
-torchOptics is absent and unpinned): exact angular spectrum, no padding,
-amplitude field.  relativeLoss uses the least-squares scale s = sum(xy)/sum(x^2); with
-tm.get_PSNR on GPU tensors it is one fixed-order f64 reduction (hbx_rel_stats) whose PSNR
-is read from host-mapped memory.
+``simulate`` runs on the MI355X through libhbx.so, on one of two paths (there is no CPU
+fallback on either):
+
+* ``binary=True`` (the default, what the reference does): one hbx_pack_mask launch turns the
+  mask into bits (ABI v14), then hbx_simulate's three HIP FFT passes with the transfer function
+  fused in.  This path propagates binary {0,1} masks only: a value other than 0 / 1 raises
+  ValueError, and a complex input is refused.  The binary check is part of the pack kernel
+  and costs no host sync: the kernel flags the value in host-mapped memory, and the shim
+  raises at the first point the host has waited for that work -- inside the
+  tt.relativeLoss(.., tm.get_PSNR) that consumes the result (it waits for its PSNR anyway,
+  env.py:174 / DBS.py:270 compare it at once), at the next tt.simulate, or at check_binary().
+  ``simulate(x, z, strict=True)`` waits and raises before returning.
+* ``binary=False`` (the continuous path, ABI v15): the samples are the field.  Real float
+  input goes through hbx_simulate_real, whose first pass reads float32 samples instead of
+  bits; a complex field, or ``field="phase"`` on real input (u = exp(i pi x)), is propagated
+  as two real planes per complex plane and recombined by linearity.  No pack kernel runs,
+  the error word is never set and ``strict`` has nothing to check.
+
+The physics follows the assumptions documented in DESIGN.md (the original torchOptics is
+absent and unpinned): no padding; exact angular spectrum and amplitude field unless
+``tf="fresnel"`` / ``field="phase"`` select the plan's other switches.  relativeLoss uses the
+least-squares scale s = sum(xy)/sum(x^2) unless ``rel_scale="none"``; with tm.get_PSNR on GPU
+tensors it is one fixed-order f64 reduction (hbx_rel_stats) whose PSNR is read from
+host-mapped memory.
 """
 from __future__ import annotations
 
@@ -69,12 +79,28 @@ def _meta_of(x) -> Dict:
     return meta
 
 
-def _plan_for(h: int, w: int, planes: int, wl: float, dx: float, dy: float, z: float, n: int, dev: int):
-    key = (h, w, planes, float(wl), float(dx), float(dy), float(z), dev)
+_TF_NAMES = {"asm": _lib.TF_ASM, "fresnel": _lib.TF_FRESNEL}
+_FIELD_NAMES = {"amplitude": _lib.FIELD_AMPLITUDE, "phase": _lib.FIELD_PHASE}
+_REL_NAMES = {"none": _lib.REL_NONE, "lsq": _lib.REL_LSQ}
+
+
+def _switch(value, names: Dict[str, int], what: str) -> int:
+    """A switch given by name or as its _lib integer -> the integer; anything else raises."""
+    if isinstance(value, str):
+        if value in names:
+            return names[value]
+    elif isinstance(value, (int, np.integer)) and not isinstance(value, bool) and int(value) in names.values():
+        return int(value)
+    raise ValueError(f"{what} must be one of {sorted(names)} (or the hbx._lib constant), got {value!r}")
+
+
+def _plan_for(h: int, w: int, planes: int, wl: float, dx: float, dy: float, z: float, n: int, dev: int,
+              tf: int = _lib.TF_ASM, field: int = _lib.FIELD_AMPLITUDE):
+    key = (h, w, planes, float(wl), float(dx), float(dy), float(z), dev, tf, field)
     p = _PLANS.get(key)
     if p is None or p.max_jobs < n:
         cfg = hbx.OpticsConfig(h, w, 1, planes, (float(wl),), float(dx), float(dy), float(z),
-                               _lib.TF_ASM, _lib.FIELD_AMPLITUDE, _lib.REL_LSQ, 1.0)
+                               tf, field, _lib.REL_LSQ, 1.0)
         p = hbx.Plan(cfg, max_jobs=max(n, 1), device=dev)
         _PLANS[key] = p
     return p
@@ -121,10 +147,27 @@ def check_binary(device: Optional[int] = None):
         _raise_pending(sc)
 
 
-def simulate(x, z: float, strict: bool = False, **_) -> torch.Tensor:
-    """Free-space propagation of a binary mask tensor [B, C, H, W] (or [C, H, W])
-    by z metres: the complex field of every plane, complex64, on the GPU.
-    strict=True waits for the binary check and raises here (one host sync)."""
+def simulate(x, z: float, strict: bool = False, binary: bool = True, tf="asm", field="amplitude",
+             **_) -> torch.Tensor:
+    """Free-space propagation of a tensor [B, C, H, W] (or [C, H, W]) by z metres: the
+    complex field of every plane, complex64, on the GPU.
+
+    tf: "asm" (exact angular spectrum) or "fresnel"; field: "amplitude" or "phase" (both also
+    take the hbx._lib TF_* / FIELD_* integers; an unknown value raises ValueError).
+
+    binary=True (default): x is a binary {0,1} mask, packed to bits; amplitude u = m, phase
+    u = exp(i pi m) = 1 - 2 m.  A value other than 0 / 1 raises ValueError -- deferred to the
+    next point the host waits (module docstring), or here with strict=True (one host sync).
+    Complex input is refused.
+
+    binary=False: the continuous path; no binary check, `strict` is ignored.
+      real x,    field="amplitude":  u = x (float64 is cast to float32), one real plane each;
+      complex x, field="amplitude":  u = x, propagated as the real planes [re0, im0, re1, ..]
+                                     and recombined as F[2c] + i F[2c+1] (exact by linearity);
+      real x,    field="phase":      u = exp(i pi x) = cos(pi x) + i sin(pi x), the same route.
+    A complex plane therefore costs two real planes (twice the time and workspace of a real one)."""
+    tf_kind = _switch(tf, _TF_NAMES, "tf")
+    field_kind = _switch(field, _FIELD_NAMES, "field")
     meta = _meta_of(x)
     wl = meta["wl"]
     if isinstance(wl, (tuple, list)):
@@ -140,7 +183,10 @@ def simulate(x, z: float, strict: bool = False, **_) -> torch.Tensor:
     if t.dim() != 4:
         raise ValueError(f"simulate expects [B, C, H, W], got {tuple(t.shape)}")
     if t.is_complex():
-        raise ValueError("tt.simulate (hbx) propagates binary {0,1} masks only, as the reference does")
+        if binary:
+            raise ValueError("tt.simulate (hbx) propagates binary {0,1} masks only, as the reference does")
+        if field_kind != _lib.FIELD_AMPLITUDE:
+            raise ValueError("tt.simulate: a complex field is used as it is (field=\"amplitude\")")
     if not torch.cuda.is_available():
         raise RuntimeError("tt.simulate needs a ROCm GPU (libhbx.so)")
     if t.is_cuda:
@@ -148,11 +194,14 @@ def simulate(x, z: float, strict: bool = False, **_) -> torch.Tensor:
     else:
         dev = torch.cuda.current_device()
         t = t.to(f"cuda:{dev}")
+    if not binary:
+        out = _simulate_continuous(t, wl, dx, dy, z, dev, tf_kind, field_kind)
+        return out[0] if squeeze else out
     sc = _scratch(dev)
     _raise_pending(sc)                              # an earlier call's input, already checked
     b, c, h, w = t.shape
     cp = c + (c % 2)                                # the kernels pack plane pairs
-    plan = _plan_for(h, w, cp, wl, dx, dy, z, b, dev)
+    plan = _plan_for(h, w, cp, wl, dx, dy, z, b, dev, tf_kind, field_kind)
     if cp == c:
         bits = hbx.pack_mask(t, error_ptr=sc.err_dev)
     else:
@@ -167,8 +216,39 @@ def simulate(x, z: float, strict: bool = False, **_) -> torch.Tensor:
     return field[0] if squeeze else field
 
 
-def relativeLoss(x: torch.Tensor, y, fn: Callable) -> torch.Tensor:
-    """fn(s * x, y) with the least-squares scale s = sum(x y) / sum(x^2), all in
+def _simulate_continuous(t: torch.Tensor, wl, dx, dy, z, dev: int, tf_kind: int, field_kind: int) -> torch.Tensor:
+    """simulate's binary=False path on a device tensor [B, C, H, W]: real planes through
+    hbx_simulate_real; complex / phase fields as (re, im) plane pairs, recombined here."""
+    b, c, h, w = t.shape
+    as_pairs = t.is_complex() or field_kind == _lib.FIELD_PHASE
+    if as_pairs:
+        if t.is_complex():
+            ri = torch.view_as_real(t.to(torch.complex64))          # [B, C, H, W, 2]
+            planes = ri.permute(0, 1, 4, 2, 3).reshape(b, 2 * c, h, w)
+        else:
+            ph = t.to(torch.float32) * np.float32(np.pi)
+            planes = torch.stack((torch.cos(ph), torch.sin(ph)), dim=2).reshape(b, 2 * c, h, w)
+        cp = 2 * c
+        vals = planes.contiguous()
+    else:
+        cp = c + (c % 2)                            # the kernels take plane pairs: pad with a zero plane
+        if cp == c:
+            vals = t.to(torch.float32).contiguous()
+        else:
+            vals = torch.zeros((b, cp, h, w), dtype=torch.float32, device=t.device)
+            vals[:, :c] = t
+    # the samples are the field: the plan's bit mapping (field_kind) plays no part
+    plan = _plan_for(h, w, cp, wl, dx, dy, z, b, dev, tf_kind, _lib.FIELD_AMPLITUDE)
+    out, _ = plan.simulate_real(vals)
+    if as_pairs:
+        return out[:, 0::2] + 1j * out[:, 1::2]
+    return out[:, :c] if cp != c else out
+
+
+def relativeLoss(x: torch.Tensor, y, fn: Callable, rel_scale="lsq") -> torch.Tensor:
+    """fn(s * x, y) with the least-squares scale s = sum(x y) / sum(x^2) (rel_scale="lsq",
+    the default) or with s = 1 (rel_scale="none"; the hbx._lib REL_* integers are accepted
+    too, an unknown value raises ValueError), all in
     float64: DBS_1024_24.py:355 compares two such PSNRs whose difference is
     ~1e-6 dB at 1024x24, below float32 resolution of the PSNR itself.
 
@@ -177,6 +257,7 @@ def relativeLoss(x: torch.Tensor, y, fn: Callable) -> torch.Tensor:
     the least-squares-scaled intensity, 10 log10(1 / ((sum y^2 - (sum xy)^2 / sum x^2) / n)),
     read from host-mapped memory after one wait -- the wait get_PSNR's float result needs
     anyway.  Other fns (F.mse_loss at env.py:131) run as torch ops."""
+    rel = _switch(rel_scale, _REL_NAMES, "rel_scale")
     x = x.as_subclass(torch.Tensor) if isinstance(x, torch.Tensor) else torch.as_tensor(x)
     y = torch.as_tensor(np.asarray(y)) if not isinstance(y, torch.Tensor) else y.as_subclass(torch.Tensor)
     if fn is _metrics.get_PSNR and x.is_cuda and y.is_cuda and x.device == y.device and x.shape == y.shape \
@@ -186,7 +267,7 @@ def relativeLoss(x: torch.Tensor, y, fn: Callable) -> torch.Tensor:
         xc, yc = x.contiguous(), y.contiguous()
         kind = _lib.SRC_F32 if x.dtype == torch.float32 else _lib.SRC_F64
         st = torch.cuda.current_stream(dev)
-        rc = _lib.load().hbx_rel_stats(xc.data_ptr(), yc.data_ptr(), kind, xc.numel(), _lib.REL_LSQ, 1.0,
+        rc = _lib.load().hbx_rel_stats(xc.data_ptr(), yc.data_ptr(), kind, xc.numel(), rel, 1.0,
                                        sc.work.data_ptr(), sc.out_dev, st.cuda_stream)
         if rc != _lib.OK:
             _lib.check(rc, "hbx_rel_stats")
@@ -194,8 +275,7 @@ def relativeLoss(x: torch.Tensor, y, fn: Callable) -> torch.Tensor:
         _raise_pending(sc)                          # the simulate that produced x, if it was not binary
         return float(sc.out[3])
     xd, yd = x.double(), y.to(x.device).double()
-    s = torch.sum(xd * yd) / torch.sum(xd * xd)
-    out = fn(s * xd, yd)
+    out = fn((torch.sum(xd * yd) / torch.sum(xd * xd)) * xd, yd) if rel == _lib.REL_LSQ else fn(xd, yd)
     if x.is_cuda and x.device.index in _SCRATCH and not isinstance(out, torch.Tensor):
         _raise_pending(_SCRATCH[x.device.index])    # fn waited for the device (a float result)
     return out

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define HBX_ABI_VERSION 14
+#define HBX_ABI_VERSION 15
 
 #define HBX_OK 0
 #define HBX_ERR_INVALID (-1)     /* bad argument / shape                          */
@@ -207,6 +207,21 @@ int hbx_propagate(hbx_plan_t plan, const uint64_t* mask, const float* target, in
  * and optionally the plane-mean intensity[B][G][H][W] (nullable). */
 int hbx_simulate(hbx_plan_t plan, const uint64_t* mask, int32_t n_env, float* field,
                  float* intensity, void* stream);
+
+/* (ABI v15) The same two calls on a real-valued field instead of a binary mask:
+ *   values[B][G*P][H][W] float32: the real field sample of every pixel, used as it is
+ *   (u = value; the plan's field_kind maps bits only and is not applied).
+ * Outputs, null-ability, chunking by the plan's max_jobs and n_env == 0 are those of
+ * hbx_simulate / hbx_propagate; only the first pass differs (it reads 4 bytes per pixel instead
+ * of one bit and fills the HBX_PASS_ROWFWD timer slot), so 0 / 1 samples give the bit path's
+ * result.  A complex field u = a + i b is two calls' worth of planes by linearity: propagate
+ * the planes a and b, then F = F[a] + i F[b].  All four built sizes; HBX_PRECISION_F32 only
+ * (a plan set to a reduced-precision store kind returns HBX_ERR_UNSUPPORTED).  No env, DBS,
+ * plane-cache or incremental mode runs on real-valued fields. */
+int hbx_simulate_real(hbx_plan_t plan, const float* values, int32_t n_env, float* field,
+                      float* intensity, void* stream);
+int hbx_propagate_real(hbx_plan_t plan, const float* values, const float* target, int32_t n_env,
+                       float* intensity, double* chan_stats, double* psnr, void* stream);
 
 /* PSNR from per-channel statistics (tt.relativeLoss(.., tm.get_PSNR),
  * env.py:174): chan_stats[B][G][3] -> psnr[B]. */
