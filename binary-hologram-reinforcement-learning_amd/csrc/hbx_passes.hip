@@ -17,6 +17,9 @@
 //             half spectrum kx < N/2 (Nyquist packed in Im of kx = 0), stored doubled:
 //             2 A, the split's 0.5 factors dropped (r06) and folded into htab = H / 2 ->
 //             LDS tile transpose -> A panel y0 / GPB       [HBM: read N^2/8 B, write 4 N^2 B per plane]
+//             (k_rowfwd32 at N = 1024.  k_rowfwd_real / k_rowfwd32_real read f32 samples instead of
+//             bits; everything after the load -- FFT, split, tile, panel stores -- is one function
+//             per size class, rowfwd_emit / rowfwd32_emit, called by the bit and the real kernel)
 //   k_col2    one lane group per half-spectrum line kx: FFT over y -> x H and
 //             x conj H (H is even in fx and ky) -> two IFFTs -> B lines kx
 //             and N - kx (N/2 for kx = 0); buffer loads / stores with one
@@ -139,326 +142,24 @@ __device__ __forceinline__ JobDesc first_pass_job(const JobDesc* jobs, const int
   return jb;
 }
 
-template <int R, int NT, int SK, int RIT = rowfwd_iters<R>()>
-__global__ __launch_bounds__(NT, 512 / NT) void k_rowfwd(const JobDesc* jobs,
-                                                   const uint32_t* __restrict__ mask,
-                                                   float2* __restrict__ ws_a,
-                                                   const float2* __restrict__ tw_glob, int P,
-                                                   int CH, float va, float vb, int pair_step,
-                                                   const int64_t* __restrict__ actions, int32_t* err,
-                                                   const uint8_t* __restrict__ phase) {
-  constexpr int N = R * R;
-  constexpr int GPB = NT / R;          // rows per row block
-  constexpr int WPR = N / 32;           // 32-bit mask words per row
-  constexpr int SCR = GPB * R * (R + 1);
-  static_assert(N * GPB <= SCR, "tile must fit in the scratch area");
-  __shared__ float2 tw[N];
-  __shared__ __attribute__((aligned(16))) float2 lds[SCR];
-
-  for (int i = threadIdx.x; i < N; i += NT) tw[i] = tw_glob[i];
-
-  const int grp = threadIdx.x / R;
-  const int t = threadIdx.x % R;
-  const int lane_base = (threadIdx.x & 63) - t;
-  constexpr int RB = N / GPB;
-  constexpr int RBW = RB / RIT;        // workgroups per plane pair
-  int bid = RIT == 1 ? xcd_pair<RB>(blockIdx.x) : (int)blockIdx.x;
-  const int rbw = bid % RBW;
-  bid /= RBW;
-  const int npair = pair_step ? 1 : P / 2;   // plane-cached step: only the flipped plane's pair
-  const int j = bid / npair;
-  const JobDesc jb = first_pass_job(jobs, actions, err, j, rbw == 0 && bid % npair == 0, (int64_t)N * N, P, CH);
-  if (jb.env < 0 || (phase && phase[j])) return;  // uniform per block (a walk slot whose A / B are kept)
-  const int q = pair_step ? (jb.flip_plane >> 1) : bid % npair;
-  const int pa = 2 * q, pb = 2 * q + 1;
-  const uint32_t* plane_a = mask + ((size_t)jb.env * CH + jb.group * P + pa) * N * WPR;
-  uint32_t wa[WPR], wb[WPR];
-  auto load_row = [&](int y) {
-    const uint32_t* rowa = plane_a + (size_t)y * WPR;
-    const uint32_t* rowb = rowa + (size_t)N * WPR;
-    if constexpr (WPR % 4 == 0) {
-#pragma unroll
-      for (int i = 0; i < WPR / 4; ++i) {
-        const uint4 a = reinterpret_cast<const uint4*>(rowa)[i];
-        const uint4 b = reinterpret_cast<const uint4*>(rowb)[i];
-        wa[4 * i] = a.x; wa[4 * i + 1] = a.y; wa[4 * i + 2] = a.z; wa[4 * i + 3] = a.w;
-        wb[4 * i] = b.x; wb[4 * i + 1] = b.y; wb[4 * i + 2] = b.z; wb[4 * i + 3] = b.w;
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < WPR; ++i) { wa[i] = rowa[i]; wb[i] = rowb[i]; }
-    }
-  };
-  load_row(rbw * RIT * GPB + grp);
-  __syncthreads();  // tw visible
-
-  constexpr size_t PLA = plane_a_elems(R);
-  float2* base = ws_a + ((size_t)j * P + pa) * PLA;
-#pragma unroll 1
-  for (int it = 0; it < RIT; ++it) {
-    const int y0 = (rbw * RIT + it) * GPB;
-    const int y = y0 + grp;
-    if (jb.flip_plane >= 0 && jb.flip_pix / N == y) {  // env.py:164 flip, on the fly
-      const int col = jb.flip_pix % N;
-      const uint32_t bit = 1u << (col & 31);
-#pragma unroll
-      for (int i = 0; i < WPR; ++i) {
-        if (i == (col >> 5)) {
-          if (jb.flip_plane == pa) wa[i] ^= bit;
-          if (jb.flip_plane == pb) wb[i] ^= bit;
-        }
-      }
-    }
-    pk2 v[R];
-    with_field_kind(va, vb, [&](auto fk) {
-#pragma unroll
-      for (int jj = 0; jj < R; ++jj) {
-        const int w = (R * jj) >> 5;
-        const int sh = ((R * jj) & 31) + t;
-        v[jj] = (pk2){bit_value<fk()>(wa[w], sh, va, vb), bit_value<fk()>(wb[w], sh, va, vb)};
-      }
-    });
-    if constexpr (RIT > 1) {
-      // next rows' words (the last iteration re-reads its own row: no conditional load)
-      load_row(it + 1 < RIT ? y + GPB : y);
-      if (it > 0) lds_barrier();   // every group has read the previous tile: scratch reusable
-    }
-    fft_group<R, false>(v, t, PaddedScratch<R>{lds + grp * R * (R + 1)}, tw);
-    lds_barrier();    // every group is done with its scratch: reuse as the tile
-
-    // Hermitian split -> tile[plane][kx][row]
-    float2* tile = lds;
-    const float2 zny = from_pk(v[R / 2]);  // Z[N/2] on lane 0
-#pragma unroll
-    for (int k2 = 0; k2 < R / 2; ++k2) {
-      const float2 z = from_pk(v[k2]);
-      const float2 m = mirror_conj<R>(v, k2, t, lane_base);
-      float2 fa = make_float2(z.x + m.x, z.y + m.y);       // 2 A (htab holds H / 2)
-      float2 fb = make_float2(z.y - m.y, m.x - z.x);
-      if (k2 == 0 && t == 0) {  // DC and Nyquist of a real row are real
-        fa = make_float2(z.x + z.x, zny.x + zny.x);
-        fb = make_float2(z.y + z.y, zny.y + zny.y);
-      }
-      const int kx = t + R * k2;
-      tile[tile_pos<R, GPB>(kx, grp)] = fa;
-      tile[tile_pos<R, GPB>(N / 2 + kx, grp)] = fb;
-    }
-    lds_barrier();
-    // store tile lines: A[pa|pb][kx][y0 .. y0+GPB), 16 B per thread per chunk
-    constexpr int CHUNKS = N * GPB / 2;
-    static_assert(CHUNKS % NT == 0, "chunking");
-#pragma unroll
-    for (int i = 0; i < CHUNKS / NT; ++i) {
-      const int c = threadIdx.x + NT * i;
-      const int r2 = (c % (GPB / 2)) * 2;
-      const int line = c / (GPB / 2);  // pl * N/2 + kx : A planes pa, pb are adjacent
-      float2 a, b;
-      if constexpr (GPB == 16) {
-        // (r05) rows r2, r2 + 1 sit in one aligned 16-B pair (the swizzle XORs whole pairs, its
-        // bit 0 swaps the halves): one ds_read_b128 from a single lane base (the swizzle keys on
-        // bits 0-4 of the line, which the chunk rounds i leave alone), conflict-free in the
-        // 4 x 16-lane model; the two ds_read_b64 it replaces were 2-way (0.79 M extra LDS cycles
-        // per 128-job launch at N = 256, profiles/r05/prof_mono_r05t); time unchanged (0.0587-0.0589
-        // vs 0.0587-0.0588 ms, profiles/r05/rowfwd16_ab_r05u.txt)
-        const int p0 = tile_pos<R, GPB>(line, r2);
-        const float4 ab = *reinterpret_cast<const float4*>(tile + (p0 & ~1));
-        const bool sw = (p0 & 1) != 0;
-        a = sw ? make_float2(ab.z, ab.w) : make_float2(ab.x, ab.y);
-        b = sw ? make_float2(ab.x, ab.y) : make_float2(ab.z, ab.w);
-      } else {
-        a = tile[tile_pos<R, GPB>(line, r2)];
-        b = tile[tile_pos<R, GPB>(line, r2 + 1)];
-      }
-      a = store_round_a<SK>(a);
-      b = store_round_a<SK>(b);
-      const int pl = line / (N / 2);
-      // panel layout: (line, y0 + r2) of plane pl -> contiguous 16-B chunks of the panel
-      st_stream4(base + (size_t)pl * PLA + LayoutA<R>::at(line - pl * (N / 2), y0 + r2),
-                 make_float4(a.x, a.y, b.x, b.y));
-    }
-  }
-}
-
-// k_rowfwd at N = 1024 with three workgroups per CU (the wide kernel above: 216 VGPRs,
-// 75.8 KB LDS, two).  The pass is bound by how many row blocks' stores a CU keeps in
-// flight, not by its arithmetic (the whole launch is ~75 us of VALU issue), so:
-//  * lane t loads ONE mask word of its row per plane (word t) and a 32 x 32 bit
-//    transpose across the group (five ds_swizzle levels) hands it bit t of every
-//    word -- the 64 VGPRs of whole-row words the wide kernel keeps for its prefetch
-//    are two here;
-//  * the FFT transposes real and imaginary parts through a 4.2-KB float tile per
-//    group (fft_group_split), and the Hermitian split goes out one plane at a time
-//    through a 32-KB tile that aliases those FFT tiles: 8 KB twiddles + 33.8 KB.
-// Same arithmetic as k_rowfwd, so the A it writes is bit-identical.
-template <int SK, int RIT = rowfwd_iters<32>()>
-__global__ __launch_bounds__(256, 3) void k_rowfwd32(const JobDesc* jobs,
-                                                     const uint32_t* __restrict__ mask,
-                                                     float2* __restrict__ ws_a,
-                                                     const float2* __restrict__ tw_glob, int P, int CH,
-                                                     float va, float vb, int pair_step,
-                                                     const int64_t* __restrict__ actions, int32_t* err,
-                                                     const uint8_t* __restrict__ phase) {
-  constexpr int R = 32, NT = 256, N = R * R;
-  constexpr int GPB = NT / R;          // 8 rows per row block
-  constexpr int WPR = N / 32;          // 32 mask words per row = one per lane
-  constexpr int SCRF = GPB * R * (R + 1);               // floats: 8 FFT tiles
-  static_assert((N / 2) * GPB * 2 <= SCRF, "one plane's tile must fit in the FFT tiles");
-  __shared__ float2 tw[N];
-  __shared__ __attribute__((aligned(16))) float lds[SCRF];
-
-  for (int i = threadIdx.x; i < N; i += NT) tw[i] = tw_glob[i];
-
-  const int grp = threadIdx.x / R;
-  const int t = threadIdx.x % R;
-  const int k1 = mirror_k1(t);         // r05: the second FFT stage in mirror-paired lane order
-  constexpr int RB = N / GPB;
-  constexpr int RBW = RB / RIT;
-  int bid = RIT == 1 ? xcd_pair<RB>(blockIdx.x) : (int)blockIdx.x;
-  const int rbw = bid % RBW;
-  bid /= RBW;
-  const int npair = pair_step ? 1 : P / 2;   // plane-cached step: only the flipped plane's pair
-  const int j = bid / npair;
-  const JobDesc jb = first_pass_job(jobs, actions, err, j, rbw == 0 && bid % npair == 0, (int64_t)N * N, P, CH);
-  if (jb.env < 0 || (phase && phase[j])) return;  // uniform per block (a walk slot whose A / B are kept)
-  const int q = pair_step ? (jb.flip_plane >> 1) : bid % npair;
-  const int pa = 2 * q, pb = 2 * q + 1;
-  const uint32_t* plane_a = mask + ((size_t)jb.env * CH + jb.group * P + pa) * N * WPR;
-  uint32_t wa, wb;
-  auto load_row = [&](int y) {
-    wa = plane_a[(size_t)y * WPR + t];
-    wb = plane_a[(size_t)(N + y) * WPR + t];
-  };
-  load_row(rbw * RIT * GPB + grp);
-  __syncthreads();  // tw visible
-
-  constexpr size_t PLA = plane_a_elems(R);
-  float2* base = ws_a + ((size_t)j * P + pa) * PLA;
-  float2* tile = reinterpret_cast<float2*>(lds);
-#pragma unroll 1
-  for (int it = 0; it < RIT; ++it) {
-    const int y0 = (rbw * RIT + it) * GPB;
-    const int y = y0 + grp;
-    // bit r of ta / tb = pixel x = t + 32 r of the row
-    uint32_t ta = group_bit_transpose(wa, t);
-    uint32_t tb = group_bit_transpose(wb, t);
-    if (jb.flip_plane >= 0 && jb.flip_pix / N == y) {  // env.py:164 flip, on the fly
-      const int col = jb.flip_pix % N;
-      if (t == (col & 31)) {
-        if (jb.flip_plane == pa) ta ^= 1u << (col >> 5);
-        if (jb.flip_plane == pb) tb ^= 1u << (col >> 5);
-      }
-    }
-    pk2 v[R];
-    with_field_kind(va, vb, [&](auto fk) {
-#pragma unroll
-      for (int jj = 0; jj < R; ++jj)
-        v[jj] = (pk2){bit_value<fk()>(ta, jj, va, vb), bit_value<fk()>(tb, jj, va, vb)};
-    });
-    if constexpr (RIT > 1) {
-      // next rows' words (the last iteration re-reads its own row: no conditional load)
-      load_row(it + 1 < RIT ? y + GPB : y);
-      if (it > 0) lds_barrier();   // every group has read the previous plane-b tile
-    }
-    // lane t now holds Z[k1 + 32 k2] (k1 = mirror_k1(t)): the mirror partner is lane t ^ 1
-    fft_group_split_mirror<false>(v, t, k1, lds + grp * R * (R + 1), tw);
-
-    // Hermitian split: plane a now, plane b kept in registers for the second tile
-    float2 fb[R / 2];
-    lds_barrier();    // every group is done with its FFT tile: reuse as the plane tile
-    const float2 zny = from_pk(v[R / 2]);  // Z[N/2] on lane 0 (k1 = 0)
-#pragma unroll
-    for (int k2 = 0; k2 < R / 2; ++k2) {
-      const float2 z = from_pk(v[k2]);
-      const float2 m = mirror_conj_paired(v, k2, t);
-      float2 fa = make_float2(z.x + m.x, z.y + m.y);       // 2 A (htab holds H / 2)
-      fb[k2] = make_float2(z.y - m.y, m.x - z.x);
-      if (k2 == 0 && t == 0) {  // DC and Nyquist of a real row are real
-        fa = make_float2(z.x + z.x, zny.x + zny.x);
-        fb[k2] = make_float2(z.y + z.y, zny.y + zny.y);
-      }
-      tile[tile_pos<R, GPB>(k1 + R * k2, grp)] = fa;
-    }
-    constexpr int CHUNKS = (N / 2) * GPB / 2;   // 16-B chunks of one plane's panel
-    static_assert(CHUNKS % NT == 0, "chunking");
-#pragma unroll
-    for (int pl = 0; pl < 2; ++pl) {
-      if (pl == 1) {
-        lds_barrier();   // plane a's tile has been read
-#pragma unroll
-        for (int k2 = 0; k2 < R / 2; ++k2) tile[tile_pos<R, GPB>(k1 + R * k2, grp)] = fb[k2];
-      }
-      lds_barrier();
-#pragma unroll
-      for (int i = 0; i < CHUNKS / NT; ++i) {
-        const int c = threadIdx.x + NT * i;
-        const int r2 = (c % (GPB / 2)) * 2;
-        const int line = c / (GPB / 2);
-        const float2 a = store_round_a<SK>(tile[tile_pos<R, GPB>(line, r2)]);
-        const float2 b = store_round_a<SK>(tile[tile_pos<R, GPB>(line, r2 + 1)]);
-        st_stream4(base + (size_t)pl * PLA + LayoutA<R>::at(line, y0 + r2), make_float4(a.x, a.y, b.x, b.y));
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Pass 1 on real-valued fields (hbx_simulate_real / hbx_propagate_real, ABI v15)
-// ---------------------------------------------------------------------------
-// values[env][CH][N][N] f32: lane t of a row's group loads pixel x = t + R jj of planes pa, pb
-// straight into the (re, im) of v[jj] -- one coalesced 4 R-byte run per lane group and jj,
-// read once (non-temporal) -- and from there on the code is k_rowfwd's / k_rowfwd32's: row
-// FFT, Hermitian split, LDS tile, panel stores.  Full propagations only (no flip, no action
-// decode, no pair step, no walk phase), f32 intermediates only.
-// One row block per workgroup: the samples land in v itself, so a prefetch of the next row
-// block would be a second v (64 VGPRs at N = 1024), which does not fit three workgroups per
-// CU; the co-resident workgroups cover each other's loads instead (DESIGN.md 4).  This is the
-// bit kernels' RIT = 1 form with another load, at every launch size (no small / large switch).
-template <int R>
-__device__ __forceinline__ void real_load_row(pk2 (&v)[R], const float* __restrict__ rowa, size_t plane, int t) {
-  const float* rowb = rowa + plane;
-  float a[R], b[R];
-#pragma unroll
-  for (int jj = 0; jj < R; ++jj) a[jj] = __builtin_nontemporal_load(rowa + t + R * jj);
-#pragma unroll
-  for (int jj = 0; jj < R; ++jj) b[jj] = __builtin_nontemporal_load(rowb + t + R * jj);
-#pragma unroll
-  for (int jj = 0; jj < R; ++jj) v[jj] = (pk2){a[jj], b[jj]};
-}
-
+// float2 of LDS a row block of NT threads needs at N = R^2: the groups' padded FFT scratch, which
+// the tile of both planes then reuses
 template <int R, int NT>
-__global__ __launch_bounds__(NT, 512 / NT) void k_rowfwd_real(const JobDesc* __restrict__ jobs,
-                                                        const float* __restrict__ values,
-                                                        float2* __restrict__ ws_a,
-                                                        const float2* __restrict__ tw_glob, int P, int CH) {
+constexpr int rowfwd_scratch() {
+  static_assert(R * R * (NT / R) <= (NT / R) * R * (R + 1), "tile must fit in the scratch area");
+  return (NT / R) * R * (R + 1);
+}
+
+// The N = 64 / 256 row block from "v holds the samples of row y0 + grp in planes pa (re), pb (im),
+// lane t pixel x = t + R jj" to its panels stored: base = A plane pa of the job, lds the
+// rowfwd_scratch float2, tw the staged twiddles.  Starts on the group's own scratch: the caller
+// has seen every group leave the previous row block's tile.
+template <int R, int NT, int SK>
+__device__ __forceinline__ void rowfwd_emit(pk2 (&v)[R], int t, int grp, int lane_base, int y0, float2* lds,
+                                            const float2* tw, float2* __restrict__ base) {
   constexpr int N = R * R;
   constexpr int GPB = NT / R;          // rows per row block
-  constexpr int SCR = GPB * R * (R + 1);
-  static_assert(N * GPB <= SCR, "tile must fit in the scratch area");
-  __shared__ float2 tw[N];
-  __shared__ __attribute__((aligned(16))) float2 lds[SCR];
-
-  for (int i = threadIdx.x; i < N; i += NT) tw[i] = tw_glob[i];
-
-  const int grp = threadIdx.x / R;
-  const int t = threadIdx.x % R;
-  const int lane_base = (threadIdx.x & 63) - t;
-  constexpr int RB = N / GPB;
-  int bid = xcd_pair<RB>(blockIdx.x);
-  const int rbw = bid % RB;
-  bid /= RB;
-  const int npair = P / 2;
-  const int j = bid / npair;
-  const JobDesc jb = jobs[j];
-  if (jb.env < 0) return;  // uniform per block
-  const int pa = 2 * (bid % npair);
-  const int y0 = rbw * GPB;
-  const int y = y0 + grp;
-  pk2 v[R];
-  real_load_row<R>(v, values + (((size_t)jb.env * CH + jb.group * P + pa) * N + y) * N, (size_t)N * N, t);
-  __syncthreads();  // tw visible
-
   constexpr size_t PLA = plane_a_elems(R);
-  float2* base = ws_a + ((size_t)j * P + pa) * PLA;
   fft_group<R, false>(v, t, PaddedScratch<R>{lds + grp * R * (R + 1)}, tw);
   lds_barrier();    // every group is done with its scratch: reuse as the tile
 
@@ -489,7 +190,13 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowfwd_real(const JobDesc* __r
     const int r2 = (c % (GPB / 2)) * 2;
     const int line = c / (GPB / 2);  // pl * N/2 + kx : A planes pa, pb are adjacent
     float2 a, b;
-    if constexpr (GPB == 16) {   // one ds_read_b128 per chunk, as k_rowfwd
+    if constexpr (GPB == 16) {
+      // (r05) rows r2, r2 + 1 sit in one aligned 16-B pair (the swizzle XORs whole pairs, its
+      // bit 0 swaps the halves): one ds_read_b128 from a single lane base (the swizzle keys on
+      // bits 0-4 of the line, which the chunk rounds i leave alone), conflict-free in the
+      // 4 x 16-lane model; the two ds_read_b64 it replaces were 2-way (0.79 M extra LDS cycles
+      // per 128-job launch at N = 256, profiles/r05/prof_mono_r05t); time unchanged (0.0587-0.0589
+      // vs 0.0587-0.0588 ms, profiles/r05/rowfwd16_ab_r05u.txt)
       const int p0 = tile_pos<R, GPB>(line, r2);
       const float4 ab = *reinterpret_cast<const float4*>(tile + (p0 & ~1));
       const bool sw = (p0 & 1) != 0;
@@ -499,46 +206,126 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowfwd_real(const JobDesc* __r
       a = tile[tile_pos<R, GPB>(line, r2)];
       b = tile[tile_pos<R, GPB>(line, r2 + 1)];
     }
+    a = store_round_a<SK>(a);
+    b = store_round_a<SK>(b);
     const int pl = line / (N / 2);
+    // panel layout: (line, y0 + r2) of plane pl -> contiguous 16-B chunks of the panel
     st_stream4(base + (size_t)pl * PLA + LayoutA<R>::at(line - pl * (N / 2), y0 + r2),
                make_float4(a.x, a.y, b.x, b.y));
   }
 }
 
-// N = 1024: k_rowfwd32's three workgroups per CU (split FFT tiles, one plane's tile at a time)
-__global__ __launch_bounds__(256, 3) void k_rowfwd32_real(const JobDesc* __restrict__ jobs,
-                                                          const float* __restrict__ values,
-                                                          float2* __restrict__ ws_a,
-                                                          const float2* __restrict__ tw_glob, int P, int CH) {
-  constexpr int R = 32, NT = 256, N = R * R;
-  constexpr int GPB = NT / R;          // 8 rows per row block
-  constexpr int SCRF = GPB * R * (R + 1);               // floats: 8 FFT tiles
-  static_assert((N / 2) * GPB * 2 <= SCRF, "one plane's tile must fit in the FFT tiles");
+template <int R, int NT, int SK, int RIT = rowfwd_iters<R>()>
+__global__ __launch_bounds__(NT, 512 / NT) void k_rowfwd(const JobDesc* jobs,
+                                                   const uint32_t* __restrict__ mask,
+                                                   float2* __restrict__ ws_a,
+                                                   const float2* __restrict__ tw_glob, int P,
+                                                   int CH, float va, float vb, int pair_step,
+                                                   const int64_t* __restrict__ actions, int32_t* err,
+                                                   const uint8_t* __restrict__ phase) {
+  constexpr int N = R * R;
+  constexpr int GPB = NT / R;          // rows per row block
+  constexpr int WPR = N / 32;           // 32-bit mask words per row
   __shared__ float2 tw[N];
-  __shared__ __attribute__((aligned(16))) float lds[SCRF];
+  __shared__ __attribute__((aligned(16))) float2 lds[rowfwd_scratch<R, NT>()];
 
-  for (int i = threadIdx.x; i < N; i += NT) tw[i] = tw_glob[i];
+  stage_twiddles<N, NT>(tw, tw_glob);
 
   const int grp = threadIdx.x / R;
   const int t = threadIdx.x % R;
-  const int k1 = mirror_k1(t);         // the second FFT stage in mirror-paired lane order
+  const int lane_base = (threadIdx.x & 63) - t;
   constexpr int RB = N / GPB;
-  int bid = xcd_pair<RB>(blockIdx.x);
-  const int rbw = bid % RB;
-  bid /= RB;
-  const int npair = P / 2;
-  const int j = bid / npair;
-  const JobDesc jb = jobs[j];
-  if (jb.env < 0) return;  // uniform per block
-  const int pa = 2 * (bid % npair);
-  const int y0 = rbw * GPB;
-  const int y = y0 + grp;
-  pk2 v[R];
-  real_load_row<R>(v, values + (((size_t)jb.env * CH + jb.group * P + pa) * N + y) * N, (size_t)N * N, t);
+  constexpr int RBW = RB / RIT;        // workgroups per plane pair
+  // plane-cached step: only the flipped plane's pair
+  const FirstPassBlock wg = first_pass_block<RBW>(RIT == 1 ? xcd_pair<RB>(blockIdx.x) : (int)blockIdx.x,
+                                                  pair_step ? 1 : P / 2);
+  const int rbw = wg.rbw, j = wg.j;
+  const JobDesc jb = first_pass_job(jobs, actions, err, j, wg.writer, (int64_t)N * N, P, CH);
+  if (jb.env < 0 || (phase && phase[j])) return;  // uniform per block (a walk slot whose A / B are kept)
+  const int q = pair_step ? (jb.flip_plane >> 1) : wg.q;
+  const int pa = 2 * q, pb = 2 * q + 1;
+  const uint32_t* plane_a = mask + ((size_t)jb.env * CH + jb.group * P + pa) * N * WPR;
+  uint32_t wa[WPR], wb[WPR];
+  auto load_row = [&](int y) {
+    const uint32_t* rowa = plane_a + (size_t)y * WPR;
+    const uint32_t* rowb = rowa + (size_t)N * WPR;
+    if constexpr (WPR % 4 == 0) {
+#pragma unroll
+      for (int i = 0; i < WPR / 4; ++i) {
+        const uint4 a = reinterpret_cast<const uint4*>(rowa)[i];
+        const uint4 b = reinterpret_cast<const uint4*>(rowb)[i];
+        wa[4 * i] = a.x; wa[4 * i + 1] = a.y; wa[4 * i + 2] = a.z; wa[4 * i + 3] = a.w;
+        wb[4 * i] = b.x; wb[4 * i + 1] = b.y; wb[4 * i + 2] = b.z; wb[4 * i + 3] = b.w;
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < WPR; ++i) { wa[i] = rowa[i]; wb[i] = rowb[i]; }
+    }
+  };
+  load_row(rbw * RIT * GPB + grp);
   __syncthreads();  // tw visible
 
+  float2* base = ws_a + ((size_t)j * P + pa) * plane_a_elems(R);
+  // RIT = 1: the loop condition is a constant and there is no loop.  Out of a loop of one row
+  // block the compiler lifts rowfwd_emit's tile and panel addresses above the FFT (N = 256:
+  // 84 VGPRs for 61, the small launch 1-3 % slower, profiles/rowfwd_dedup/small_launch_time.txt)
+  int it = 0;
+#pragma unroll 1
+  do {
+    const int y0 = (rbw * RIT + it) * GPB;
+    const int y = y0 + grp;
+    if (jb.flip_plane >= 0 && jb.flip_pix / N == y) {  // env.py:164 flip, on the fly
+      const int col = jb.flip_pix % N;
+      const uint32_t bit = 1u << (col & 31);
+#pragma unroll
+      for (int i = 0; i < WPR; ++i) {
+        if (i == (col >> 5)) {
+          if (jb.flip_plane == pa) wa[i] ^= bit;
+          if (jb.flip_plane == pb) wb[i] ^= bit;
+        }
+      }
+    }
+    pk2 v[R];
+    with_field_kind(va, vb, [&](auto fk) {
+#pragma unroll
+      for (int jj = 0; jj < R; ++jj) {
+        const int w = (R * jj) >> 5;
+        const int sh = ((R * jj) & 31) + t;
+        v[jj] = (pk2){bit_value<fk()>(wa[w], sh, va, vb), bit_value<fk()>(wb[w], sh, va, vb)};
+      }
+    });
+    if constexpr (RIT > 1) {
+      // next rows' words (the last iteration re-reads its own row: no conditional load)
+      load_row(it + 1 < RIT ? y + GPB : y);
+      if (it > 0) lds_barrier();   // every group has read the previous tile: scratch reusable
+    }
+    rowfwd_emit<R, NT, SK>(v, t, grp, lane_base, y0, lds, tw, base);
+  } while (RIT > 1 && ++it < RIT);
+}
+
+// k_rowfwd at N = 1024 with three workgroups per CU (the wide kernel above: 216 VGPRs,
+// 75.8 KB LDS, two).  The pass is bound by how many row blocks' stores a CU keeps in
+// flight, not by its arithmetic (the whole launch is ~75 us of VALU issue), so:
+//  * lane t loads ONE mask word of its row per plane (word t) and a 32 x 32 bit
+//    transpose across the group (five ds_swizzle levels) hands it bit t of every
+//    word -- the 64 VGPRs of whole-row words the wide kernel keeps for its prefetch
+//    are two here;
+//  * the FFT transposes real and imaginary parts through a 4.2-KB float tile per
+//    group (fft_group_split), and the Hermitian split goes out one plane at a time
+//    through a 32-KB tile that aliases those FFT tiles: 8 KB twiddles + 33.8 KB.
+// Same arithmetic as k_rowfwd, so the A it writes is bit-identical.
+constexpr int kRowfwd32Scr = 8 * 32 * (32 + 1);          // floats: 8 FFT tiles
+static_assert((1024 / 2) * 8 * 2 <= kRowfwd32Scr, "one plane's tile must fit in the FFT tiles");
+
+// The N = 1024 row block from "v holds the samples of row y0 + grp in planes pa (re), pb (im), lane
+// t pixel x = t + 32 jj" to its two panels stored: base = A plane pa of the job, lds the
+// kRowfwd32Scr floats, tw the staged twiddles; k1 = mirror_k1(t).  Starts on the group's own FFT
+// tile: the caller has seen every group leave the previous row block's tile.
+template <int SK>
+__device__ __forceinline__ void rowfwd32_emit(pk2 (&v)[32], int t, int k1, int grp, int y0, float* lds,
+                                              const float2* tw, float2* __restrict__ base) {
+  constexpr int R = 32, NT = 256, N = R * R, GPB = NT / R;
   constexpr size_t PLA = plane_a_elems(R);
-  float2* base = ws_a + ((size_t)j * P + pa) * PLA;
   float2* tile = reinterpret_cast<float2*>(lds);
   // lane t now holds Z[k1 + 32 k2] (k1 = mirror_k1(t)): the mirror partner is lane t ^ 1
   fft_group_split_mirror<false>(v, t, k1, lds + grp * R * (R + 1), tw);
@@ -574,11 +361,157 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd32_real(const JobDesc* __restr
       const int c = threadIdx.x + NT * i;
       const int r2 = (c % (GPB / 2)) * 2;
       const int line = c / (GPB / 2);
-      const float2 a = tile[tile_pos<R, GPB>(line, r2)];
-      const float2 b = tile[tile_pos<R, GPB>(line, r2 + 1)];
+      const float2 a = store_round_a<SK>(tile[tile_pos<R, GPB>(line, r2)]);
+      const float2 b = store_round_a<SK>(tile[tile_pos<R, GPB>(line, r2 + 1)]);
       st_stream4(base + (size_t)pl * PLA + LayoutA<R>::at(line, y0 + r2), make_float4(a.x, a.y, b.x, b.y));
     }
   }
+}
+
+template <int SK, int RIT = rowfwd_iters<32>()>
+__global__ __launch_bounds__(256, 3) void k_rowfwd32(const JobDesc* jobs,
+                                                     const uint32_t* __restrict__ mask,
+                                                     float2* __restrict__ ws_a,
+                                                     const float2* __restrict__ tw_glob, int P, int CH,
+                                                     float va, float vb, int pair_step,
+                                                     const int64_t* __restrict__ actions, int32_t* err,
+                                                     const uint8_t* __restrict__ phase) {
+  constexpr int R = 32, NT = 256, N = R * R;
+  constexpr int GPB = NT / R;          // 8 rows per row block
+  constexpr int WPR = N / 32;          // 32 mask words per row = one per lane
+  __shared__ float2 tw[N];
+  __shared__ __attribute__((aligned(16))) float lds[kRowfwd32Scr];
+
+  stage_twiddles<N, NT>(tw, tw_glob);
+
+  const int grp = threadIdx.x / R;
+  const int t = threadIdx.x % R;
+  const int k1 = mirror_k1(t);         // r05: the second FFT stage in mirror-paired lane order
+  constexpr int RB = N / GPB;
+  constexpr int RBW = RB / RIT;
+  // first_pass_block written out: with the helper the pair index is formed ahead of the job load,
+  // and the 12-job launch of k_rowfwd32<SK, 1> measured 95.1-97.1 us for 91.7-93.5
+  // (profiles/rowfwd_dedup/small_launch_time.txt); this order measured 93.2-93.6
+  int bid = RIT == 1 ? xcd_pair<RB>(blockIdx.x) : (int)blockIdx.x;
+  const int rbw = bid % RBW;
+  bid /= RBW;
+  const int npair = pair_step ? 1 : P / 2;   // plane-cached step: only the flipped plane's pair
+  const int j = bid / npair;
+  const JobDesc jb = first_pass_job(jobs, actions, err, j, rbw == 0 && bid % npair == 0, (int64_t)N * N, P, CH);
+  if (jb.env < 0 || (phase && phase[j])) return;  // uniform per block (a walk slot whose A / B are kept)
+  const int q = pair_step ? (jb.flip_plane >> 1) : bid % npair;
+  const int pa = 2 * q, pb = 2 * q + 1;
+  const uint32_t* plane_a = mask + ((size_t)jb.env * CH + jb.group * P + pa) * N * WPR;
+  uint32_t wa, wb;
+  auto load_row = [&](int y) {
+    wa = plane_a[(size_t)y * WPR + t];
+    wb = plane_a[(size_t)(N + y) * WPR + t];
+  };
+  load_row(rbw * RIT * GPB + grp);
+  __syncthreads();  // tw visible
+
+  float2* base = ws_a + ((size_t)j * P + pa) * plane_a_elems(R);
+  int it = 0;   // (RIT = 1: no loop, as k_rowfwd)
+#pragma unroll 1
+  do {
+    const int y0 = (rbw * RIT + it) * GPB;
+    const int y = y0 + grp;
+    // bit r of ta / tb = pixel x = t + 32 r of the row
+    uint32_t ta = group_bit_transpose(wa, t);
+    uint32_t tb = group_bit_transpose(wb, t);
+    if (jb.flip_plane >= 0 && jb.flip_pix / N == y) {  // env.py:164 flip, on the fly
+      const int col = jb.flip_pix % N;
+      if (t == (col & 31)) {
+        if (jb.flip_plane == pa) ta ^= 1u << (col >> 5);
+        if (jb.flip_plane == pb) tb ^= 1u << (col >> 5);
+      }
+    }
+    pk2 v[R];
+    with_field_kind(va, vb, [&](auto fk) {
+#pragma unroll
+      for (int jj = 0; jj < R; ++jj)
+        v[jj] = (pk2){bit_value<fk()>(ta, jj, va, vb), bit_value<fk()>(tb, jj, va, vb)};
+    });
+    if constexpr (RIT > 1) {
+      // next rows' words (the last iteration re-reads its own row: no conditional load)
+      load_row(it + 1 < RIT ? y + GPB : y);
+      if (it > 0) lds_barrier();   // every group has read the previous plane-b tile
+    }
+    rowfwd32_emit<SK>(v, t, k1, grp, y0, lds, tw, base);
+  } while (RIT > 1 && ++it < RIT);
+}
+
+// ---------------------------------------------------------------------------
+// Pass 1 on real-valued fields (hbx_simulate_real / hbx_propagate_real, ABI v15)
+// ---------------------------------------------------------------------------
+// values[env][CH][N][N] f32: real_load_row (hbx_rowcol.hpp) puts the samples of the row in planes
+// pa, pb straight into the (re, im) of v, and rowfwd_emit / rowfwd32_emit -- the bit kernels' own
+// row FFT, split, LDS tile and panel stores -- take it from there.  Full propagations
+// only (no flip, no action decode, no pair step, no walk phase), f32 intermediates only.
+// One row block per workgroup: the samples land in v itself, so a prefetch of the next row
+// block would be a second v (64 VGPRs at N = 1024), which does not fit three workgroups per
+// CU; the co-resident workgroups cover each other's loads instead (DESIGN.md 4).  This is the
+// bit kernels' RIT = 1 form with another load, at every launch size (no small / large switch).
+template <int R, int NT>
+__global__ __launch_bounds__(NT, 512 / NT) void k_rowfwd_real(const JobDesc* __restrict__ jobs,
+                                                        const float* __restrict__ values,
+                                                        float2* __restrict__ ws_a,
+                                                        const float2* __restrict__ tw_glob, int P, int CH) {
+  constexpr int N = R * R;
+  constexpr int GPB = NT / R;          // rows per row block
+  __shared__ float2 tw[N];
+  __shared__ __attribute__((aligned(16))) float2 lds[rowfwd_scratch<R, NT>()];
+
+  stage_twiddles<N, NT>(tw, tw_glob);
+
+  const int grp = threadIdx.x / R;
+  const int t = threadIdx.x % R;
+  const int lane_base = (threadIdx.x & 63) - t;
+  constexpr int RB = N / GPB;
+  const FirstPassBlock wg = first_pass_block<RB>(xcd_pair<RB>(blockIdx.x), P / 2);
+  const int j = wg.j;
+  const JobDesc jb = jobs[j];
+  if (jb.env < 0) return;  // uniform per block
+  const int pa = 2 * wg.q;
+  const int y0 = wg.rbw * GPB;
+  const int y = y0 + grp;
+  pk2 v[R];
+  real_load_row<R>(v, values + (((size_t)jb.env * CH + jb.group * P + pa) * N + y) * N, (size_t)N * N, t);
+  __syncthreads();  // tw visible
+
+  float2* base = ws_a + ((size_t)j * P + pa) * plane_a_elems(R);
+  rowfwd_emit<R, NT, HBX_PRECISION_F32>(v, t, grp, lane_base, y0, lds, tw, base);
+}
+
+// N = 1024: k_rowfwd32's three workgroups per CU (split FFT tiles, one plane's tile at a time)
+__global__ __launch_bounds__(256, 3) void k_rowfwd32_real(const JobDesc* __restrict__ jobs,
+                                                          const float* __restrict__ values,
+                                                          float2* __restrict__ ws_a,
+                                                          const float2* __restrict__ tw_glob, int P, int CH) {
+  constexpr int R = 32, NT = 256, N = R * R;
+  constexpr int GPB = NT / R;          // 8 rows per row block
+  __shared__ float2 tw[N];
+  __shared__ __attribute__((aligned(16))) float lds[kRowfwd32Scr];
+
+  stage_twiddles<N, NT>(tw, tw_glob);
+
+  const int grp = threadIdx.x / R;
+  const int t = threadIdx.x % R;
+  const int k1 = mirror_k1(t);         // the second FFT stage in mirror-paired lane order
+  constexpr int RB = N / GPB;
+  const FirstPassBlock wg = first_pass_block<RB>(xcd_pair<RB>(blockIdx.x), P / 2);
+  const int j = wg.j;
+  const JobDesc jb = jobs[j];
+  if (jb.env < 0) return;  // uniform per block
+  const int pa = 2 * wg.q;
+  const int y0 = wg.rbw * GPB;
+  const int y = y0 + grp;
+  pk2 v[R];
+  real_load_row<R>(v, values + (((size_t)jb.env * CH + jb.group * P + pa) * N + y) * N, (size_t)N * N, t);
+  __syncthreads();  // tw visible
+
+  float2* base = ws_a + ((size_t)j * P + pa) * plane_a_elems(R);
+  rowfwd32_emit<HBX_PRECISION_F32>(v, t, k1, grp, y0, lds, tw, base);
 }
 
 // ---------------------------------------------------------------------------

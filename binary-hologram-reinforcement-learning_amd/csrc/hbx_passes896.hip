@@ -11,6 +11,8 @@
 //                per row pair (plane a real, plane b imaginary) -> Hermitian
 //                split -> half spectrum kx < 448 (Nyquist in Im of kx = 0) ->
 //                LDS tile transpose -> A[kx][y0..y0+8)   [read N^2/8, write 4 N^2 B per plane]
+//                (k_rowfwd896_real reads f32 samples instead of bits; everything after the
+//                load is rowfwd896_emit, called by both)
 //   k_col896     one lane group per half-spectrum line kx: FFT over y ->
 //                x H and x conj H (H even in fx and ky) -> two IFFTs -> B lines
 //                kx and N - kx (448 for kx = 0)           [read 4 N^2, write 8 N^2]
@@ -93,161 +95,15 @@ __device__ __forceinline__ int tile896_pos(int kx, int r) {
 constexpr int kRit896 = 8;
 static_assert(kRB % kRit896 == 0, "row-block walk");
 
-__global__ __launch_bounds__(256, 3) void k_rowfwd896(const JobDesc* __restrict__ jobs,
-                                                      const uint32_t* __restrict__ mask,
-                                                      float2* __restrict__ ws_a,
-                                                      const float2* __restrict__ tw_glob, int P, int CH,
-                                                      float va, float vb, int pair_step) {
-  constexpr int SCRF = kGPB * kR * (kR + 1);      // floats: 8 FFT tiles (33.8 KB)
-  static_assert(kHalf * kGPB * 2 <= SCRF, "one plane's tile must fit in the FFT tiles");
-  constexpr int RBW = kRB / kRit896;
-  __shared__ float2 tw[kN];
-  __shared__ __attribute__((aligned(16))) float lds[SCRF];
-  for (int i = threadIdx.x; i < kN; i += 256) tw[i] = tw_glob[i];
+constexpr int kRowfwd896Scr = kGPB * kR * (kR + 1);      // floats: 8 FFT tiles (33.8 KB)
+static_assert(kHalf * kGPB * 2 <= kRowfwd896Scr, "one plane's tile must fit in the FFT tiles");
 
-  const int grp = threadIdx.x / kR;
-  const int t = threadIdx.x % kR;
-  const int lane_base = (threadIdx.x & 63) - t;
-  int bid = blockIdx.x;
-  const int rbw = bid % RBW;
-  bid /= RBW;
-  const int npair = pair_step ? 1 : P / 2;   // (r06) plane-cached step: only the flipped plane's pair
-  const int j = bid / npair;
-  const JobDesc jb = jobs[j];
-  if (jb.env < 0) return;  // uniform per block
-  const int q = pair_step ? (jb.flip_plane >> 1) : bid % npair;
-  const int pa = 2 * q, pb = 2 * q + 1;
-  const uint32_t* plane_a = mask + ((size_t)jb.env * CH + jb.group * P + pa) * kN * kWPR;
-  const int wt = t < kWPR ? t : kWPR - 1;
-  uint32_t wa, wb;
-  auto load_row = [&](int y) {
-    wa = plane_a[(size_t)y * kWPR + wt];
-    wb = plane_a[(size_t)(kN + y) * kWPR + wt];
-  };
-  load_row(rbw * kRit896 * kGPB + grp);
-  __syncthreads();  // tw visible
-
-  float2* base = ws_a + ((size_t)j * P + pa) * kPlaneA;
-  float2* tile = reinterpret_cast<float2*>(lds);
-  constexpr int CHUNKS = kHalf * kGPB / 2;      // 16-B chunks of one plane's panel (1792)
-  static_assert(CHUNKS % 256 == 0, "chunking");
-#pragma unroll 1
-  for (int it = 0; it < kRit896; ++it) {
-    const int y0 = (rbw * kRit896 + it) * kGPB;
-    const int y = y0 + grp;
-    uint32_t ta = group_bit_transpose(wa, t);   // bit r = pixel x = t + 32 r of the row
-    uint32_t tb = group_bit_transpose(wb, t);
-    if (jb.flip_plane >= 0 && jb.flip_pix / kN == y) {  // env.py:164 flip, on the fly
-      const int col = jb.flip_pix % kN;
-      if (t == (col & 31)) {
-        if (jb.flip_plane == pa) ta ^= 1u << (col >> 5);
-        if (jb.flip_plane == pb) tb ^= 1u << (col >> 5);
-      }
-    }
-    float2 v[32];
-    with_field_kind(va, vb, [&](auto fk) {
-#pragma unroll
-      for (int jj = 0; jj < kL; ++jj)
-        v[jj] = make_float2(bit_value<fk()>(ta, jj, va, vb), bit_value<fk()>(tb, jj, va, vb));
-    });
-#pragma unroll
-    for (int jj = kL; jj < 32; ++jj) v[jj] = make_float2(0.f, 0.f);
-    // next rows' words (the last iteration re-reads its own row: no conditional load)
-    load_row(it + 1 < kRit896 ? y + kGPB : y);
-    if (it > 0) lds_barrier();   // every group has read the previous plane-b tile
-    fft896_ns_split<false>(v, t, lds + grp * kR * (kR + 1), tw);
-
-    // Hermitian split of the slot-layout spectrum (kx = t + 28 k2 < 448: k2 < 16): plane a
-    // now, plane b kept in registers for the second tile
-    float2 fb[16];
-    lds_barrier();    // every group is done with its FFT tile: reuse as the plane tile
-    const float2 zny = v[16];  // Z[448] on lane 0
-#pragma unroll
-    for (int k2 = 0; k2 < 16; ++k2) {
-      const float2 z = v[k2];
-      const float2 m = mirror_conj896(v, k2, t, lane_base);
-      float2 fa = make_float2(z.x + m.x, z.y + m.y);       // 2 A (htab holds H / 2)
-      fb[k2] = make_float2(z.y - m.y, m.x - z.x);
-      if (k2 == 0 && t == 0) {  // DC and Nyquist of a real row are real
-        fa = make_float2(z.x + z.x, zny.x + zny.x);
-        fb[k2] = make_float2(z.y + z.y, zny.y + zny.y);
-      }
-      if (t < kL) tile[tile896_pos(t + kL * k2, grp)] = fa;
-    }
-#pragma unroll
-    for (int pl = 0; pl < 2; ++pl) {
-      if (pl == 1) {
-        lds_barrier();   // plane a's tile has been read
-#pragma unroll
-        for (int k2 = 0; k2 < 16; ++k2)
-          if (t < kL) tile[tile896_pos(t + kL * k2, grp)] = fb[k2];
-      }
-      lds_barrier();
-      float2* panel = base + (size_t)pl * kPlaneA + a896_at(0, y0);
-#pragma unroll
-      for (int i = 0; i < CHUNKS / 256; ++i) {
-        const int c = threadIdx.x + 256 * i;
-        const int r2 = (c % (kGPB / 2)) * 2;
-        const int line = c / (kGPB / 2);
-        // rows r2, r2 + 1 of the line sit in one aligned 16-B pair (the XOR swizzle permutes whole
-        // pairs; its bit 0 swaps the two halves): one ds_read_b128, whose 16-lane groups cover
-        // four whole lines -- conflict-free for any swizzle inside a line (r05; two ds_read_b64
-        // cost 16 extra LDS cycles per 56 reads, 1.8 M per 128-job launch)
-        const int p0 = tile896_pos(line, r2);
-        const float4 ab = *reinterpret_cast<const float4*>(tile + (p0 & ~1));
-        const bool sw = (p0 & 1) != 0;
-        st_stream4(panel + 2 * c, sw ? make_float4(ab.z, ab.w, ab.x, ab.y) : ab);   // = a896_at(line, y0 + r2)
-      }
-    }
-  }
-}
-
-// Pass 1 on real-valued fields (hbx_simulate_real / hbx_propagate_real, ABI v15):
-// values[env][CH][896][896] f32.  Lane t loads pixel x = t + 32 jj (jj < 28) of planes pa, pb
-// into the (re, im) of v[jj] (one coalesced 128-B run per lane group and jj, non-temporal);
-// the FFT, the split, the tile and the panel stores are k_rowfwd896's.  One row block per
-// workgroup (no register room for a second row's samples at three workgroups per CU); full
-// propagations only.
-__global__ __launch_bounds__(256, 3) void k_rowfwd896_real(const JobDesc* __restrict__ jobs,
-                                                           const float* __restrict__ values,
-                                                           float2* __restrict__ ws_a,
-                                                           const float2* __restrict__ tw_glob, int P, int CH) {
-  constexpr int SCRF = kGPB * kR * (kR + 1);      // floats: 8 FFT tiles (33.8 KB)
-  static_assert(kHalf * kGPB * 2 <= SCRF, "one plane's tile must fit in the FFT tiles");
-  __shared__ float2 tw[kN];
-  __shared__ __attribute__((aligned(16))) float lds[SCRF];
-  for (int i = threadIdx.x; i < kN; i += 256) tw[i] = tw_glob[i];
-
-  const int grp = threadIdx.x / kR;
-  const int t = threadIdx.x % kR;
-  const int lane_base = (threadIdx.x & 63) - t;
-  int bid = blockIdx.x;
-  const int rbw = bid % kRB;
-  bid /= kRB;
-  const int npair = P / 2;
-  const int j = bid / npair;
-  const JobDesc jb = jobs[j];
-  if (jb.env < 0) return;  // uniform per block
-  const int pa = 2 * (bid % npair);
-  const int y0 = rbw * kGPB;
-  const int y = y0 + grp;
-  const float* rowa = values + (((size_t)jb.env * CH + jb.group * P + pa) * kN + y) * kN + t;
-  const float* rowb = rowa + (size_t)kN * kN;
-  float2 v[32];
-  {
-    float a[kL], b[kL];
-#pragma unroll
-    for (int jj = 0; jj < kL; ++jj) a[jj] = __builtin_nontemporal_load(rowa + kR * jj);
-#pragma unroll
-    for (int jj = 0; jj < kL; ++jj) b[jj] = __builtin_nontemporal_load(rowb + kR * jj);
-#pragma unroll
-    for (int jj = 0; jj < kL; ++jj) v[jj] = make_float2(a[jj], b[jj]);
-  }
-#pragma unroll
-  for (int jj = kL; jj < 32; ++jj) v[jj] = make_float2(0.f, 0.f);
-  __syncthreads();  // tw visible
-
-  float2* base = ws_a + ((size_t)j * P + pa) * kPlaneA;
+// The 896 row block from "v holds the samples of row y0 + grp in planes pa (re), pb (im), lane t
+// pixel x = t + 32 jj, jj < 28, zeros above" to its two panels stored: base = A plane pa of the
+// job, lds the kRowfwd896Scr floats, tw the staged twiddles.  Starts on the group's own FFT tile:
+// the caller has seen every group leave the previous row block's tile.
+__device__ __forceinline__ void rowfwd896_emit(float2 (&v)[32], int t, int grp, int lane_base, int y0, float* lds,
+                                               const float2* tw, float2* __restrict__ base) {
   float2* tile = reinterpret_cast<float2*>(lds);
   constexpr int CHUNKS = kHalf * kGPB / 2;      // 16-B chunks of one plane's panel (1792)
   static_assert(CHUNKS % 256 == 0, "chunking");
@@ -285,12 +141,107 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd896_real(const JobDesc* __rest
       const int c = threadIdx.x + 256 * i;
       const int r2 = (c % (kGPB / 2)) * 2;
       const int line = c / (kGPB / 2);
+      // rows r2, r2 + 1 of the line sit in one aligned 16-B pair (the XOR swizzle permutes whole
+      // pairs; its bit 0 swaps the two halves): one ds_read_b128, whose 16-lane groups cover
+      // four whole lines -- conflict-free for any swizzle inside a line (r05; two ds_read_b64
+      // cost 16 extra LDS cycles per 56 reads, 1.8 M per 128-job launch)
       const int p0 = tile896_pos(line, r2);
       const float4 ab = *reinterpret_cast<const float4*>(tile + (p0 & ~1));
       const bool sw = (p0 & 1) != 0;
       st_stream4(panel + 2 * c, sw ? make_float4(ab.z, ab.w, ab.x, ab.y) : ab);   // = a896_at(line, y0 + r2)
     }
   }
+}
+
+__global__ __launch_bounds__(256, 3) void k_rowfwd896(const JobDesc* __restrict__ jobs,
+                                                      const uint32_t* __restrict__ mask,
+                                                      float2* __restrict__ ws_a,
+                                                      const float2* __restrict__ tw_glob, int P, int CH,
+                                                      float va, float vb, int pair_step) {
+  constexpr int RBW = kRB / kRit896;
+  __shared__ float2 tw[kN];
+  __shared__ __attribute__((aligned(16))) float lds[kRowfwd896Scr];
+  stage_twiddles<kN, 256>(tw, tw_glob);
+
+  const int grp = threadIdx.x / kR;
+  const int t = threadIdx.x % kR;
+  const int lane_base = (threadIdx.x & 63) - t;
+  // (r06) plane-cached step: only the flipped plane's pair
+  const FirstPassBlock wg = first_pass_block<RBW>(blockIdx.x, pair_step ? 1 : P / 2);
+  const int rbw = wg.rbw, j = wg.j;
+  const JobDesc jb = jobs[j];
+  if (jb.env < 0) return;  // uniform per block
+  const int q = pair_step ? (jb.flip_plane >> 1) : wg.q;
+  const int pa = 2 * q, pb = 2 * q + 1;
+  const uint32_t* plane_a = mask + ((size_t)jb.env * CH + jb.group * P + pa) * kN * kWPR;
+  const int wt = t < kWPR ? t : kWPR - 1;
+  uint32_t wa, wb;
+  auto load_row = [&](int y) {
+    wa = plane_a[(size_t)y * kWPR + wt];
+    wb = plane_a[(size_t)(kN + y) * kWPR + wt];
+  };
+  load_row(rbw * kRit896 * kGPB + grp);
+  __syncthreads();  // tw visible
+
+  float2* base = ws_a + ((size_t)j * P + pa) * kPlaneA;
+#pragma unroll 1
+  for (int it = 0; it < kRit896; ++it) {
+    const int y0 = (rbw * kRit896 + it) * kGPB;
+    const int y = y0 + grp;
+    uint32_t ta = group_bit_transpose(wa, t);   // bit r = pixel x = t + 32 r of the row
+    uint32_t tb = group_bit_transpose(wb, t);
+    if (jb.flip_plane >= 0 && jb.flip_pix / kN == y) {  // env.py:164 flip, on the fly
+      const int col = jb.flip_pix % kN;
+      if (t == (col & 31)) {
+        if (jb.flip_plane == pa) ta ^= 1u << (col >> 5);
+        if (jb.flip_plane == pb) tb ^= 1u << (col >> 5);
+      }
+    }
+    float2 v[32];
+    with_field_kind(va, vb, [&](auto fk) {
+#pragma unroll
+      for (int jj = 0; jj < kL; ++jj)
+        v[jj] = make_float2(bit_value<fk()>(ta, jj, va, vb), bit_value<fk()>(tb, jj, va, vb));
+    });
+#pragma unroll
+    for (int jj = kL; jj < 32; ++jj) v[jj] = make_float2(0.f, 0.f);
+    // next rows' words (the last iteration re-reads its own row: no conditional load)
+    load_row(it + 1 < kRit896 ? y + kGPB : y);
+    if (it > 0) lds_barrier();   // every group has read the previous plane-b tile
+    rowfwd896_emit(v, t, grp, lane_base, y0, lds, tw, base);
+  }
+}
+
+// Pass 1 on real-valued fields (hbx_simulate_real / hbx_propagate_real, ABI v15):
+// values[env][CH][896][896] f32.  real_load_row (hbx_rowcol.hpp) puts pixel x = t + 32 jj (jj < 28)
+// of the row in planes pa, pb into the (re, im) of v[jj] and zeros above, and rowfwd896_emit --
+// k_rowfwd896's own FFT, split, tile and panel stores -- takes it from there.  One row block per
+// workgroup (no register room for a second row's samples at three workgroups per CU), in
+// blockIdx order; full propagations only.
+__global__ __launch_bounds__(256, 3) void k_rowfwd896_real(const JobDesc* __restrict__ jobs,
+                                                           const float* __restrict__ values,
+                                                           float2* __restrict__ ws_a,
+                                                           const float2* __restrict__ tw_glob, int P, int CH) {
+  __shared__ float2 tw[kN];
+  __shared__ __attribute__((aligned(16))) float lds[kRowfwd896Scr];
+  stage_twiddles<kN, 256>(tw, tw_glob);
+
+  const int grp = threadIdx.x / kR;
+  const int t = threadIdx.x % kR;
+  const int lane_base = (threadIdx.x & 63) - t;
+  const FirstPassBlock wg = first_pass_block<kRB>(blockIdx.x, P / 2);
+  const int j = wg.j;
+  const JobDesc jb = jobs[j];
+  if (jb.env < 0) return;  // uniform per block
+  const int pa = 2 * wg.q;
+  const int y0 = wg.rbw * kGPB;
+  const int y = y0 + grp;
+  float2 v[32];
+  real_load_row<kR, kL>(v, values + (((size_t)jb.env * CH + jb.group * P + pa) * kN + y) * kN, (size_t)kN * kN, t);
+  __syncthreads();  // tw visible
+
+  float2* base = ws_a + ((size_t)j * P + pa) * kPlaneA;
+  rowfwd896_emit(v, t, grp, lane_base, y0, lds, tw, base);
 }
 
 // ---------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 // hbx_rowcol.hpp -- helpers shared by the row / column passes (hbx_passes.hip,
-// hbx_passes896.hip): LDS tile swizzle, XCD-aware row-block order, buffer
-// descriptors of wave-uniform planes.
+// hbx_passes896.hip): LDS tile swizzle, XCD-aware row-block order, the first pass's
+// workgroup decode, twiddle staging and real-field row load, buffer descriptors of
+// wave-uniform planes.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -112,6 +113,45 @@ __device__ __forceinline__ int xcd_pair(int bid) {
   if constexpr (GS > 1 && RB % SPAN == 0)
     return (bid / SPAN) * SPAN + (bid % 8) * GS + (bid / 8) % GS;
   else return bid;
+}
+
+// Where a first-pass workgroup works.  bid counts [job j][plane pair q of npair][rbw of the RBW
+// workgroups that share a plane pair], rbw fastest; the caller passes blockIdx.x, or
+// xcd_pair<RB>(blockIdx.x) where a workgroup is one row block.  writer: the one workgroup of job j
+// that records what the job decoded to (first_pass_job).
+struct FirstPassBlock {
+  int rbw, j, q;
+  bool writer;
+};
+template <int RBW>
+__device__ __forceinline__ FirstPassBlock first_pass_block(int bid, int npair) {
+  const int rbw = bid % RBW;
+  bid /= RBW;
+  return {rbw, bid / npair, bid % npair, rbw == 0 && bid % npair == 0};
+}
+
+// the row FFT's twiddles into LDS (visible after the caller's next block barrier)
+template <int N, int NT>
+__device__ __forceinline__ void stage_twiddles(float2* tw, const float2* __restrict__ tw_glob) {
+  for (int i = threadIdx.x; i < N; i += NT) tw[i] = tw_glob[i];
+}
+
+// Real-valued fields (hbx_simulate_real / hbx_propagate_real): lane t of a row's group loads pixel
+// x = t + R jj, jj < L, of the row at rowa and of the same row one plane further straight into the
+// (re, im) of v[jj] -- one coalesced 4 R-byte run per lane group and jj, read once (non-temporal);
+// v[L ..] = 0 (N = 896: L = 28 of the 32 slots, as the bit kernel).
+template <int R, int L = R, class V>
+__device__ __forceinline__ void real_load_row(V (&v)[R], const float* __restrict__ rowa, size_t plane, int t) {
+  const float* rowb = rowa + plane;
+  float a[L], b[L];
+#pragma unroll
+  for (int jj = 0; jj < L; ++jj) a[jj] = __builtin_nontemporal_load(rowa + t + R * jj);
+#pragma unroll
+  for (int jj = 0; jj < L; ++jj) b[jj] = __builtin_nontemporal_load(rowb + t + R * jj);
+#pragma unroll
+  for (int jj = 0; jj < L; ++jj) v[jj] = V{a[jj], b[jj]};
+#pragma unroll
+  for (int jj = L; jj < R; ++jj) v[jj] = V{0.f, 0.f};
 }
 
 // ---------------------------------------------------------------------------
