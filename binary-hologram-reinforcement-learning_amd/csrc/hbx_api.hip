@@ -505,9 +505,11 @@ int hbx_simulate(hbx_plan_t p, const uint64_t* mask, int32_t n_env, float* field
 }
 
 namespace {
-int check_real_plan(hbx_plan_t p) {
+int check_real_plan(hbx_plan_t p, bool complex_field = false) {
   if (p->pd.store_kind != HBX_PRECISION_F32)
-    return fail(HBX_ERR_UNSUPPORTED, "real-valued fields: HBX_PRECISION_F32 only (the plan stores reduced-precision intermediates)");
+    return fail(HBX_ERR_UNSUPPORTED, complex_field
+        ? "complex fields: HBX_PRECISION_F32 only (the plan stores reduced-precision intermediates)"
+        : "real-valued fields: HBX_PRECISION_F32 only (the plan stores reduced-precision intermediates)");
   return HBX_OK;
 }
 }  // namespace
@@ -534,6 +536,30 @@ int hbx_simulate_real(hbx_plan_t p, const float* values, int32_t n_env, float* f
   HBX_HIP(hipSetDevice(p->device));
   return propagate_full(p, nullptr, nullptr, nullptr, n_env, intensity, nullptr, nullptr, nullptr,
                         reinterpret_cast<float2*>(field), (hipStream_t)stream, nullptr, nullptr, 1, values);
+}
+
+// complex fields: propagate_full's chunk loop with the complex first and last passes (ids are
+// chunk-local, every buffer is offset by the chunk's first env); nothing to finalize or scatter
+int hbx_simulate_complex(hbx_plan_t p, const float* values, int32_t n_env, float* field, float* real_part,
+                         void* stream) {
+  int rc = check_plan(p);
+  if (rc) return rc;
+  if (n_env <= 0) return n_env == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "n_env");
+  if (!values || (!field && !real_part)) return fail(HBX_ERR_INVALID, "null buffer");
+  if ((rc = check_real_plan(p, true))) return rc;
+  HBX_HIP(hipSetDevice(p->device));
+  const PlanDev& pd = p->pd;
+  const int chunk = p->max_jobs / pd.G;
+  const size_t per_env = (size_t)pd.G * (pd.P / 2) * pd.N * pd.N;   // complex planes x pixels
+  for (int i0 = 0; i0 < n_env; i0 += chunk) {
+    const int n = std::min(chunk, n_env - i0);
+    PlanDev pdx = pd;
+    pdx.complex_values = reinterpret_cast<const float2*>(values) + (size_t)i0 * per_env;
+    pdx.complex_field = field ? reinterpret_cast<float2*>(field) + (size_t)i0 * per_env : nullptr;
+    pdx.real_part = real_part ? real_part + (size_t)i0 * per_env : nullptr;
+    HBX_HIP(hbx::run_jobs(pdx, p->full_jobs, n * pd.G, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream));
+  }
+  return HBX_OK;
 }
 
 int hbx_psnr(hbx_plan_t p, const double* chan_stats, int32_t n_env, double* psnr, void* stream) {

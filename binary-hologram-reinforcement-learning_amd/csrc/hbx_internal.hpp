@@ -209,6 +209,14 @@ struct PlanDev {
   // pass reads instead of the mask bits (u = value; va / vb are not applied).  f32 intermediates,
   // no plane cache, no actions, no walk
   const float* real_values = nullptr;
+  // (ABI v15, additive) full propagation of a complex field (hbx_simulate_complex):
+  // [env][G*P/2][N][N] complex64 samples the first pass reads, complex plane q into plane-pair slot
+  // q; the last pass recombines each pair and writes complex_field [env][G*P/2][N][N] complex64
+  // and / or real_part [env][G*P/2][N][N] f32 (at least one non-null) and nothing else: no
+  // intensity, partials or statistics.  f32 intermediates, no plane cache, no actions, no walk
+  const float2* complex_values = nullptr;
+  float2* complex_field = nullptr;
+  float* real_part = nullptr;
 };
 constexpr int kPlanesOff = 0, kPlanesFill = 1, kPlanesStep = 2;
 

@@ -19,7 +19,8 @@
 //             LDS tile transpose -> A panel y0 / GPB       [HBM: read N^2/8 B, write 4 N^2 B per plane]
 //             (k_rowfwd32 at N = 1024.  k_rowfwd_real / k_rowfwd32_real read f32 samples instead of
 //             bits; everything after the load -- FFT, split, tile, panel stores -- is one function
-//             per size class, rowfwd_emit / rowfwd32_emit, called by the bit and the real kernel)
+//             per size class, rowfwd_emit / rowfwd32_emit, called by the bit and the real kernel;
+//             k_rowfwd_cplx / k_rowfwd32_cplx read complex64 samples, one complex plane per plane pair)
 //   k_col2    one lane group per half-spectrum line kx: FFT over y -> x H and
 //             x conj H (H is even in fx and ky) -> two IFFTs -> B lines kx
 //             and N - kx (N/2 for kx = 0); buffer loads / stores with one
@@ -29,6 +30,8 @@
 //             rows y0..y0+GPB (next plane's tile prefetched into registers
 //             behind LDS-only barriers) -> IFFT over kx -> |U|^2 -> plane
 //             mean -> f64 partials of (I*T, I^2, T^2) vs the target row   [read 8 N^2 per plane + 4 N^2]
+//             (complex fields: k_rowinv_d_cplx / k_rowinv_cplx add B planes 2q and i * 2q + 1 on load,
+//             one IFFT per complex plane, and store the field / its real part; nothing else)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -515,6 +518,74 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd32_real(const JobDesc* __restr
 }
 
 // ---------------------------------------------------------------------------
+// Pass 1 on complex fields (hbx_simulate_complex)
+// ---------------------------------------------------------------------------
+// values[env][CH / 2][N][N] complex64: a job's group carries P / 2 complex planes, and complex plane
+// q fills the plane-pair slot q of the workspace.  complex_load_row (hbx_rowcol.hpp) puts the row's
+// samples into v as they are, and the shared tail does what it does for two real planes: the row
+// FFT of u = a + i b, split into the half spectra of a = Re u (A plane 2q) and b = Im u (2q + 1).
+// The real kernels' geometry: one row block per workgroup, wg.q = the complex plane.
+template <int R, int NT>
+__global__ __launch_bounds__(NT, 512 / NT) void k_rowfwd_cplx(const JobDesc* __restrict__ jobs,
+                                                        const float2* __restrict__ values,
+                                                        float2* __restrict__ ws_a,
+                                                        const float2* __restrict__ tw_glob, int P, int CH) {
+  constexpr int N = R * R;
+  constexpr int GPB = NT / R;          // rows per row block
+  __shared__ float2 tw[N];
+  __shared__ __attribute__((aligned(16))) float2 lds[rowfwd_scratch<R, NT>()];
+
+  stage_twiddles<N, NT>(tw, tw_glob);
+
+  const int grp = threadIdx.x / R;
+  const int t = threadIdx.x % R;
+  const int lane_base = (threadIdx.x & 63) - t;
+  constexpr int RB = N / GPB;
+  const FirstPassBlock wg = first_pass_block<RB>(xcd_pair<RB>(blockIdx.x), P / 2);
+  const int j = wg.j;
+  const JobDesc jb = jobs[j];
+  if (jb.env < 0) return;  // uniform per block
+  const int y0 = wg.rbw * GPB;
+  const int y = y0 + grp;
+  pk2 v[R];
+  complex_load_row<R>(v, values + (((size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q) * N + y) * N, t);
+  __syncthreads();  // tw visible
+
+  float2* base = ws_a + ((size_t)j * P + 2 * wg.q) * plane_a_elems(R);
+  rowfwd_emit<R, NT, HBX_PRECISION_F32>(v, t, grp, lane_base, y0, lds, tw, base);
+}
+
+// N = 1024: k_rowfwd32's three workgroups per CU
+__global__ __launch_bounds__(256, 3) void k_rowfwd32_cplx(const JobDesc* __restrict__ jobs,
+                                                          const float2* __restrict__ values,
+                                                          float2* __restrict__ ws_a,
+                                                          const float2* __restrict__ tw_glob, int P, int CH) {
+  constexpr int R = 32, NT = 256, N = R * R;
+  constexpr int GPB = NT / R;          // 8 rows per row block
+  __shared__ float2 tw[N];
+  __shared__ __attribute__((aligned(16))) float lds[kRowfwd32Scr];
+
+  stage_twiddles<N, NT>(tw, tw_glob);
+
+  const int grp = threadIdx.x / R;
+  const int t = threadIdx.x % R;
+  const int k1 = mirror_k1(t);         // the second FFT stage in mirror-paired lane order
+  constexpr int RB = N / GPB;
+  const FirstPassBlock wg = first_pass_block<RB>(xcd_pair<RB>(blockIdx.x), P / 2);
+  const int j = wg.j;
+  const JobDesc jb = jobs[j];
+  if (jb.env < 0) return;  // uniform per block
+  const int y0 = wg.rbw * GPB;
+  const int y = y0 + grp;
+  pk2 v[R];
+  complex_load_row<R>(v, values + (((size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q) * N + y) * N, t);
+  __syncthreads();  // tw visible
+
+  float2* base = ws_a + ((size_t)j * P + 2 * wg.q) * plane_a_elems(R);
+  rowfwd32_emit<HBX_PRECISION_F32>(v, t, k1, grp, y0, lds, tw, base);
+}
+
+// ---------------------------------------------------------------------------
 // Pass 2
 // ---------------------------------------------------------------------------
 // Column pass, one lane group per input line and both of its output lines:
@@ -805,6 +876,32 @@ __device__ __forceinline__ void rowinv_epilogue(float (&acc)[R], int P, int G, c
 // plane's FFT is done (two blocks per CU cover them; a second register set for a plane in
 // flight took one block per CU and measured 1.80 ms against 1.47).  The r02
 // kernel staged every plane through an LDS tile between three block barriers (1.80 ms).
+// Lane bases (bytes from the job's first B plane) of row y for lane t of the row's group; slot s at
+// TileB<R>::at(s, y):
+//   jj < R/2 (and kx = N/2 for t = 0): s = kx = t + R jj -> lo + 16 R jj float2
+//   jj >= R/2 otherwise: s = 3N/2 - kx -> hi - 16 R jj, written hiB + 16 R (R - 1 - jj)
+//   so every offset stays non-negative
+template <int R>
+struct RowinvLanes {
+  static constexpr int N = R * R, TL = 256 / R;
+  static constexpr int JS = 16 * R * 8;             // bytes per jj
+  int lo, hiB, vmid;
+  __device__ __forceinline__ RowinvLanes(int y, int t) {
+    const int yb = (y >> 4) * 16 * N + (y & 15) * TL;
+    const int m = t / TL, u = t % TL;
+    lo = (yb + m * 16 * TL + u) * 8;
+    hiB = (yb + (u ? (3 * N / (2 * TL) - m - 1) * 16 * TL + TL - u : (3 * N / (2 * TL) - m) * 16 * TL) -
+           16 * R * (R - 1)) * 8;
+    vmid = t == 0 ? lo + JS * (R / 2) : hiB + JS * (R / 2 - 1);
+  }
+  // the lane's FFT input jj (kx = t + R jj) of the plane at byte offset po (wave-uniform)
+  __device__ __forceinline__ float2 load(__amdgpu_buffer_rsrc_t rs, int po, int jj) const {
+    const int vo = jj < R / 2 ? lo : (jj == R / 2 ? vmid : hiB);
+    const int so = po + (jj < R / 2 ? JS * jj : (jj == R / 2 ? 0 : JS * (R - 1 - jj)));
+    return buf_ld2s(rs, vo, so);
+  }
+};
+
 template <int R, bool WALK = false, bool LEAN = false>
 __global__ __launch_bounds__(256, 2) void k_rowinv_d(const JobDesc* __restrict__ jobs,
                                                      const float2* __restrict__ ws_b,
@@ -816,7 +913,7 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_d(const JobDesc* __restrict__
                                                      const int32_t* __restrict__ plane_slot, int plane_spares,
                                                      int spare_base, const int32_t* __restrict__ rc_pending,
                                                      float* __restrict__ rc_cache, WalkPlanesArgs wk) {
-  constexpr int N = R * R, GPB = 256 / R, RB = N / GPB, TL = 256 / R;
+  constexpr int N = R * R, GPB = 256 / R, RB = N / GPB;
   static_assert(!WALK || walk_planes_lds_bytes(RB) <= GPB * R * (R + 1) * 8, "the decision's LDS fits the scratch");
   __shared__ float2 tw[N];
   __shared__ float2 scratch[GPB * R * (R + 1)];
@@ -857,25 +954,11 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_d(const JobDesc* __restrict__
   const int y = rb * GPB + grp;
   constexpr int PLB = N * N;                 // float2 per B plane
   const __amdgpu_buffer_rsrc_t rs = plane_rsrc(ws_b + (size_t)j * P * PLB, (unsigned)((size_t)P * PLB * 8));
-  // lane bases (bytes) of this row, slot s at TileB<R>::at(s, y):
-  //   jj < R/2 (and kx = N/2 for t = 0): s = kx = t + R jj -> lo + 16 R jj float2
-  //   jj >= R/2 otherwise: s = 3N/2 - kx -> hi - 16 R jj, written hiB + 16 R (R - 1 - jj)
-  //   so every offset stays non-negative
-  constexpr int JS = 16 * R * 8;             // bytes per jj
-  const int yb = (y >> 4) * 16 * N + (y & 15) * TL;
-  const int m = t / TL, u = t % TL;
-  const int lo = (yb + m * 16 * TL + u) * 8;
-  const int hiB = (yb + (u ? (3 * N / (2 * TL) - m - 1) * 16 * TL + TL - u : (3 * N / (2 * TL) - m) * 16 * TL) -
-                   16 * R * (R - 1)) * 8;
-  const int vmid = t == 0 ? lo + JS * (R / 2) : hiB + JS * (R / 2 - 1);
+  const RowinvLanes<R> ln(y, t);
   auto load_plane = [&](pk2 (&v)[R], int p) {
     const int po = p * PLB * 8;
 #pragma unroll
-    for (int jj = 0; jj < R; ++jj) {
-      const int vo = jj < R / 2 ? lo : (jj == R / 2 ? vmid : hiB);
-      const int so = po + (jj < R / 2 ? JS * jj : (jj == R / 2 ? 0 : JS * (R - 1 - jj)));
-      v[jj] = to_pk(buf_ld2s(rs, vo, so));
-    }
+    for (int jj = 0; jj < R; ++jj) v[jj] = to_pk(ln.load(rs, po, jj));
   };
   float acc[R];
 #pragma unroll
@@ -1066,6 +1149,172 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv(const JobDesc* __restri
 }
 
 // ---------------------------------------------------------------------------
+// Pass 3 on complex fields (hbx_simulate_complex): recombine a plane pair
+// ---------------------------------------------------------------------------
+// After k_col2, B planes 2q and 2q + 1 of a job hold the column-pass output of a = Re u_q and
+// b = Im u_q, and the propagated plane is F_q = F[a] + i F[b].  The inverse row FFT is linear, so
+// the pair is combined on load, v = B[2q] + i B[2q + 1], and ONE inverse FFT per complex plane gives
+// F_q, stored once: 8 N^2 bytes to field and / or 4 N^2 bytes of Re F_q to real_part (both
+// [env][CH / 2][N][N], either nullable).  No |.|^2, partials, plane cache or reconcile.
+//
+// N = 1024 / 256: k_rowinv_d's direct loads from the tiled B (RowinvLanes).
+// Plane 2q + 1 arrives in two halves of R / 2 values that are folded into v as they land, so the
+// kernel never holds two whole lines (the second register set that cost k_rowinv_d its second
+// block per CU).  N = 256 has the registers for a second line and keeps the next pair in flight
+// under this one's FFT, as k_rowinv_d does with the next plane.
+template <int R>
+__global__ __launch_bounds__(256, 2) void k_rowinv_d_cplx(const JobDesc* __restrict__ jobs,
+                                                          const float2* __restrict__ ws_b,
+                                                          const float2* __restrict__ tw_glob, int P, int G,
+                                                          float2* __restrict__ field_out,
+                                                          float* __restrict__ real_out) {
+  constexpr int N = R * R, GPB = 256 / R, RB = N / GPB;
+  __shared__ float2 tw[N];
+  __shared__ float2 scratch[GPB * R * (R + 1)];
+  for (int i = threadIdx.x; i < N; i += 256) tw[i] = tw_glob[i];
+
+  const int grp = threadIdx.x / R;
+  const int t = threadIdx.x % R;
+  const int bid = xcd_pair<RB>(blockIdx.x);
+  const int rb = bid % RB;
+  const int j = bid / RB;
+  const JobDesc jb = jobs[j];
+  if (jb.env < 0) return;  // uniform per block
+  const int y = rb * GPB + grp;
+  const int Q = P / 2;                        // complex planes per group
+  constexpr int PLB = N * N;                 // float2 per B plane
+  const __amdgpu_buffer_rsrc_t rs = plane_rsrc(ws_b + (size_t)j * P * PLB, (unsigned)((size_t)P * PLB * 8));
+  const RowinvLanes<R> ln(y, t);
+  auto load_pair = [&](pk2 (&v)[R], int q) {   // v = B[2q] + i B[2q + 1]
+    const int po = 2 * q * PLB * 8;
+#pragma unroll
+    for (int jj = 0; jj < R; ++jj) v[jj] = to_pk(ln.load(rs, po, jj));
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      float2 w[R / 2];
+#pragma unroll
+      for (int jj = 0; jj < R / 2; ++jj) w[jj] = ln.load(rs, po + PLB * 8, h * (R / 2) + jj);
+#pragma unroll
+      for (int jj = 0; jj < R / 2; ++jj) {
+        v[h * (R / 2) + jj].x -= w[jj].y;
+        v[h * (R / 2) + jj].y += w[jj].x;
+      }
+    }
+  };
+  const PaddedScratch<R> sc{scratch + grp * R * (R + 1)};
+  const size_t row0 = (((size_t)jb.env * G + jb.group) * Q * N + y) * N + t;   // complex plane 0, pixel x = t
+  auto finish_plane = [&](pk2 (&v)[R], int q) {
+    fft_group<R, true>(v, t, sc, tw);
+    const size_t row = row0 + (size_t)q * N * N;
+    if (field_out) {
+#pragma unroll
+      for (int k = 0; k < R; ++k) field_out[row + R * k] = from_pk(v[k]);
+    }
+    if (real_out) {
+#pragma unroll
+      for (int k = 0; k < R; ++k) real_out[row + R * k] = v[k].x;
+    }
+  };
+  pk2 va[R];
+  load_pair(va, 0);
+  __syncthreads();  // tw visible
+  if constexpr (R == 16) {
+    pk2 vb[R];
+#pragma unroll 1
+    for (int q = 0; q < Q; q += 2) {
+      if (q + 1 < Q) load_pair(vb, q + 1);
+      finish_plane(va, q);
+      if (q + 1 < Q) {
+        if (q + 2 < Q) load_pair(va, q + 2);
+        finish_plane(vb, q + 1);
+      }
+    }
+  } else {
+#pragma unroll 1
+    for (int q = 0; q < Q; ++q) {
+      finish_plane(va, q);
+      if (q + 1 < Q) load_pair(va, q + 1);   // uniform: no pair is read twice
+    }
+  }
+}
+
+// N = 64: k_rowinv's LDS tile transpose; both planes' shares of the tile are prefetched one pair
+// ahead and combined as they are written into the tile.
+template <int R, int NT>
+__global__ __launch_bounds__(NT, 512 / NT) void k_rowinv_cplx(const JobDesc* __restrict__ jobs,
+                                                        const float2* __restrict__ ws_b,
+                                                        const float2* __restrict__ tw_glob, int P, int G,
+                                                        float2* __restrict__ field_out,
+                                                        float* __restrict__ real_out) {
+  constexpr int N = R * R;
+  constexpr int GPB = NT / R;          // rows per block
+  constexpr int RB = N / GPB;
+  constexpr int CH16 = N * GPB / 2;     // 16-B chunks per plane tile
+  constexpr int PER = CH16 / NT;
+  static_assert(CH16 % NT == 0, "chunking");
+  constexpr int SCR = GPB * R * (R + 1);   // padded transpose scratch reuses the tile
+  __shared__ float2 tw[N];
+  __shared__ __attribute__((aligned(16))) float2 tile[SCR > N * GPB ? SCR : N * GPB];
+
+  for (int i = threadIdx.x; i < N; i += NT) tw[i] = tw_glob[i];
+
+  const int grp = threadIdx.x / R;
+  const int t = threadIdx.x % R;
+  const int bid = xcd_pair<RB>(blockIdx.x);
+  const int rb = bid % RB;
+  const int j = bid / RB;
+  const JobDesc jb = jobs[j];
+  if (jb.env < 0) return;  // uniform per block
+  const int y0 = rb * GPB;
+  const int y = y0 + grp;
+  const int Q = P / 2;
+  constexpr size_t PLB = plane_b_elems(R);
+  const float2* jbase = ws_b + (size_t)j * P * PLB;
+
+  float4 pa[PER], pb[PER];   // this thread's share of the pair's two plane tiles, one pair ahead
+  auto load_pair = [&](int q) {
+    const float2* a = jbase + (size_t)(2 * q) * PLB;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const int c = threadIdx.x + NT * i;
+      const int line = c / (GPB / 2), r2 = (c % (GPB / 2)) * 2;
+      pa[i] = ld_stream4(a + LayoutB<R>::at(line, y0 + r2));
+      pb[i] = ld_stream4(a + PLB + LayoutB<R>::at(line, y0 + r2));
+    }
+  };
+  load_pair(0);
+  const size_t row0 = (((size_t)jb.env * G + jb.group) * Q * N + y) * N + t;
+
+#pragma unroll 1
+  for (int q = 0; q < Q; ++q) {
+    lds_barrier();  // previous plane's scratch use is over (also publishes tw)
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {   // B[2q] + i B[2q + 1]
+      const int c = threadIdx.x + NT * i;
+      const int line = c / (GPB / 2), r2 = (c % (GPB / 2)) * 2;
+      tile[tile_pos<R, GPB>(line, r2)] = make_float2(pa[i].x - pb[i].y, pa[i].y + pb[i].x);
+      tile[tile_pos<R, GPB>(line, r2 + 1)] = make_float2(pa[i].z - pb[i].w, pa[i].w + pb[i].z);
+    }
+    if (q + 1 < Q) load_pair(q + 1);   // next pair's tiles in flight under this plane's FFT
+    lds_barrier();
+    pk2 v[R];
+#pragma unroll
+    for (int jj = 0; jj < R; ++jj) v[jj] = to_pk(tile[tile_pos<R, GPB>(t + R * jj, grp)]);
+    lds_barrier();  // tile consumed: reuse it as transpose scratch
+    fft_group<R, true>(v, t, PaddedScratch<R>{tile + grp * R * (R + 1)}, tw);
+    const size_t row = row0 + (size_t)q * N * N;
+    if (field_out) {
+#pragma unroll
+      for (int k = 0; k < R; ++k) field_out[row + R * k] = from_pk(v[k]);
+    }
+    if (real_out) {
+#pragma unroll
+      for (int k = 0; k < R; ++k) real_out[row + R * k] = v[k].x;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Generic complex 2-D FFT (flip-map correlations): a row pass that writes its
 // result transposed.  in [n][N][N] row-major -> out[n][k][y] = FFT_x in[n][y][x];
 // two applications give the 2-D transform in natural orientation.  Same
@@ -1221,9 +1470,20 @@ static hipError_t launch_passes(const PlanDev& pd, const JobDesc* jobs, int n_jo
   const unsigned rf_blocks = (unsigned)n_jobs * (pair ? 1 : P / 2) * (N / (kRowNT<R> / R)) / rowfwd_iters<R>();
   const unsigned col_blocks = (unsigned)n_jobs * (pair ? 2 : P) * ((N / 2) / (GPB * col2_iters<R>()));
   const bool small = kTiledB<R> && rf_blocks < kSmallBlocks && col_blocks < kSmallBlocks;
+  if (pd.complex_values && (SK != HBX_PRECISION_F32 || pd.plane_mode != kPlanesOff || pd.actions || pd.walk_phase ||
+                            pd.real_values || (!pd.complex_field && !pd.real_part)))
+    return hipErrorInvalidValue;   // before the timer opens a slot, as run_jobs_896
   {
     if (tm) tm->begin(0, st);
-    if (pd.real_values) {   // real-valued field: one row block per workgroup at every launch size
+    if (pd.complex_values) {   // complex field: the real kernels' geometry, wg.q = the complex plane
+      const unsigned blocks = (unsigned)n_jobs * (P / 2) * (N / (kRowNT<R> / R));
+      if constexpr (R == 32)
+        hipLaunchKernelGGL(k_rowfwd32_cplx, dim3(blocks), dim3(256), 0, st, jobs, pd.complex_values, pd.ws_a, pd.tw,
+                           P, CH);
+      else
+        hipLaunchKernelGGL((k_rowfwd_cplx<R, kRowNT<R>>), dim3(blocks), dim3(kRowNT<R>), 0, st, jobs,
+                           pd.complex_values, pd.ws_a, pd.tw, P, CH);
+    } else if (pd.real_values) {   // real-valued field: one row block per workgroup at every launch size
       if (SK != HBX_PRECISION_F32 || pair || pd.actions || pd.walk_phase) return hipErrorInvalidValue;
       const unsigned blocks = (unsigned)n_jobs * (P / 2) * (N / (kRowNT<R> / R));
       if constexpr (R == 32)
@@ -1270,6 +1530,16 @@ static hipError_t launch_passes(const PlanDev& pd, const JobDesc* jobs, int n_jo
   {
     const unsigned blocks = (unsigned)n_jobs * (N / (kRowNT<R> / R));
     if (tm) tm->begin(2, st);
+    if (pd.complex_values) {   // recombine each plane pair; nothing to reduce
+      if constexpr (kTiledB<R>)
+        hipLaunchKernelGGL((k_rowinv_d_cplx<R>), dim3(blocks), dim3(256), 0, st, jobs, pd.ws_b, pd.tw, P, pd.G,
+                           pd.complex_field, pd.real_part);
+      else
+        hipLaunchKernelGGL((k_rowinv_cplx<R, kRowNT<R>>), dim3(blocks), dim3(kRowNT<R>), 0, st, jobs, pd.ws_b,
+                           pd.tw, P, pd.G, pd.complex_field, pd.real_part);
+      if (tm) tm->end(2, n_jobs, st);
+      return hipGetLastError();
+    }
     if constexpr (kTiledB<R>) {
       if (pd.walk_planes) {   // (r05) a plane-cache walk batch: the last workgroup decides
         if (pd.plane_mode != kPlanesStep) return hipErrorInvalidValue;

@@ -12,7 +12,8 @@
 //                split -> half spectrum kx < 448 (Nyquist in Im of kx = 0) ->
 //                LDS tile transpose -> A[kx][y0..y0+8)   [read N^2/8, write 4 N^2 B per plane]
 //                (k_rowfwd896_real reads f32 samples instead of bits; everything after the
-//                load is rowfwd896_emit, called by both)
+//                load is rowfwd896_emit, called by both and by k_rowfwd896_cplx, which reads
+//                complex64 samples; k_rowinv896_cplx is the last pass of that path)
 //   k_col896     one lane group per half-spectrum line kx: FFT over y ->
 //                x H and x conj H (H even in fx and ky) -> two IFFTs -> B lines
 //                kx and N - kx (448 for kx = 0)           [read 4 N^2, write 8 N^2]
@@ -244,6 +245,35 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd896_real(const JobDesc* __rest
   rowfwd896_emit(v, t, grp, lane_base, y0, lds, tw, base);
 }
 
+// Pass 1 on complex fields (hbx_simulate_complex): values[env][CH / 2][896][896] complex64.
+// complex_load_row puts the complex sample of pixel x = t + 32 jj (jj < 28) into v[jj] as it is and
+// zeros above; rowfwd896_emit then leaves the half spectra of Re u_q and Im u_q in A planes 2q and
+// 2q + 1.  k_rowfwd896_real's geometry, wg.q = the complex plane.
+__global__ __launch_bounds__(256, 3) void k_rowfwd896_cplx(const JobDesc* __restrict__ jobs,
+                                                           const float2* __restrict__ values,
+                                                           float2* __restrict__ ws_a,
+                                                           const float2* __restrict__ tw_glob, int P, int CH) {
+  __shared__ float2 tw[kN];
+  __shared__ __attribute__((aligned(16))) float lds[kRowfwd896Scr];
+  stage_twiddles<kN, 256>(tw, tw_glob);
+
+  const int grp = threadIdx.x / kR;
+  const int t = threadIdx.x % kR;
+  const int lane_base = (threadIdx.x & 63) - t;
+  const FirstPassBlock wg = first_pass_block<kRB>(blockIdx.x, P / 2);
+  const int j = wg.j;
+  const JobDesc jb = jobs[j];
+  if (jb.env < 0) return;  // uniform per block
+  const int y0 = wg.rbw * kGPB;
+  const int y = y0 + grp;
+  float2 v[32];
+  complex_load_row<kR, kL>(v, values + (((size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q) * kN + y) * kN, t);
+  __syncthreads();  // tw visible
+
+  float2* base = ws_a + ((size_t)j * P + 2 * wg.q) * kPlaneA;
+  rowfwd896_emit(v, t, grp, lane_base, y0, lds, tw, base);
+}
+
 // ---------------------------------------------------------------------------
 // Pass 2 (r04: k_col2's scheme at 896): one lane group per input line and both of its
 // output lines.  FFT over y -> Z (slot layout); H(kx, ky) for ky <= 448 only (17 of 32
@@ -392,6 +422,28 @@ __global__ __launch_bounds__(256, 2) void k_col896(const JobDesc* __restrict__ j
 // ---------------------------------------------------------------------------
 constexpr bool kInvScalar = false;   // packed DFTs (one line live)
 
+// the lane bases above (bytes from the job's first B plane) of row y for lane t, and the load of
+// the lane's slot-layout register k2 of the plane at byte offset po (wave-uniform)
+struct Rowinv896Lanes {
+  static constexpr int TL = 8;                    // slots per tile (1-KB tiles, as N = 1024)
+  static constexpr int MS = 7 * 16 * TL * 8;      // bytes per m: 7 tiles
+  int lo0, lo1, hi0, hi1, mid;
+  __device__ __forceinline__ Rowinv896Lanes(int y, int t) {
+    const int k1 = t < kL ? t : 0;                // lanes 28..31 mirror lane 0 (don't-care values)
+    const int yb = (y >> 4) * 16 * kN + (y & 15) * TL;
+    auto at = [&](int slot) { return (yb + (slot / TL) * 16 * TL + slot % TL) * 8; };   // bytes
+    lo0 = at(k1), lo1 = at(28 + k1);
+    hi0 = at(476 - k1), hi1 = at(504 - k1);
+    mid = k1 == 0 ? at(kHalf) : hi1 + 7 * MS;
+  }
+  __device__ __forceinline__ float2 load(__amdgpu_buffer_rsrc_t rs, int po, int k2) const {
+    if (k2 < 16) return buf_ld2s(rs, (k2 & 1) ? lo1 : lo0, po + (k2 >> 1) * MS);
+    if (k2 == 16) return buf_ld2s(rs, mid, po);
+    const int q = 31 - k2;
+    return buf_ld2s(rs, (q & 1) ? hi1 : hi0, po + (q >> 1) * MS);
+  }
+};
+
 template <bool LEAN>
 __global__ __launch_bounds__(256, 2) void k_rowinv896(const JobDesc* __restrict__ jobs,
                                                       const float2* __restrict__ ws_b,
@@ -404,7 +456,6 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896(const JobDesc* __restrict_
                                                       float* __restrict__ plane_pool,
                                                       const int32_t* __restrict__ plane_slot, int plane_spares,
                                                       int spare_base) {
-  constexpr int TL = 8;                           // slots per tile (1-KB tiles, as N = 1024)
   if constexpr (LEAN) {   // (r06) the plain FFT-mode launch: no plane-cache / field code (as k_rowinv_d)
     plane_mode = kPlanesOff;
     field_out = nullptr;
@@ -429,24 +480,11 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896(const JobDesc* __restrict_
   }
   const int y = rb * kGPB + grp;
   const __amdgpu_buffer_rsrc_t rs = plane_rsrc(ws_b + (size_t)j * P * kPlaneB, (unsigned)((size_t)P * kPlaneB * 8));
-  const int k1 = t < kL ? t : 0;                  // lanes 28..31 mirror lane 0 (don't-care values)
-  const int yb = (y >> 4) * 16 * kN + (y & 15) * TL;
-  auto at = [&](int slot) { return (yb + (slot / TL) * 16 * TL + slot % TL) * 8; };   // bytes
-  const int lo0 = at(k1), lo1 = at(28 + k1);
-  const int hi0 = at(476 - k1), hi1 = at(504 - k1);
-  constexpr int MS = 7 * 16 * TL * 8;             // bytes per m: 7 tiles
-  const int mid = k1 == 0 ? at(kHalf) : hi1 + 7 * MS;
+  const Rowinv896Lanes ln(y, t);
   auto load_plane = [&](float2 (&v)[32], int p) {
     const int po = p * (int)(kPlaneB * 8);
 #pragma unroll
-    for (int k2 = 0; k2 < 32; ++k2) {
-      if (k2 < 16) v[k2] = buf_ld2s(rs, (k2 & 1) ? lo1 : lo0, po + (k2 >> 1) * MS);
-      else if (k2 == 16) v[k2] = buf_ld2s(rs, mid, po);
-      else {
-        const int q = 31 - k2;
-        v[k2] = buf_ld2s(rs, (q & 1) ? hi1 : hi0, po + (q >> 1) * MS);
-      }
-    }
+    for (int k2 = 0; k2 < 32; ++k2) v[k2] = ln.load(rs, po, k2);
   };
   float acc[kL];
 #pragma unroll
@@ -543,6 +581,68 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896(const JobDesc* __restrict_
   }
 }
 
+// Pass 3 on complex fields (hbx_simulate_complex): B planes 2q and 2q + 1 hold the column-pass
+// output of Re u_q and Im u_q; combined on load, v = B[2q] + i B[2q + 1] (plane 2q + 1 in two
+// halves of 16 registers, so two whole lines are never live), ONE inverse FFT per complex plane, and
+// the plane F_q stored once to field_out and / or its real part to real_out, both
+// [env][CH / 2][896][896].  k_rowinv896's lane bases; no |.|^2, partials or plane cache.
+__global__ __launch_bounds__(256, 2) void k_rowinv896_cplx(const JobDesc* __restrict__ jobs,
+                                                           const float2* __restrict__ ws_b,
+                                                           const float2* __restrict__ tw_glob, int P, int G,
+                                                           float2* __restrict__ field_out,
+                                                           float* __restrict__ real_out) {
+  __shared__ float2 tw[kN];
+  __shared__ float2 scratch[kSCR];
+  for (int i = threadIdx.x; i < kN; i += 256) tw[i] = tw_glob[i];
+
+  const int grp = threadIdx.x / kR;
+  const int t = threadIdx.x % kR;
+  const int bid = xcd_pair<kRB>(blockIdx.x);
+  const int rb = bid % kRB;
+  const int j = bid / kRB;
+  const JobDesc jb = jobs[j];
+  if (jb.env < 0) return;  // uniform per block
+  const int y = rb * kGPB + grp;
+  const int Q = P / 2;                            // complex planes per group
+  const __amdgpu_buffer_rsrc_t rs = plane_rsrc(ws_b + (size_t)j * P * kPlaneB, (unsigned)((size_t)P * kPlaneB * 8));
+  const Rowinv896Lanes ln(y, t);
+  auto load_pair = [&](float2 (&v)[32], int q) {   // v = B[2q] + i B[2q + 1]
+    const int po = 2 * q * (int)(kPlaneB * 8);
+#pragma unroll
+    for (int k2 = 0; k2 < 32; ++k2) v[k2] = ln.load(rs, po, k2);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      float2 w[16];
+#pragma unroll
+      for (int k2 = 0; k2 < 16; ++k2) w[k2] = ln.load(rs, po + (int)(kPlaneB * 8), 16 * h + k2);
+#pragma unroll
+      for (int k2 = 0; k2 < 16; ++k2) {
+        v[16 * h + k2].x -= w[k2].y;
+        v[16 * h + k2].y += w[k2].x;
+      }
+    }
+  };
+  const PaddedScratch<kR> sc{scratch + grp * kR * (kR + 1)};
+  const size_t row0 = (((size_t)jb.env * G + jb.group) * Q * kN + y) * kN + t;   // complex plane 0, pixel x = t
+  float2 v[32];
+  load_pair(v, 0);
+  __syncthreads();  // tw visible
+#pragma unroll 1
+  for (int q = 0; q < Q; ++q) {
+    fft896_sn<true, kInvScalar>(v, t, sc, tw);      // slot layout in, natural out: x = t + 32 k
+    const size_t row = row0 + (size_t)q * kN * kN;
+    if (field_out) {
+#pragma unroll
+      for (int k = 0; k < kL; ++k) field_out[row + kR * k] = v[k];
+    }
+    if (real_out) {
+#pragma unroll
+      for (int k = 0; k < kL; ++k) real_out[row + kR * k] = v[k].x;
+    }
+    if (q + 1 < Q) load_pair(v, q + 1);   // uniform: no pair is read twice
+  }
+}
+
 __global__ void k_reduce_partials(const double* __restrict__ partial, int n_jobs, int RB,
                                   double* __restrict__ job_stats);
 
@@ -556,8 +656,14 @@ hipError_t run_jobs_896(const PlanDev& pd, const JobDesc* jobs, int n_jobs, cons
   const int pair = pd.plane_mode == kPlanesStep ? 1 : 0;
   if (pd.plane_mode != kPlanesOff && (!pd.plane_pool || !pd.plane_slot)) return hipErrorInvalidValue;
   if (pd.real_values && (pair || pd.store_kind != HBX_PRECISION_F32)) return hipErrorInvalidValue;
+  if (pd.complex_values && (pair || pd.store_kind != HBX_PRECISION_F32 || pd.real_values ||
+                            pd.plane_mode != kPlanesOff || (!pd.complex_field && !pd.real_part)))
+    return hipErrorInvalidValue;
   if (tm) tm->begin(0, st);
-  if (pd.real_values)
+  if (pd.complex_values)
+    hipLaunchKernelGGL(k_rowfwd896_cplx, dim3((unsigned)n_jobs * (P / 2) * kRB), dim3(256), 0, st, jobs,
+                       pd.complex_values, pd.ws_a, pd.tw, P, CH);
+  else if (pd.real_values)
     hipLaunchKernelGGL(k_rowfwd896_real, dim3((unsigned)n_jobs * (P / 2) * kRB), dim3(256), 0, st, jobs,
                        pd.real_values, pd.ws_a, pd.tw, P, CH);
   else
@@ -569,6 +675,12 @@ hipError_t run_jobs_896(const PlanDev& pd, const JobDesc* jobs, int n_jobs, cons
                      pd.ws_b, pd.htab, pd.tw, P, pair);
   if (tm) tm->end(1, n_jobs, st);
   if (tm) tm->begin(2, st);
+  if (pd.complex_values) {   // recombine each plane pair; nothing to reduce
+    hipLaunchKernelGGL(k_rowinv896_cplx, dim3((unsigned)n_jobs * kRB), dim3(256), 0, st, jobs, pd.ws_b, pd.tw, P,
+                       pd.G, pd.complex_field, pd.real_part);
+    if (tm) tm->end(2, n_jobs, st);
+    return hipGetLastError();
+  }
   // (r06) the plain FFT-mode launch gets the lean instantiation (profiles/r06/rowinv896_lean_ab_r06i.txt)
   const bool lean = pd.plane_mode == kPlanesOff && !field_out;
   if (lean)

@@ -1,6 +1,6 @@
 // hbx_rowcol.hpp -- helpers shared by the row / column passes (hbx_passes.hip,
 // hbx_passes896.hip): LDS tile swizzle, XCD-aware row-block order, the first pass's
-// workgroup decode, twiddle staging and real-field row load, buffer descriptors of
+// workgroup decode, twiddle staging and real- / complex-field row loads, buffer descriptors of
 // wave-uniform planes.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -150,6 +150,23 @@ __device__ __forceinline__ void real_load_row(V (&v)[R], const float* __restrict
   for (int jj = 0; jj < L; ++jj) b[jj] = __builtin_nontemporal_load(rowb + t + R * jj);
 #pragma unroll
   for (int jj = 0; jj < L; ++jj) v[jj] = V{a[jj], b[jj]};
+#pragma unroll
+  for (int jj = L; jj < R; ++jj) v[jj] = V{0.f, 0.f};
+}
+
+// Complex fields (hbx_simulate_complex): lane t loads the complex64 sample of pixel x = t + R jj,
+// jj < L, of the row at `row` straight into the (re, im) of v[jj] -- one 8-byte non-temporal load
+// per element, a coalesced 8 R-byte run per lane group and jj; v[L ..] = 0 (N = 896).  The row FFT
+// of u = a + i b followed by the Hermitian split is then the real path's pair of planes (a, b).
+template <int R, int L = R, class V>
+__device__ __forceinline__ void complex_load_row(V (&v)[R], const float2* __restrict__ row, int t) {
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  const f32x2* r2 = reinterpret_cast<const f32x2*>(row);
+#pragma unroll
+  for (int jj = 0; jj < L; ++jj) {
+    const f32x2 s = __builtin_nontemporal_load(r2 + t + R * jj);
+    v[jj] = V{s.x, s.y};
+  }
 #pragma unroll
   for (int jj = L; jj < R; ++jj) v[jj] = V{0.f, 0.f};
 }

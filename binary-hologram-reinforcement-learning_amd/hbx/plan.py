@@ -306,12 +306,35 @@ class Plan:
         n = values.shape[0] if isinstance(values, torch.Tensor) and values.dim() else 0
         c = self.cfg
         _need(values, "values", torch.float32, self.values_shape(n), self.device)
+        values = values.resolve_neg()              # a lazily negated view shares the un-negated memory
         field = torch.empty((n, c.channels, c.height, c.width, 2), dtype=torch.float32, device=self.device)
         inten = torch.empty((n, c.groups, c.height, c.width), dtype=torch.float32,
                             device=self.device) if want_intensity else None
         _lib.check(self.lib.hbx_simulate_real(self._h, _ptr(values), n, _ptr(field), _ptr(inten),
                                               _stream(stream)), "hbx_simulate_real")
         return torch.view_as_complex(field), inten
+
+    def simulate_complex(self, values: torch.Tensor, want_field: bool = True, want_real: bool = False,
+                         stream=None):
+        """`simulate` on a complex field (hbx_simulate_complex): `values` complex64
+        [B, CH/2, H, W] are the field samples themselves; a plan with CH real planes carries CH/2
+        complex planes.  Returns (field complex64 [B, CH/2, H, W] | None, real_part float32
+        [B, CH/2, H, W] | None); real_part is field.real, written without the complex plane when
+        want_field is off (the gradient of a real input: the plan for -z is the adjoint)."""
+        if not (want_field or want_real):
+            raise ValueError("simulate_complex: want_field and want_real are both off")
+        n = values.shape[0] if isinstance(values, torch.Tensor) and values.dim() else 0
+        c = self.cfg
+        shape = (n, c.channels // 2, c.height, c.width)
+        _need(values, "values", torch.complex64, shape, self.device)
+        # a lazily conjugated / negated view (values.conj()) shares the unconjugated memory the
+        # kernel would read: materialise it (a copy only when such a bit is set)
+        values = values.resolve_conj().resolve_neg()
+        field = torch.empty(shape + (2,), dtype=torch.float32, device=self.device) if want_field else None
+        real = torch.empty(shape, dtype=torch.float32, device=self.device) if want_real else None
+        _lib.check(self.lib.hbx_simulate_complex(self._h, _ptr(values), n, _ptr(field), _ptr(real),
+                                                 _stream(stream)), "hbx_simulate_complex")
+        return (torch.view_as_complex(field) if want_field else None), real
 
     def propagate_real(self, values: torch.Tensor, target: torch.Tensor, want_intensity: bool = True,
                        stream=None):
@@ -320,6 +343,7 @@ class Plan:
         n = values.shape[0] if isinstance(values, torch.Tensor) and values.dim() else 0
         c = self.cfg
         _need(values, "values", torch.float32, self.values_shape(n), self.device)
+        values = values.resolve_neg()              # a lazily negated view shares the un-negated memory
         _need(target, "target", torch.float32, self.target_shape(n), self.device)
         inten = torch.empty((n, c.groups, c.height, c.width), dtype=torch.float32,
                             device=self.device) if want_intensity else None

@@ -22,9 +22,17 @@ fallback on either):
   ``simulate(x, z, strict=True)`` waits and raises before returning.
 * ``binary=False`` (the continuous path, ABI v15): the samples are the field.  Real float
   input goes through hbx_simulate_real, whose first pass reads float32 samples instead of
-  bits; a complex field, or ``field="phase"`` on real input (u = exp(i pi x)), is propagated
-  as two real planes per complex plane and recombined by linearity.  No pack kernel runs,
-  the error word is never set and ``strict`` has nothing to check.
+  bits; a complex field, or ``field="phase"`` on real input (u = exp(i pi x), formed with
+  torch ops), goes through hbx_simulate_complex, whose first pass reads complex64 samples and
+  whose last pass writes each complex plane once.  No pack kernel runs, the error word is
+  never set and ``strict`` has nothing to check.
+  This path is differentiable: when the input requires grad the propagation runs as a
+  torch.autograd.Function whose backward pass is hbx_simulate_complex of grad_output on the
+  plan for -z (the adjoint: H(-z) = conj H(z)); a real input receives the real part only.
+  Without a gradient request the call is the plain one, with no graph.  Limits: the -z plan
+  is a second workspace in the plan cache; there is no double backward; ``binary=True`` stays
+  non-differentiable and builds no graph; ``relativeLoss(.., tm.get_PSNR)`` returns a float
+  (its ``F.mse_loss`` form is torch ops and differentiates by itself).
 
 The physics follows the assumptions documented in DESIGN.md (the original torchOptics is
 absent and unpinned): no padding; exact angular spectrum and amplitude field unless
@@ -162,10 +170,10 @@ def simulate(x, z: float, strict: bool = False, binary: bool = True, tf="asm", f
 
     binary=False: the continuous path; no binary check, `strict` is ignored.
       real x,    field="amplitude":  u = x (float64 is cast to float32), one real plane each;
-      complex x, field="amplitude":  u = x, propagated as the real planes [re0, im0, re1, ..]
-                                     and recombined as F[2c] + i F[2c+1] (exact by linearity);
+      complex x, field="amplitude":  u = x (cast to complex64), through hbx_simulate_complex;
       real x,    field="phase":      u = exp(i pi x) = cos(pi x) + i sin(pi x), the same route.
-    A complex plane therefore costs two real planes (twice the time and workspace of a real one)."""
+    A complex plane takes the workspace of two real planes.  If x requires grad the result
+    carries a grad_fn and loss.backward() reaches x (module docstring); otherwise it has none."""
     tf_kind = _switch(tf, _TF_NAMES, "tf")
     field_kind = _switch(field, _FIELD_NAMES, "field")
     meta = _meta_of(x)
@@ -216,33 +224,70 @@ def simulate(x, z: float, strict: bool = False, binary: bool = True, tf="asm", f
     return field[0] if squeeze else field
 
 
-def _simulate_continuous(t: torch.Tensor, wl, dx, dy, z, dev: int, tf_kind: int, field_kind: int) -> torch.Tensor:
-    """simulate's binary=False path on a device tensor [B, C, H, W]: real planes through
-    hbx_simulate_real; complex / phase fields as (re, im) plane pairs, recombined here."""
-    b, c, h, w = t.shape
-    as_pairs = t.is_complex() or field_kind == _lib.FIELD_PHASE
-    if as_pairs:
-        if t.is_complex():
-            ri = torch.view_as_real(t.to(torch.complex64))          # [B, C, H, W, 2]
-            planes = ri.permute(0, 1, 4, 2, 3).reshape(b, 2 * c, h, w)
-        else:
-            ph = t.to(torch.float32) * np.float32(np.pi)
-            planes = torch.stack((torch.cos(ph), torch.sin(ph)), dim=2).reshape(b, 2 * c, h, w)
-        cp = 2 * c
-        vals = planes.contiguous()
-    else:
-        cp = c + (c % 2)                            # the kernels take plane pairs: pad with a zero plane
-        if cp == c:
-            vals = t.to(torch.float32).contiguous()
-        else:
-            vals = torch.zeros((b, cp, h, w), dtype=torch.float32, device=t.device)
-            vals[:, :c] = t
+def _propagate_complex(u: torch.Tensor, wl, dx, dy, z, dev: int, tf_kind: int, want_field: bool = True):
+    """IFFT2(FFT2(u) H(z)) of a complex device tensor [B, C, H, W] through hbx_simulate_complex, on
+    the plan with 2 C real planes (= C complex planes): the complex field, or with
+    want_field=False its real part only (float32)."""
+    b, c, h, w = u.shape
     # the samples are the field: the plan's bit mapping (field_kind) plays no part
+    plan = _plan_for(h, w, 2 * c, wl, dx, dy, z, b, dev, tf_kind, _lib.FIELD_AMPLITUDE)
+    # resolve_conj / resolve_neg: torch conjugates and negates lazily (x.conj(), and the grad_output
+    # of a loss that ends in F.conj()), and the kernels read the memory behind data_ptr()
+    u = u.to(torch.complex64).resolve_conj().resolve_neg().contiguous()
+    field, real = plan.simulate_complex(u, want_field=want_field, want_real=not want_field)
+    return field if want_field else real
+
+
+def _propagate_real(t: torch.Tensor, wl, dx, dy, z, dev: int, tf_kind: int) -> torch.Tensor:
+    """The same of a real device tensor [B, C, H, W] through hbx_simulate_real."""
+    b, c, h, w = t.shape
+    cp = c + (c % 2)                                # the kernels take plane pairs: pad with a zero plane
+    if cp == c:
+        vals = t.to(torch.float32).resolve_neg().contiguous()   # a lazy negation (x.conj().imag) made real
+    else:
+        vals = torch.zeros((b, cp, h, w), dtype=torch.float32, device=t.device)
+        vals[:, :c] = t
     plan = _plan_for(h, w, cp, wl, dx, dy, z, b, dev, tf_kind, _lib.FIELD_AMPLITUDE)
     out, _ = plan.simulate_real(vals)
-    if as_pairs:
-        return out[:, 0::2] + 1j * out[:, 1::2]
     return out[:, :c] if cp != c else out
+
+
+class _Propagate(torch.autograd.Function):
+    """u -> A u = IFFT2(FFT2(u) H(z)) with its adjoint as the backward pass.  A^H g =
+    IFFT2(FFT2(g) conj H(z)), and conj H(z) = H(-z) for both transfer functions, so the gradient
+    is hbx_simulate_complex of grad_output on the plan for -z: the whole field for a complex
+    input, its real part (the only output written) for a real one.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, t, geom):
+        ctx.geom = geom
+        ctx.in_dtype = t.dtype
+        wl, dx, dy, z, dev, tf_kind = geom
+        if t.is_complex():
+            return _propagate_complex(t, wl, dx, dy, z, dev, tf_kind)
+        return _propagate_real(t, wl, dx, dy, z, dev, tf_kind)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        wl, dx, dy, z, dev, tf_kind = ctx.geom
+        grad = _propagate_complex(grad_output, wl, dx, dy, -z, dev, tf_kind, want_field=ctx.in_dtype.is_complex)
+        return grad.to(ctx.in_dtype), None
+
+
+def _simulate_continuous(t: torch.Tensor, wl, dx, dy, z, dev: int, tf_kind: int, field_kind: int) -> torch.Tensor:
+    """simulate's binary=False path on a device tensor [B, C, H, W]: real planes through
+    hbx_simulate_real, complex and phase fields through hbx_simulate_complex; through
+    _Propagate when a gradient is wanted."""
+    if field_kind == _lib.FIELD_PHASE and not t.is_complex():
+        ph = t.to(torch.float32) * np.float32(np.pi)
+        t = torch.complex(torch.cos(ph), torch.sin(ph))   # torch ops: autograd carries du/dx
+    geom = (wl, dx, dy, z, dev, tf_kind)
+    if t.requires_grad and torch.is_grad_enabled():
+        return _Propagate.apply(t, geom)
+    if t.is_complex():
+        return _propagate_complex(t, *geom)
+    return _propagate_real(t, *geom)
 
 
 def relativeLoss(x: torch.Tensor, y, fn: Callable, rel_scale="lsq") -> torch.Tensor:

@@ -214,14 +214,34 @@ int hbx_simulate(hbx_plan_t plan, const uint64_t* mask, int32_t n_env, float* fi
  * Outputs, null-ability, chunking by the plan's max_jobs and n_env == 0 are those of
  * hbx_simulate / hbx_propagate; only the first pass differs (it reads 4 bytes per pixel instead
  * of one bit and fills the HBX_PASS_ROWFWD timer slot), so 0 / 1 samples give the bit path's
- * result.  A complex field u = a + i b is two calls' worth of planes by linearity: propagate
- * the planes a and b, then F = F[a] + i F[b].  All four built sizes; HBX_PRECISION_F32 only
+ * result.  A complex field u = a + i b goes through hbx_simulate_complex below (two calls' worth
+ * of real planes a and b with F = F[a] + i F[b] is the same field by linearity, at about twice
+ * the memory traffic).  All four built sizes; HBX_PRECISION_F32 only
  * (a plan set to a reduced-precision store kind returns HBX_ERR_UNSUPPORTED).  No env, DBS,
  * plane-cache or incremental mode runs on real-valued fields. */
 int hbx_simulate_real(hbx_plan_t plan, const float* values, int32_t n_env, float* field,
                       float* intensity, void* stream);
 int hbx_propagate_real(hbx_plan_t plan, const float* values, const float* target, int32_t n_env,
                        float* intensity, double* chan_stats, double* psnr, void* stream);
+
+/* (ABI v15, additive) tt.simulate on a complex field.  A plan with P real planes per group
+ * carries P/2 complex planes per group; each takes one plane-pair slot of the workspace.
+ *   values   [B][G*P/2][H][W][2] complex64 samples as re/im pairs, used as they are (u = value)
+ *   field    [B][G*P/2][H][W][2] = IFFT2(FFT2(u) H_g), complex64            (nullable)
+ *   real_part[B][G*P/2][H][W]    = Re of the same field, float32            (nullable)
+ * At least one of field and real_part must be non-null; with both, real_part holds exactly the
+ * real parts stored in field.  The first pass reads the complex samples directly (the row FFT of
+ * a + i b, split into the half spectra of a and b), the column pass is hbx_simulate_real's, and
+ * the last pass forms B[a] + i B[b] on load, runs one inverse row FFT per complex plane and
+ * writes it once -- about 64 N^2 bytes per complex plane against about 112 N^2 by way of two
+ * real planes.  The adjoint of u -> IFFT2(FFT2(u) H) is this propagation on the plan for -z
+ * (H(-z) = conj H(z)); real_part alone is then the gradient with respect to a real u.
+ * Chunking by max_jobs, n_env (0: OK, < 0: HBX_ERR_INVALID), null arguments (HBX_ERR_INVALID),
+ * HBX_PRECISION_F32 only (else HBX_ERR_UNSUPPORTED), the four built sizes and the pass-timer
+ * slots HBX_PASS_ROWFWD / COL / ROWINV are those of hbx_simulate_real.  No intensity, statistics,
+ * env, DBS, plane-cache or incremental mode runs on complex fields. */
+int hbx_simulate_complex(hbx_plan_t plan, const float* values, int32_t n_env, float* field,
+                         float* real_part, void* stream);
 
 /* PSNR from per-channel statistics (tt.relativeLoss(.., tm.get_PSNR),
  * env.py:174): chan_stats[B][G][3] -> psnr[B]. */
