@@ -540,6 +540,31 @@ int hbx_simulate_real(hbx_plan_t p, const float* values, int32_t n_env, float* f
 
 // complex fields: propagate_full's chunk loop with the complex first and last passes (ids are
 // chunk-local, every buffer is offset by the chunk's first env); nothing to finalize or scatter
+namespace {
+// weight (hbx_simulate_complex_weighted, else null): [n_env][G][N][N] f32, one image per env and
+// group -- its chunk stride is G N^2, the complex planes' is G (P/2) N^2
+int simulate_complex(hbx_plan_t p, const float* values, const float* weight, float scale, int32_t n_env,
+                     float* field, float* real_part, hipStream_t st) {
+  const PlanDev& pd = p->pd;
+  const int chunk = p->max_jobs / pd.G;
+  const size_t per_env = (size_t)pd.G * (pd.P / 2) * pd.N * pd.N;   // complex planes x pixels
+  const size_t w_per_env = (size_t)pd.G * pd.N * pd.N;
+  for (int i0 = 0; i0 < n_env; i0 += chunk) {
+    const int n = std::min(chunk, n_env - i0);
+    PlanDev pdx = pd;
+    pdx.complex_values = reinterpret_cast<const float2*>(values) + (size_t)i0 * per_env;
+    if (weight) {
+      pdx.complex_weight = weight + (size_t)i0 * w_per_env;
+      pdx.complex_scale = scale;
+    }
+    pdx.complex_field = field ? reinterpret_cast<float2*>(field) + (size_t)i0 * per_env : nullptr;
+    pdx.real_part = real_part ? real_part + (size_t)i0 * per_env : nullptr;
+    HBX_HIP(hbx::run_jobs(pdx, p->full_jobs, n * pd.G, nullptr, nullptr, nullptr, nullptr, st));
+  }
+  return HBX_OK;
+}
+}  // namespace
+
 int hbx_simulate_complex(hbx_plan_t p, const float* values, int32_t n_env, float* field, float* real_part,
                          void* stream) {
   int rc = check_plan(p);
@@ -548,18 +573,32 @@ int hbx_simulate_complex(hbx_plan_t p, const float* values, int32_t n_env, float
   if (!values || (!field && !real_part)) return fail(HBX_ERR_INVALID, "null buffer");
   if ((rc = check_real_plan(p, true))) return rc;
   HBX_HIP(hipSetDevice(p->device));
-  const PlanDev& pd = p->pd;
-  const int chunk = p->max_jobs / pd.G;
-  const size_t per_env = (size_t)pd.G * (pd.P / 2) * pd.N * pd.N;   // complex planes x pixels
-  for (int i0 = 0; i0 < n_env; i0 += chunk) {
-    const int n = std::min(chunk, n_env - i0);
-    PlanDev pdx = pd;
-    pdx.complex_values = reinterpret_cast<const float2*>(values) + (size_t)i0 * per_env;
-    pdx.complex_field = field ? reinterpret_cast<float2*>(field) + (size_t)i0 * per_env : nullptr;
-    pdx.real_part = real_part ? real_part + (size_t)i0 * per_env : nullptr;
-    HBX_HIP(hbx::run_jobs(pdx, p->full_jobs, n * pd.G, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream));
-  }
-  return HBX_OK;
+  return simulate_complex(p, values, nullptr, 1.0f, n_env, field, real_part, (hipStream_t)stream);
+}
+
+int hbx_simulate_complex_weighted(hbx_plan_t p, const float* values, const float* weight, float scale,
+                                  int32_t n_env, float* field, float* real_part, void* stream) {
+  int rc = check_plan(p);
+  if (rc) return rc;
+  if (n_env <= 0) return n_env == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "n_env");
+  if (!values || !weight || (!field && !real_part)) return fail(HBX_ERR_INVALID, "null buffer");
+  if ((rc = check_real_plan(p, true))) return rc;
+  HBX_HIP(hipSetDevice(p->device));
+  return simulate_complex(p, values, weight, scale, n_env, field, real_part, (hipStream_t)stream);
+}
+
+// the plane-mean intensity of a real field and nothing else: the last pass takes the null target
+// (the plan's zero row) and the null field as hbx_propagate_real's lean launch does, and
+// propagate_full skips the finalize when no statistics are asked for
+int hbx_intensity_real(hbx_plan_t p, const float* values, int32_t n_env, float* intensity, void* stream) {
+  int rc = check_plan(p);
+  if (rc) return rc;
+  if (n_env <= 0) return n_env == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "n_env");
+  if (!values || !intensity) return fail(HBX_ERR_INVALID, "null buffer");
+  if ((rc = check_real_plan(p))) return rc;
+  HBX_HIP(hipSetDevice(p->device));
+  return propagate_full(p, nullptr, nullptr, nullptr, n_env, intensity, nullptr, nullptr, nullptr, nullptr,
+                        (hipStream_t)stream, nullptr, nullptr, 1, values);
 }
 
 int hbx_psnr(hbx_plan_t p, const double* chan_stats, int32_t n_env, double* psnr, void* stream) {

@@ -215,6 +215,10 @@ struct PlanDev {
   // and / or real_part [env][G*P/2][N][N] f32 (at least one non-null) and nothing else: no
   // intensity, partials or statistics.  f32 intermediates, no plane cache, no actions, no walk
   const float2* complex_values = nullptr;
+  // (ABI v15, additive) hbx_simulate_complex_weighted: [env][G][N][N] f32, non-null only with
+  // complex_values; the first pass propagates (complex_scale * complex_weight[env][group]) * values
+  const float* complex_weight = nullptr;
+  float complex_scale = 1.0f;
   float2* complex_field = nullptr;
   float* real_part = nullptr;
 };

@@ -525,11 +525,15 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd32_real(const JobDesc* __restr
 // samples into v as they are, and the shared tail does what it does for two real planes: the row
 // FFT of u = a + i b, split into the half spectra of a = Re u (A plane 2q) and b = Im u (2q + 1).
 // The real kernels' geometry: one row block per workgroup, wg.q = the complex plane.
-template <int R, int NT>
+// WT (hbx_simulate_complex_weighted): complex_load_row_weighted multiplies the samples by scale *
+// weight[env][group][y][x] as it loads them -- R more VGPRs live across the load (the weights), the
+// tail and the geometry unchanged; weight / scale are unused without WT.
+template <int R, int NT, bool WT = false>
 __global__ __launch_bounds__(NT, 512 / NT) void k_rowfwd_cplx(const JobDesc* __restrict__ jobs,
                                                         const float2* __restrict__ values,
                                                         float2* __restrict__ ws_a,
-                                                        const float2* __restrict__ tw_glob, int P, int CH) {
+                                                        const float2* __restrict__ tw_glob, int P, int CH,
+                                                        const float* __restrict__ weight, float scale) {
   constexpr int N = R * R;
   constexpr int GPB = NT / R;          // rows per row block
   __shared__ float2 tw[N];
@@ -548,18 +552,25 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowfwd_cplx(const JobDesc* __r
   const int y0 = wg.rbw * GPB;
   const int y = y0 + grp;
   pk2 v[R];
-  complex_load_row<R>(v, values + (((size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q) * N + y) * N, t);
+  const float2* row = values + (((size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q) * N + y) * N;
+  if constexpr (WT)
+    complex_load_row_weighted<R>(v, row, weight + (((size_t)jb.env * (CH / P) + jb.group) * N + y) * N, scale, t);
+  else
+    complex_load_row<R>(v, row, t);
   __syncthreads();  // tw visible
 
   float2* base = ws_a + ((size_t)j * P + 2 * wg.q) * plane_a_elems(R);
   rowfwd_emit<R, NT, HBX_PRECISION_F32>(v, t, grp, lane_base, y0, lds, tw, base);
 }
 
-// N = 1024: k_rowfwd32's three workgroups per CU
+// N = 1024: k_rowfwd32's three workgroups per CU (WT: 111 VGPRs against 112, the weights die before the
+// row FFT's temporaries are born; profiles/intensity_grad/resource_usage.txt)
+template <bool WT = false>
 __global__ __launch_bounds__(256, 3) void k_rowfwd32_cplx(const JobDesc* __restrict__ jobs,
                                                           const float2* __restrict__ values,
                                                           float2* __restrict__ ws_a,
-                                                          const float2* __restrict__ tw_glob, int P, int CH) {
+                                                          const float2* __restrict__ tw_glob, int P, int CH,
+                                                          const float* __restrict__ weight, float scale) {
   constexpr int R = 32, NT = 256, N = R * R;
   constexpr int GPB = NT / R;          // 8 rows per row block
   __shared__ float2 tw[N];
@@ -578,7 +589,11 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd32_cplx(const JobDesc* __restr
   const int y0 = wg.rbw * GPB;
   const int y = y0 + grp;
   pk2 v[R];
-  complex_load_row<R>(v, values + (((size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q) * N + y) * N, t);
+  const float2* row = values + (((size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q) * N + y) * N;
+  if constexpr (WT)
+    complex_load_row_weighted<R>(v, row, weight + (((size_t)jb.env * (CH / P) + jb.group) * N + y) * N, scale, t);
+  else
+    complex_load_row<R>(v, row, t);
   __syncthreads();  // tw visible
 
   float2* base = ws_a + ((size_t)j * P + 2 * wg.q) * plane_a_elems(R);
@@ -1473,16 +1488,28 @@ static hipError_t launch_passes(const PlanDev& pd, const JobDesc* jobs, int n_jo
   if (pd.complex_values && (SK != HBX_PRECISION_F32 || pd.plane_mode != kPlanesOff || pd.actions || pd.walk_phase ||
                             pd.real_values || (!pd.complex_field && !pd.real_part)))
     return hipErrorInvalidValue;   // before the timer opens a slot, as run_jobs_896
+  if (pd.complex_weight && !pd.complex_values) return hipErrorInvalidValue;   // the weight scales complex samples only
   {
     if (tm) tm->begin(0, st);
     if (pd.complex_values) {   // complex field: the real kernels' geometry, wg.q = the complex plane
       const unsigned blocks = (unsigned)n_jobs * (P / 2) * (N / (kRowNT<R> / R));
-      if constexpr (R == 32)
-        hipLaunchKernelGGL(k_rowfwd32_cplx, dim3(blocks), dim3(256), 0, st, jobs, pd.complex_values, pd.ws_a, pd.tw,
-                           P, CH);
-      else
-        hipLaunchKernelGGL((k_rowfwd_cplx<R, kRowNT<R>>), dim3(blocks), dim3(kRowNT<R>), 0, st, jobs,
-                           pd.complex_values, pd.ws_a, pd.tw, P, CH);
+      const float* cw = pd.complex_weight;   // hbx_simulate_complex_weighted: u = (scale * weight) * values
+      const float cs = pd.complex_scale;
+      if constexpr (R == 32) {
+        if (cw)
+          hipLaunchKernelGGL(k_rowfwd32_cplx<true>, dim3(blocks), dim3(256), 0, st, jobs, pd.complex_values, pd.ws_a,
+                             pd.tw, P, CH, cw, cs);
+        else
+          hipLaunchKernelGGL(k_rowfwd32_cplx<false>, dim3(blocks), dim3(256), 0, st, jobs, pd.complex_values, pd.ws_a,
+                             pd.tw, P, CH, cw, cs);
+      } else {
+        if (cw)
+          hipLaunchKernelGGL((k_rowfwd_cplx<R, kRowNT<R>, true>), dim3(blocks), dim3(kRowNT<R>), 0, st, jobs,
+                             pd.complex_values, pd.ws_a, pd.tw, P, CH, cw, cs);
+        else
+          hipLaunchKernelGGL((k_rowfwd_cplx<R, kRowNT<R>, false>), dim3(blocks), dim3(kRowNT<R>), 0, st, jobs,
+                             pd.complex_values, pd.ws_a, pd.tw, P, CH, cw, cs);
+      }
     } else if (pd.real_values) {   // real-valued field: one row block per workgroup at every launch size
       if (SK != HBX_PRECISION_F32 || pair || pd.actions || pd.walk_phase) return hipErrorInvalidValue;
       const unsigned blocks = (unsigned)n_jobs * (P / 2) * (N / (kRowNT<R> / R));

@@ -248,11 +248,15 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd896_real(const JobDesc* __rest
 // Pass 1 on complex fields (hbx_simulate_complex): values[env][CH / 2][896][896] complex64.
 // complex_load_row puts the complex sample of pixel x = t + 32 jj (jj < 28) into v[jj] as it is and
 // zeros above; rowfwd896_emit then leaves the half spectra of Re u_q and Im u_q in A planes 2q and
-// 2q + 1.  k_rowfwd896_real's geometry, wg.q = the complex plane.
+// 2q + 1.  k_rowfwd896_real's geometry, wg.q = the complex plane.  WT (hbx_simulate_complex_weighted):
+// complex_load_row_weighted scales the 28 loaded samples by scale * weight[env][group][y][x]; slots >= 28
+// stay zero.
+template <bool WT = false>
 __global__ __launch_bounds__(256, 3) void k_rowfwd896_cplx(const JobDesc* __restrict__ jobs,
                                                            const float2* __restrict__ values,
                                                            float2* __restrict__ ws_a,
-                                                           const float2* __restrict__ tw_glob, int P, int CH) {
+                                                           const float2* __restrict__ tw_glob, int P, int CH,
+                                                           const float* __restrict__ weight, float scale) {
   __shared__ float2 tw[kN];
   __shared__ __attribute__((aligned(16))) float lds[kRowfwd896Scr];
   stage_twiddles<kN, 256>(tw, tw_glob);
@@ -267,7 +271,11 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd896_cplx(const JobDesc* __rest
   const int y0 = wg.rbw * kGPB;
   const int y = y0 + grp;
   float2 v[32];
-  complex_load_row<kR, kL>(v, values + (((size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q) * kN + y) * kN, t);
+  const float2* row = values + (((size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q) * kN + y) * kN;
+  if constexpr (WT)
+    complex_load_row_weighted<kR, kL>(v, row, weight + (((size_t)jb.env * (CH / P) + jb.group) * kN + y) * kN, scale, t);
+  else
+    complex_load_row<kR, kL>(v, row, t);
   __syncthreads();  // tw visible
 
   float2* base = ws_a + ((size_t)j * P + 2 * wg.q) * kPlaneA;
@@ -659,10 +667,15 @@ hipError_t run_jobs_896(const PlanDev& pd, const JobDesc* jobs, int n_jobs, cons
   if (pd.complex_values && (pair || pd.store_kind != HBX_PRECISION_F32 || pd.real_values ||
                             pd.plane_mode != kPlanesOff || (!pd.complex_field && !pd.real_part)))
     return hipErrorInvalidValue;
+  if (pd.complex_weight && !pd.complex_values) return hipErrorInvalidValue;   // the weight scales complex samples only
   if (tm) tm->begin(0, st);
   if (pd.complex_values)
-    hipLaunchKernelGGL(k_rowfwd896_cplx, dim3((unsigned)n_jobs * (P / 2) * kRB), dim3(256), 0, st, jobs,
-                       pd.complex_values, pd.ws_a, pd.tw, P, CH);
+    if (pd.complex_weight)   // hbx_simulate_complex_weighted: u = (scale * weight) * values
+      hipLaunchKernelGGL(k_rowfwd896_cplx<true>, dim3((unsigned)n_jobs * (P / 2) * kRB), dim3(256), 0, st, jobs,
+                         pd.complex_values, pd.ws_a, pd.tw, P, CH, pd.complex_weight, pd.complex_scale);
+    else
+      hipLaunchKernelGGL(k_rowfwd896_cplx<false>, dim3((unsigned)n_jobs * (P / 2) * kRB), dim3(256), 0, st, jobs,
+                         pd.complex_values, pd.ws_a, pd.tw, P, CH, pd.complex_weight, pd.complex_scale);
   else if (pd.real_values)
     hipLaunchKernelGGL(k_rowfwd896_real, dim3((unsigned)n_jobs * (P / 2) * kRB), dim3(256), 0, st, jobs,
                        pd.real_values, pd.ws_a, pd.tw, P, CH);

@@ -171,6 +171,32 @@ __device__ __forceinline__ void complex_load_row(V (&v)[R], const float2* __rest
   for (int jj = L; jj < R; ++jj) v[jj] = V{0.f, 0.f};
 }
 
+// Weighted complex fields (hbx_simulate_complex_weighted): complex_load_row's samples times the
+// real image scale * wrow[x], wrow = the [N] f32 weight row of the plane's colour group.  All L
+// sample loads and all L weight loads are issued before the first use (as real_load_row's two
+// planes); the samples are read once (non-temporal), the weight row is re-read by every complex
+// plane of its group and keeps the default cache policy.  Three f32 multiplies per sample, in this
+// order and never contracted (there is nothing to add): m = scale * w, re * m, im * m.
+template <int R, int L = R, class V>
+__device__ __forceinline__ void complex_load_row_weighted(V (&v)[R], const float2* __restrict__ row,
+                                                          const float* __restrict__ wrow, float scale, int t) {
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  const f32x2* r2 = reinterpret_cast<const f32x2*>(row);
+  f32x2 s[L];
+  float w[L];
+#pragma unroll
+  for (int jj = 0; jj < L; ++jj) s[jj] = __builtin_nontemporal_load(r2 + t + R * jj);
+#pragma unroll
+  for (int jj = 0; jj < L; ++jj) w[jj] = wrow[t + R * jj];
+#pragma unroll
+  for (int jj = 0; jj < L; ++jj) {
+    const float m = scale * w[jj];
+    v[jj] = V{s[jj].x * m, s[jj].y * m};
+  }
+#pragma unroll
+  for (int jj = L; jj < R; ++jj) v[jj] = V{0.f, 0.f};
+}
+
 // ---------------------------------------------------------------------------
 // Staged slot-tile stores of the column passes (k_col2 at N = 1024 / 256, k_col896 since r04):
 // the output line sets of a block (TL lines: group g = slot g of slot tile st, TileB) go out

@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = (
     "hbx_planes_fill", "hbx_eval_flips_planes", "hbx_commit_flip_planes", "hbx_dbs_walk_planes",
     "hbx_dbs_walk_planes_fill", "hbx_host_alloc", "hbx_host_free", "hbx_pack_mask", "hbx_rel_stats",
     "hbx_simulate_real", "hbx_propagate_real", "hbx_simulate_complex",
+    "hbx_simulate_complex_weighted", "hbx_intensity_real",
 )
 NUM_PASSES = 5
 PASS_NAMES = ("k_rowfwd", "k_col", "k_rowinv", "k_psf_eval", "k_psf_commit")
@@ -129,6 +130,8 @@ def _declare(lib):
     lib.hbx_simulate_real.argtypes = [VP, VP, I32, VP, VP, VP]
     lib.hbx_propagate_real.argtypes = [VP, VP, VP, I32, VP, VP, VP, VP]
     lib.hbx_simulate_complex.argtypes = [VP, VP, I32, VP, VP, VP]
+    lib.hbx_simulate_complex_weighted.argtypes = [VP, VP, VP, C.c_float, I32, VP, VP, VP]
+    lib.hbx_intensity_real.argtypes = [VP, VP, I32, VP, VP]
     lib.hbx_flip_map.argtypes = [VP, VP, VP, VP, VP, VP]
     lib.hbx_eval_flips_psf.argtypes = [VP, VP, VP, VP, VP, VP, VP, I32, VP, VP, VP]
     lib.hbx_commit_flip_psf.argtypes = [VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, I32, VP]

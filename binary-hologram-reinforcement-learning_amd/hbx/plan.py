@@ -315,12 +315,18 @@ class Plan:
         return torch.view_as_complex(field), inten
 
     def simulate_complex(self, values: torch.Tensor, want_field: bool = True, want_real: bool = False,
-                         stream=None):
+                         weight: Optional[torch.Tensor] = None, scale: float = 1.0, stream=None):
         """`simulate` on a complex field (hbx_simulate_complex): `values` complex64
         [B, CH/2, H, W] are the field samples themselves; a plan with CH real planes carries CH/2
         complex planes.  Returns (field complex64 [B, CH/2, H, W] | None, real_part float32
         [B, CH/2, H, W] | None); real_part is field.real, written without the complex plane when
-        want_field is off (the gradient of a real input: the plan for -z is the adjoint)."""
+        want_field is off (the gradient of a real input: the plan for -z is the adjoint).
+
+        weight float32 [B, G, H, W] (hbx_simulate_complex_weighted): the first pass propagates
+        (scale * weight[b, g]) * values[b, c] for the complex planes c of group g, applied as it
+        loads the samples -- with the saved field as values, the intensity's incoming gradient as
+        weight and scale = 2 / planes this is the gradient of the plane-mean intensity.  weight
+        None is hbx_simulate_complex itself (scale is then not applied)."""
         if not (want_field or want_real):
             raise ValueError("simulate_complex: want_field and want_real are both off")
         n = values.shape[0] if isinstance(values, torch.Tensor) and values.dim() else 0
@@ -330,11 +336,31 @@ class Plan:
         # a lazily conjugated / negated view (values.conj()) shares the unconjugated memory the
         # kernel would read: materialise it (a copy only when such a bit is set)
         values = values.resolve_conj().resolve_neg()
+        if weight is not None:
+            _need(weight, "weight", torch.float32, (n, c.groups, c.height, c.width), self.device)
+            weight = weight.resolve_neg()
         field = torch.empty(shape + (2,), dtype=torch.float32, device=self.device) if want_field else None
         real = torch.empty(shape, dtype=torch.float32, device=self.device) if want_real else None
-        _lib.check(self.lib.hbx_simulate_complex(self._h, _ptr(values), n, _ptr(field), _ptr(real),
-                                                 _stream(stream)), "hbx_simulate_complex")
+        if weight is None:
+            _lib.check(self.lib.hbx_simulate_complex(self._h, _ptr(values), n, _ptr(field), _ptr(real),
+                                                     _stream(stream)), "hbx_simulate_complex")
+        else:
+            _lib.check(self.lib.hbx_simulate_complex_weighted(self._h, _ptr(values), _ptr(weight), float(scale), n,
+                                                              _ptr(field), _ptr(real), _stream(stream)),
+                       "hbx_simulate_complex_weighted")
         return (torch.view_as_complex(field) if want_field else None), real
+
+    def intensity_real(self, values: torch.Tensor, stream=None) -> torch.Tensor:
+        """Plane-mean intensity float32 [B, G, H, W] of a real-valued field (hbx_intensity_real):
+        `simulate_real(.., want_intensity=True)`'s intensity, bit for bit, with no field written."""
+        n = values.shape[0] if isinstance(values, torch.Tensor) and values.dim() else 0
+        c = self.cfg
+        _need(values, "values", torch.float32, self.values_shape(n), self.device)
+        values = values.resolve_neg()              # a lazily negated view shares the un-negated memory
+        inten = torch.empty((n, c.groups, c.height, c.width), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.hbx_intensity_real(self._h, _ptr(values), n, _ptr(inten), _stream(stream)),
+                   "hbx_intensity_real")
+        return inten
 
     def propagate_real(self, values: torch.Tensor, target: torch.Tensor, want_intensity: bool = True,
                        stream=None):

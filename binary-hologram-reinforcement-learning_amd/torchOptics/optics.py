@@ -34,6 +34,12 @@ fallback on either):
   non-differentiable and builds no graph; ``relativeLoss(.., tm.get_PSNR)`` returns a float
   (its ``F.mse_loss`` form is torch ops and differentiates by itself).
 
+``intensity`` returns the plane-mean intensity mean_p |A u_p|^2 per colour group -- what every loss
+of the project is built on -- on the continuous path: several wavelengths in one call, no field
+written when no gradient is wanted (hbx_intensity_real), and with a gradient request a backward
+pass that is one hbx_simulate_complex_weighted on the plan for -z (the saved field times
+(2 / P) grad_output, formed in the first pass's load).
+
 The physics follows the assumptions documented in DESIGN.md (the original torchOptics is
 absent and unpinned): no padding; exact angular spectrum and amplitude field unless
 ``tf="fresnel"`` / ``field="phase"`` select the plan's other switches.  relativeLoss uses the
@@ -53,7 +59,7 @@ from hbx import _lib
 
 from . import metrics as _metrics
 
-__all__ = ["Tensor", "simulate", "relativeLoss", "imread", "check_binary"]
+__all__ = ["Tensor", "simulate", "intensity", "relativeLoss", "imread", "check_binary"]
 
 
 class Tensor(torch.Tensor):
@@ -102,14 +108,18 @@ def _switch(value, names: Dict[str, int], what: str) -> int:
     raise ValueError(f"{what} must be one of {sorted(names)} (or the hbx._lib constant), got {value!r}")
 
 
-def _plan_for(h: int, w: int, planes: int, wl: float, dx: float, dy: float, z: float, n: int, dev: int,
+def _plan_for(h: int, w: int, planes: int, wl, dx: float, dy: float, z: float, n: int, dev: int,
               tf: int = _lib.TF_ASM, field: int = _lib.FIELD_AMPLITUDE):
-    key = (h, w, planes, float(wl), float(dx), float(dy), float(z), dev, tf, field)
+    """The cached plan of `planes` real planes per group; wl: one wavelength, or a tuple of G (one
+    colour group each, tt.intensity); n: envs per launch (the plan holds n * G jobs)."""
+    wls = tuple(float(v) for v in wl) if isinstance(wl, (tuple, list)) else (float(wl),)
+    groups = len(wls)
+    key = (h, w, groups, planes, wls, float(dx), float(dy), float(z), dev, tf, field)
     p = _PLANS.get(key)
-    if p is None or p.max_jobs < n:
-        cfg = hbx.OpticsConfig(h, w, 1, planes, (float(wl),), float(dx), float(dy), float(z),
+    if p is None or p.max_jobs < n * groups:
+        cfg = hbx.OpticsConfig(h, w, groups, planes, wls, float(dx), float(dy), float(z),
                                tf, field, _lib.REL_LSQ, 1.0)
-        p = hbx.Plan(cfg, max_jobs=max(n, 1), device=dev)
+        p = hbx.Plan(cfg, max_jobs=max(n, 1) * groups, device=dev)
         _PLANS[key] = p
     return p
 
@@ -288,6 +298,150 @@ def _simulate_continuous(t: torch.Tensor, wl, dx, dy, z, dev: int, tf_kind: int,
     if t.is_complex():
         return _propagate_complex(t, *geom)
     return _propagate_real(t, *geom)
+
+
+def _pad_real(t: torch.Tensor, cp: int) -> torch.Tensor:
+    """float32 contiguous [B, cp, H, W] of a real device tensor [B, C, H, W], cp = C or C + 1 (a
+    zero plane: the kernels take plane pairs)."""
+    b, c, h, w = t.shape
+    if cp == c:
+        return t.to(torch.float32).resolve_neg().contiguous()
+    vals = torch.zeros((b, cp, h, w), dtype=torch.float32, device=t.device)
+    vals[:, :c] = t
+    return vals
+
+
+def _plane_mean(field: torch.Tensor, groups: int) -> torch.Tensor:
+    """mean over each group's planes of |field|^2: complex [B, C, H, W] -> float32 [B, G, H, W]"""
+    b, c, h, w = field.shape
+    return torch.view_as_real(field).square().sum(-1).view(b, groups, c // groups, h, w).mean(2)
+
+
+class _Intensity(torch.autograd.Function):
+    """u -> I = mean_p |A u_p|^2 per colour group, A u = IFFT2(FFT2(u) H_g(z)).  With F = A u saved,
+    dL/du = A^H((2 / P) gI F): one hbx_simulate_complex_weighted of F on the plan for -z (twice the
+    real planes per group), whose first pass applies (2 / P) gI as it loads F -- the complex
+    tensor (2 / P) gI F is never written.  A real u receives the real part (the only output
+    written), a complex u the field.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, t, geom, groups, save_field):
+        wls, dx, dy, z, dev, tf_kind = geom
+        b, c, h, w = t.shape
+        ctx.geom, ctx.groups, ctx.in_dtype, ctx.planes = geom, groups, t.dtype, c
+        if t.is_complex():
+            plan = _plan_for(h, w, 2 * c // groups, wls, dx, dy, z, b, dev, tf_kind)
+            field, _ = plan.simulate_complex(t.to(torch.complex64).resolve_conj().resolve_neg().contiguous())
+            ctx.save_for_backward(field)
+            return _plane_mean(field, groups)
+        cp = c + (c % 2)
+        vals = _pad_real(t, cp)
+        plan = _plan_for(h, w, cp // groups, wls, dx, dy, z, b, dev, tf_kind)
+        if save_field:
+            field, inten = plan.simulate_real(vals, want_intensity=True)
+            ctx.save_for_backward(field)
+        else:
+            inten = plan.intensity_real(vals)
+            ctx.save_for_backward(t)
+        ctx.recompute = not save_field
+        return inten * (cp / c) if cp != c else inten      # the kernel's mean counts the zero plane
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        wls, dx, dy, z, dev, tf_kind = ctx.geom
+        groups, c = ctx.groups, ctx.planes
+        saved, = ctx.saved_tensors
+        b, _, h, w = saved.shape
+        cplx = ctx.in_dtype.is_complex
+        if not cplx and ctx.recompute:                     # save_field=False: the field again, from the input
+            cp = c + (c % 2)
+            field, _ = _plan_for(h, w, cp // groups, wls, dx, dy, z, b, dev, tf_kind).simulate_real(_pad_real(saved, cp))
+        else:
+            field = saved
+        cf = field.shape[1]                                # complex planes of the adjoint: C, or C + 1 padded
+        gi = grad_output.to(torch.float32).resolve_neg().contiguous()
+        adj = _plan_for(h, w, 2 * cf // groups, wls, dx, dy, -z, b, dev, tf_kind)
+        gf, gr = adj.simulate_complex(field, want_field=cplx, want_real=not cplx, weight=gi,
+                                      scale=2.0 / (c // groups))
+        grad = gf if cplx else gr
+        if cf != c:
+            grad = grad[:, :c]
+        return grad.to(ctx.in_dtype), None, None, None
+
+
+def intensity(x, z: float, tf="asm", field="amplitude", save_field: bool = True) -> torch.Tensor:
+    """Plane-mean intensity of the propagated field, the quantity every loss of the project goes
+    through: float32 [B, G, H, W] (or [G, H, W] for a 3-D x) with
+        I[b, g] = mean over the planes p of group g of |IFFT2(FFT2(u[b, p]) H_g(z))|^2,
+    what ``(tt.simulate(x, z, binary=False).abs() ** 2)`` averaged over each group's planes gives,
+    without leaving the HIP path.  The continuous path only: the samples are the field, as with
+    simulate(.., binary=False) (0 / 1 samples give the bit path's intensity); tf and field as there.
+
+    meta['wl'] is one wavelength (G = 1) or a tuple of G <= 4 wavelengths: the C planes are then G
+    colour groups of C / G planes in order (channel c belongs to group c // (C / G)), one plan and
+    one launch set for all of them -- the reference's RGB reconstruction (env_1024_24.py:149-166)
+    in one call.  C % G != 0 raises ValueError, and so does an odd C / G with G > 1; with G = 1 an
+    odd C is padded with a zero plane and the mean is still over the C planes given.
+
+    Without a gradient request no graph is built: real x goes through hbx_intensity_real, which
+    writes the intensity and no field; complex x, or field="phase" on real x (u = exp(i pi x),
+    formed with torch ops), through hbx_simulate_complex, with |.|^2 and the mean as torch ops.
+    If x requires grad the result carries a grad_fn whose backward pass is ONE
+    hbx_simulate_complex_weighted on the plan for -z: the saved field is read with (2 / P) times
+    the incoming gradient applied in the first pass's load, and a real x receives the real part
+    only (a float64 leaf a float64 gradient).  The forward of a real x takes the intensity the
+    last pass accumulates beside the field (hbx_simulate_real, one launch set).
+    save_field=True keeps the complex field for the backward pass (8 bytes per pixel and plane);
+    save_field=False (real x) keeps only x, writes no field in the forward pass and recomputes it
+    at the start of the backward pass.  No double backward."""
+    tf_kind = _switch(tf, _TF_NAMES, "tf")
+    field_kind = _switch(field, _FIELD_NAMES, "field")
+    meta = _meta_of(x)
+    wl = meta["wl"]
+    wls = tuple(float(v) for v in wl) if isinstance(wl, (tuple, list)) else (float(wl),)
+    groups = len(wls)
+    if not 1 <= groups <= _lib.MAX_GROUPS:
+        raise ValueError(f"intensity: 1 to {_lib.MAX_GROUPS} wavelengths, got {groups}")
+    dx, dy = meta.get("dx", (hbx.plan.PIXEL_PITCH,) * 2)
+    t = x.as_subclass(torch.Tensor) if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+    squeeze = t.dim() == 3
+    if squeeze:
+        t = t.unsqueeze(0)
+    if t.dim() != 4:
+        raise ValueError(f"intensity expects [B, C, H, W] or [C, H, W], got {tuple(t.shape)}")
+    c = t.shape[1]
+    if c == 0 or c % groups:
+        raise ValueError(f"intensity: {c} planes do not split into {groups} colour groups")
+    if groups > 1 and (c // groups) % 2:
+        raise ValueError(f"intensity: {groups} colour groups need an even number of planes each, got {c // groups}")
+    if t.is_complex() and field_kind != _lib.FIELD_AMPLITUDE:
+        raise ValueError("tt.intensity: a complex field is used as it is (field=\"amplitude\")")
+    if not torch.cuda.is_available():
+        raise RuntimeError("tt.intensity needs a ROCm GPU (libhbx.so)")
+    if t.is_cuda:
+        dev = t.device.index
+    else:
+        dev = torch.cuda.current_device()
+        t = t.to(f"cuda:{dev}")
+    if field_kind == _lib.FIELD_PHASE:
+        ph = t.to(torch.float32) * np.float32(np.pi)
+        t = torch.complex(torch.cos(ph), torch.sin(ph))   # torch ops: autograd carries du/dx
+    geom = (wls, dx, dy, z, dev, tf_kind)
+    b, _, h, w = t.shape
+    if t.requires_grad and torch.is_grad_enabled():
+        out = _Intensity.apply(t, geom, groups, bool(save_field))
+    elif t.is_complex():
+        plan = _plan_for(h, w, 2 * c // groups, wls, dx, dy, z, b, dev, tf_kind)
+        fld, _ = plan.simulate_complex(t.to(torch.complex64).resolve_conj().resolve_neg().contiguous())
+        out = _plane_mean(fld, groups)
+    else:
+        cp = c + (c % 2)
+        plan = _plan_for(h, w, cp // groups, wls, dx, dy, z, b, dev, tf_kind)
+        out = plan.intensity_real(_pad_real(t, cp))
+        if cp != c:
+            out = out * (cp / c)
+    return out[0] if squeeze else out
 
 
 def relativeLoss(x: torch.Tensor, y, fn: Callable, rel_scale="lsq") -> torch.Tensor:

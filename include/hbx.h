@@ -243,6 +243,37 @@ int hbx_propagate_real(hbx_plan_t plan, const float* values, const float* target
 int hbx_simulate_complex(hbx_plan_t plan, const float* values, int32_t n_env, float* field,
                          float* real_part, void* stream);
 
+/* (ABI v15, additive) hbx_simulate_complex on samples scaled by a real image per env and group:
+ *   u[b][c][y][x] = (scale * weight[b][g(c)][y][x]) * values[b][c][y][x],
+ *   g(c) = c / (P/2), the colour group of complex plane c
+ *   weight[B][G][H][W] float32 (HBX_ERR_INVALID when null)
+ * values, field and real_part are hbx_simulate_complex's, and so is every other rule (null
+ * arguments, n_env, HBX_PRECISION_F32 only, chunking by max_jobs, the four built sizes, the timer
+ * slots).  The first pass applies the weight as it loads the samples -- m = scale * w, then
+ * re * m and im * m, one float32 multiply each -- so the result equals hbx_simulate_complex on
+ * samples multiplied in that way bit for bit, and no weighted copy of values is written: the
+ * first pass reads 12 N^2 bytes per complex plane instead of 8 N^2, the rest is unchanged.
+ *
+ * This is the vector-Jacobian product of the plane-mean intensity I = mean_p |A u_p|^2 (P planes
+ * u_p per group, A u = IFFT2(FFT2(u) H_g)): with the saved field A u_p as values, the incoming
+ * gradient gI[B][G][H][W] as weight and scale = 2/P, on the plan for -z that carries 2P real
+ * planes (P complex planes) per group,
+ *   for real u    dL/du = real_part of hbx_simulate_complex_weighted(field, gI, 2/P),
+ *   for complex u dL/du = field of the same call (the conjugate-gradient convention, d/d conj u
+ *                         times two, which is what torch.autograd uses). */
+int hbx_simulate_complex_weighted(hbx_plan_t plan, const float* values, const float* weight,
+                                  float scale, int32_t n_env, float* field, float* real_part,
+                                  void* stream);
+
+/* (ABI v15, additive) The plane-mean intensity of a real-valued field and nothing else:
+ *   intensity[B][G][H][W] = mean_p |IFFT2(FFT2(u_p) H_g)|^2, values as hbx_simulate_real's.
+ * hbx_simulate_real must write the field and hbx_propagate_real needs a target; this call writes
+ * neither field nor statistics, and its intensity equals hbx_simulate_real's bit for bit.  Null
+ * values or intensity: HBX_ERR_INVALID; n_env, HBX_PRECISION_F32 only and chunking by max_jobs as
+ * hbx_simulate_real. */
+int hbx_intensity_real(hbx_plan_t plan, const float* values, int32_t n_env, float* intensity,
+                       void* stream);
+
 /* PSNR from per-channel statistics (tt.relativeLoss(.., tm.get_PSNR),
  * env.py:174): chan_stats[B][G][3] -> psnr[B]. */
 int hbx_psnr(hbx_plan_t plan, const double* chan_stats, int32_t n_env, double* psnr,
