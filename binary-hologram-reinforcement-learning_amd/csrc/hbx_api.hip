@@ -601,6 +601,97 @@ int hbx_intensity_real(hbx_plan_t p, const float* values, int32_t n_env, float* 
                         (hipStream_t)stream, nullptr, nullptr, 1, values);
 }
 
+// hbx_propagate_real that may also write the field: propagate_full takes the target and the field
+// at once (the last pass's general form, the one hbx_simulate_real launches)
+int hbx_evaluate_real(hbx_plan_t p, const float* values, const float* target, int32_t n_env, float* field,
+                      float* intensity, double* chan_stats, double* psnr, void* stream) {
+  int rc = check_plan(p);
+  if (rc) return rc;
+  if (n_env <= 0) return n_env == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "n_env");  // empty: null buffers allowed
+  if (!values || !target || !chan_stats) return fail(HBX_ERR_INVALID, "null buffer");
+  if ((rc = check_real_plan(p))) return rc;
+  HBX_HIP(hipSetDevice(p->device));
+  return propagate_full(p, nullptr, target, nullptr, n_env, intensity, chan_stats, psnr, nullptr,
+                        reinterpret_cast<float2*>(field), (hipStream_t)stream, nullptr, nullptr, 1, values);
+}
+
+// simulate_complex's chunk loop with the last pass's statistics form; three chunk strides: complex
+// planes G (P/2) N^2, images G N^2, statistics 3 G.  The jobs are the plan's constant table (ids
+// chunk-local, job j = env j / G, group j % G), so the job-major intensity rows are the caller's
+// [env][G][N][N] of the chunk: the last pass writes them in place, nothing to scatter
+int hbx_evaluate_complex(hbx_plan_t p, const float* values, const float* target, int32_t n_env, float* field,
+                         float* intensity, double* chan_stats, double* psnr, void* stream) {
+  int rc = check_plan(p);
+  if (rc) return rc;
+  if (n_env <= 0) return n_env == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "n_env");
+  if (!values) return fail(HBX_ERR_INVALID, "null buffer");
+  if ((target == nullptr) != (chan_stats == nullptr))
+    return fail(HBX_ERR_INVALID, "target and chan_stats are given together or not at all");
+  if (!target && (!intensity || psnr))
+    return fail(HBX_ERR_INVALID, "without a target: intensity is the output, and there is no psnr");
+  if ((rc = check_real_plan(p, true))) return rc;
+  HBX_HIP(hipSetDevice(p->device));
+  hipStream_t st = (hipStream_t)stream;
+  const PlanDev& pd = p->pd;
+  const int G = pd.G;
+  const int chunk = p->max_jobs / G;
+  const size_t hw = (size_t)pd.N * pd.N;
+  const size_t per_env = (size_t)G * (pd.P / 2) * hw;   // complex planes x pixels
+  EnvDev dummy;
+  std::memset(&dummy, 0, sizeof(dummy));
+  for (int i0 = 0; i0 < n_env; i0 += chunk) {
+    const int n = std::min(chunk, n_env - i0);
+    PlanDev pdx = pd;
+    pdx.complex_values = reinterpret_cast<const float2*>(values) + (size_t)i0 * per_env;
+    pdx.complex_field = field ? reinterpret_cast<float2*>(field) + (size_t)i0 * per_env : nullptr;
+    pdx.complex_stats = 1;
+    HBX_HIP(hbx::run_jobs(pdx, p->full_jobs, n * G, nullptr, target ? target + (size_t)i0 * G * hw : nullptr,
+                          intensity ? intensity + (size_t)i0 * G * hw : nullptr, nullptr, st));
+    if (chan_stats)
+      HBX_HIP(hbx::launch_full_finalize(p->full_jobs, pd.job_stats, n, G, chan_stats + (size_t)i0 * G * 3,
+                                        psnr ? psnr + i0 : nullptr, pixel_count(p), p->optics.rel_scale,
+                                        p->optics.peak, dummy, 0, st));
+  }
+  return HBX_OK;
+}
+
+namespace {
+int check_loss_kind(int32_t kind, int32_t rel_scale) {
+  if (kind != HBX_LOSS_MSE && kind != HBX_LOSS_PSNR) return fail(HBX_ERR_INVALID, "kind: HBX_LOSS_MSE or HBX_LOSS_PSNR");
+  if (rel_scale != HBX_REL_NONE && rel_scale != HBX_REL_LSQ)
+    return fail(HBX_ERR_INVALID, "rel_scale: HBX_REL_NONE or HBX_REL_LSQ");
+  return HBX_OK;
+}
+}  // namespace
+
+int hbx_loss(hbx_plan_t p, const double* chan_stats, int32_t n_env, int32_t kind, int32_t rel_scale, double* loss,
+             void* stream) {
+  int rc = check_plan(p);
+  if (rc) return rc;
+  if ((rc = check_loss_kind(kind, rel_scale))) return rc;
+  if (n_env <= 0) return n_env == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "n_env");
+  if (!chan_stats || !loss) return fail(HBX_ERR_INVALID, "null buffer");
+  HBX_HIP(hipSetDevice(p->device));
+  HBX_HIP(hbx::launch_loss(chan_stats, n_env, p->pd.G, kind, rel_scale, pixel_count(p), p->optics.peak, loss,
+                           (hipStream_t)stream));
+  return HBX_OK;
+}
+
+int hbx_loss_weight(hbx_plan_t p, const float* intensity, const float* target, const double* chan_stats,
+                    const double* grad_loss, int32_t n_env, int32_t kind, int32_t rel_scale, float* weight,
+                    void* stream) {
+  int rc = check_plan(p);
+  if (rc) return rc;
+  if ((rc = check_loss_kind(kind, rel_scale))) return rc;
+  if (n_env <= 0) return n_env == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "n_env");
+  if (!intensity || !target || !chan_stats || !weight) return fail(HBX_ERR_INVALID, "null buffer");
+  HBX_HIP(hipSetDevice(p->device));
+  HBX_HIP(hbx::launch_loss_weight(intensity, target, chan_stats, grad_loss, n_env, p->pd.G,
+                                  (size_t)p->pd.N * p->pd.N, kind, rel_scale, pixel_count(p), weight,
+                                  (hipStream_t)stream));
+  return HBX_OK;
+}
+
 int hbx_psnr(hbx_plan_t p, const double* chan_stats, int32_t n_env, double* psnr, void* stream) {
   int rc = check_plan(p);
   if (rc) return rc;

@@ -212,8 +212,9 @@ struct PlanDev {
   // (ABI v15, additive) full propagation of a complex field (hbx_simulate_complex):
   // [env][G*P/2][N][N] complex64 samples the first pass reads, complex plane q into plane-pair slot
   // q; the last pass recombines each pair and writes complex_field [env][G*P/2][N][N] complex64
-  // and / or real_part [env][G*P/2][N][N] f32 (at least one non-null) and nothing else: no
-  // intensity, partials or statistics.  f32 intermediates, no plane cache, no actions, no walk
+  // and / or real_part [env][G*P/2][N][N] f32 (at least one non-null) and nothing else -- intensity,
+  // partials and statistics only with complex_stats below.  f32 intermediates, no plane cache, no
+  // actions, no walk
   const float2* complex_values = nullptr;
   // (ABI v15, additive) hbx_simulate_complex_weighted: [env][G][N][N] f32, non-null only with
   // complex_values; the first pass propagates (complex_scale * complex_weight[env][group]) * values
@@ -221,6 +222,12 @@ struct PlanDev {
   float complex_scale = 1.0f;
   float2* complex_field = nullptr;
   float* real_part = nullptr;
+  // (ABI v15, additive) hbx_evaluate_complex: 1 with complex_values = the last pass also accumulates
+  // |F_q|^2 over the group's P/2 complex planes and runs the real last pass's tail -- the plane-mean
+  // intensity to run_jobs' inten_out [job][N][N] (job-major; nullable) and the partials against
+  // run_jobs' target (null: the zero row, nothing reduced).  complex_field and real_part may then
+  // both be null
+  int complex_stats = 0;
 };
 constexpr int kPlanesOff = 0, kPlanesFill = 1, kPlanesStep = 2;
 
@@ -380,5 +387,12 @@ hipError_t launch_pack_mask(const void* src, int kind, int64_t n_words, int mode
 int rel_partial_slots();
 hipError_t launch_rel_stats(const void* x, const void* y, int kind, int64_t n, double count, int rel_scale,
                             double peak, double* part, double* out, hipStream_t st);
+// (ABI v15, additive) hbx_pack.hip: chan_stats[n][G][3] -> loss[n] (kind HBX_LOSS_*), and the
+// loss's gradient with respect to the intensity, weight[n][G][hw] = a_b I + c_b T
+hipError_t launch_loss(const double* chan_stats, int n, int G, int kind, int rel_scale, double count, double peak,
+                       double* loss, hipStream_t st);
+hipError_t launch_loss_weight(const float* inten, const float* target, const double* chan_stats,
+                              const double* grad_loss, int n, int G, size_t hw, int kind, int rel_scale, double count,
+                              float* weight, hipStream_t st);
 
 }  // namespace hbx

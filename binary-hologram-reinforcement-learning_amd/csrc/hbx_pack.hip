@@ -14,6 +14,9 @@
 //   DBS_1024_24.py:332) as sufficient statistics sum xy, sum x^2, sum y^2 in f64 (the products
 //   formed in f64, as torch's x.double() * y.double()), a fixed-order two-stage reduction
 //   (deterministic), then the same PSNR / MSE formula as the env kernels (psnr_from).
+// k_loss / k_loss_weight: the same loss (env.py:131-132,174) per env from the statistics the last
+//   pass left, and its gradient with respect to the intensity, weight = a_b I + c_b T: one
+//   streaming pass, 8 bytes read and 4 written per pixel, no host wait (hbx_loss, hbx_loss_weight).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -161,7 +164,103 @@ __global__ __launch_bounds__(64) void k_rel_final(const double* __restrict__ par
   }
 }
 
+// the relative MSE as k_rel_final and psnr_from (hbx_internal.hpp) form it: the same expressions in the
+// same order (k_rel_final keeps its own copy: its instructions are those of the build before this one)
+__device__ __forceinline__ double rel_mse_from(double sxy, double sxx, double syy, double count, int rel_scale) {
+  if (rel_scale == HBX_REL_LSQ) return (sxx > 0.0) ? (syy - sxy * sxy / sxx) / count : syy / count;
+  return (sxx - 2.0 * sxy + syy) / count;
+}
+
+// an env's sums over its G groups, in k_psnr's order
+__device__ __forceinline__ void env_sums(const double* __restrict__ chan_stats, int b, int G, double& sxy,
+                                         double& sxx, double& syy) {
+  sxy = 0.0; sxx = 0.0; syy = 0.0;
+  for (int g = 0; g < G; ++g) {
+    const double* s = chan_stats + ((size_t)b * G + g) * 3;
+    sxy += s[0]; sxx += s[1]; syy += s[2];
+  }
+}
+
+// hbx_loss: chan_stats[B][G][3] -> loss[B], the relative MSE or its PSNR
+__global__ void k_loss(const double* __restrict__ chan_stats, int n, int G, int kind, int rel_scale, double count,
+                       double peak, double* __restrict__ loss) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= n) return;
+  double sxy, sxx, syy;
+  env_sums(chan_stats, b, G, sxy, sxx, syy);
+  loss[b] = kind == HBX_LOSS_PSNR ? psnr_from(sxy, sxx, syy, count, rel_scale, peak)
+                                  : rel_mse_from(sxy, sxx, syy, count, rel_scale);
+}
+
+// hbx_loss_weight: weight = a_b I + c_b T, the gradient of env b's loss with respect to its
+// intensity (include/hbx.h has the formulas).  bx workgroups per env; a workgroup forms its env's two
+// coefficients in f64 from 3 G statistics -- uniform per workgroup, so scalar loads and no LDS --
+// rounds them to f32 once and streams kLossPer 16-byte pieces per thread
+constexpr int kLossPer = 4;
+__global__ __launch_bounds__(256) void k_loss_weight(const float4* __restrict__ inten, const float4* __restrict__ target,
+                                                     const double* __restrict__ chan_stats,
+                                                     const double* __restrict__ grad_loss, int G, int64_t n4,
+                                                     unsigned bx, int kind, int rel_scale, double count,
+                                                     float4* __restrict__ weight) {
+  const int b = blockIdx.x / bx;
+  double sxy, sxx, syy;
+  env_sums(chan_stats, b, G, sxy, sxx, syy);
+  double a, c;   // dMSE/dI = a I + c T
+  if (rel_scale == HBX_REL_LSQ) {
+    const double s = sxx > 0.0 ? sxy / sxx : 0.0;   // no scale to differentiate: a = c = 0
+    a = 2.0 * s * s / count;
+    c = sxx > 0.0 ? -2.0 * s / count : 0.0;
+  } else {
+    a = 2.0 / count;
+    c = -2.0 / count;
+  }
+  if (kind == HBX_LOSS_PSNR) {   // PSNR = 10 log10(peak^2 / MSE): dPSNR = -(10 / ln 10) dMSE / MSE
+    const double mse = rel_mse_from(sxy, sxx, syy, count, rel_scale);
+    const double f = mse > 0.0 ? -(10.0 / 2.302585092994045684) / mse : 0.0;
+    a *= f;
+    c *= f;
+  }
+  const double up = grad_loss ? grad_loss[b] : 1.0;
+  const float af = (float)(a * up), cf = (float)(c * up);
+  const int64_t base = (int64_t)b * n4;
+  const int64_t i0 = (int64_t)(blockIdx.x % bx) * (256 * kLossPer) + threadIdx.x;
+  float4 I[kLossPer], T[kLossPer];
+#pragma unroll
+  for (int k = 0; k < kLossPer; ++k) {
+    const int64_t i = i0 + 256 * k;
+    if (i < n4) {
+      I[k] = inten[base + i];
+      T[k] = target[base + i];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < kLossPer; ++k) {
+    const int64_t i = i0 + 256 * k;
+    if (i < n4)
+      weight[base + i] = make_float4(fmaf(af, I[k].x, cf * T[k].x), fmaf(af, I[k].y, cf * T[k].y),
+                                     fmaf(af, I[k].z, cf * T[k].z), fmaf(af, I[k].w, cf * T[k].w));
+  }
+}
+
 }  // namespace
+
+hipError_t launch_loss(const double* chan_stats, int n, int G, int kind, int rel_scale, double count, double peak,
+                       double* loss, hipStream_t st) {
+  hipLaunchKernelGGL(k_loss, dim3((n + 63) / 64), dim3(64), 0, st, chan_stats, n, G, kind, rel_scale, count, peak,
+                     loss);
+  return hipGetLastError();
+}
+
+hipError_t launch_loss_weight(const float* inten, const float* target, const double* chan_stats,
+                              const double* grad_loss, int n, int G, size_t hw, int kind, int rel_scale, double count,
+                              float* weight, hipStream_t st) {
+  const int64_t n4 = (int64_t)G * (int64_t)hw / 4;   // 16-byte pieces per env (N^2 is a multiple of 4)
+  const unsigned bx = (unsigned)((n4 + 256 * kLossPer - 1) / (256 * kLossPer));
+  hipLaunchKernelGGL(k_loss_weight, dim3(bx * (unsigned)n), dim3(256), 0, st,
+                     reinterpret_cast<const float4*>(inten), reinterpret_cast<const float4*>(target), chan_stats,
+                     grad_loss, G, n4, bx, kind, rel_scale, count, reinterpret_cast<float4*>(weight));
+  return hipGetLastError();
+}
 
 hipError_t launch_pack_mask(const void* src, int kind, int64_t n_words, int mode, double thr, uint64_t* bits,
                             int32_t* err, hipStream_t st) {

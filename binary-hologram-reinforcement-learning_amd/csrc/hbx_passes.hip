@@ -31,7 +31,8 @@
 //             behind LDS-only barriers) -> IFFT over kx -> |U|^2 -> plane
 //             mean -> f64 partials of (I*T, I^2, T^2) vs the target row   [read 8 N^2 per plane + 4 N^2]
 //             (complex fields: k_rowinv_d_cplx / k_rowinv_cplx add B planes 2q and i * 2q + 1 on load,
-//             one IFFT per complex plane, and store the field / its real part; nothing else)
+//             one IFFT per complex plane, and store the field / its real part; their statistics
+//             form, hbx_evaluate_complex, also sums |F_q|^2 and ends in the same plane mean and partials)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -1163,6 +1164,14 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv(const JobDesc* __restri
   rowinv_epilogue<R, GPB>(acc, P, G, jb, j, y, rb, grp, t, target, tmask, inten_out, inten_by_env, partial, red);
 }
 
+// an invalid job's row block in the statistics form of the complex last pass: neutral partials
+__device__ __forceinline__ void rowinv_zero_partial(double* __restrict__ partial, int j, int RB, int rb) {
+  if (threadIdx.x == 0) {
+    double* o = partial + ((size_t)j * RB + rb) * 3;
+    o[0] = 0.0; o[1] = 0.0; o[2] = 0.0;
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Pass 3 on complex fields (hbx_simulate_complex): recombine a plane pair
 // ---------------------------------------------------------------------------
@@ -1171,18 +1180,26 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv(const JobDesc* __restri
 // the pair is combined on load, v = B[2q] + i B[2q + 1], and ONE inverse FFT per complex plane gives
 // F_q, stored once: 8 N^2 bytes to field and / or 4 N^2 bytes of Re F_q to real_part (both
 // [env][CH / 2][N][N], either nullable).  No |.|^2, partials, plane cache or reconcile.
+// ST (hbx_evaluate_complex; off by default, and the kernels without it compile as before): every
+// plane's |F_q|^2 is also accumulated per pixel, acc += fmaf(re, re, im * im) as k_rowinv_d does, and
+// k_rowinv's tail (rowinv_epilogue) runs with Q = P / 2 as the plane count: the plane-mean intensity
+// row to inten_out [job][N][N], the f64 partials against the target row (tmask = 0: the zero row).
+// field_out and real_out may then both be null.
 //
 // N = 1024 / 256: k_rowinv_d's direct loads from the tiled B (RowinvLanes).
 // Plane 2q + 1 arrives in two halves of R / 2 values that are folded into v as they land, so the
 // kernel never holds two whole lines (the second register set that cost k_rowinv_d its second
 // block per CU).  N = 256 has the registers for a second line and keeps the next pair in flight
 // under this one's FFT, as k_rowinv_d does with the next plane.
-template <int R>
+template <int R, bool ST = false>
 __global__ __launch_bounds__(256, 2) void k_rowinv_d_cplx(const JobDesc* __restrict__ jobs,
                                                           const float2* __restrict__ ws_b,
                                                           const float2* __restrict__ tw_glob, int P, int G,
                                                           float2* __restrict__ field_out,
-                                                          float* __restrict__ real_out) {
+                                                          float* __restrict__ real_out,
+                                                          const float* __restrict__ target, size_t tmask,
+                                                          double* __restrict__ partial,
+                                                          float* __restrict__ inten_out) {
   constexpr int N = R * R, GPB = 256 / R, RB = N / GPB;
   __shared__ float2 tw[N];
   __shared__ float2 scratch[GPB * R * (R + 1)];
@@ -1194,7 +1211,10 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_d_cplx(const JobDesc* __restr
   const int rb = bid % RB;
   const int j = bid / RB;
   const JobDesc jb = jobs[j];
-  if (jb.env < 0) return;  // uniform per block
+  if (jb.env < 0) {  // uniform per block
+    if constexpr (ST) rowinv_zero_partial(partial, j, RB, rb);
+    return;
+  }
   const int y = rb * GPB + grp;
   const int Q = P / 2;                        // complex planes per group
   constexpr int PLB = N * N;                 // float2 per B plane
@@ -1218,8 +1238,17 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_d_cplx(const JobDesc* __restr
   };
   const PaddedScratch<R> sc{scratch + grp * R * (R + 1)};
   const size_t row0 = (((size_t)jb.env * G + jb.group) * Q * N + y) * N + t;   // complex plane 0, pixel x = t
+  float acc[ST ? R : 1];
+  if constexpr (ST) {
+#pragma unroll
+    for (int k = 0; k < R; ++k) acc[k] = 0.0f;
+  }
   auto finish_plane = [&](pk2 (&v)[R], int q) {
     fft_group<R, true>(v, t, sc, tw);
+    if constexpr (ST) {
+#pragma unroll
+      for (int k = 0; k < R; ++k) acc[k] += fmaf(v[k].x, v[k].x, v[k].y * v[k].y);
+    }
     const size_t row = row0 + (size_t)q * N * N;
     if (field_out) {
 #pragma unroll
@@ -1251,16 +1280,23 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_d_cplx(const JobDesc* __restr
       if (q + 1 < Q) load_pair(va, q + 1);   // uniform: no pair is read twice
     }
   }
+  if constexpr (ST) {
+    __shared__ double red[GPB][3];
+    rowinv_epilogue<R, GPB>(acc, Q, G, jb, j, y, rb, grp, t, target, tmask, inten_out, 0, partial, red);
+  }
 }
 
 // N = 64: k_rowinv's LDS tile transpose; both planes' shares of the tile are prefetched one pair
 // ahead and combined as they are written into the tile.
-template <int R, int NT>
+template <int R, int NT, bool ST = false>
 __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv_cplx(const JobDesc* __restrict__ jobs,
                                                         const float2* __restrict__ ws_b,
                                                         const float2* __restrict__ tw_glob, int P, int G,
                                                         float2* __restrict__ field_out,
-                                                        float* __restrict__ real_out) {
+                                                        float* __restrict__ real_out,
+                                                        const float* __restrict__ target, size_t tmask,
+                                                        double* __restrict__ partial,
+                                                        float* __restrict__ inten_out) {
   constexpr int N = R * R;
   constexpr int GPB = NT / R;          // rows per block
   constexpr int RB = N / GPB;
@@ -1279,7 +1315,10 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv_cplx(const JobDesc* __r
   const int rb = bid % RB;
   const int j = bid / RB;
   const JobDesc jb = jobs[j];
-  if (jb.env < 0) return;  // uniform per block
+  if (jb.env < 0) {  // uniform per block
+    if constexpr (ST) rowinv_zero_partial(partial, j, RB, rb);
+    return;
+  }
   const int y0 = rb * GPB;
   const int y = y0 + grp;
   const int Q = P / 2;
@@ -1299,6 +1338,11 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv_cplx(const JobDesc* __r
   };
   load_pair(0);
   const size_t row0 = (((size_t)jb.env * G + jb.group) * Q * N + y) * N + t;
+  float acc[ST ? R : 1];
+  if constexpr (ST) {
+#pragma unroll
+    for (int k = 0; k < R; ++k) acc[k] = 0.0f;
+  }
 
 #pragma unroll 1
   for (int q = 0; q < Q; ++q) {
@@ -1317,6 +1361,10 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv_cplx(const JobDesc* __r
     for (int jj = 0; jj < R; ++jj) v[jj] = to_pk(tile[tile_pos<R, GPB>(t + R * jj, grp)]);
     lds_barrier();  // tile consumed: reuse it as transpose scratch
     fft_group<R, true>(v, t, PaddedScratch<R>{tile + grp * R * (R + 1)}, tw);
+    if constexpr (ST) {
+#pragma unroll
+      for (int k = 0; k < R; ++k) acc[k] += fmaf(v[k].x, v[k].x, v[k].y * v[k].y);
+    }
     const size_t row = row0 + (size_t)q * N * N;
     if (field_out) {
 #pragma unroll
@@ -1326,6 +1374,10 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv_cplx(const JobDesc* __r
 #pragma unroll
       for (int k = 0; k < R; ++k) real_out[row + R * k] = v[k].x;
     }
+  }
+  if constexpr (ST) {
+    __shared__ double red[GPB][3];
+    rowinv_epilogue<R, GPB>(acc, Q, G, jb, j, y, rb, grp, t, target, tmask, inten_out, 0, partial, red);
   }
 }
 
@@ -1486,7 +1538,7 @@ static hipError_t launch_passes(const PlanDev& pd, const JobDesc* jobs, int n_jo
   const unsigned col_blocks = (unsigned)n_jobs * (pair ? 2 : P) * ((N / 2) / (GPB * col2_iters<R>()));
   const bool small = kTiledB<R> && rf_blocks < kSmallBlocks && col_blocks < kSmallBlocks;
   if (pd.complex_values && (SK != HBX_PRECISION_F32 || pd.plane_mode != kPlanesOff || pd.actions || pd.walk_phase ||
-                            pd.real_values || (!pd.complex_field && !pd.real_part)))
+                            pd.real_values || (!pd.complex_field && !pd.real_part && !pd.complex_stats)))
     return hipErrorInvalidValue;   // before the timer opens a slot, as run_jobs_896
   if (pd.complex_weight && !pd.complex_values) return hipErrorInvalidValue;   // the weight scales complex samples only
   {
@@ -1557,14 +1609,30 @@ static hipError_t launch_passes(const PlanDev& pd, const JobDesc* jobs, int n_jo
   {
     const unsigned blocks = (unsigned)n_jobs * (N / (kRowNT<R> / R));
     if (tm) tm->begin(2, st);
-    if (pd.complex_values) {   // recombine each plane pair; nothing to reduce
-      if constexpr (kTiledB<R>)
-        hipLaunchKernelGGL((k_rowinv_d_cplx<R>), dim3(blocks), dim3(256), 0, st, jobs, pd.ws_b, pd.tw, P, pd.G,
-                           pd.complex_field, pd.real_part);
-      else
-        hipLaunchKernelGGL((k_rowinv_cplx<R, kRowNT<R>>), dim3(blocks), dim3(kRowNT<R>), 0, st, jobs, pd.ws_b,
-                           pd.tw, P, pd.G, pd.complex_field, pd.real_part);
+    if (pd.complex_values) {   // recombine each plane pair
+      const float* tg = target ? target : pd.zero_row;
+      const size_t tmask = target ? ~(size_t)0 : (size_t)0;
+      if constexpr (kTiledB<R>) {
+        if (pd.complex_stats)
+          hipLaunchKernelGGL((k_rowinv_d_cplx<R, true>), dim3(blocks), dim3(256), 0, st, jobs, pd.ws_b, pd.tw, P,
+                             pd.G, pd.complex_field, pd.real_part, tg, tmask, pd.partial, inten_out);
+        else
+          hipLaunchKernelGGL((k_rowinv_d_cplx<R>), dim3(blocks), dim3(256), 0, st, jobs, pd.ws_b, pd.tw, P, pd.G,
+                             pd.complex_field, pd.real_part, tg, tmask, pd.partial, inten_out);
+      } else {
+        if (pd.complex_stats)
+          hipLaunchKernelGGL((k_rowinv_cplx<R, kRowNT<R>, true>), dim3(blocks), dim3(kRowNT<R>), 0, st, jobs,
+                             pd.ws_b, pd.tw, P, pd.G, pd.complex_field, pd.real_part, tg, tmask, pd.partial,
+                             inten_out);
+        else
+          hipLaunchKernelGGL((k_rowinv_cplx<R, kRowNT<R>>), dim3(blocks), dim3(kRowNT<R>), 0, st, jobs, pd.ws_b,
+                             pd.tw, P, pd.G, pd.complex_field, pd.real_part, tg, tmask, pd.partial, inten_out);
+      }
       if (tm) tm->end(2, n_jobs, st);
+      // hbx_evaluate_complex with a target: the statistics form left partials to reduce
+      if (pd.complex_stats && target)
+        hipLaunchKernelGGL(k_reduce_partials, dim3(n_jobs), dim3(64), 0, st, pd.partial, n_jobs,
+                           N / (kRowNT<R> / R), pd.job_stats);
       return hipGetLastError();
     }
     if constexpr (kTiledB<R>) {

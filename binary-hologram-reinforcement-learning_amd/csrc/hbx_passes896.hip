@@ -452,6 +452,47 @@ struct Rowinv896Lanes {
   }
 };
 
+// the last pass's tail (hbx_passes.hip rowinv_epilogue at 28 values per lane): plane mean, f64
+// partials of (I*T, I^2, T^2) against the target row (tmask = 0: the plan's zero row), fixed-order
+// reduction over the group's lanes and the block's rows
+__device__ __forceinline__ void rowinv896_epilogue(float (&acc)[kL], int P, int G, const JobDesc& jb, int j, int y,
+                                                   int rb, int grp, int t, const float* __restrict__ target,
+                                                   size_t tmask, float* __restrict__ inten_out, int inten_by_env,
+                                                   double* __restrict__ partial, double (&red)[kGPB][3]) {
+  const float invp = 1.0f / (float)P;
+  const float* trow = target + ((((size_t)jb.env * G + jb.group) * kN + y) * kN & tmask);
+  double sxy = 0.0, sxx = 0.0, syy = 0.0;
+#pragma unroll
+  for (int k = 0; k < kL; ++k) {
+    const float I = acc[k] * invp;
+    const float T = trow[t + kR * k];
+    sxy = fma((double)I, (double)T, sxy);
+    sxx = fma((double)I, (double)I, sxx);
+    syy = fma((double)T, (double)T, syy);
+    acc[k] = I;
+  }
+  if (inten_out) {
+    const size_t slot = inten_by_env ? (size_t)jb.env * G + jb.group : (size_t)j;
+    float* orow = inten_out + (slot * kN + y) * kN;
+#pragma unroll
+    for (int k = 0; k < kL; ++k) orow[t + kR * k] = acc[k];
+  }
+#pragma unroll
+  for (int off = kR / 2; off >= 1; off >>= 1) {
+    sxy += __shfl_xor(sxy, off, 64);
+    sxx += __shfl_xor(sxx, off, 64);
+    syy += __shfl_xor(syy, off, 64);
+  }
+  if (t == 0) { red[grp][0] = sxy; red[grp][1] = sxx; red[grp][2] = syy; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double a = 0.0, b = 0.0, cc = 0.0;
+    for (int g = 0; g < kGPB; ++g) { a += red[g][0]; b += red[g][1]; cc += red[g][2]; }
+    double* o = partial + ((size_t)j * kRB + rb) * 3;
+    o[0] = a; o[1] = b; o[2] = cc;
+  }
+}
+
 template <bool LEAN>
 __global__ __launch_bounds__(256, 2) void k_rowinv896(const JobDesc* __restrict__ jobs,
                                                       const float2* __restrict__ ws_b,
@@ -555,38 +596,7 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896(const JobDesc* __restrict_
     }
   }
 
-  const float invp = 1.0f / (float)P;
-  const float* trow = target + ((((size_t)jb.env * G + jb.group) * kN + y) * kN & tmask);
-  double sxy = 0.0, sxx = 0.0, syy = 0.0;
-#pragma unroll
-  for (int k = 0; k < kL; ++k) {
-    const float I = acc[k] * invp;
-    const float T = trow[t + kR * k];
-    sxy = fma((double)I, (double)T, sxy);
-    sxx = fma((double)I, (double)I, sxx);
-    syy = fma((double)T, (double)T, syy);
-    acc[k] = I;
-  }
-  if (inten_out) {
-    const size_t slot = inten_by_env ? (size_t)jb.env * G + jb.group : (size_t)j;
-    float* orow = inten_out + (slot * kN + y) * kN;
-#pragma unroll
-    for (int k = 0; k < kL; ++k) orow[t + kR * k] = acc[k];
-  }
-#pragma unroll
-  for (int off = kR / 2; off >= 1; off >>= 1) {
-    sxy += __shfl_xor(sxy, off, 64);
-    sxx += __shfl_xor(sxx, off, 64);
-    syy += __shfl_xor(syy, off, 64);
-  }
-  if (t == 0) { red[grp][0] = sxy; red[grp][1] = sxx; red[grp][2] = syy; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double a = 0.0, b = 0.0, cc = 0.0;
-    for (int g = 0; g < kGPB; ++g) { a += red[g][0]; b += red[g][1]; cc += red[g][2]; }
-    double* o = partial + ((size_t)j * kRB + rb) * 3;
-    o[0] = a; o[1] = b; o[2] = cc;
-  }
+  rowinv896_epilogue(acc, P, G, jb, j, y, rb, grp, t, target, tmask, inten_out, inten_by_env, partial, red);
 }
 
 // Pass 3 on complex fields (hbx_simulate_complex): B planes 2q and 2q + 1 hold the column-pass
@@ -594,11 +604,19 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896(const JobDesc* __restrict_
 // halves of 16 registers, so two whole lines are never live), ONE inverse FFT per complex plane, and
 // the plane F_q stored once to field_out and / or its real part to real_out, both
 // [env][CH / 2][896][896].  k_rowinv896's lane bases; no |.|^2, partials or plane cache.
+// ST (hbx_evaluate_complex; off by default, and that kernel compiles as before): |F_q|^2 is also
+// accumulated per pixel as k_rowinv896 does and its tail runs with Q = P / 2 as the plane count --
+// the plane-mean intensity row to inten_out [job][896][896] and the f64 partials against the target
+// row; field_out and real_out may then both be null.
+template <bool ST = false>
 __global__ __launch_bounds__(256, 2) void k_rowinv896_cplx(const JobDesc* __restrict__ jobs,
                                                            const float2* __restrict__ ws_b,
                                                            const float2* __restrict__ tw_glob, int P, int G,
                                                            float2* __restrict__ field_out,
-                                                           float* __restrict__ real_out) {
+                                                           float* __restrict__ real_out,
+                                                           const float* __restrict__ target, size_t tmask,
+                                                           double* __restrict__ partial,
+                                                           float* __restrict__ inten_out) {
   __shared__ float2 tw[kN];
   __shared__ float2 scratch[kSCR];
   for (int i = threadIdx.x; i < kN; i += 256) tw[i] = tw_glob[i];
@@ -609,7 +627,15 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896_cplx(const JobDesc* __rest
   const int rb = bid % kRB;
   const int j = bid / kRB;
   const JobDesc jb = jobs[j];
-  if (jb.env < 0) return;  // uniform per block
+  if (jb.env < 0) {  // uniform per block
+    if constexpr (ST) {
+      if (threadIdx.x == 0) {
+        double* o = partial + ((size_t)j * kRB + rb) * 3;
+        o[0] = 0.0; o[1] = 0.0; o[2] = 0.0;
+      }
+    }
+    return;
+  }
   const int y = rb * kGPB + grp;
   const int Q = P / 2;                            // complex planes per group
   const __amdgpu_buffer_rsrc_t rs = plane_rsrc(ws_b + (size_t)j * P * kPlaneB, (unsigned)((size_t)P * kPlaneB * 8));
@@ -632,12 +658,21 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896_cplx(const JobDesc* __rest
   };
   const PaddedScratch<kR> sc{scratch + grp * kR * (kR + 1)};
   const size_t row0 = (((size_t)jb.env * G + jb.group) * Q * kN + y) * kN + t;   // complex plane 0, pixel x = t
+  float acc[ST ? kL : 1];
+  if constexpr (ST) {
+#pragma unroll
+    for (int k = 0; k < kL; ++k) acc[k] = 0.0f;
+  }
   float2 v[32];
   load_pair(v, 0);
   __syncthreads();  // tw visible
 #pragma unroll 1
   for (int q = 0; q < Q; ++q) {
     fft896_sn<true, kInvScalar>(v, t, sc, tw);      // slot layout in, natural out: x = t + 32 k
+    if constexpr (ST) {
+#pragma unroll
+      for (int k = 0; k < kL; ++k) acc[k] += fmaf(v[k].x, v[k].x, v[k].y * v[k].y);
+    }
     const size_t row = row0 + (size_t)q * kN * kN;
     if (field_out) {
 #pragma unroll
@@ -648,6 +683,10 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896_cplx(const JobDesc* __rest
       for (int k = 0; k < kL; ++k) real_out[row + kR * k] = v[k].x;
     }
     if (q + 1 < Q) load_pair(v, q + 1);   // uniform: no pair is read twice
+  }
+  if constexpr (ST) {
+    __shared__ double red[kGPB][3];
+    rowinv896_epilogue(acc, Q, G, jb, j, y, rb, grp, t, target, tmask, inten_out, 0, partial, red);
   }
 }
 
@@ -665,7 +704,8 @@ hipError_t run_jobs_896(const PlanDev& pd, const JobDesc* jobs, int n_jobs, cons
   if (pd.plane_mode != kPlanesOff && (!pd.plane_pool || !pd.plane_slot)) return hipErrorInvalidValue;
   if (pd.real_values && (pair || pd.store_kind != HBX_PRECISION_F32)) return hipErrorInvalidValue;
   if (pd.complex_values && (pair || pd.store_kind != HBX_PRECISION_F32 || pd.real_values ||
-                            pd.plane_mode != kPlanesOff || (!pd.complex_field && !pd.real_part)))
+                            pd.plane_mode != kPlanesOff ||
+                            (!pd.complex_field && !pd.real_part && !pd.complex_stats)))
     return hipErrorInvalidValue;
   if (pd.complex_weight && !pd.complex_values) return hipErrorInvalidValue;   // the weight scales complex samples only
   if (tm) tm->begin(0, st);
@@ -688,10 +728,19 @@ hipError_t run_jobs_896(const PlanDev& pd, const JobDesc* jobs, int n_jobs, cons
                      pd.ws_b, pd.htab, pd.tw, P, pair);
   if (tm) tm->end(1, n_jobs, st);
   if (tm) tm->begin(2, st);
-  if (pd.complex_values) {   // recombine each plane pair; nothing to reduce
-    hipLaunchKernelGGL(k_rowinv896_cplx, dim3((unsigned)n_jobs * kRB), dim3(256), 0, st, jobs, pd.ws_b, pd.tw, P,
-                       pd.G, pd.complex_field, pd.real_part);
+  if (pd.complex_values) {   // recombine each plane pair
+    const float* tg = target ? target : pd.zero_row;
+    const size_t tmask = target ? ~(size_t)0 : (size_t)0;
+    if (pd.complex_stats)
+      hipLaunchKernelGGL(k_rowinv896_cplx<true>, dim3((unsigned)n_jobs * kRB), dim3(256), 0, st, jobs, pd.ws_b, pd.tw,
+                         P, pd.G, pd.complex_field, pd.real_part, tg, tmask, pd.partial, inten_out);
+    else
+      hipLaunchKernelGGL(k_rowinv896_cplx<false>, dim3((unsigned)n_jobs * kRB), dim3(256), 0, st, jobs, pd.ws_b,
+                         pd.tw, P, pd.G, pd.complex_field, pd.real_part, tg, tmask, pd.partial, inten_out);
     if (tm) tm->end(2, n_jobs, st);
+    // hbx_evaluate_complex with a target: the statistics form left partials to reduce
+    if (pd.complex_stats && target)
+      hipLaunchKernelGGL(k_reduce_partials, dim3(n_jobs), dim3(64), 0, st, pd.partial, n_jobs, kRB, pd.job_stats);
     return hipGetLastError();
   }
   // (r06) the plain FFT-mode launch gets the lean instantiation (profiles/r06/rowinv896_lean_ab_r06i.txt)

@@ -29,6 +29,7 @@ OBS_STATE, OBS_RECON, OBS_RESOLVE, OBS_SETTLE = 1, 2, 4, 8   # hbx_env_obs_sync
 SRC_U8, SRC_F32, SRC_F64 = 0, 1, 2             # hbx_pack_mask / hbx_rel_stats value kinds (ABI v14)
 PACK_BINARY, PACK_THRESHOLD = 0, 1
 REL_WORKSPACE_DOUBLES = 3072
+LOSS_MSE, LOSS_PSNR = 0, 1                      # hbx_loss / hbx_loss_weight kinds
 
 EXPORTED_SYMBOLS = (
     "hbx_abi_version", "hbx_last_error", "hbx_plan_create", "hbx_plan_destroy",
@@ -41,6 +42,7 @@ EXPORTED_SYMBOLS = (
     "hbx_dbs_walk_planes_fill", "hbx_host_alloc", "hbx_host_free", "hbx_pack_mask", "hbx_rel_stats",
     "hbx_simulate_real", "hbx_propagate_real", "hbx_simulate_complex",
     "hbx_simulate_complex_weighted", "hbx_intensity_real",
+    "hbx_evaluate_real", "hbx_evaluate_complex", "hbx_loss", "hbx_loss_weight",
 )
 NUM_PASSES = 5
 PASS_NAMES = ("k_rowfwd", "k_col", "k_rowinv", "k_psf_eval", "k_psf_commit")
@@ -132,6 +134,10 @@ def _declare(lib):
     lib.hbx_simulate_complex.argtypes = [VP, VP, I32, VP, VP, VP]
     lib.hbx_simulate_complex_weighted.argtypes = [VP, VP, VP, C.c_float, I32, VP, VP, VP]
     lib.hbx_intensity_real.argtypes = [VP, VP, I32, VP, VP]
+    lib.hbx_evaluate_real.argtypes = [VP, VP, VP, I32, VP, VP, VP, VP, VP]
+    lib.hbx_evaluate_complex.argtypes = [VP, VP, VP, I32, VP, VP, VP, VP, VP]
+    lib.hbx_loss.argtypes = [VP, VP, I32, I32, I32, VP, VP]
+    lib.hbx_loss_weight.argtypes = [VP, VP, VP, VP, VP, I32, I32, I32, VP, VP]
     lib.hbx_flip_map.argtypes = [VP, VP, VP, VP, VP, VP]
     lib.hbx_eval_flips_psf.argtypes = [VP, VP, VP, VP, VP, VP, VP, I32, VP, VP, VP]
     lib.hbx_commit_flip_psf.argtypes = [VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, I32, VP]

@@ -379,6 +379,83 @@ class Plan:
                                                _ptr(stats), _ptr(psnr), _stream(stream)), "hbx_propagate_real")
         return inten, stats, psnr
 
+    def evaluate_real(self, values: torch.Tensor, target: torch.Tensor, want_field: bool = True,
+                      want_intensity: bool = True, stream=None):
+        """`propagate_real` that may also write `simulate_real`'s field, in one launch set
+        (hbx_evaluate_real): returns (field complex64 [B, CH, H, W] | None, intensity | None,
+        chan_stats, psnr), each bit for bit what those two calls give."""
+        n = values.shape[0] if isinstance(values, torch.Tensor) and values.dim() else 0
+        c = self.cfg
+        _need(values, "values", torch.float32, self.values_shape(n), self.device)
+        values = values.resolve_neg()              # a lazily negated view shares the un-negated memory
+        _need(target, "target", torch.float32, self.target_shape(n), self.device)
+        field = torch.empty((n, c.channels, c.height, c.width, 2), dtype=torch.float32,
+                            device=self.device) if want_field else None
+        inten = torch.empty(self.target_shape(n), dtype=torch.float32, device=self.device) if want_intensity else None
+        stats = torch.empty((n, c.groups, 3), dtype=torch.float64, device=self.device)
+        psnr = torch.empty((n,), dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.hbx_evaluate_real(self._h, _ptr(values), _ptr(target), n, _ptr(field), _ptr(inten),
+                                              _ptr(stats), _ptr(psnr), _stream(stream)), "hbx_evaluate_real")
+        return (torch.view_as_complex(field) if want_field else None), inten, stats, psnr
+
+    def evaluate_complex(self, values: torch.Tensor, target: Optional[torch.Tensor] = None, want_field: bool = True,
+                         want_intensity: bool = True, stream=None):
+        """A complex field's propagation with the plane-mean intensity and the statistics from the
+        same last pass (hbx_evaluate_complex): `values` complex64 [B, CH/2, H, W] as
+        `simulate_complex`; returns (field complex64 [B, CH/2, H, W] | None, intensity float32
+        [B, G, H, W] | None, chan_stats | None, psnr | None).  intensity[b, g] is the mean of
+        |field|^2 over the group's CH/2G complex planes; the field is `simulate_complex`'s bit for
+        bit.  target None: the intensity alone (no statistics, no psnr)."""
+        n = values.shape[0] if isinstance(values, torch.Tensor) and values.dim() else 0
+        c = self.cfg
+        shape = (n, c.channels // 2, c.height, c.width)
+        _need(values, "values", torch.complex64, shape, self.device)
+        values = values.resolve_conj().resolve_neg()   # as simulate_complex: the kernel reads the memory
+        if target is None:
+            if not want_intensity:
+                raise ValueError("evaluate_complex: without a target the intensity is the only output")
+        else:
+            _need(target, "target", torch.float32, self.target_shape(n), self.device)
+        field = torch.empty(shape + (2,), dtype=torch.float32, device=self.device) if want_field else None
+        inten = torch.empty(self.target_shape(n), dtype=torch.float32, device=self.device) if want_intensity else None
+        stats = psnr = None
+        if target is not None:
+            stats = torch.empty((n, c.groups, 3), dtype=torch.float64, device=self.device)
+            psnr = torch.empty((n,), dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.hbx_evaluate_complex(self._h, _ptr(values), _ptr(target), n, _ptr(field), _ptr(inten),
+                                                 _ptr(stats), _ptr(psnr), _stream(stream)), "hbx_evaluate_complex")
+        return (torch.view_as_complex(field) if want_field else None), inten, stats, psnr
+
+    def loss(self, chan_stats: torch.Tensor, kind: int = _lib.LOSS_MSE, rel_scale: int = _lib.REL_LSQ,
+             stream=None) -> torch.Tensor:
+        """chan_stats [B, G, 3] -> the relative MSE or PSNR per env, float64 [B] on the device
+        (hbx_loss): tt.relativeLoss(.., F.mse_loss / tm.get_PSNR) without the host wait."""
+        n = chan_stats.shape[0] if isinstance(chan_stats, torch.Tensor) and chan_stats.dim() else 0
+        _need(chan_stats, "chan_stats", torch.float64, (n, self.cfg.groups, 3), self.device)
+        out = torch.empty((n,), dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.hbx_loss(self._h, _ptr(chan_stats), n, int(kind), int(rel_scale), _ptr(out),
+                                     _stream(stream)), "hbx_loss")
+        return out
+
+    def loss_weight(self, intensity: torch.Tensor, target: torch.Tensor, chan_stats: torch.Tensor,
+                    grad_loss: Optional[torch.Tensor] = None, kind: int = _lib.LOSS_MSE,
+                    rel_scale: int = _lib.REL_LSQ, stream=None) -> torch.Tensor:
+        """The loss's gradient with respect to the intensity, float32 [B, G, H, W]
+        (hbx_loss_weight): grad_loss[b] * d loss_b / d intensity[b] = a_b I + c_b T; grad_loss
+        float64 [B] or None (ones).  `simulate_complex(field, weight=.., scale=2 / planes)` on the
+        plan for -z turns it into the gradient with respect to the hologram."""
+        n = intensity.shape[0] if isinstance(intensity, torch.Tensor) and intensity.dim() else 0
+        _need(intensity, "intensity", torch.float32, self.target_shape(n), self.device)
+        _need(target, "target", torch.float32, self.target_shape(n), self.device)
+        _need(chan_stats, "chan_stats", torch.float64, (n, self.cfg.groups, 3), self.device)
+        if grad_loss is not None:
+            _need(grad_loss, "grad_loss", torch.float64, (n,), self.device)
+        weight = torch.empty(self.target_shape(n), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.hbx_loss_weight(self._h, _ptr(intensity), _ptr(target), _ptr(chan_stats),
+                                            _ptr(grad_loss), n, int(kind), int(rel_scale), _ptr(weight),
+                                            _stream(stream)), "hbx_loss_weight")
+        return weight
+
     def psnr(self, chan_stats: torch.Tensor, stream=None) -> torch.Tensor:
         n = chan_stats.shape[0]
         _need(chan_stats, "chan_stats", torch.float64, (n, self.cfg.groups, 3), self.device)

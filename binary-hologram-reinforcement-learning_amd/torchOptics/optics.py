@@ -40,6 +40,12 @@ written when no gradient is wanted (hbx_intensity_real), and with a gradient req
 pass that is one hbx_simulate_complex_weighted on the plan for -z (the saved field times
 (2 / P) grad_output, formed in the first pass's load).
 
+``loss`` is ``relativeLoss(intensity(x, z), target, F.mse_loss)`` -- or its PSNR -- per env in one
+launch set: the last pass leaves the float64 sums of I T, I^2 and T^2 (hbx_evaluate_real /
+hbx_evaluate_complex), hbx_loss turns them into a float64 device tensor with no host wait, and
+the backward pass is hbx_loss_weight (dL/dI = a I + c T per env) followed by the same weighted
+launch set on the plan for -z.
+
 The physics follows the assumptions documented in DESIGN.md (the original torchOptics is
 absent and unpinned): no padding; exact angular spectrum and amplitude field unless
 ``tf="fresnel"`` / ``field="phase"`` select the plan's other switches.  relativeLoss uses the
@@ -59,7 +65,7 @@ from hbx import _lib
 
 from . import metrics as _metrics
 
-__all__ = ["Tensor", "simulate", "intensity", "relativeLoss", "imread", "check_binary"]
+__all__ = ["Tensor", "simulate", "intensity", "loss", "relativeLoss", "imread", "check_binary"]
 
 
 class Tensor(torch.Tensor):
@@ -441,6 +447,130 @@ def intensity(x, z: float, tf="asm", field="amplitude", save_field: bool = True)
         out = plan.intensity_real(_pad_real(t, cp))
         if cp != c:
             out = out * (cp / c)
+    return out[0] if squeeze else out
+
+
+_METRIC_NAMES = {"mse": _lib.LOSS_MSE, "psnr": _lib.LOSS_PSNR}
+
+
+def _evaluate(t: torch.Tensor, target: torch.Tensor, geom, groups: int, want_field: bool):
+    """One launch set on a device tensor [B, C, H, W] (real: hbx_evaluate_real, complex:
+    hbx_evaluate_complex) -> (plan, field | None, intensity | None, chan_stats); the intensity is
+    written only beside the field (the backward pass reads both)."""
+    wls, dx, dy, z, dev, tf_kind = geom
+    b, c, h, w = t.shape
+    if t.is_complex():
+        plan = _plan_for(h, w, 2 * c // groups, wls, dx, dy, z, b, dev, tf_kind)
+        field, inten, stats, _ = plan.evaluate_complex(
+            t.to(torch.complex64).resolve_conj().resolve_neg().contiguous(), target, want_field=want_field,
+            want_intensity=want_field)
+    else:
+        plan = _plan_for(h, w, c // groups, wls, dx, dy, z, b, dev, tf_kind)
+        field, inten, stats, _ = plan.evaluate_real(_pad_real(t, c), target, want_field=want_field,
+                                                    want_intensity=want_field)
+    return plan, field, inten, stats
+
+
+class _Loss(torch.autograd.Function):
+    """u -> the relative MSE or PSNR per env of I = mean_p |A u_p|^2 against a constant target.  The
+    forward pass is one launch set that leaves the field F = A u, I and the statistics; with
+    w = gL dL/dI = a I + c T (hbx_loss_weight: a, c per env from the statistics and the incoming
+    gradient gL), dL/du = A^H((2 / P) w F): one hbx_simulate_complex_weighted of F on the plan for -z,
+    as tt.intensity's backward pass.  A real u receives the real part, a complex u the field.  No
+    double backward."""
+
+    @staticmethod
+    def forward(ctx, t, target, geom, groups, kind, rel):
+        ctx.geom, ctx.groups, ctx.kind, ctx.rel = geom, groups, kind, rel
+        ctx.in_dtype, ctx.planes = t.dtype, t.shape[1]
+        plan, field, inten, stats = _evaluate(t, target, geom, groups, True)
+        ctx.save_for_backward(field, inten, stats, target)
+        return plan.loss(stats, kind, rel)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        wls, dx, dy, z, dev, tf_kind = ctx.geom
+        groups, c = ctx.groups, ctx.planes
+        field, inten, stats, target = ctx.saved_tensors
+        b, cf, h, w = field.shape
+        cplx = ctx.in_dtype.is_complex
+        adj = _plan_for(h, w, 2 * cf // groups, wls, dx, dy, -z, b, dev, tf_kind)
+        gl = grad_output.to(torch.float64).resolve_neg().contiguous()
+        wgt = adj.loss_weight(inten, target, stats, gl, ctx.kind, ctx.rel)   # the plan's G and N only
+        gf, gr = adj.simulate_complex(field, want_field=cplx, want_real=not cplx, weight=wgt,
+                                      scale=2.0 / (c // groups))
+        return (gf if cplx else gr).to(ctx.in_dtype), None, None, None, None, None
+
+
+def loss(x, target, z: float, metric="mse", rel_scale="lsq", tf="asm", field="amplitude") -> torch.Tensor:
+    """The relative loss of a continuous hologram against a target, one value per env, without
+    leaving the HIP path and without a host wait: float64 [B] on the device (0-dim for a 3-D x),
+        metric="mse"   what tt.relativeLoss(I[b], target[b], F.mse_loss) gives (env.py:131),
+        metric="psnr"  what tt.relativeLoss(I[b], target[b], tm.get_PSNR) gives (env.py:132,174),
+    with I = tt.intensity(x, z, tf, field) -- the plane-mean intensity per colour group -- and
+    rel_scale "lsq" (the least-squares scale, the default) or "none" as in relativeLoss.
+
+    x, meta['wl'] (one wavelength or up to four: C planes in G groups), tf and field are
+    tt.intensity's; C / G must be even for a real x with field="amplitude" and may be any number
+    >= 1 for a complex x or field="phase" (anything else raises ValueError).  target: float32
+    [B, G, H, W] (or [G, H, W] for a 3-D x), a constant -- a target that requires grad raises
+    ValueError.
+
+    The last pass of the propagation accumulates the intensity and the float64 sums of I T, I^2
+    and T^2 (hbx_evaluate_real / hbx_evaluate_complex) and hbx_loss turns them into the loss.
+    Without a gradient request there is no graph, and neither field nor intensity is written.  If
+    x requires grad the result carries a grad_fn: the forward pass also writes the field and the
+    intensity, and the backward pass is hbx_loss_weight (the loss's gradient with respect to the
+    intensity, a I + c T per env) followed by one hbx_simulate_complex_weighted on the plan for
+    -z.  A real x receives the real part, a complex x the field; field="phase" forms u =
+    exp(i pi x) with torch ops, which carry du/dx.  No double backward."""
+    kind = _switch(metric, _METRIC_NAMES, "metric")
+    rel = _switch(rel_scale, _REL_NAMES, "rel_scale")
+    tf_kind = _switch(tf, _TF_NAMES, "tf")
+    field_kind = _switch(field, _FIELD_NAMES, "field")
+    meta = _meta_of(x)
+    wl = meta["wl"]
+    wls = tuple(float(v) for v in wl) if isinstance(wl, (tuple, list)) else (float(wl),)
+    groups = len(wls)
+    if not 1 <= groups <= _lib.MAX_GROUPS:
+        raise ValueError(f"loss: 1 to {_lib.MAX_GROUPS} wavelengths, got {groups}")
+    dx, dy = meta.get("dx", (hbx.plan.PIXEL_PITCH,) * 2)
+    t = x.as_subclass(torch.Tensor) if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+    tg = target.as_subclass(torch.Tensor) if isinstance(target, torch.Tensor) else torch.as_tensor(np.asarray(target))
+    squeeze = t.dim() == 3
+    if squeeze:
+        t, tg = t.unsqueeze(0), tg.unsqueeze(0)
+    if t.dim() != 4:
+        raise ValueError(f"loss expects [B, C, H, W] or [C, H, W], got {tuple(x.shape)}")
+    b, c, h, w = t.shape
+    if c == 0 or c % groups:
+        raise ValueError(f"loss: {c} planes do not split into {groups} colour groups")
+    if t.is_complex() and field_kind != _lib.FIELD_AMPLITUDE:
+        raise ValueError("tt.loss: a complex field is used as it is (field=\"amplitude\")")
+    if not t.is_complex() and field_kind == _lib.FIELD_AMPLITUDE and (c // groups) % 2:
+        raise ValueError(f"loss: a real field needs an even number of planes per colour group, got {c // groups}")
+    if tg.requires_grad:
+        raise ValueError("loss: the target is a constant (it requires grad)")
+    if tg.is_complex() or tuple(tg.shape) != (b, groups, h, w):
+        raise ValueError(f"loss: target must be real {(b, groups, h, w)}, got {tuple(tg.shape)} {tg.dtype}")
+    if not torch.cuda.is_available():
+        raise RuntimeError("tt.loss needs a ROCm GPU (libhbx.so)")
+    if t.is_cuda:
+        dev = t.device.index
+    else:
+        dev = torch.cuda.current_device()
+        t = t.to(f"cuda:{dev}")
+    tg = tg.to(device=t.device, dtype=torch.float32).contiguous()
+    if field_kind == _lib.FIELD_PHASE:
+        ph = t.to(torch.float32) * np.float32(np.pi)
+        t = torch.complex(torch.cos(ph), torch.sin(ph))   # torch ops: autograd carries du/dx
+    geom = (wls, dx, dy, z, dev, tf_kind)
+    if t.requires_grad and torch.is_grad_enabled():
+        out = _Loss.apply(t, tg, geom, groups, kind, rel)
+    else:
+        plan, _, _, stats = _evaluate(t, tg, geom, groups, False)
+        out = plan.loss(stats, kind, rel)
     return out[0] if squeeze else out
 
 

@@ -238,8 +238,9 @@ int hbx_propagate_real(hbx_plan_t plan, const float* values, const float* target
  * (H(-z) = conj H(z)); real_part alone is then the gradient with respect to a real u.
  * Chunking by max_jobs, n_env (0: OK, < 0: HBX_ERR_INVALID), null arguments (HBX_ERR_INVALID),
  * HBX_PRECISION_F32 only (else HBX_ERR_UNSUPPORTED), the four built sizes and the pass-timer
- * slots HBX_PASS_ROWFWD / COL / ROWINV are those of hbx_simulate_real.  No intensity, statistics,
- * env, DBS, plane-cache or incremental mode runs on complex fields. */
+ * slots HBX_PASS_ROWFWD / COL / ROWINV are those of hbx_simulate_real.  This call writes no
+ * intensity or statistics (hbx_evaluate_complex does); no env, DBS, plane-cache or incremental
+ * mode runs on complex fields. */
 int hbx_simulate_complex(hbx_plan_t plan, const float* values, int32_t n_env, float* field,
                          float* real_part, void* stream);
 
@@ -273,6 +274,67 @@ int hbx_simulate_complex_weighted(hbx_plan_t plan, const float* values, const fl
  * hbx_simulate_real. */
 int hbx_intensity_real(hbx_plan_t plan, const float* values, int32_t n_env, float* intensity,
                        void* stream);
+
+/* (ABI v15, additive) The loss of a continuous hologram in one launch set (env.py:131-132,174:
+ * tt.relativeLoss of the plane-mean intensity against the target).
+ *
+ * hbx_evaluate_real is hbx_propagate_real that may also write the field hbx_simulate_real writes:
+ *   field[B][G*P][H][W][2] (nullable) equals hbx_simulate_real's bit for bit, and intensity
+ *   (nullable), chan_stats and psnr (nullable) equal hbx_propagate_real's bit for bit; null
+ *   values, target or chan_stats: HBX_ERR_INVALID.  One propagation where a loss with a gradient
+ *   needed hbx_simulate_real (the field the backward pass reads) and a second one for the
+ *   statistics.
+ *
+ * hbx_evaluate_complex is the same on a complex field: values and field are
+ * hbx_simulate_complex's ([B][G*P/2][H][W][2]; a written field equals that call's bit for bit), and
+ *   intensity[B][G][H][W] = mean over the group's P/2 complex planes q of |F_q|^2
+ *   chan_stats[B][G][3]   = sum I*T, sum I^2, sum T^2 per channel against target[B][G][H][W]
+ *   psnr[B]               = the plan's rel_scale and peak, as hbx_propagate
+ * The last pass accumulates re^2 + im^2 per pixel after each complex plane's inverse row FFT and
+ * ends in the real last pass's tail (plane mean, float64 partials in fixed order: results are
+ * reproducible bit for bit); with field null it writes nothing but the intensity and the partials.
+ * field, intensity and psnr are nullable.  target and chan_stats are given together or not at all:
+ * without them the call returns the intensity alone (intensity is then required and psnr must be
+ * null); with them at least chan_stats is written.  Anything else: HBX_ERR_INVALID.  Chunking by
+ * max_jobs, n_env (0: OK, < 0: HBX_ERR_INVALID), HBX_PRECISION_F32 only (else
+ * HBX_ERR_UNSUPPORTED), the four built sizes and the pass-timer slots are hbx_simulate_complex's. */
+int hbx_evaluate_real(hbx_plan_t plan, const float* values, const float* target, int32_t n_env,
+                      float* field, float* intensity, double* chan_stats, double* psnr, void* stream);
+int hbx_evaluate_complex(hbx_plan_t plan, const float* values, const float* target, int32_t n_env,
+                         float* field, float* intensity, double* chan_stats, double* psnr,
+                         void* stream);
+
+/* (ABI v15, additive) The relative loss per env from the statistics, on the device
+ * (tt.relativeLoss(.., F.mse_loss) env.py:131, tt.relativeLoss(.., tm.get_PSNR) env.py:132,174,
+ * without the host wait): chan_stats[B][G][3] -> loss[B] float64.  With S_xy, S_xx, S_yy the sums
+ * over the env's G groups and n = G*H*W,
+ *   rel_scale HBX_REL_LSQ   s = S_xy / S_xx, MSE = (S_yy - S_xy^2 / S_xx) / n  (S_xx = 0: S_yy / n)
+ *   rel_scale HBX_REL_NONE  MSE = (S_xx - 2 S_xy + S_yy) / n
+ *   kind HBX_LOSS_MSE  loss = MSE;  kind HBX_LOSS_PSNR  loss = 10 log10(peak^2 / MSE), +inf for MSE <= 0
+ * rel_scale is the argument, not the plan's; HBX_LOSS_PSNR with the plan's own rel_scale gives
+ * hbx_psnr's bits.  An unknown kind or rel_scale, or a null buffer: HBX_ERR_INVALID. */
+#define HBX_LOSS_MSE 0
+#define HBX_LOSS_PSNR 1
+int hbx_loss(hbx_plan_t plan, const double* chan_stats, int32_t n_env, int32_t kind, int32_t rel_scale,
+             double* loss, void* stream);
+
+/* (ABI v15, additive) The gradient of that loss with respect to the intensity, one streaming pass
+ * over intensity, target, weight [B][G][H][W] float32 (the plan's G, H, W):
+ *   weight[b] = grad_loss[b] * d loss_b / d I[b] = a_b * I[b] + c_b * T[b]
+ *   HBX_REL_LSQ   dMSE/dI = (2 s / n) (s I - T):  a = 2 s^2 / n, c = -2 s / n
+ *   HBX_REL_NONE  dMSE/dI = (2 / n) (I - T):      a = 2 / n,     c = -2 / n
+ *   HBX_LOSS_PSNR both times -(10 / ln 10) / MSE
+ * grad_loss[B] float64 is the incoming gradient of the B losses (null: ones).  Each workgroup forms
+ * its env's a and c in float64 from chan_stats and grad_loss, rounds them to float32 once and
+ * computes fmaf(a, I, c * T) per pixel.  A degenerate env -- S_xx = 0 under HBX_REL_LSQ, or
+ * MSE <= 0 with HBX_LOSS_PSNR -- gets a = c = 0: an all-zero weight, never a NaN or infinity.
+ * Null intensity, target, chan_stats or weight, or an unknown kind or rel_scale: HBX_ERR_INVALID.
+ * The backward pass of the loss is then hbx_simulate_complex_weighted(saved field, weight,
+ * 2 / P_c) on the plan for -z, P_c the planes the mean ran over (P for hbx_evaluate_real, P/2 for
+ * hbx_evaluate_complex). */
+int hbx_loss_weight(hbx_plan_t plan, const float* intensity, const float* target,
+                    const double* chan_stats, const double* grad_loss, int32_t n_env, int32_t kind,
+                    int32_t rel_scale, float* weight, void* stream);
 
 /* PSNR from per-channel statistics (tt.relativeLoss(.., tm.get_PSNR),
  * env.py:174): chan_stats[B][G][3] -> psnr[B]. */
