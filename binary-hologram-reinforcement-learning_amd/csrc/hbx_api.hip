@@ -21,6 +21,7 @@
 using hbx::EnvDev;
 using hbx::EnvParams;
 using hbx::JobDesc;
+using hbx::PassCall;
 using hbx::PlanDev;
 
 namespace {
@@ -37,6 +38,14 @@ int fail(int code, const std::string& msg) {
     hipError_t e_ = (expr);                                                              \
     if (e_ != hipSuccess)                                                                \
       return fail(HBX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));       \
+  } while (0)
+
+// The preamble of the batched entry points: a null plan and a negative count are errors, an empty
+// batch returns HBX_OK before any buffer is looked at (null buffers allowed)
+#define HBX_ENTER(p, n, name)                                                            \
+  do {                                                                                   \
+    if (!(p)) return fail(HBX_ERR_INVALID, "null plan");                                 \
+    if ((n) <= 0) return (n) == 0 ? HBX_OK : fail(HBX_ERR_INVALID, name);                \
   } while (0)
 
 }  // namespace
@@ -359,9 +368,14 @@ int ensure_hpsf(hbx_plan_t p, hipStream_t st) {
   amp.vb = 1.0f;
   amp.timer = nullptr;
   amp.store_kind = HBX_PRECISION_F32;   // h is a table of the product path, whatever the plan's precision
+  PassCall c;
+  c.jobs = p->jobs;
+  c.n_jobs = G;
+  c.mask = mask;
+  c.target = target;
+  c.field_out = field;
   hipError_t e = hbx::launch_jobs_full(nullptr, 1, G, p->jobs, st);
-  if (e == hipSuccess)
-    e = hbx::run_jobs(amp, p->jobs, G, reinterpret_cast<const uint32_t*>(mask), target, nullptr, field, st);
+  if (e == hipSuccess) e = hbx::run_jobs(amp, c, st);
   for (int g = 0; g < G && e == hipSuccess; ++g)
     e = hipMemcpyAsync(h + (size_t)g * hw, field + (size_t)g * P * hw, hw * sizeof(float2),
                        hipMemcpyDeviceToDevice, st);
@@ -388,6 +402,15 @@ EnvDev env_dev(const hbx_env_buffers_t* e) {
   d.error = e->error;
   d.error_host = e->error_host;
   return d;
+}
+
+EnvParams env_params(const hbx_env_params_t* prm) {
+  EnvParams ep;
+  ep.max_steps = prm->max_steps; ep.t_psnr = prm->t_psnr; ep.t_steps = prm->t_steps;
+  ep.t_psnr_diff = prm->t_psnr_diff; ep.reward_weight = prm->reward_weight;
+  ep.accept_rule = prm->accept_rule;
+  ep.reward_kind = prm->reward_kind;
+  return ep;
 }
 
 EnvDev env_offset(const EnvDev& d, size_t e0, int CH, int G, int N) {
@@ -419,61 +442,106 @@ int check_obs_buffers(const hbx_env_buffers_t* e) {
   return HBX_OK;
 }
 
-// full propagation of n_ids envs (absolute ids from env_ids, or 0..n_ids-1)
-int propagate_full(hbx_plan_t p, const uint64_t* mask, const float* target, const int32_t* env_ids,
-                   int n_ids, float* intensity, double* chan_stats, double* psnr, const EnvDev* env,
-                   float2* field, hipStream_t st, float* plane_pool = nullptr, int32_t* plane_slot = nullptr,
-                   int spares = 1, const float* values = nullptr) {
-  // values (ABI v15, with mask, env_ids and plane_pool null): [n_ids][G*P][N][N] f32 samples of a
-  // real-valued field, read by the first pass in place of the mask bits
+int check_real_plan(hbx_plan_t p, bool complex_field = false) {
+  if (p->pd.store_kind != HBX_PRECISION_F32)
+    return fail(HBX_ERR_UNSUPPORTED, complex_field
+        ? "complex fields: HBX_PRECISION_F32 only (the plan stores reduced-precision intermediates)"
+        : "real-valued fields: HBX_PRECISION_F32 only (the plan stores reduced-precision intermediates)");
+  return HBX_OK;
+}
+
+// One full propagation of n envs: every plane of every colour group, no flip.
+struct FullRequest {
+  // the input, one of: mask bits [n][G*P][N][N/64]; (ABI v15) real samples [n][G*P][N][N] f32;
+  // complex samples [n][G*P/2][N][N] complex64, optionally times scale * weight[n][G][N][N]
+  const uint64_t* mask = nullptr;
+  const float* real_values = nullptr;
+  const float2* complex_values = nullptr;
+  const float* weight = nullptr;
+  float scale = 1.0f;
+  const float* target = nullptr;       // [n][G][N][N]; null: no statistics
+  const int32_t* env_ids = nullptr;    // absolute env ids into every buffer (mask input only); null: 0 .. n - 1
+  int n = 0;
+  // outputs, all nullable
+  float* intensity = nullptr;          // [n][G][N][N]
+  double* chan_stats = nullptr;        // [n][G][3]
+  double* psnr = nullptr;              // [n]
+  const EnvDev* env = nullptr;         // reset: the finalize also initialises the envs' episode state
+  float2* field = nullptr;             // [n][G*P][N][N] complex64 (mask / real input)
+  float2* complex_field = nullptr;     // [n][G*P/2][N][N] complex64 (complex input)
+  float* real_part = nullptr;          // [n][G*P/2][N][N] f32 (complex input)
+  bool complex_stats = false;          // complex input: the last pass's intensity / statistics form
+  // plane cache (ABI v9): identity slots, then every plane's |U|^2 into its slot
+  float* plane_pool = nullptr;
+  int32_t* plane_slot = nullptr;
+  int spares = 1;
+};
+
+int propagate_full(hbx_plan_t p, const FullRequest& r, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
   const PlanDev& pd = p->pd;
-  const int CHs = pd.G * pd.P + 2 * spares;   // plane-cache slots per env
-  if (plane_pool) {                           // identity slots, then every plane's |U|^2 into its slot
+  const int G = pd.G, CH = pd.G * pd.P;
+  const int CHs = CH + 2 * r.spares;   // plane-cache slots per env
+  const int chunk = p->max_jobs / G;
+  const bool cplx = r.complex_values != nullptr;
+  HBX_HIP(hipSetDevice(p->device));
+  if (r.plane_pool) {
     if (pd.R != 32 && pd.R != 16 && pd.R != 0)
       return fail(HBX_ERR_UNSUPPORTED, "plane cache: N = 1024, 896 or 256 only");
-    HBX_HIP(hbx::launch_plane_slot_init(env_ids, n_ids, plane_slot, CHs, st));
+    HBX_HIP(hbx::launch_plane_slot_init(r.env_ids, r.n, r.plane_slot, CHs, st));
   }
-  const int G = pd.G;
-  const int chunk = p->max_jobs / G;
-  if (intensity) {
+  // Complex input: the jobs are the plan's constant table (job j = env j / G, group j % G), so the
+  // job-major intensity rows are the caller's [env][G][N][N] of the chunk and the last pass writes
+  // them in place.  Mask and real input: through job_inten and a scatter (jobs may carry env ids)
+  const bool scatter = r.intensity && !cplx;
+  if (scatter) {
     int rc = ensure_job_inten(p);
     if (rc) return rc;
   }
-  EnvDev dummy;
-  std::memset(&dummy, 0, sizeof(dummy));
-  for (int i0 = 0; i0 < n_ids; i0 += chunk) {
-    const int n = std::min(chunk, n_ids - i0);
-    // with env_ids the jobs carry absolute env ids; without, ids are chunk-local
-    // and every per-env buffer is offset by i0 instead
-    // with env ids the jobs are built per chunk; without, they are the plan's constant table
-    JobDesc* jobs = env_ids ? p->jobs : p->full_jobs;
-    if (env_ids) HBX_HIP(hbx::launch_jobs_full(env_ids + i0, n, G, jobs, st));
-    const size_t mwords = (size_t)G * pd.P * pd.N * (pd.N / 64);
-    const uint64_t* m = (env_ids || !mask) ? mask : mask + (size_t)i0 * mwords;
-    const float* tg = (env_ids || !target) ? target : target + (size_t)i0 * G * pd.N * pd.N;
-    float2* fo = field ? (env_ids ? field : field + (size_t)i0 * G * pd.P * pd.N * pd.N) : nullptr;
-    PlanDev pdx = pd;
-    if (values) pdx.real_values = values + (size_t)i0 * G * pd.P * pd.N * pd.N;
-    if (plane_pool) {
-      pdx.plane_mode = hbx::kPlanesFill;
-      pdx.plane_spares = spares;
-      pdx.plane_pool = env_ids ? plane_pool : plane_pool + (size_t)i0 * CHs * pd.N * pd.N;
-      pdx.plane_slot = env_ids ? plane_slot : plane_slot + (size_t)i0 * CHs;
+  // per-env strides of the caller's buffers, in elements
+  const size_t hw = (size_t)pd.N * pd.N;
+  const size_t s_mask = (size_t)CH * pd.N * (pd.N / 64);   // mask words
+  const size_t s_real = (size_t)CH * hw;                   // real samples, field planes
+  const size_t s_cplx = (size_t)(CH / 2) * hw;             // complex planes
+  const size_t s_img = (size_t)G * hw;                     // images: target, intensity, weight
+  const size_t s_stat = (size_t)G * 3;                     // statistics
+  const size_t s_pool = (size_t)CHs * hw, s_slot = (size_t)CHs;
+  for (int i0 = 0; i0 < r.n; i0 += chunk) {
+    const int n = std::min(chunk, r.n - i0);
+    // with env ids the jobs are built per chunk and carry absolute ids into unshifted buffers; without,
+    // they are the plan's constant table (ids chunk-local) and every buffer starts at the chunk's first env
+    const size_t e0 = r.env_ids ? 0 : (size_t)i0;
+    auto at = [e0](auto* q, size_t stride) { return q ? q + e0 * stride : nullptr; };
+    JobDesc* jobs = r.env_ids ? p->jobs : p->full_jobs;
+    if (r.env_ids) HBX_HIP(hbx::launch_jobs_full(r.env_ids + i0, n, G, jobs, st));
+    PassCall c;
+    c.jobs = jobs;
+    c.n_jobs = n * G;
+    c.mask = at(r.mask, s_mask);
+    c.real_values = at(r.real_values, s_real);
+    c.complex_values = at(r.complex_values, s_cplx);
+    c.complex_weight = at(r.weight, s_img);
+    c.complex_scale = r.scale;
+    c.target = at(r.target, s_img);
+    c.inten_out = cplx ? at(r.intensity, s_img) : (r.intensity ? p->job_inten : nullptr);
+    c.field_out = at(r.field, s_real);
+    c.complex_field = at(r.complex_field, s_cplx);
+    c.real_part = at(r.real_part, s_cplx);
+    c.complex_stats = r.complex_stats;
+    if (r.plane_pool) {
+      c.plane_mode = hbx::kPlanesFill;
+      c.plane_spares = r.spares;
+      c.plane_pool = at(r.plane_pool, s_pool);
+      c.plane_slot = at(r.plane_slot, s_slot);
     }
-    HBX_HIP(hbx::run_jobs(pdx, jobs, n * G, reinterpret_cast<const uint32_t*>(m), tg,
-                          intensity ? p->job_inten : nullptr, fo, st));
-    double* cs = (env_ids || !chan_stats) ? chan_stats : chan_stats + (size_t)i0 * G * 3;
-    double* ps = psnr ? (env_ids ? psnr : psnr + i0) : nullptr;
-    EnvDev ed = dummy;
-    if (env) ed = env_ids ? *env : env_offset(*env, i0, G * pd.P, G, pd.N);
-    if (cs || ps || env)   // tt.simulate alone (fields only) has nothing to finalize
-      HBX_HIP(hbx::launch_full_finalize(jobs, pd.job_stats, n, G, cs, ps, pixel_count(p),
-                                        p->optics.rel_scale, p->optics.peak, ed, env ? 1 : 0, st));
-    if (intensity) {
-      float* cache = env_ids ? intensity : intensity + (size_t)i0 * G * pd.N * pd.N;
-      HBX_HIP(hbx::launch_scatter_intensity(jobs, n * G, p->job_inten, cache, G,
-                                            (size_t)pd.N * pd.N, nullptr, st));
-    }
+    HBX_HIP(hbx::run_jobs(pd, c, st));
+    // fields or intensity alone have nothing to finalize (complex input: psnr comes with chan_stats)
+    if (r.chan_stats || r.psnr || r.env)
+      HBX_HIP(hbx::launch_full_finalize(jobs, pd.job_stats, n, G, at(r.chan_stats, s_stat), at(r.psnr, 1),
+                                        pixel_count(p), p->optics.rel_scale, p->optics.peak,
+                                        r.env ? env_offset(*r.env, e0, CH, G, pd.N) : EnvDev{}, r.env ? 1 : 0, st));
+    if (scatter)
+      HBX_HIP(hbx::launch_scatter_intensity(jobs, n * G, p->job_inten, at(r.intensity, s_img), G, hw, nullptr, st));
   }
   return HBX_OK;
 }
@@ -484,175 +552,102 @@ extern "C" {
 
 int hbx_propagate(hbx_plan_t p, const uint64_t* mask, const float* target, int32_t n_env,
                   float* intensity, double* chan_stats, double* psnr, void* stream) {
-  int rc = check_plan(p);
-  if (rc) return rc;
-  if (n_env <= 0) return n_env == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "n_env");  // empty: null buffers allowed
+  HBX_ENTER(p, n_env, "n_env");
   if (!mask || !target || !chan_stats) return fail(HBX_ERR_INVALID, "null buffer");
-  HBX_HIP(hipSetDevice(p->device));
-  return propagate_full(p, mask, target, nullptr, n_env, intensity, chan_stats, psnr, nullptr,
-                        nullptr, (hipStream_t)stream);
+  FullRequest r;
+  r.mask = mask; r.target = target; r.n = n_env;
+  r.intensity = intensity; r.chan_stats = chan_stats; r.psnr = psnr;
+  return propagate_full(p, r, stream);
 }
 
 int hbx_simulate(hbx_plan_t p, const uint64_t* mask, int32_t n_env, float* field, float* intensity,
                  void* stream) {
-  int rc = check_plan(p);
-  if (rc) return rc;
-  if (n_env <= 0) return n_env == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "n_env");
+  HBX_ENTER(p, n_env, "n_env");
   if (!mask || !field) return fail(HBX_ERR_INVALID, "null buffer");
-  HBX_HIP(hipSetDevice(p->device));
-  return propagate_full(p, mask, nullptr, nullptr, n_env, intensity, nullptr, nullptr, nullptr,
-                        reinterpret_cast<float2*>(field), (hipStream_t)stream);
+  FullRequest r;
+  r.mask = mask; r.n = n_env;
+  r.field = reinterpret_cast<float2*>(field); r.intensity = intensity;
+  return propagate_full(p, r, stream);
 }
-
-namespace {
-int check_real_plan(hbx_plan_t p, bool complex_field = false) {
-  if (p->pd.store_kind != HBX_PRECISION_F32)
-    return fail(HBX_ERR_UNSUPPORTED, complex_field
-        ? "complex fields: HBX_PRECISION_F32 only (the plan stores reduced-precision intermediates)"
-        : "real-valued fields: HBX_PRECISION_F32 only (the plan stores reduced-precision intermediates)");
-  return HBX_OK;
-}
-}  // namespace
 
 int hbx_propagate_real(hbx_plan_t p, const float* values, const float* target, int32_t n_env,
                        float* intensity, double* chan_stats, double* psnr, void* stream) {
-  int rc = check_plan(p);
-  if (rc) return rc;
-  if (n_env <= 0) return n_env == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "n_env");  // empty: null buffers allowed
-  if (!values || !target || !chan_stats) return fail(HBX_ERR_INVALID, "null buffer");
-  if ((rc = check_real_plan(p))) return rc;
-  HBX_HIP(hipSetDevice(p->device));
-  return propagate_full(p, nullptr, target, nullptr, n_env, intensity, chan_stats, psnr, nullptr,
-                        nullptr, (hipStream_t)stream, nullptr, nullptr, 1, values);
+  return hbx_evaluate_real(p, values, target, n_env, nullptr, intensity, chan_stats, psnr, stream);
 }
 
 int hbx_simulate_real(hbx_plan_t p, const float* values, int32_t n_env, float* field, float* intensity,
                       void* stream) {
-  int rc = check_plan(p);
-  if (rc) return rc;
-  if (n_env <= 0) return n_env == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "n_env");
+  HBX_ENTER(p, n_env, "n_env");
   if (!values || !field) return fail(HBX_ERR_INVALID, "null buffer");
-  if ((rc = check_real_plan(p))) return rc;
-  HBX_HIP(hipSetDevice(p->device));
-  return propagate_full(p, nullptr, nullptr, nullptr, n_env, intensity, nullptr, nullptr, nullptr,
-                        reinterpret_cast<float2*>(field), (hipStream_t)stream, nullptr, nullptr, 1, values);
+  if (int rc = check_real_plan(p)) return rc;
+  FullRequest r;
+  r.real_values = values; r.n = n_env;
+  r.field = reinterpret_cast<float2*>(field); r.intensity = intensity;
+  return propagate_full(p, r, stream);
 }
-
-// complex fields: propagate_full's chunk loop with the complex first and last passes (ids are
-// chunk-local, every buffer is offset by the chunk's first env); nothing to finalize or scatter
-namespace {
-// weight (hbx_simulate_complex_weighted, else null): [n_env][G][N][N] f32, one image per env and
-// group -- its chunk stride is G N^2, the complex planes' is G (P/2) N^2
-int simulate_complex(hbx_plan_t p, const float* values, const float* weight, float scale, int32_t n_env,
-                     float* field, float* real_part, hipStream_t st) {
-  const PlanDev& pd = p->pd;
-  const int chunk = p->max_jobs / pd.G;
-  const size_t per_env = (size_t)pd.G * (pd.P / 2) * pd.N * pd.N;   // complex planes x pixels
-  const size_t w_per_env = (size_t)pd.G * pd.N * pd.N;
-  for (int i0 = 0; i0 < n_env; i0 += chunk) {
-    const int n = std::min(chunk, n_env - i0);
-    PlanDev pdx = pd;
-    pdx.complex_values = reinterpret_cast<const float2*>(values) + (size_t)i0 * per_env;
-    if (weight) {
-      pdx.complex_weight = weight + (size_t)i0 * w_per_env;
-      pdx.complex_scale = scale;
-    }
-    pdx.complex_field = field ? reinterpret_cast<float2*>(field) + (size_t)i0 * per_env : nullptr;
-    pdx.real_part = real_part ? real_part + (size_t)i0 * per_env : nullptr;
-    HBX_HIP(hbx::run_jobs(pdx, p->full_jobs, n * pd.G, nullptr, nullptr, nullptr, nullptr, st));
-  }
-  return HBX_OK;
-}
-}  // namespace
 
 int hbx_simulate_complex(hbx_plan_t p, const float* values, int32_t n_env, float* field, float* real_part,
                          void* stream) {
-  int rc = check_plan(p);
-  if (rc) return rc;
-  if (n_env <= 0) return n_env == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "n_env");
+  HBX_ENTER(p, n_env, "n_env");
   if (!values || (!field && !real_part)) return fail(HBX_ERR_INVALID, "null buffer");
-  if ((rc = check_real_plan(p, true))) return rc;
-  HBX_HIP(hipSetDevice(p->device));
-  return simulate_complex(p, values, nullptr, 1.0f, n_env, field, real_part, (hipStream_t)stream);
+  if (int rc = check_real_plan(p, true)) return rc;
+  FullRequest r;
+  r.complex_values = reinterpret_cast<const float2*>(values); r.n = n_env;
+  r.complex_field = reinterpret_cast<float2*>(field); r.real_part = real_part;
+  return propagate_full(p, r, stream);
 }
 
 int hbx_simulate_complex_weighted(hbx_plan_t p, const float* values, const float* weight, float scale,
                                   int32_t n_env, float* field, float* real_part, void* stream) {
-  int rc = check_plan(p);
-  if (rc) return rc;
-  if (n_env <= 0) return n_env == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "n_env");
+  HBX_ENTER(p, n_env, "n_env");
   if (!values || !weight || (!field && !real_part)) return fail(HBX_ERR_INVALID, "null buffer");
-  if ((rc = check_real_plan(p, true))) return rc;
-  HBX_HIP(hipSetDevice(p->device));
-  return simulate_complex(p, values, weight, scale, n_env, field, real_part, (hipStream_t)stream);
+  if (int rc = check_real_plan(p, true)) return rc;
+  FullRequest r;
+  r.complex_values = reinterpret_cast<const float2*>(values); r.weight = weight; r.scale = scale; r.n = n_env;
+  r.complex_field = reinterpret_cast<float2*>(field); r.real_part = real_part;
+  return propagate_full(p, r, stream);
 }
 
-// the plane-mean intensity of a real field and nothing else: the last pass takes the null target
-// (the plan's zero row) and the null field as hbx_propagate_real's lean launch does, and
-// propagate_full skips the finalize when no statistics are asked for
+// the plane-mean intensity of a real field and nothing else: no target (the last pass reads the
+// plan's zero row), no field -- the lean last pass of hbx_propagate_real -- and nothing to finalize
 int hbx_intensity_real(hbx_plan_t p, const float* values, int32_t n_env, float* intensity, void* stream) {
-  int rc = check_plan(p);
-  if (rc) return rc;
-  if (n_env <= 0) return n_env == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "n_env");
+  HBX_ENTER(p, n_env, "n_env");
   if (!values || !intensity) return fail(HBX_ERR_INVALID, "null buffer");
-  if ((rc = check_real_plan(p))) return rc;
-  HBX_HIP(hipSetDevice(p->device));
-  return propagate_full(p, nullptr, nullptr, nullptr, n_env, intensity, nullptr, nullptr, nullptr, nullptr,
-                        (hipStream_t)stream, nullptr, nullptr, 1, values);
+  if (int rc = check_real_plan(p)) return rc;
+  FullRequest r;
+  r.real_values = values; r.n = n_env;
+  r.intensity = intensity;
+  return propagate_full(p, r, stream);
 }
 
-// hbx_propagate_real that may also write the field: propagate_full takes the target and the field
-// at once (the last pass's general form, the one hbx_simulate_real launches)
+// hbx_propagate_real that may also write the field (with it the last pass's general form, the one
+// hbx_simulate_real launches; without, hbx_propagate_real itself)
 int hbx_evaluate_real(hbx_plan_t p, const float* values, const float* target, int32_t n_env, float* field,
                       float* intensity, double* chan_stats, double* psnr, void* stream) {
-  int rc = check_plan(p);
-  if (rc) return rc;
-  if (n_env <= 0) return n_env == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "n_env");  // empty: null buffers allowed
+  HBX_ENTER(p, n_env, "n_env");
   if (!values || !target || !chan_stats) return fail(HBX_ERR_INVALID, "null buffer");
-  if ((rc = check_real_plan(p))) return rc;
-  HBX_HIP(hipSetDevice(p->device));
-  return propagate_full(p, nullptr, target, nullptr, n_env, intensity, chan_stats, psnr, nullptr,
-                        reinterpret_cast<float2*>(field), (hipStream_t)stream, nullptr, nullptr, 1, values);
+  if (int rc = check_real_plan(p)) return rc;
+  FullRequest r;
+  r.real_values = values; r.target = target; r.n = n_env;
+  r.field = reinterpret_cast<float2*>(field); r.intensity = intensity; r.chan_stats = chan_stats; r.psnr = psnr;
+  return propagate_full(p, r, stream);
 }
 
-// simulate_complex's chunk loop with the last pass's statistics form; three chunk strides: complex
-// planes G (P/2) N^2, images G N^2, statistics 3 G.  The jobs are the plan's constant table (ids
-// chunk-local, job j = env j / G, group j % G), so the job-major intensity rows are the caller's
-// [env][G][N][N] of the chunk: the last pass writes them in place, nothing to scatter
+// hbx_simulate_complex with the last pass's statistics form
 int hbx_evaluate_complex(hbx_plan_t p, const float* values, const float* target, int32_t n_env, float* field,
                          float* intensity, double* chan_stats, double* psnr, void* stream) {
-  int rc = check_plan(p);
-  if (rc) return rc;
-  if (n_env <= 0) return n_env == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "n_env");
+  HBX_ENTER(p, n_env, "n_env");
   if (!values) return fail(HBX_ERR_INVALID, "null buffer");
   if ((target == nullptr) != (chan_stats == nullptr))
     return fail(HBX_ERR_INVALID, "target and chan_stats are given together or not at all");
   if (!target && (!intensity || psnr))
     return fail(HBX_ERR_INVALID, "without a target: intensity is the output, and there is no psnr");
-  if ((rc = check_real_plan(p, true))) return rc;
-  HBX_HIP(hipSetDevice(p->device));
-  hipStream_t st = (hipStream_t)stream;
-  const PlanDev& pd = p->pd;
-  const int G = pd.G;
-  const int chunk = p->max_jobs / G;
-  const size_t hw = (size_t)pd.N * pd.N;
-  const size_t per_env = (size_t)G * (pd.P / 2) * hw;   // complex planes x pixels
-  EnvDev dummy;
-  std::memset(&dummy, 0, sizeof(dummy));
-  for (int i0 = 0; i0 < n_env; i0 += chunk) {
-    const int n = std::min(chunk, n_env - i0);
-    PlanDev pdx = pd;
-    pdx.complex_values = reinterpret_cast<const float2*>(values) + (size_t)i0 * per_env;
-    pdx.complex_field = field ? reinterpret_cast<float2*>(field) + (size_t)i0 * per_env : nullptr;
-    pdx.complex_stats = 1;
-    HBX_HIP(hbx::run_jobs(pdx, p->full_jobs, n * G, nullptr, target ? target + (size_t)i0 * G * hw : nullptr,
-                          intensity ? intensity + (size_t)i0 * G * hw : nullptr, nullptr, st));
-    if (chan_stats)
-      HBX_HIP(hbx::launch_full_finalize(p->full_jobs, pd.job_stats, n, G, chan_stats + (size_t)i0 * G * 3,
-                                        psnr ? psnr + i0 : nullptr, pixel_count(p), p->optics.rel_scale,
-                                        p->optics.peak, dummy, 0, st));
-  }
-  return HBX_OK;
+  if (int rc = check_real_plan(p, true)) return rc;
+  FullRequest r;
+  r.complex_values = reinterpret_cast<const float2*>(values); r.target = target; r.n = n_env;
+  r.complex_field = reinterpret_cast<float2*>(field); r.complex_stats = true;
+  r.intensity = intensity; r.chan_stats = chan_stats; r.psnr = psnr;
+  return propagate_full(p, r, stream);
 }
 
 namespace {
@@ -693,9 +688,7 @@ int hbx_loss_weight(hbx_plan_t p, const float* intensity, const float* target, c
 }
 
 int hbx_psnr(hbx_plan_t p, const double* chan_stats, int32_t n_env, double* psnr, void* stream) {
-  int rc = check_plan(p);
-  if (rc) return rc;
-  if (n_env <= 0) return n_env == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "n_env");
+  HBX_ENTER(p, n_env, "n_env");
   if (!chan_stats || !psnr) return fail(HBX_ERR_INVALID, "null buffer");
   HBX_HIP(hipSetDevice(p->device));
   HBX_HIP(hbx::launch_psnr(chan_stats, n_env, p->pd.G, psnr, pixel_count(p), p->optics.rel_scale,
@@ -731,9 +724,12 @@ int hbx_env_reset(hbx_plan_t p, const hbx_env_buffers_t* e, int32_t n_env, const
   if ((e->plane_inten != nullptr) != (e->plane_slot != nullptr))
     return fail(HBX_ERR_INVALID, "plane cache: give both plane_inten and plane_slot");
   if (planes && e->field) return fail(HBX_ERR_INVALID, "plane cache and env.field (incremental mode) are exclusive");
-  rc = propagate_full(p, e->mask, e->target, env_ids, n, e->intensity, e->chan_stats, nullptr, &ed,
-                      reinterpret_cast<float2*>(e->field), st, planes ? e->plane_inten : nullptr,
-                      planes ? e->plane_slot : nullptr);
+  FullRequest r;
+  r.mask = e->mask; r.target = e->target; r.env_ids = env_ids; r.n = n;
+  r.intensity = e->intensity; r.chan_stats = e->chan_stats; r.env = &ed;
+  r.field = reinterpret_cast<float2*>(e->field);
+  if (planes) { r.plane_pool = e->plane_inten; r.plane_slot = e->plane_slot; }
+  rc = propagate_full(p, r, stream);
   if (rc) return rc;
   HBX_HIP(hbx::launch_obs_sync(env_ids, n, e->mask, e->state_bytes, e->intensity, e->recon, e->recon_pending,
                                0, CH, pd.G, (size_t)pd.N * pd.N, st));
@@ -774,9 +770,10 @@ int hbx_env_obs_sync(hbx_plan_t p, const hbx_env_buffers_t* e, int32_t n_env, co
     // (ABI v12) one group: the step keeps no accepted-intensity cache, so the accepted state's
     // intensity is re-propagated from the mask (the same kernels: the bits the steps compute)
     if (!e->target) return fail(HBX_ERR_INVALID, "HBX_OBS_RECON needs env.target");
-    int rc2 = propagate_full(p, e->mask, e->target, env_ids, n, e->intensity, nullptr, nullptr, nullptr, nullptr,
-                             (hipStream_t)stream);
-    if (rc2) return rc2;
+    FullRequest r;
+    r.mask = e->mask; r.target = e->target; r.env_ids = env_ids; r.n = n;
+    r.intensity = e->intensity;
+    if ((rc = propagate_full(p, r, stream))) return rc;
   }
   HBX_HIP(hbx::launch_obs_sync(env_ids, n, e->mask, st_on ? e->state_bytes : nullptr, e->intensity,
                                rc_on ? e->recon : nullptr, e->recon_pending, (what & HBX_OBS_RESOLVE) ? 1 : 0,
@@ -795,9 +792,11 @@ int hbx_field_refresh(hbx_plan_t p, const hbx_env_buffers_t* e, int32_t n_env, c
       return fail(HBX_ERR_INVALID, "plane-cache refresh needs mask, target and chan_stats");
     const int n = env_ids ? n_ids : n_env;
     if (n <= 0) return n == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "n_env");
-    HBX_HIP(hipSetDevice(p->device));
-    return propagate_full(p, e->mask, e->target, env_ids, n, e->intensity, e->chan_stats, nullptr, nullptr,
-                          nullptr, (hipStream_t)stream, e->plane_inten, e->plane_slot);
+    FullRequest r;
+    r.mask = e->mask; r.target = e->target; r.env_ids = env_ids; r.n = n;
+    r.intensity = e->intensity; r.chan_stats = e->chan_stats;
+    r.plane_pool = e->plane_inten; r.plane_slot = e->plane_slot;
+    return propagate_full(p, r, stream);
   }
   if (!e || !e->mask || !e->target || !e->chan_stats || !e->intensity || !e->field)
     return fail(HBX_ERR_INVALID, "refresh needs mask, target, chan_stats, intensity and field");
@@ -807,8 +806,11 @@ int hbx_field_refresh(hbx_plan_t p, const hbx_env_buffers_t* e, int32_t n_env, c
   hipStream_t st = (hipStream_t)stream;
   rc = ensure_hpsf(p, st);
   if (rc) return rc;
-  return propagate_full(p, e->mask, e->target, env_ids, n, e->intensity, e->chan_stats, nullptr, nullptr,
-                        reinterpret_cast<float2*>(e->field), st);
+  FullRequest r;
+  r.mask = e->mask; r.target = e->target; r.env_ids = env_ids; r.n = n;
+  r.intensity = e->intensity; r.chan_stats = e->chan_stats;
+  r.field = reinterpret_cast<float2*>(e->field);
+  return propagate_full(p, r, stream);
 }
 
 int hbx_env_step_psf(hbx_plan_t p, const hbx_env_buffers_t* e, const hbx_env_params_t* prm,
@@ -834,11 +836,7 @@ int hbx_env_step_psf(hbx_plan_t p, const hbx_env_buffers_t* e, const hbx_env_par
   const PlanDev& pd = p->pd;
   const int N = pd.N, G = pd.G, P = pd.P, CH = G * P;
   const size_t hw = (size_t)N * N;
-  EnvParams ep;
-  ep.max_steps = prm->max_steps; ep.t_psnr = prm->t_psnr; ep.t_steps = prm->t_steps;
-  ep.t_psnr_diff = prm->t_psnr_diff; ep.reward_weight = prm->reward_weight;
-  ep.accept_rule = prm->accept_rule;
-  ep.reward_kind = prm->reward_kind;
+  const EnvParams ep = env_params(prm);
   EnvDev base = env_dev(e);
   base.plane_slot = nullptr;   // the incremental step leaves a plane cache alone (the modes are exclusive)
   for (int b0 = 0; b0 < n_env; b0 += p->max_jobs) {
@@ -892,19 +890,21 @@ int hbx_env_step(hbx_plan_t p, const hbx_env_buffers_t* e, const hbx_env_params_
     rc = ensure_job_inten(p);
     if (rc) return rc;
   }
-  PlanDev pdx = p->pd;            // with recon, k_rowinv writes the stepped group straight into it
-  pdx.inten_by_env = to_recon ? 1 : 0;
+  PassCall c;
+  c.jobs = p->jobs;
+  c.inten_by_env = to_recon ? 1 : 0;   // with recon, k_rowinv writes the stepped group straight into it
   if ((e->plane_inten != nullptr) != (e->plane_slot != nullptr))
     return fail(HBX_ERR_INVALID, "plane cache: give both plane_inten and plane_slot");
   const bool planes = e->plane_inten != nullptr;
   if (planes && pd.R != 32 && pd.R != 16 && pd.R != 0)
     return fail(HBX_ERR_UNSUPPORTED, "plane cache: N = 1024, 896 or 256 only");
-  if (planes) pdx.plane_mode = hbx::kPlanesStep;
-  EnvParams ep;
-  ep.max_steps = prm->max_steps; ep.t_psnr = prm->t_psnr; ep.t_steps = prm->t_steps;
-  ep.t_psnr_diff = prm->t_psnr_diff; ep.reward_weight = prm->reward_weight;
-  ep.accept_rule = prm->accept_rule;
-  ep.reward_kind = prm->reward_kind;
+  if (planes) c.plane_mode = hbx::kPlanesStep;
+  // N = 1024 / 256: the finalize kernel sums the row-block partials itself (no k_reduce_partials) and
+  // the first pass decodes the actions itself (no k_jobs_from_actions)
+  const bool fused = pd.R == 32 || pd.R == 16;
+  c.skip_reduce = fused ? 1 : 0;
+  c.act_err = fused ? (e->error ? e->error : p->err) : nullptr;
+  const EnvParams ep = env_params(prm);
   EnvDev base = env_dev(e);
   if (!base.error) base.error = p->err;   // the word k_jobs_from_actions sets
   // (ABI v12) one colour group: every step rewrites recon whole, so nothing is ever restored from
@@ -915,34 +915,32 @@ int hbx_env_step(hbx_plan_t p, const hbx_env_buffers_t* e, const hbx_env_params_
     const EnvDev ed = env_offset(base, b0, CH, G, N);
     float* rec = to_recon ? e->recon + (size_t)b0 * G * hw : nullptr;
     if (planes) {
-      pdx.plane_pool = e->plane_inten + (size_t)b0 * (CH + 2) * hw;
-      pdx.plane_slot = e->plane_slot + (size_t)b0 * (CH + 2);
+      c.plane_pool = e->plane_inten + (size_t)b0 * (CH + 2) * hw;
+      c.plane_slot = e->plane_slot + (size_t)b0 * (CH + 2);
     }
     // the previous step's group: recon and intensity agree again before it is overwritten -- in
     // k_rowinv_d's epilogue at N = 1024 / 256 (no launch of its own), else k_recon_reconcile
-    const bool fuse_rc = to_recon && ed.recon_pending && (pd.R == 32 || pd.R == 16);
-    pdx.rc_pending = fuse_rc ? ed.recon_pending : nullptr;
-    pdx.rc_cache = fuse_rc ? e->intensity + (size_t)b0 * G * hw : nullptr;
-    // N = 1024 / 256: the finalize kernel sums the row-block partials itself (no k_reduce_partials)
-    pdx.skip_reduce = (pd.R == 32 || pd.R == 16) ? 1 : 0;
+    const bool fuse_rc = to_recon && ed.recon_pending && fused;
+    c.rc_pending = fuse_rc ? ed.recon_pending : nullptr;
+    c.rc_cache = fuse_rc ? e->intensity + (size_t)b0 * G * hw : nullptr;
     if (to_recon && ed.recon_pending && !fuse_rc)
       HBX_HIP(hbx::launch_recon_reconcile(ed.recon_pending, rec, e->intensity + (size_t)b0 * G * hw, n, G, hw, st));
-    if (pdx.skip_reduce) {     // N = 1024 / 256: the first pass decodes the actions itself
-      pdx.actions = actions + b0;
-      pdx.act_err = e->error ? e->error : p->err;
-    } else {
+    if (fused)
+      c.actions = actions + b0;
+    else
       HBX_HIP(hbx::launch_jobs_from_actions(actions + b0, n, N, N, P, CH, p->jobs, e->error ? e->error : p->err, st));
-    }
-    HBX_HIP(hbx::run_jobs(pdx, p->jobs, n, reinterpret_cast<const uint32_t*>(ed.mask), ed.target,
-                          to_recon ? rec : (want_inten ? p->job_inten : nullptr), nullptr, st));
+    c.n_jobs = n;
+    c.mask = ed.mask;
+    c.target = ed.target;
+    c.inten_out = to_recon ? rec : (want_inten ? p->job_inten : nullptr);
+    HBX_HIP(hbx::run_jobs(pd, c, st));
     HBX_HIP(hbx::launch_env_step_finalize(p->jobs, pd.job_stats, n, G, P, N, N, ed, ep, pixel_count(p),
                                           p->optics.rel_scale, p->optics.peak,
                                           reward ? reward + b0 : nullptr, psnr ? psnr + b0 : nullptr,
                                           accepted ? accepted + b0 : nullptr,
                                           terminated ? terminated + b0 : nullptr,
                                           truncated ? truncated + b0 : nullptr, p->accept_flag, p->delta,
-                                          st, pdx.skip_reduce ? pd.partial : nullptr,
-                                          pdx.skip_reduce ? pd.N / (256 / pd.R) : 0));
+                                          st, fused ? pd.partial : nullptr, fused ? pd.N / (256 / pd.R) : 0));
     if (group_intensity)
       HBX_HIP(hipMemcpyAsync(group_intensity + (size_t)b0 * hw, p->job_inten, (size_t)n * hw * sizeof(float),
                              hipMemcpyDeviceToDevice, st));
@@ -970,7 +968,9 @@ int hbx_step(hbx_plan_t p, uint64_t* mask, const int64_t* actions, int32_t n_env
     uint64_t* m = mask + (size_t)b0 * CH * N * (N / 64);
     const float* tg = target + (size_t)b0 * G * N * N;
     HBX_HIP(hbx::launch_jobs_from_actions(actions + b0, n, N, N, P, CH, p->jobs, p->err, st));
-    HBX_HIP(hbx::run_jobs(pd, p->jobs, n, reinterpret_cast<const uint32_t*>(m), tg, nullptr, nullptr, st));
+    PassCall c;
+    c.jobs = p->jobs; c.n_jobs = n; c.mask = m; c.target = tg;
+    HBX_HIP(hbx::run_jobs(pd, c, st));
     HBX_HIP(hbx::launch_dbs_step_finalize(p->jobs, pd.job_stats, n, G, P, N, N, m,
                                           chan_stats + (size_t)b0 * G * 3, prev_psnr + b0,
                                           psnr_out ? psnr_out + b0 : nullptr,
@@ -983,20 +983,20 @@ int hbx_step(hbx_plan_t p, uint64_t* mask, const int64_t* actions, int32_t n_env
 int hbx_eval_flips(hbx_plan_t p, const uint64_t* base_mask, const float* target,
                    const double* base_chan_stats, const int64_t* flips, int32_t K, double* psnr_out,
                    double* group_stats, void* stream) {
-  int rc = check_plan(p);
-  if (rc) return rc;
-  if (K <= 0) return K == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "K");  // empty batch: null buffers allowed
+  HBX_ENTER(p, K, "K");
   if (!base_mask || !target || !base_chan_stats || !flips || !psnr_out)
     return fail(HBX_ERR_INVALID, "null buffer");
   HBX_HIP(hipSetDevice(p->device));
   hipStream_t st = (hipStream_t)stream;
   const PlanDev& pd = p->pd;
   const int N = pd.N, G = pd.G, P = pd.P, CH = G * P;
+  PassCall c;
+  c.jobs = p->jobs; c.mask = base_mask; c.target = target;
   for (int k0 = 0; k0 < K; k0 += p->max_jobs) {
     const int n = std::min(p->max_jobs, K - k0);
     HBX_HIP(hbx::launch_jobs_from_flips(flips + k0, n, N, N, P, CH, p->jobs, st));
-    HBX_HIP(hbx::run_jobs(pd, p->jobs, n, reinterpret_cast<const uint32_t*>(base_mask), target, nullptr,
-                          nullptr, st));
+    c.n_jobs = n;
+    HBX_HIP(hbx::run_jobs(pd, c, st));
     HBX_HIP(hbx::launch_eval_finalize(p->jobs, pd.job_stats, n, G, base_chan_stats, psnr_out + k0,
                                       group_stats ? group_stats + (size_t)k0 * 3 : nullptr,
                                       pixel_count(p), p->optics.rel_scale, p->optics.peak, st));
@@ -1048,8 +1048,11 @@ int hbx_flip_map(hbx_plan_t p, const uint64_t* mask, const float* target, float*
   const PlanDev& pd = p->pd;
   const int G = pd.G;
   double* stats = p->map_stats;
-  rc = propagate_full(p, mask, target, nullptr, 1, p->map_inten, stats, stats + 3 * G, nullptr,
-                      p->map_field, st);
+  FullRequest r;
+  r.mask = mask; r.target = target; r.n = 1;
+  r.intensity = p->map_inten; r.chan_stats = stats; r.psnr = stats + 3 * G;
+  r.field = p->map_field;
+  rc = propagate_full(p, r, stream);
   if (rc) return rc;
   for (int g = 0; g < G; ++g)
     HBX_HIP(hbx::map_group(pd, g, p->map_field, p->map_inten, target, mask, stats, p->map_q, p->map_d4,
@@ -1063,9 +1066,7 @@ int hbx_flip_map(hbx_plan_t p, const uint64_t* mask, const float* target, float*
 int hbx_commit_flip(hbx_plan_t p, uint64_t* base_mask, double* base_chan_stats, double* prev_psnr,
                     const int64_t* flips, const double* psnr_out, const double* group_stats,
                     const int32_t* k, int32_t K, void* stream) {
-  int rc = check_plan(p);
-  if (rc) return rc;
-  if (K <= 0) return K == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "K");
+  HBX_ENTER(p, K, "K");
   if (!base_mask || !base_chan_stats || !prev_psnr || !flips || !psnr_out || !group_stats || !k)
     return fail(HBX_ERR_INVALID, "null buffer");
   HBX_HIP(hipSetDevice(p->device));
@@ -1083,18 +1084,18 @@ int hbx_planes_fill(hbx_plan_t p, const uint64_t* mask, const float* target, flo
     return fail(HBX_ERR_INVALID, "planes fill needs mask, target, plane_inten, plane_slot and chan_stats");
   if (n_spare_pairs < 1) return fail(HBX_ERR_INVALID, "n_spare_pairs >= 1");
   if (p->max_jobs < p->pd.G) return fail(HBX_ERR_INVALID, "planes fill needs max_jobs >= groups");
-  HBX_HIP(hipSetDevice(p->device));
-  return propagate_full(p, mask, target, nullptr, 1, nullptr, chan_stats, psnr, nullptr, nullptr,
-                        (hipStream_t)stream, plane_inten, plane_slot, n_spare_pairs);
+  FullRequest r;
+  r.mask = mask; r.target = target; r.n = 1;
+  r.chan_stats = chan_stats; r.psnr = psnr;
+  r.plane_pool = plane_inten; r.plane_slot = plane_slot; r.spares = n_spare_pairs;
+  return propagate_full(p, r, stream);
 }
 
 int hbx_eval_flips_planes(hbx_plan_t p, const uint64_t* base_mask, const float* target,
                           const double* base_chan_stats, float* plane_inten, const int32_t* plane_slot,
                           int32_t n_spare_pairs, const int64_t* flips, int32_t K, double* psnr_out,
                           double* group_stats, void* stream) {
-  int rc = check_plan(p);
-  if (rc) return rc;
-  if (K <= 0) return K == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "K");
+  HBX_ENTER(p, K, "K");
   if (!base_mask || !target || !base_chan_stats || !plane_inten || !plane_slot || !flips || !psnr_out)
     return fail(HBX_ERR_INVALID, "null buffer");
   if (p->pd.R != 32 && p->pd.R != 16 && p->pd.R != 0)
@@ -1104,17 +1105,18 @@ int hbx_eval_flips_planes(hbx_plan_t p, const uint64_t* base_mask, const float* 
   hipStream_t st = (hipStream_t)stream;
   const PlanDev& pd = p->pd;
   const int N = pd.N, G = pd.G, P = pd.P, CH = G * P;
-  PlanDev pdx = pd;
-  pdx.plane_mode = hbx::kPlanesStep;
-  pdx.plane_pool = plane_inten;
-  pdx.plane_slot = plane_slot;
-  pdx.plane_spares = n_spare_pairs;   // > 1: spare pair = candidate index (1: K = 1, pair 0)
+  PassCall c;
+  c.jobs = p->jobs; c.mask = base_mask; c.target = target;
+  c.plane_mode = hbx::kPlanesStep;
+  c.plane_pool = plane_inten;
+  c.plane_slot = plane_slot;
+  c.plane_spares = n_spare_pairs;   // > 1: spare pair = candidate index (1: K = 1, pair 0)
   for (int k0 = 0; k0 < K; k0 += p->max_jobs) {
     const int n = std::min(p->max_jobs, K - k0);
-    pdx.spare_base = k0;
+    c.n_jobs = n;
+    c.spare_base = k0;
     HBX_HIP(hbx::launch_jobs_from_flips(flips + k0, n, N, N, P, CH, p->jobs, st));
-    HBX_HIP(hbx::run_jobs(pdx, p->jobs, n, reinterpret_cast<const uint32_t*>(base_mask), target, nullptr,
-                          nullptr, st));
+    HBX_HIP(hbx::run_jobs(pd, c, st));
     HBX_HIP(hbx::launch_eval_finalize(p->jobs, pd.job_stats, n, G, base_chan_stats, psnr_out + k0,
                                       group_stats ? group_stats + (size_t)k0 * 3 : nullptr,
                                       pixel_count(p), p->optics.rel_scale, p->optics.peak, st));
@@ -1126,9 +1128,7 @@ int hbx_commit_flip_planes(hbx_plan_t p, uint64_t* base_mask, double* base_chan_
                            int32_t* plane_slot, int32_t n_spare_pairs, const int64_t* flips,
                            const double* psnr_out, const double* group_stats, const int32_t* k, int32_t K,
                            void* stream) {
-  int rc = check_plan(p);
-  if (rc) return rc;
-  if (K <= 0) return K == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "K");
+  HBX_ENTER(p, K, "K");
   if (!base_mask || !base_chan_stats || !prev_psnr || !plane_slot || !flips || !psnr_out || !group_stats || !k)
     return fail(HBX_ERR_INVALID, "null buffer");
   if (K > n_spare_pairs) return fail(HBX_ERR_INVALID, "K > n_spare_pairs");
@@ -1170,13 +1170,17 @@ int hbx_dbs_walk_planes_fill(hbx_plan_t p, uint64_t* base_mask, const float* tar
   HBX_HIP(hipSetDevice(p->device));
   hipStream_t st = (hipStream_t)stream;
   const PlanDev& pd = p->pd;
-  PlanDev pdx = pd;
-  pdx.plane_mode = hbx::kPlanesStep;
-  pdx.plane_pool = plane_inten;
-  pdx.plane_slot = plane_slot;
-  pdx.plane_spares = n_spare_pairs;
-  pdx.spare_base = 0;
-  pdx.skip_reduce = 1;                     // the decision reduces the row-block partials itself
+  // (r05) each batch's decision runs in the last-arriving k_rowinv_d workgroup of that batch
+  // (k_rowinv_d<R, true>): three launches per batch instead of four.  (r06) N = 896: the decision
+  // in a launch of its own behind each batch (k_walk_planes, decide = 1)
+  const bool fused = pd.R != 0;
+  PassCall c;
+  c.jobs = p->jobs; c.n_jobs = K; c.mask = base_mask; c.target = target;
+  c.plane_mode = hbx::kPlanesStep;
+  c.plane_pool = plane_inten;
+  c.plane_slot = plane_slot;
+  c.plane_spares = n_spare_pairs;
+  c.skip_reduce = fused ? 1 : 0;           // the fused decision reduces the row-block partials itself
   const int RB = pd.R ? pd.N / (256 / pd.R) : pd.N / 8;
   hbx::WalkPlanesArgs wa;
   wa.w = walk; wa.order = order; wa.jobs = p->jobs; wa.partial = pd.partial; wa.mask = base_mask;
@@ -1185,11 +1189,7 @@ int hbx_dbs_walk_planes_fill(hbx_plan_t p, uint64_t* base_mask, const float* tar
   wa.RB = RB; wa.K = K; wa.G = pd.G; wa.P = pd.P; wa.H = pd.N; wa.W = pd.N;
   wa.count = pixel_count(p); wa.rel_scale = p->optics.rel_scale; wa.peak = p->optics.peak;
   wa.fill_count = fill_count; wa.fill_target = fill_target; wa.fill_tol = fill_tol;
-  // (r05) each batch's decision runs in the last-arriving k_rowinv_d workgroup of that batch
-  // (k_rowinv_d<R, true>): three launches per batch instead of four.  (r06) N = 896: the decision
-  // in a launch of its own behind each batch (k_walk_planes, decide = 1)
-  const bool fused = pd.R != 0;
-  pdx.walk_planes = fused ? &wa : nullptr;
+  c.walk_planes = fused ? &wa : nullptr;
   // (r06) candidates a batch propagated but did not visit keep their job slot, their pair's B and,
   // when their colour group saw no accept, their partials: the next batch skips those passes for
   // them (fused decision only; the 896 path decides in its own launch and re-propagates)
@@ -1197,12 +1197,11 @@ int hbx_dbs_walk_planes_fill(hbx_plan_t p, uint64_t* base_mask, const float* tar
   if (fused && pd.G * pd.P / 2 <= 48 && !std::getenv("HBX_WALK_NO_RETAIN")) {
     wa.ring = p->walk_ring;
     wa.phase = p->walk_phase;
-    pdx.walk_phase = p->walk_phase;
+    c.walk_phase = p->walk_phase;
   }
   HBX_HIP(hbx::launch_walk_planes(wa, 0, st));   // this call's first batch of jobs, from the walk state
   for (int b = 0; b < batches; ++b) {
-    HBX_HIP(hbx::run_jobs(pdx, p->jobs, K, reinterpret_cast<const uint32_t*>(base_mask), target, nullptr,
-                          nullptr, st));
+    HBX_HIP(hbx::run_jobs(pd, c, st));
     if (!fused) HBX_HIP(hbx::launch_walk_planes(wa, 1, st));
   }
   return HBX_OK;
@@ -1212,14 +1211,12 @@ int hbx_eval_flips_psf(hbx_plan_t p, const uint64_t* base_mask, const float* tar
                        const double* base_chan_stats, const float* field, const float* intensity,
                        const int64_t* flips, int32_t K, double* psnr_out, double* group_stats,
                        void* stream) {
-  int rc = check_plan(p);
-  if (rc) return rc;
-  if (K <= 0) return K == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "K");
+  HBX_ENTER(p, K, "K");
   if (!base_mask || !target || !base_chan_stats || !field || !intensity || !flips || !psnr_out)
     return fail(HBX_ERR_INVALID, "null buffer");
   HBX_HIP(hipSetDevice(p->device));
   hipStream_t st = (hipStream_t)stream;
-  rc = ensure_hpsf(p, st);
+  int rc = ensure_hpsf(p, st);
   if (rc) return rc;
   const PlanDev& pd = p->pd;
   const int N = pd.N, G = pd.G, P = pd.P, CH = G * P;
@@ -1238,15 +1235,13 @@ int hbx_eval_flips_psf(hbx_plan_t p, const uint64_t* base_mask, const float* tar
 int hbx_commit_flip_psf(hbx_plan_t p, uint64_t* base_mask, double* base_chan_stats, double* prev_psnr,
                         float* field, float* intensity, const int64_t* flips, const double* psnr_out,
                         const double* group_stats, const int32_t* k, int32_t K, void* stream) {
-  int rc = check_plan(p);
-  if (rc) return rc;
-  if (K <= 0) return K == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "K");
+  HBX_ENTER(p, K, "K");
   if (!base_mask || !base_chan_stats || !prev_psnr || !field || !intensity || !flips || !psnr_out ||
       !group_stats || !k)
     return fail(HBX_ERR_INVALID, "null buffer");
   HBX_HIP(hipSetDevice(p->device));
   hipStream_t st = (hipStream_t)stream;
-  rc = ensure_hpsf(p, st);
+  int rc = ensure_hpsf(p, st);
   if (rc) return rc;
   const PlanDev& pd = p->pd;
   const int N = pd.N, G = pd.G, P = pd.P, CH = G * P;

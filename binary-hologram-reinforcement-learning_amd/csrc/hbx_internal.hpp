@@ -160,6 +160,8 @@ struct WalkPlanesArgs {
   uint8_t* phase = nullptr;
 };
 
+// What a plan owns: geometry, tables, workspaces.  Never copied to describe a launch -- what one
+// propagation needs beyond the plan is a PassCall (below).
 struct PlanDev {
   int R;               // N = R * R; 0: N = 896 = 28 x 32 (generic path)
   int N, G, P;
@@ -176,60 +178,96 @@ struct PlanDev {
   int32_t* psf_order;  // [max_jobs] jobs sorted by colour group (launch order)
   float* zero_row;     // [N] zeros: the target row of a propagation without a target
   int store_kind;      // HBX_PRECISION_*: rounding of the pass intermediates (0 = f32, the product)
-  int inten_by_env;    // intensity output rows: 0 = job-major [job][N][N]; 1 = env-major
-                       // [env][G][N][N] at (job.env, job.group) (the obs recon buffer, ABI v8)
   PassTimer* timer;    // nullable
-  // plane-cached FFT mode (ABI v9; N = 1024 / 256), set per call on a copy of the plan's PlanDev:
-  //   kPlanesOff    no plane cache
-  //   kPlanesFill   full propagation: every plane's |U_p|^2 also goes to its pool slot
-  //   kPlanesStep   env step: only the flipped plane's pair is propagated, the other planes'
-  //                 |U_q|^2 come from the pool (k_rowinv_d sums them in the same plane order,
-  //                 so the group intensity is the FFT mode's bit for bit); the pair's fresh
-  //                 |U|^2 go to the env's two spare slots (swapped in on accept)
-  int plane_mode;
-  float* plane_pool;         // [env][CH + 2S][N][N] f32 per-plane |U|^2 (env ids as the jobs carry them)
-  const int32_t* plane_slot; // [env][CH + 2S] pool slot of every plane; [CH + 2s], [CH + 2s + 1] = spare pair s
-  int plane_spares;          // S: spare pairs per env (0 / 1: the env step's one pair).  S > 1 (ABI v10,
-                             // hbx_eval_flips_planes): candidate j of a launch writes its pair to spare
-  int spare_base;            // pair spare_base + j, so K candidates of one base keep K fresh pairs
-  // (r04) env step with the recon observation at N = 1024 / 256: k_rowinv_d applies the previous
-  // step's recon / intensity-cache reconcile (recon_pending, env-major like inten_out) itself
-  const int32_t* rc_pending; // [env] nullable
-  float* rc_cache;           // [env][G][N][N] the intensity cache
-  int skip_reduce = 0;       // 1: leave the per-row-block partials (a caller reduces them itself)
-  const uint8_t* walk_phase = nullptr;           // (r06) per job slot: 0 all passes, 1 k_rowinv_d only,
-                                                 // 2 none (WalkPlanesArgs::phase; nullptr = all)
-  const WalkPlanesArgs* walk_planes = nullptr;   // (r05) plane-cache walk batch: the last k_rowinv_d
-                                                 // workgroup decides (hbx_walk_planes.hpp)
-  // env step at N = 1024 / 256: the first pass decodes the actions itself (no k_jobs_from_actions
-  // launch) and one of its workgroups per job writes the JobDesc the later passes read
-  const int64_t* actions = nullptr;
-  int32_t* act_err = nullptr;
-  // (ABI v15) full propagation of a real-valued field: [env][G*P][N][N] f32 samples the first
-  // pass reads instead of the mask bits (u = value; va / vb are not applied).  f32 intermediates,
-  // no plane cache, no actions, no walk
+};
+
+// plane-cached FFT mode (ABI v9; N = 1024 / 896 / 256), PassCall::plane_mode:
+//   kPlanesOff    no plane cache
+//   kPlanesFill   full propagation: every plane's |U_p|^2 also goes to its pool slot
+//   kPlanesStep   env step: only the flipped plane's pair is propagated, the other planes'
+//                 |U_q|^2 come from the pool (k_rowinv_d sums them in the same plane order,
+//                 so the group intensity is the FFT mode's bit for bit); the pair's fresh
+//                 |U|^2 go to the env's two spare slots (swapped in on accept)
+constexpr int kPlanesOff = 0, kPlanesFill = 1, kPlanesStep = 2;
+
+// One three-pass propagation (run_jobs): everything a launch needs beyond the plan.  A call site
+// names what it sets; check_pass_call states which combinations mean something.
+struct PassCall {
+  const JobDesc* jobs = nullptr;
+  int n_jobs = 0;
+  // the input, exactly one of three: the packed mask bits (u = va + vb * bit) ...
+  const uint64_t* mask = nullptr;
+  // ... (ABI v15) a real-valued field: [env][G*P][N][N] f32 samples the first pass reads instead of
+  // the mask bits (u = value; va / vb are not applied).  f32 intermediates, no plane cache, no
+  // actions, no walk ...
   const float* real_values = nullptr;
-  // (ABI v15, additive) full propagation of a complex field (hbx_simulate_complex):
-  // [env][G*P/2][N][N] complex64 samples the first pass reads, complex plane q into plane-pair slot
-  // q; the last pass recombines each pair and writes complex_field [env][G*P/2][N][N] complex64
-  // and / or real_part [env][G*P/2][N][N] f32 (at least one non-null) and nothing else -- intensity,
-  // partials and statistics only with complex_stats below.  f32 intermediates, no plane cache, no
-  // actions, no walk
+  // ... or (ABI v15, additive) a complex field (hbx_simulate_complex): [env][G*P/2][N][N] complex64
+  // samples the first pass reads, complex plane q into plane-pair slot q; the last pass recombines
+  // each pair and writes complex_field [env][G*P/2][N][N] complex64 and / or real_part
+  // [env][G*P/2][N][N] f32 (at least one non-null) and nothing else -- intensity, partials and
+  // statistics only with complex_stats below.  f32 intermediates, no plane cache, no actions, no walk
   const float2* complex_values = nullptr;
   // (ABI v15, additive) hbx_simulate_complex_weighted: [env][G][N][N] f32, non-null only with
   // complex_values; the first pass propagates (complex_scale * complex_weight[env][group]) * values
   const float* complex_weight = nullptr;
   float complex_scale = 1.0f;
-  float2* complex_field = nullptr;
+  // env step at N = 1024 / 256: the first pass decodes the actions itself (no
+  // k_jobs_from_actions launch) and one of its workgroups per job writes the JobDesc the later
+  // passes read
+  const int64_t* actions = nullptr;
+  int32_t* act_err = nullptr;
+  // the outputs
+  const float* target = nullptr;   // [env][G][N][N]; null: the plan's zero row, nothing meaningful reduced
+  float* inten_out = nullptr;      // plane-mean intensity rows (nullable)
+  int inten_by_env = 0;            // their order: 0 = job-major [job][N][N]; 1 = env-major
+                                   // [env][G][N][N] at (job.env, job.group) (the obs recon buffer, ABI v8)
+  float2* field_out = nullptr;     // [env][G*P][N][N] complex field of every propagated plane (nullable)
+  float2* complex_field = nullptr; // complex input only, see complex_values
   float* real_part = nullptr;
   // (ABI v15, additive) hbx_evaluate_complex: 1 with complex_values = the last pass also accumulates
   // |F_q|^2 over the group's P/2 complex planes and runs the real last pass's tail -- the plane-mean
-  // intensity to run_jobs' inten_out [job][N][N] (job-major; nullable) and the partials against
-  // run_jobs' target (null: the zero row, nothing reduced).  complex_field and real_part may then
-  // both be null
+  // intensity to inten_out [job][N][N] (job-major; nullable) and the partials against target (null:
+  // the zero row, nothing reduced).  complex_field and real_part may then both be null
   int complex_stats = 0;
+  // the plane cache (kPlanes* above)
+  int plane_mode = kPlanesOff;
+  float* plane_pool = nullptr;          // [env][CH + 2S][N][N] f32 per-plane |U|^2 (env ids as the jobs carry them)
+  const int32_t* plane_slot = nullptr;  // [env][CH + 2S] pool slot of every plane; [CH + 2s], [CH + 2s + 1] = spare pair s
+  int plane_spares = 0;                 // S: spare pairs per env (0 / 1: the env step's one pair).  S > 1 (ABI v10,
+                                        // hbx_eval_flips_planes): candidate j of a launch writes its pair to spare
+  int spare_base = 0;                   // pair spare_base + j, so K candidates of one base keep K fresh pairs
+  // (r04) env step with the recon observation at N = 1024 / 256: k_rowinv_d applies the previous
+  // step's recon / intensity-cache reconcile (recon_pending, env-major like inten_out) itself
+  const int32_t* rc_pending = nullptr;  // [env]
+  float* rc_cache = nullptr;            // [env][G][N][N] the intensity cache
+  int skip_reduce = 0;                  // 1: leave the per-row-block partials (a caller reduces them itself)
+  const uint8_t* walk_phase = nullptr;          // (r06) per job slot: 0 all passes, 1 k_rowinv_d only,
+                                                // 2 none (WalkPlanesArgs::phase; nullptr = all)
+  const WalkPlanesArgs* walk_planes = nullptr;  // (r05) plane-cache walk batch: the last k_rowinv_d
+                                                // workgroup decides (hbx_walk_planes.hpp)
 };
-constexpr int kPlanesOff = 0, kPlanesFill = 1, kPlanesStep = 2;
+
+// Which PassCalls the pass kernels of this plan can run: every field a selected kernel would not
+// read is refused, not ignored.  run_jobs calls it before a timer slot opens or a kernel is enqueued.
+inline hipError_t check_pass_call(const PlanDev& pd, const PassCall& c) {
+  const bool tiled = pd.R == 32 || pd.R == 16;   // the k_rowinv_d sizes
+  const bool f32 = pd.store_kind == HBX_PRECISION_F32;
+  const bool planes = c.plane_mode != kPlanesOff;
+  const bool walk = c.walk_phase || c.walk_planes;
+  const bool complex_out = c.complex_field || c.real_part || c.complex_stats;
+  bool ok = (c.mask != nullptr) + (c.real_values != nullptr) + (c.complex_values != nullptr) == 1;
+  ok = ok && (!planes || (c.plane_pool && c.plane_slot && (tiled || pd.R == 0)));
+  ok = ok && (!c.walk_planes || (c.plane_mode == kPlanesStep && tiled));
+  ok = ok && (!c.rc_pending == !c.rc_cache) && (!c.rc_pending || tiled);
+  ok = ok && (c.actions || !c.act_err);
+  if (pd.R == 0) ok = ok && !c.walk_phase && !c.actions && !c.skip_reduce;
+  // real and complex samples: the f32 product path alone
+  if (!c.mask) ok = ok && f32 && !planes && !c.actions && !walk;
+  // complex in, complex out: the pair-recombining last pass writes these and nothing else
+  ok = ok && (c.complex_values ? complex_out && !c.field_out && !c.inten_by_env && !c.rc_pending && !c.skip_reduce
+                               : !complex_out && !c.complex_weight);
+  return ok ? hipSuccess : hipErrorInvalidValue;
+}
 
 constexpr int kPsfBlocks = 128;   // blocks per job of the incremental-field kernels
                                   // (measured 128 > 256 > 64 > 32, profiles/r01_psf_blocks_ab.txt)
@@ -267,12 +305,16 @@ struct EnvParams {
   int32_t reward_kind;  // 0 env.py, 1 env_group.py
 };
 
-// field_out (nullable): [env][G*P][N][N] complex field of every propagated plane
-hipError_t run_jobs(const PlanDev& pd, const JobDesc* jobs, int n_jobs, const uint32_t* mask,
-                    const float* target, float* inten_out, float2* field_out, hipStream_t st);
-// fused three-pass propagation at N = 896 (hbx_passes896.hip)
-hipError_t run_jobs_896(const PlanDev& pd, const JobDesc* jobs, int n_jobs, const uint32_t* mask,
-                        const float* target, float* inten_out, float2* field_out, hipStream_t st);
+// the three passes of one PassCall: check_pass_call, then the launches
+hipError_t run_jobs(const PlanDev& pd, const PassCall& c, hipStream_t st);
+// its N = 896 form (hbx_passes896.hip; run_jobs has checked the call)
+hipError_t run_jobs_896(const PlanDev& pd, const PassCall& c, hipStream_t st);
+// One kernel launch of `blocks` workgroups of `nt` threads: the caller picks the instantiation (a
+// function pointer: every variant of a kernel family has one signature) and writes the arguments once
+template <class K, class... A>
+inline void launch_kernel(K k, unsigned blocks, unsigned nt, hipStream_t st, A... a) {
+  hipLaunchKernelGGL(k, dim3(blocks), dim3(nt), 0, st, a...);
+}
 // 2-D FFT of n_planes [N][N] complex planes in a (result in a; b is scratch of
 // the same size).  Unnormalised both ways.
 hipError_t run_fft2d(const PlanDev& pd, float2* a, float2* b, int n_planes, bool inverse,

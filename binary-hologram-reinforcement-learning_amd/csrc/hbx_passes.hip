@@ -1518,167 +1518,113 @@ __global__ void k_reduce_partials(const double* __restrict__ partial, int n_jobs
                                   double* __restrict__ job_stats);
 
 template <int R, int SK>
-static hipError_t launch_passes(const PlanDev& pd, const JobDesc* jobs, int n_jobs,
-                                const uint32_t* mask, const float* target, float* inten_out,
-                                float2* field_out, hipStream_t st) {
+static hipError_t launch_passes(const PlanDev& pd, const PassCall& c, hipStream_t st) {
   constexpr int N = R * R;
   constexpr int GPB = 256 / R;
+  constexpr int NT = kRowNT<R>;
+  constexpr int kRowBlocks = N / (NT / R);        // row blocks per plane (pair)
+  const JobDesc* jobs = c.jobs;
+  const int n_jobs = c.n_jobs;
   const int P = pd.P;
   const int CH = pd.G * pd.P;
   PassTimer* tm = pd.timer;
-  const int pair = pd.plane_mode == kPlanesStep ? 1 : 0;
-  if (pd.plane_mode != kPlanesOff && (!kTiledB<R> || !pd.plane_pool || !pd.plane_slot)) return hipErrorInvalidValue;
+  const int pair = c.plane_mode == kPlanesStep ? 1 : 0;
+  // no target: the last pass reads the plan's zero row, every row offset masked to 0
+  const float* tg = c.target ? c.target : pd.zero_row;
+  const size_t tmask = c.target ? ~(size_t)0 : (size_t)0;
   // Small batches (greedy DBS, a few candidates per launch): the walk-per-workgroup loops
   // (rowfwd_iters row blocks, col2_iters lines) trade parallelism for store overlap, which pays
   // only when the launch fills the chip many times over.  Below kSmallBlocks workgroups the
   // launch runs one row block / one line per workgroup instead -- the same arithmetic, so
   // bit-identical results (tests/test_gpu_dbs_headline.py plane-cache / full re-propagation).
   constexpr unsigned kSmallBlocks = 2048;
-  const unsigned rf_blocks = (unsigned)n_jobs * (pair ? 1 : P / 2) * (N / (kRowNT<R> / R)) / rowfwd_iters<R>();
+  const unsigned rf_blocks = (unsigned)n_jobs * (pair ? 1 : P / 2) * kRowBlocks / rowfwd_iters<R>();
   const unsigned col_blocks = (unsigned)n_jobs * (pair ? 2 : P) * ((N / 2) / (GPB * col2_iters<R>()));
   const bool small = kTiledB<R> && rf_blocks < kSmallBlocks && col_blocks < kSmallBlocks;
-  if (pd.complex_values && (SK != HBX_PRECISION_F32 || pd.plane_mode != kPlanesOff || pd.actions || pd.walk_phase ||
-                            pd.real_values || (!pd.complex_field && !pd.real_part && !pd.complex_stats)))
-    return hipErrorInvalidValue;   // before the timer opens a slot, as run_jobs_896
-  if (pd.complex_weight && !pd.complex_values) return hipErrorInvalidValue;   // the weight scales complex samples only
-  {
-    if (tm) tm->begin(0, st);
-    if (pd.complex_values) {   // complex field: the real kernels' geometry, wg.q = the complex plane
-      const unsigned blocks = (unsigned)n_jobs * (P / 2) * (N / (kRowNT<R> / R));
-      const float* cw = pd.complex_weight;   // hbx_simulate_complex_weighted: u = (scale * weight) * values
-      const float cs = pd.complex_scale;
-      if constexpr (R == 32) {
-        if (cw)
-          hipLaunchKernelGGL(k_rowfwd32_cplx<true>, dim3(blocks), dim3(256), 0, st, jobs, pd.complex_values, pd.ws_a,
-                             pd.tw, P, CH, cw, cs);
-        else
-          hipLaunchKernelGGL(k_rowfwd32_cplx<false>, dim3(blocks), dim3(256), 0, st, jobs, pd.complex_values, pd.ws_a,
-                             pd.tw, P, CH, cw, cs);
-      } else {
-        if (cw)
-          hipLaunchKernelGGL((k_rowfwd_cplx<R, kRowNT<R>, true>), dim3(blocks), dim3(kRowNT<R>), 0, st, jobs,
-                             pd.complex_values, pd.ws_a, pd.tw, P, CH, cw, cs);
-        else
-          hipLaunchKernelGGL((k_rowfwd_cplx<R, kRowNT<R>, false>), dim3(blocks), dim3(kRowNT<R>), 0, st, jobs,
-                             pd.complex_values, pd.ws_a, pd.tw, P, CH, cw, cs);
-      }
-    } else if (pd.real_values) {   // real-valued field: one row block per workgroup at every launch size
-      if (SK != HBX_PRECISION_F32 || pair || pd.actions || pd.walk_phase) return hipErrorInvalidValue;
-      const unsigned blocks = (unsigned)n_jobs * (P / 2) * (N / (kRowNT<R> / R));
-      if constexpr (R == 32)
-        hipLaunchKernelGGL(k_rowfwd32_real, dim3(blocks), dim3(256), 0, st, jobs, pd.real_values, pd.ws_a, pd.tw, P,
-                           CH);
-      else
-        hipLaunchKernelGGL((k_rowfwd_real<R, kRowNT<R>>), dim3(blocks), dim3(kRowNT<R>), 0, st, jobs,
-                           pd.real_values, pd.ws_a, pd.tw, P, CH);
-    } else if constexpr (R == 32) {
-      if (small)
-        hipLaunchKernelGGL((k_rowfwd32<SK, 1>), dim3(rf_blocks * rowfwd_iters<R>()), dim3(256), 0, st, jobs, mask,
-                           pd.ws_a, pd.tw, P, CH, pd.va, pd.vb, pair, pd.actions, pd.act_err, pd.walk_phase);
-      else
-        hipLaunchKernelGGL((k_rowfwd32<SK>), dim3(rf_blocks), dim3(256), 0, st, jobs, mask, pd.ws_a, pd.tw, P, CH,
-                           pd.va, pd.vb, pair, pd.actions, pd.act_err, pd.walk_phase);
-    } else if constexpr (kTiledB<R>) {
-      if (small)
-        hipLaunchKernelGGL((k_rowfwd<R, kRowNT<R>, SK, 1>), dim3(rf_blocks * rowfwd_iters<R>()), dim3(kRowNT<R>), 0,
-                           st, jobs, mask, pd.ws_a, pd.tw, P, CH, pd.va, pd.vb, pair, pd.actions, pd.act_err, pd.walk_phase);
-      else
-        hipLaunchKernelGGL((k_rowfwd<R, kRowNT<R>, SK>), dim3(rf_blocks), dim3(kRowNT<R>), 0, st, jobs, mask,
-                           pd.ws_a, pd.tw, P, CH, pd.va, pd.vb, pair, pd.actions, pd.act_err, pd.walk_phase);
-    } else {
-      hipLaunchKernelGGL((k_rowfwd<R, kRowNT<R>, SK>), dim3(rf_blocks), dim3(kRowNT<R>), 0, st, jobs, mask, pd.ws_a,
-                         pd.tw, P, CH, pd.va, pd.vb, pair, pd.actions, pd.act_err, pd.walk_phase);
-    }
-    if (tm) tm->end(0, n_jobs, st);
+  // real and complex samples: the bit kernels' geometry (complex: wg.q = the complex plane), one row
+  // block per workgroup at every launch size
+  const unsigned sample_blocks = (unsigned)n_jobs * (P / 2) * kRowBlocks;
+
+  if (tm) tm->begin(0, st);
+  if (c.complex_values) {   // WT (hbx_simulate_complex_weighted): u = (scale * weight) * values
+    const bool wt = c.complex_weight != nullptr;
+    auto k = [&] {
+      if constexpr (R == 32) return wt ? k_rowfwd32_cplx<true> : k_rowfwd32_cplx<false>;
+      else return wt ? k_rowfwd_cplx<R, NT, true> : k_rowfwd_cplx<R, NT, false>;
+    }();
+    launch_kernel(k, sample_blocks, NT, st, jobs, c.complex_values, pd.ws_a, pd.tw, P, CH, c.complex_weight,
+                  c.complex_scale);
+  } else if (c.real_values) {
+    auto k = [&] {
+      if constexpr (R == 32) return k_rowfwd32_real;
+      else return k_rowfwd_real<R, NT>;
+    }();
+    launch_kernel(k, sample_blocks, NT, st, jobs, c.real_values, pd.ws_a, pd.tw, P, CH);
+  } else {
+    auto k = [&] {
+      if constexpr (R == 32) return small ? k_rowfwd32<SK, 1> : k_rowfwd32<SK>;
+      else if constexpr (kTiledB<R>) return small ? k_rowfwd<R, NT, SK, 1> : k_rowfwd<R, NT, SK>;
+      else return k_rowfwd<R, NT, SK>;
+    }();
+    launch_kernel(k, small ? rf_blocks * rowfwd_iters<R>() : rf_blocks, NT, st, jobs,
+                  reinterpret_cast<const uint32_t*>(c.mask), pd.ws_a, pd.tw, P, CH, pd.va, pd.vb, pair, c.actions,
+                  c.act_err, c.walk_phase);
   }
+  if (tm) tm->end(0, n_jobs, st);
+
+  if (tm) tm->begin(1, st);
   {
-    if (tm) tm->begin(1, st);
-    if constexpr (kTiledB<R>) {
-      if (small)
-        hipLaunchKernelGGL((k_col2<R, SK, 1>), dim3(col_blocks * col2_iters<R>()), dim3(256), 0, st, jobs, pd.ws_a,
-                           pd.ws_b, pd.htab, pd.tw, P, pair, pd.walk_phase);
-      else
-        hipLaunchKernelGGL((k_col2<R, SK>), dim3(col_blocks), dim3(256), 0, st, jobs, pd.ws_a, pd.ws_b, pd.htab,
-                           pd.tw, P, pair, pd.walk_phase);
-    } else {
-      hipLaunchKernelGGL((k_col2<R, SK>), dim3(col_blocks), dim3(256), 0, st, jobs, pd.ws_a, pd.ws_b, pd.htab,
-                         pd.tw, P, pair, pd.walk_phase);
-    }
-    if (tm) tm->end(1, n_jobs, st);
+    auto k = [&] {
+      if constexpr (kTiledB<R>) return small ? k_col2<R, SK, 1> : k_col2<R, SK>;
+      else return k_col2<R, SK>;
+    }();
+    launch_kernel(k, small ? col_blocks * col2_iters<R>() : col_blocks, 256, st, jobs, pd.ws_a, pd.ws_b, pd.htab,
+                  pd.tw, P, pair, c.walk_phase);
   }
-  {
-    const unsigned blocks = (unsigned)n_jobs * (N / (kRowNT<R> / R));
-    if (tm) tm->begin(2, st);
-    if (pd.complex_values) {   // recombine each plane pair
-      const float* tg = target ? target : pd.zero_row;
-      const size_t tmask = target ? ~(size_t)0 : (size_t)0;
-      if constexpr (kTiledB<R>) {
-        if (pd.complex_stats)
-          hipLaunchKernelGGL((k_rowinv_d_cplx<R, true>), dim3(blocks), dim3(256), 0, st, jobs, pd.ws_b, pd.tw, P,
-                             pd.G, pd.complex_field, pd.real_part, tg, tmask, pd.partial, inten_out);
-        else
-          hipLaunchKernelGGL((k_rowinv_d_cplx<R>), dim3(blocks), dim3(256), 0, st, jobs, pd.ws_b, pd.tw, P, pd.G,
-                             pd.complex_field, pd.real_part, tg, tmask, pd.partial, inten_out);
-      } else {
-        if (pd.complex_stats)
-          hipLaunchKernelGGL((k_rowinv_cplx<R, kRowNT<R>, true>), dim3(blocks), dim3(kRowNT<R>), 0, st, jobs,
-                             pd.ws_b, pd.tw, P, pd.G, pd.complex_field, pd.real_part, tg, tmask, pd.partial,
-                             inten_out);
-        else
-          hipLaunchKernelGGL((k_rowinv_cplx<R, kRowNT<R>>), dim3(blocks), dim3(kRowNT<R>), 0, st, jobs, pd.ws_b,
-                             pd.tw, P, pd.G, pd.complex_field, pd.real_part, tg, tmask, pd.partial, inten_out);
-      }
-      if (tm) tm->end(2, n_jobs, st);
-      // hbx_evaluate_complex with a target: the statistics form left partials to reduce
-      if (pd.complex_stats && target)
-        hipLaunchKernelGGL(k_reduce_partials, dim3(n_jobs), dim3(64), 0, st, pd.partial, n_jobs,
-                           N / (kRowNT<R> / R), pd.job_stats);
-      return hipGetLastError();
-    }
-    if constexpr (kTiledB<R>) {
-      if (pd.walk_planes) {   // (r05) a plane-cache walk batch: the last workgroup decides
-        if (pd.plane_mode != kPlanesStep) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((k_rowinv_d<R, true>), dim3(blocks), dim3(256), 0, st, jobs, pd.ws_b,
-                           target ? target : pd.zero_row, pd.tw, P, pd.G, pd.partial, inten_out, field_out,
-                           target ? ~(size_t)0 : (size_t)0, pd.inten_by_env, pd.plane_mode, pd.plane_pool,
-                           pd.plane_slot, pd.plane_spares, pd.spare_base, pd.rc_pending, pd.rc_cache,
-                           *pd.walk_planes);
-      } else if (pd.plane_mode == kPlanesOff && !field_out && !pd.rc_pending) {
-        // (r06) the plain FFT-mode launch (the headline): its own instantiation without the plane
-        // cache / field / reconcile / walk code -- 1,687 instead of 4,988 instructions; same
-        // arithmetic and bits, k_rowinv 1.465-1.515 -> 1.444-1.457 ms alternated on one box
-        // (profiles/r06/rowinv_lean_ab_r06e.txt)
-        hipLaunchKernelGGL((k_rowinv_d<R, false, true>), dim3(blocks), dim3(256), 0, st, jobs, pd.ws_b,
-                           target ? target : pd.zero_row, pd.tw, P, pd.G, pd.partial, inten_out, field_out,
-                           target ? ~(size_t)0 : (size_t)0, pd.inten_by_env, pd.plane_mode, pd.plane_pool,
-                           pd.plane_slot, pd.plane_spares, pd.spare_base, pd.rc_pending, pd.rc_cache,
-                           WalkPlanesArgs{});
-      } else {
-        hipLaunchKernelGGL((k_rowinv_d<R>), dim3(blocks), dim3(256), 0, st, jobs, pd.ws_b,
-                           target ? target : pd.zero_row, pd.tw, P, pd.G, pd.partial, inten_out, field_out,
-                           target ? ~(size_t)0 : (size_t)0, pd.inten_by_env, pd.plane_mode, pd.plane_pool,
-                           pd.plane_slot, pd.plane_spares, pd.spare_base, pd.rc_pending, pd.rc_cache,
-                           WalkPlanesArgs{});
-      }
-    }
-    else
-      hipLaunchKernelGGL((k_rowinv<R, kRowNT<R>>), dim3(blocks), dim3(kRowNT<R>), 0, st, jobs, pd.ws_b,
-                         target ? target : pd.zero_row, pd.tw, P, pd.G, pd.partial, inten_out,
-                         field_out, target ? ~(size_t)0 : (size_t)0, pd.inten_by_env);
-    if (tm) tm->end(2, n_jobs, st);
+  if (tm) tm->end(1, n_jobs, st);
+
+  const unsigned blocks = (unsigned)n_jobs * kRowBlocks;
+  bool reduce = !c.skip_reduce;
+  if (tm) tm->begin(2, st);
+  if (c.complex_values) {   // recombine each plane pair; ST (hbx_evaluate_complex): intensity and partials too
+    const bool stats = c.complex_stats != 0;
+    auto k = [&] {
+      if constexpr (kTiledB<R>) return stats ? k_rowinv_d_cplx<R, true> : k_rowinv_d_cplx<R>;
+      else return stats ? k_rowinv_cplx<R, NT, true> : k_rowinv_cplx<R, NT>;
+    }();
+    launch_kernel(k, blocks, NT, st, jobs, pd.ws_b, pd.tw, P, pd.G, c.complex_field, c.real_part, tg, tmask,
+                  pd.partial, c.inten_out);
+    reduce = stats && c.target;   // only the statistics form with a target left partials to reduce
+  } else if constexpr (kTiledB<R>) {
+    // WALK (r05): a plane-cache walk batch, the last workgroup decides.  LEAN (r06): the plain
+    // FFT-mode launch (the headline), its own instantiation without the plane cache / field /
+    // reconcile / walk code -- 1,687 instead of 4,988 instructions; same arithmetic and bits,
+    // k_rowinv 1.465-1.515 -> 1.444-1.457 ms alternated on one box (profiles/r06/rowinv_lean_ab_r06e.txt)
+    const bool lean = c.plane_mode == kPlanesOff && !c.field_out && !c.rc_pending;
+    // (named WALK, LEAN, general on purpose: first use fixes a kernel's place in the code object, and
+    // the timings on record were taken with this layout -- tools/isa_cmp.py reports a reordering)
+    auto k = k_rowinv_d<R, true>;
+    if (!c.walk_planes) k = lean ? k_rowinv_d<R, false, true> : k_rowinv_d<R>;
+    launch_kernel(k, blocks, 256, st, jobs, pd.ws_b, tg, pd.tw, P, pd.G, pd.partial, c.inten_out, c.field_out, tmask,
+                  c.inten_by_env, c.plane_mode, c.plane_pool, c.plane_slot, c.plane_spares, c.spare_base,
+                  c.rc_pending, c.rc_cache, c.walk_planes ? *c.walk_planes : WalkPlanesArgs{});
+  } else {
+    launch_kernel(k_rowinv<R, NT>, blocks, NT, st, jobs, pd.ws_b, tg, pd.tw, P, pd.G, pd.partial, c.inten_out,
+                  c.field_out, tmask, c.inten_by_env);
   }
-  if (!pd.skip_reduce)
-    hipLaunchKernelGGL(k_reduce_partials, dim3(n_jobs), dim3(64), 0, st, pd.partial,
-                       n_jobs, N / (kRowNT<R> / R), pd.job_stats);
+  if (tm) tm->end(2, n_jobs, st);
+  if (reduce)
+    hipLaunchKernelGGL(k_reduce_partials, dim3(n_jobs), dim3(64), 0, st, pd.partial, n_jobs, kRowBlocks, pd.job_stats);
   return hipGetLastError();
 }
 
-hipError_t run_jobs(const PlanDev& pd, const JobDesc* jobs, int n_jobs, const uint32_t* mask,
-                    const float* target, float* inten_out, float2* field_out, hipStream_t st) {
-  if (pd.R == 0) return run_jobs_896(pd, jobs, n_jobs, mask, target, inten_out, field_out, st);
+hipError_t run_jobs(const PlanDev& pd, const PassCall& c, hipStream_t st) {
+  const hipError_t e = check_pass_call(pd, c);
+  if (e != hipSuccess) return e;
+  if (pd.R == 0) return run_jobs_896(pd, c, st);
   switch (pd.R * 4 + pd.store_kind) {
 #define HBX_PASSES_CASE(R_, SK_) \
-    case R_ * 4 + SK_: return launch_passes<R_, SK_>(pd, jobs, n_jobs, mask, target, inten_out, field_out, st);
+    case R_ * 4 + SK_: return launch_passes<R_, SK_>(pd, c, st);
     HBX_PASSES_CASE(32, HBX_PRECISION_F32)
     HBX_PASSES_CASE(32, HBX_PRECISION_BF16_STORE)
     HBX_PASSES_CASE(32, HBX_PRECISION_F16_STORE)

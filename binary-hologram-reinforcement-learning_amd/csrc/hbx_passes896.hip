@@ -693,71 +693,52 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896_cplx(const JobDesc* __rest
 __global__ void k_reduce_partials(const double* __restrict__ partial, int n_jobs, int RB,
                                   double* __restrict__ job_stats);
 
-hipError_t run_jobs_896(const PlanDev& pd, const JobDesc* jobs, int n_jobs, const uint32_t* mask,
-                        const float* target, float* inten_out, float2* field_out, hipStream_t st) {
+hipError_t run_jobs_896(const PlanDev& pd, const PassCall& c, hipStream_t st) {
+  const JobDesc* jobs = c.jobs;
+  const int n_jobs = c.n_jobs;
   const int P = pd.P;
   const int CH = pd.G * pd.P;
   PassTimer* tm = pd.timer;
   // (r06) plane-cached mode at 896: a fill writes every plane's |U|^2, a step propagates the
   // flipped plane's pair only (the walk's decision runs in a launch of its own at 896)
-  const int pair = pd.plane_mode == kPlanesStep ? 1 : 0;
-  if (pd.plane_mode != kPlanesOff && (!pd.plane_pool || !pd.plane_slot)) return hipErrorInvalidValue;
-  if (pd.real_values && (pair || pd.store_kind != HBX_PRECISION_F32)) return hipErrorInvalidValue;
-  if (pd.complex_values && (pair || pd.store_kind != HBX_PRECISION_F32 || pd.real_values ||
-                            pd.plane_mode != kPlanesOff ||
-                            (!pd.complex_field && !pd.real_part && !pd.complex_stats)))
-    return hipErrorInvalidValue;
-  if (pd.complex_weight && !pd.complex_values) return hipErrorInvalidValue;   // the weight scales complex samples only
+  const int pair = c.plane_mode == kPlanesStep ? 1 : 0;
+  // no target: the last pass reads the plan's zero row, every row offset masked to 0
+  const float* tg = c.target ? c.target : pd.zero_row;
+  const size_t tmask = c.target ? ~(size_t)0 : (size_t)0;
+  const unsigned blocks = (unsigned)n_jobs * kRB;   // one workgroup per row block of a job
+
   if (tm) tm->begin(0, st);
-  if (pd.complex_values)
-    if (pd.complex_weight)   // hbx_simulate_complex_weighted: u = (scale * weight) * values
-      hipLaunchKernelGGL(k_rowfwd896_cplx<true>, dim3((unsigned)n_jobs * (P / 2) * kRB), dim3(256), 0, st, jobs,
-                         pd.complex_values, pd.ws_a, pd.tw, P, CH, pd.complex_weight, pd.complex_scale);
-    else
-      hipLaunchKernelGGL(k_rowfwd896_cplx<false>, dim3((unsigned)n_jobs * (P / 2) * kRB), dim3(256), 0, st, jobs,
-                         pd.complex_values, pd.ws_a, pd.tw, P, CH, pd.complex_weight, pd.complex_scale);
-  else if (pd.real_values)
-    hipLaunchKernelGGL(k_rowfwd896_real, dim3((unsigned)n_jobs * (P / 2) * kRB), dim3(256), 0, st, jobs,
-                       pd.real_values, pd.ws_a, pd.tw, P, CH);
+  if (c.complex_values)   // WT (hbx_simulate_complex_weighted): u = (scale * weight) * values
+    launch_kernel(c.complex_weight ? k_rowfwd896_cplx<true> : k_rowfwd896_cplx<false>, blocks * (P / 2), 256, st, jobs,
+                  c.complex_values, pd.ws_a, pd.tw, P, CH, c.complex_weight, c.complex_scale);
+  else if (c.real_values)
+    launch_kernel(k_rowfwd896_real, blocks * (P / 2), 256, st, jobs, c.real_values, pd.ws_a, pd.tw, P, CH);
   else
-    hipLaunchKernelGGL(k_rowfwd896, dim3((unsigned)n_jobs * (pair ? 1 : P / 2) * (kRB / kRit896)), dim3(256), 0, st,
-                     jobs, mask, pd.ws_a, pd.tw, P, CH, pd.va, pd.vb, pair);
+    launch_kernel(k_rowfwd896, blocks / kRit896 * (pair ? 1 : P / 2), 256, st, jobs,
+                  reinterpret_cast<const uint32_t*>(c.mask), pd.ws_a, pd.tw, P, CH, pd.va, pd.vb, pair);
   if (tm) tm->end(0, n_jobs, st);
+
   if (tm) tm->begin(1, st);
-  hipLaunchKernelGGL(k_col896, dim3((unsigned)n_jobs * (pair ? 2 : P) * kColLB), dim3(256), 0, st, jobs, pd.ws_a,
-                     pd.ws_b, pd.htab, pd.tw, P, pair);
+  launch_kernel(k_col896, (unsigned)n_jobs * (pair ? 2 : P) * kColLB, 256, st, jobs, pd.ws_a, pd.ws_b, pd.htab,
+                pd.tw, P, pair);
   if (tm) tm->end(1, n_jobs, st);
+
+  bool reduce = true;
   if (tm) tm->begin(2, st);
-  if (pd.complex_values) {   // recombine each plane pair
-    const float* tg = target ? target : pd.zero_row;
-    const size_t tmask = target ? ~(size_t)0 : (size_t)0;
-    if (pd.complex_stats)
-      hipLaunchKernelGGL(k_rowinv896_cplx<true>, dim3((unsigned)n_jobs * kRB), dim3(256), 0, st, jobs, pd.ws_b, pd.tw,
-                         P, pd.G, pd.complex_field, pd.real_part, tg, tmask, pd.partial, inten_out);
-    else
-      hipLaunchKernelGGL(k_rowinv896_cplx<false>, dim3((unsigned)n_jobs * kRB), dim3(256), 0, st, jobs, pd.ws_b,
-                         pd.tw, P, pd.G, pd.complex_field, pd.real_part, tg, tmask, pd.partial, inten_out);
-    if (tm) tm->end(2, n_jobs, st);
-    // hbx_evaluate_complex with a target: the statistics form left partials to reduce
-    if (pd.complex_stats && target)
-      hipLaunchKernelGGL(k_reduce_partials, dim3(n_jobs), dim3(64), 0, st, pd.partial, n_jobs, kRB, pd.job_stats);
-    return hipGetLastError();
+  if (c.complex_values) {   // recombine each plane pair; ST (hbx_evaluate_complex): intensity and partials too
+    launch_kernel(c.complex_stats ? k_rowinv896_cplx<true> : k_rowinv896_cplx<false>, blocks, 256, st, jobs, pd.ws_b,
+                  pd.tw, P, pd.G, c.complex_field, c.real_part, tg, tmask, pd.partial, c.inten_out);
+    reduce = c.complex_stats && c.target;   // only the statistics form with a target left partials to reduce
+  } else {
+    // (r06) the plain FFT-mode launch gets the lean instantiation (profiles/r06/rowinv896_lean_ab_r06i.txt)
+    const bool lean = c.plane_mode == kPlanesOff && !c.field_out;
+    launch_kernel(lean ? k_rowinv896<true> : k_rowinv896<false>, blocks, 256, st, jobs, pd.ws_b, tg, pd.tw, P, pd.G,
+                  pd.partial, c.inten_out, c.field_out, tmask, c.inten_by_env, c.plane_mode, c.plane_pool,
+                  c.plane_slot, c.plane_spares, c.spare_base);
   }
-  // (r06) the plain FFT-mode launch gets the lean instantiation (profiles/r06/rowinv896_lean_ab_r06i.txt)
-  const bool lean = pd.plane_mode == kPlanesOff && !field_out;
-  if (lean)
-    hipLaunchKernelGGL(k_rowinv896<true>, dim3((unsigned)n_jobs * kRB), dim3(256), 0, st, jobs, pd.ws_b,
-                       target ? target : pd.zero_row, pd.tw, P, pd.G, pd.partial, inten_out, field_out,
-                       target ? ~(size_t)0 : (size_t)0, pd.inten_by_env, pd.plane_mode, pd.plane_pool, pd.plane_slot,
-                       pd.plane_spares, pd.spare_base);
-  else
-    hipLaunchKernelGGL(k_rowinv896<false>, dim3((unsigned)n_jobs * kRB), dim3(256), 0, st, jobs, pd.ws_b,
-                       target ? target : pd.zero_row, pd.tw, P, pd.G, pd.partial, inten_out, field_out,
-                       target ? ~(size_t)0 : (size_t)0, pd.inten_by_env, pd.plane_mode, pd.plane_pool, pd.plane_slot,
-                       pd.plane_spares, pd.spare_base);
   if (tm) tm->end(2, n_jobs, st);
-  hipLaunchKernelGGL(k_reduce_partials, dim3(n_jobs), dim3(64), 0, st, pd.partial, n_jobs, kRB,
-                     pd.job_stats);
+  if (reduce)
+    hipLaunchKernelGGL(k_reduce_partials, dim3(n_jobs), dim3(64), 0, st, pd.partial, n_jobs, kRB, pd.job_stats);
   return hipGetLastError();
 }
 

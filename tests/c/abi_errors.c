@@ -44,6 +44,19 @@ int main(void) {
   CHECK(strstr(hbx_last_error(), "null plan") != NULL);
   CHECK(hbx_simulate(NULL, NULL, 1, NULL, NULL, NULL) == HBX_ERR_INVALID);
   CHECK(hbx_psnr(NULL, NULL, 0, NULL, NULL) == HBX_ERR_INVALID);
+  /* (ABI v15) the real / complex / loss entry points: a null plan comes before the count */
+  CHECK(hbx_propagate_real(NULL, NULL, NULL, 1, NULL, NULL, NULL, NULL) == HBX_ERR_INVALID);
+  CHECK(strstr(hbx_last_error(), "null plan") != NULL);
+  CHECK(hbx_simulate_real(NULL, NULL, 1, NULL, NULL, NULL) == HBX_ERR_INVALID);
+  CHECK(hbx_simulate_complex(NULL, NULL, 1, NULL, NULL, NULL) == HBX_ERR_INVALID);
+  CHECK(hbx_simulate_complex_weighted(NULL, NULL, NULL, 1.0f, 1, NULL, NULL, NULL) == HBX_ERR_INVALID);
+  CHECK(hbx_intensity_real(NULL, NULL, 0, NULL, NULL) == HBX_ERR_INVALID);
+  CHECK(hbx_evaluate_real(NULL, NULL, NULL, 1, NULL, NULL, NULL, NULL, NULL) == HBX_ERR_INVALID);
+  CHECK(hbx_evaluate_complex(NULL, NULL, NULL, 0, NULL, NULL, NULL, NULL, NULL) == HBX_ERR_INVALID);
+  CHECK(strstr(hbx_last_error(), "null plan") != NULL);
+  CHECK(hbx_loss(NULL, NULL, 1, HBX_LOSS_MSE, HBX_REL_LSQ, NULL, NULL) == HBX_ERR_INVALID);
+  CHECK(hbx_loss_weight(NULL, NULL, NULL, NULL, NULL, 1, HBX_LOSS_PSNR, HBX_REL_NONE, NULL, NULL) == HBX_ERR_INVALID);
+  CHECK(strstr(hbx_last_error(), "null plan") != NULL);
   CHECK(hbx_env_reset(NULL, NULL, 0, NULL, 0, NULL) == HBX_ERR_INVALID);
   CHECK(hbx_env_step(NULL, NULL, NULL, 0, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL) == HBX_ERR_INVALID);
   CHECK(hbx_env_step_psf(NULL, NULL, NULL, 0, NULL, NULL, NULL, NULL, NULL, NULL, NULL) == HBX_ERR_INVALID);

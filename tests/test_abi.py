@@ -105,3 +105,22 @@ def test_abi_error_paths_under_asan(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=env)
     assert r.returncode == 0 and "OK" in r.stdout, r.stdout + r.stderr
     assert "AddressSanitizer" not in r.stderr, r.stderr
+
+
+def test_pass_call_rules_under_asan(tmp_path):
+    """hbx::check_pass_call (csrc/hbx_internal.hpp), the one validator in front of the three-pass
+    launches: tests/c/pass_call_check.hip feeds it every PassCall shape the C-ABI layer builds
+    (accepted) and one call per rule (rejected), host code under ASan + UBSan.  A stand-alone
+    program: no GPU, no library, nothing reaches a launch."""
+    hipcc = "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not present")
+    csrc = os.path.join(ROOT, "binary-hologram-reinforcement-learning_amd", "csrc")
+    exe = str(tmp_path / "pass_call_check")
+    subprocess.run([hipcc, "-std=c++17", "--offload-arch=gfx950", "-Xarch_host", "-fsanitize=address,undefined",
+                    "-I", os.path.join(ROOT, "include"), "-I", csrc,
+                    os.path.join(ROOT, "tests", "c", "pass_call_check.hip"), "-o", exe], check=True, timeout=300)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1", HIP_VISIBLE_DEVICES="")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=env)
+    assert r.returncode == 0 and r.stdout.strip() == "OK", r.stdout + r.stderr
+    assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr

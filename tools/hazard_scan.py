@@ -96,14 +96,16 @@ def scan(path, window=WAIT_STATES):
     return hits
 
 
-def compile_all(outdir, srcs=None, defines=()):
-    srcs = srcs or sorted(glob.glob(os.path.join(CSRC, "*.hip")))
+def compile_all(outdir, srcs=None, defines=(), root=ROOT):
+    """Device assembly of root's csrc/*.hip (or srcs) into outdir; the list of .s files."""
+    csrc = os.path.join(root, os.path.relpath(CSRC, ROOT))
+    srcs = srcs or sorted(glob.glob(os.path.join(csrc, "*.hip")))
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
     def one(src):
         out = os.path.join(outdir, os.path.basename(src) + ".s")
         subprocess.run([hipcc, "-O3", "-std=c++17", "-fno-slp-vectorize", "--offload-arch=gfx950",
-                        "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
+                        "-I" + os.path.join(root, "include"), "-I" + csrc,
                         "-mllvm", "-disable-promote-alloca-to-lds", *defines,
                         "--offload-device-only", "-S", "-o", out, src], check=True,
                        stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
