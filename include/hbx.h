@@ -60,7 +60,12 @@ extern "C" {
 #define HBX_MAX_GROUPS 4
 
 /* Optics of one plan; replaces tt.Tensor meta {'dx','wl'} + simulate's z
- * (env.py:124,172; env_1024_24.py:135-138; DBS_1024_24.py:230-233). */
+ * (env.py:124,172; env_1024_24.py:135-138; DBS_1024_24.py:230-233).
+ * dx is the pitch along the width axis (fx = kx / (N dx)), dy along the height axis; they may
+ * differ.  HBX_TF_ASM: H(fx, fy) = exp(i 2 pi z sqrt(1/wl^2 - fx^2 - fy^2)) where the radicand is
+ * positive and exactly 0 in the evanescent bins (radicand <= 0, reached once the pitch is below
+ * wl / sqrt(2)); no path assumes |H| = 1.  H(-z) = conj H(z) in every bin, the zeros included, so
+ * the plan for -z is the exact adjoint of the plan for z with or without a cut. */
 typedef struct hbx_optics {
   int32_t height;                        /* N (64, 256, 896 or 1024), square */
   int32_t width;                         /* == height                         */
