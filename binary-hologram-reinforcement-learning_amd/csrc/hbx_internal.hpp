@@ -268,6 +268,19 @@ inline hipError_t check_pass_call(const PlanDev& pd, const PassCall& c) {
                                : !complex_out && !c.complex_weight);
   return ok ? hipSuccess : hipErrorInvalidValue;
 }
+// The target rows the last pass reads.  No target: the plan's zero row, every row offset masked to 0
+struct PassTarget {
+  const float* rows;
+  size_t mask;
+};
+inline PassTarget pass_target(const PlanDev& pd, const PassCall& c) {
+  return c.target ? PassTarget{c.target, ~(size_t)0} : PassTarget{pd.zero_row, (size_t)0};
+}
+// Whether k_reduce_partials runs behind the last pass.  Complex samples: only the statistics form with
+// a target left partials to reduce; otherwise unless the caller reduces them itself
+inline bool pass_reduces(const PassCall& c) {
+  return c.complex_values ? c.complex_stats && c.target : !c.skip_reduce;
+}
 
 constexpr int kPsfBlocks = 128;   // blocks per job of the incremental-field kernels
                                   // (measured 128 > 256 > 64 > 32, profiles/r01_psf_blocks_ab.txt)

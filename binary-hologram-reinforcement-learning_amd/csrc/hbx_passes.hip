@@ -39,6 +39,7 @@
 #include "hbx_fft.hpp"
 #include "hbx_internal.hpp"
 #include "hbx_rowcol.hpp"
+#include "hbx_rowinv.hpp"
 #include "hbx_walk_planes.hpp"
 
 namespace hbx {
@@ -800,123 +801,8 @@ __global__ __launch_bounds__(256, 2) void k_col2(const JobDesc* __restrict__ job
 // ---------------------------------------------------------------------------
 // Pass 3
 // ---------------------------------------------------------------------------
-// k_rowinv's tail: plane mean, f64 partials of (I*T, I^2, T^2) against the target row,
-// fixed-order reduction over the group's lanes and the block's rows.
-template <int R, int GPB, bool SC1 = false, bool TPRE = false>
-__device__ __forceinline__ void rowinv_epilogue(float (&acc)[R], int P, int G, const JobDesc& jb, int j, int y,
-                                                int rb, int grp, int t, const float* __restrict__ target,
-                                                size_t tmask, float* __restrict__ inten_out, int inten_by_env,
-                                                double* __restrict__ partial, double (&red)[GPB][3],
-                                                const int32_t* __restrict__ rc_pending = nullptr,
-                                                float* __restrict__ rc_cache = nullptr,
-                                                const float* tpre = nullptr) {
-  constexpr int N = R * R;
-  constexpr int RB = N / GPB;
-  const float invp = 1.0f / (float)P;
-  // tmask = 0 points every row at the plan's zero row (no target): the loads
-  // stay unconditional, so they issue early like the rest of the stream
-  const float* trow = target + ((((size_t)jb.env * G + jb.group) * N + y) * N & tmask);
-  double sxy = 0.0, sxx = 0.0, syy = 0.0;
-#pragma unroll
-  for (int k = 0; k < R; ++k) {
-    const float I = acc[k] * invp;
-    const float T = TPRE ? tpre[k] : trow[t + R * k];   // TPRE: the caller loaded the row ahead
-    sxy = fma((double)I, (double)T, sxy);
-    sxx = fma((double)I, (double)I, sxx);
-    syy = fma((double)T, (double)T, syy);
-    acc[k] = I;
-  }
-  if (inten_out) {
-    const size_t slot = inten_by_env ? (size_t)jb.env * G + jb.group : (size_t)j;
-    float* orow = inten_out + (slot * N + y) * N;
-    if (rc_pending) {
-      // (r04) the previous step's recon / intensity-cache reconcile of this env, fused here
-      // instead of its own launch before the step (k_recon_reconcile): the previous step left
-      // group gp's new intensity in recon only (p > 0, accepted: recon -> cache) or its stepped
-      // intensity in recon (p < 0, rolled back: cache -> recon).  Row y of group gp is moved
-      // by the lane group of row y; when gp is this step's group, an accepted row is read out
-      // before this step overwrites it and a rolled-back one needs nothing.
-      const int p = rc_pending[jb.env];
-      if (p != 0) {
-        const int gp = (p > 0 ? p : -p) - 1;
-        const size_t grow = (((size_t)jb.env * G + gp) * N + y) * N;
-        if (p > 0) {
-#pragma unroll
-          for (int k = 0; k < R; ++k) rc_cache[grow + t + R * k] = inten_out[grow + t + R * k];
-        } else if (gp != jb.group) {
-#pragma unroll
-          for (int k = 0; k < R; ++k) inten_out[grow + t + R * k] = rc_cache[grow + t + R * k];
-        }
-      }
-    }
-    if (inten_by_env) {
-      // obs["recon_image"] (r05): streamed out non-temporal -- nothing on the device reads it
-      // before the next step rewrites it (the settle copy at G > 1 takes the accepted half)
-#pragma unroll
-      for (int k = 0; k < R; ++k) __builtin_nontemporal_store(acc[k], orow + t + R * k);
-    } else {
-#pragma unroll
-      for (int k = 0; k < R; ++k) orow[t + R * k] = acc[k];
-    }
-  }
-  // reduce over the R lanes of the group, fixed order -> bitwise reproducible
-#pragma unroll
-  for (int off = R / 2; off >= 1; off >>= 1) {
-    sxy += __shfl_xor(sxy, off, 64);
-    sxx += __shfl_xor(sxx, off, 64);
-    syy += __shfl_xor(syy, off, 64);
-  }
-  if (t == 0) { red[grp][0] = sxy; red[grp][1] = sxx; red[grp][2] = syy; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double a = 0.0, b = 0.0, cc = 0.0;
-    for (int g = 0; g < GPB; ++g) { a += red[g][0]; b += red[g][1]; cc += red[g][2]; }
-    double* o = partial + ((size_t)j * RB + rb) * 3;
-    if constexpr (SC1) {   // read by the deciding workgroup of this launch (walk_planes_arrive)
-      const __amdgpu_buffer_rsrc_t ro = walk_planes_rsrc(o, 24);
-      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, a), ro, 0, 0, kSc1Bit);
-      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, b), ro, 8, 0, kSc1Bit);
-      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, cc), ro, 16, 0, kSc1Bit);
-    } else {
-      o[0] = a; o[1] = b; o[2] = cc;
-    }
-  }
-}
-
-// k_rowinv at N = 1024 / 256 (r03): every lane loads its own FFT input straight from
-// the tiled B (TileB) -- lane t of group g (row y0 + g) needs kx = t + R jj, which for TL
-// consecutive lanes is TL consecutive slots of one tile row (64 B at N = 1024: the two rows
-// of a wave are adjacent, 128 B; 128 B at N = 256: a wave's four rows are one 512-B run),
-// so no LDS tile and no block barrier sit in the plane loop: the group's FFT transpose
-// (wave_sync) is its only LDS traffic.  The next plane's loads are issued as soon as this
-// plane's FFT is done (two blocks per CU cover them; a second register set for a plane in
-// flight took one block per CU and measured 1.80 ms against 1.47).  The r02
-// kernel staged every plane through an LDS tile between three block barriers (1.80 ms).
-// Lane bases (bytes from the job's first B plane) of row y for lane t of the row's group; slot s at
-// TileB<R>::at(s, y):
-//   jj < R/2 (and kx = N/2 for t = 0): s = kx = t + R jj -> lo + 16 R jj float2
-//   jj >= R/2 otherwise: s = 3N/2 - kx -> hi - 16 R jj, written hiB + 16 R (R - 1 - jj)
-//   so every offset stays non-negative
-template <int R>
-struct RowinvLanes {
-  static constexpr int N = R * R, TL = 256 / R;
-  static constexpr int JS = 16 * R * 8;             // bytes per jj
-  int lo, hiB, vmid;
-  __device__ __forceinline__ RowinvLanes(int y, int t) {
-    const int yb = (y >> 4) * 16 * N + (y & 15) * TL;
-    const int m = t / TL, u = t % TL;
-    lo = (yb + m * 16 * TL + u) * 8;
-    hiB = (yb + (u ? (3 * N / (2 * TL) - m - 1) * 16 * TL + TL - u : (3 * N / (2 * TL) - m) * 16 * TL) -
-           16 * R * (R - 1)) * 8;
-    vmid = t == 0 ? lo + JS * (R / 2) : hiB + JS * (R / 2 - 1);
-  }
-  // the lane's FFT input jj (kx = t + R jj) of the plane at byte offset po (wave-uniform)
-  __device__ __forceinline__ float2 load(__amdgpu_buffer_rsrc_t rs, int po, int jj) const {
-    const int vo = jj < R / 2 ? lo : (jj == R / 2 ? vmid : hiB);
-    const int so = po + (jj < R / 2 ? JS * jj : (jj == R / 2 ? 0 : JS * (R - 1 - jj)));
-    return buf_ld2s(rs, vo, so);
-  }
-};
+// The tail (rowinv_epilogue), the lane bases of the direct loads (RowinvLanes), the plane cache and the
+// other pieces shared with the N = 896 kernels are in hbx_rowinv.hpp.
 
 template <int R, bool WALK = false, bool LEAN = false>
 __global__ __launch_bounds__(256, 2) void k_rowinv_d(const JobDesc* __restrict__ jobs,
@@ -949,15 +835,7 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_d(const JobDesc* __restrict__
     }
   }
   if (jb.env < 0) {
-    if (threadIdx.x == 0) {
-      double* o = partial + ((size_t)j * RB + rb) * 3;
-      if constexpr (WALK) {
-        const __amdgpu_buffer_rsrc_t ro = walk_planes_rsrc(o, 24);
-        for (int i = 0; i < 3; ++i) __builtin_amdgcn_raw_buffer_store_b64(u32x2{0u, 0u}, ro, 8 * i, 0, kSc1Bit);
-      } else {
-        o[0] = 0.0; o[1] = 0.0; o[2] = 0.0;
-      }
-    }
+    rowinv_zero_partial<WALK>(partial, j, RB, rb);
     if constexpr (WALK) walk_planes_arrive(wk, reinterpret_cast<char*>(scratch));
     return;
   }
@@ -971,67 +849,21 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_d(const JobDesc* __restrict__
   constexpr int PLB = N * N;                 // float2 per B plane
   const __amdgpu_buffer_rsrc_t rs = plane_rsrc(ws_b + (size_t)j * P * PLB, (unsigned)((size_t)P * PLB * 8));
   const RowinvLanes<R> ln(y, t);
-  auto load_plane = [&](pk2 (&v)[R], int p) {
-    const int po = p * PLB * 8;
-#pragma unroll
-    for (int jj = 0; jj < R; ++jj) v[jj] = to_pk(ln.load(rs, po, jj));
-  };
+  auto load_plane = [&](pk2 (&v)[R], int p) { rowinv_load_plane(v, ln, rs, p); };
   float acc[R];
 #pragma unroll
   for (int k = 0; k < R; ++k) acc[k] = 0.0f;
   const PaddedScratch<R> sc{scratch + grp * R * (R + 1)};
-  // plane cache (ABI v9): slots of this env's planes, pool rows of this lane group's row y
-  const int CH = G * P;
-  const int CHS = CH + 2 * (plane_spares > 1 ? plane_spares : 1);   // pool slots per env
-  const int spare = CH + 2 * (plane_spares > 1 ? spare_base + j : 0);  // this job's fresh pair
-  const int32_t* slots = plane_slot ? plane_slot + (size_t)jb.env * CHS : nullptr;
-  auto pool_row = [&](int slot) { return plane_pool + (((size_t)jb.env * CHS + slot) * N + y) * N; };
+  const PlaneCache<R> pc(jb, j, y, G, P, plane_spares, spare_base, plane_pool, plane_slot);
   auto finish_plane = [&](pk2 (&v)[R], int p) {
     fft_group<R, true>(v, t, sc, tw);
-    float f[R];
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-      f[k] = fmaf(v[k].x, v[k].x, v[k].y * v[k].y);
-      acc[k] += f[k];
-    }
-    if (field_out) {  // exact field of this plane (incremental mode init / refresh)
-      float2* frow = field_out + (((size_t)jb.env * G * P + jb.group * P + p) * N + y) * N;
-#pragma unroll
-      for (int k = 0; k < R; ++k) frow[t + R * k] = from_pk(v[k]);
-    }
-    // |U_p|^2 to the plane cache: every plane on a fill; on a step both planes of the flipped pair
-    // go to the two spares -- the partner's bits change too (the pair is ONE complex row FFT, so
-    // its rounding sees the flipped plane), which is why a step keeps both
-    if (plane_mode != kPlanesOff) {
-      float* orow = pool_row(slots[plane_mode == kPlanesFill ? jb.group * P + p : spare + (p & 1)]);
-#pragma unroll
-      for (int k = 0; k < R; ++k) __builtin_nontemporal_store(f[k], orow + t + R * k);
-    }
-  };
-  // a cached plane's |U_q|^2 added in its place in the plane order (the sum is the FFT mode's
-  // sum bit for bit: acc = ((0 + c_0) + c_1) + ..., each c_q the same f32 value)
-  auto add_cached = [&](int q) {
-    const float* crow = pool_row(slots[jb.group * P + q]);
-    float c[R];
-#pragma unroll
-    for (int k = 0; k < R; ++k) c[k] = __builtin_nontemporal_load(crow + t + R * k);
-#pragma unroll
-    for (int k = 0; k < R; ++k) acc[k] += c[k];
+    plane_out<R, R>(v, acc, pc, jb, G, P, p, t, field_out, plane_mode);
   };
   pk2 va[R];
   if (plane_mode == kPlanesStep) {   // only the flipped plane's pair is in B
-    const int pa = jb.flip_plane & ~1;
-    load_plane(va, pa);
-    __syncthreads();  // tw visible
-#pragma unroll 1
-    for (int q = 0; q < pa; ++q) add_cached(q);
-    finish_plane(va, pa);
-    load_plane(va, pa + 1);
-    finish_plane(va, pa + 1);
-#pragma unroll 1
-    for (int q = pa + 2; q < P; ++q) add_cached(q);
-    rowinv_epilogue<R, GPB, WALK>(acc, P, G, jb, j, y, rb, grp, t, target, tmask, inten_out, inten_by_env, partial,
-                                  red, rc_pending, rc_cache);
+    rowinv_planes_step(va, acc, pc, jb, P, t, load_plane, finish_plane);
+    rowinv_epilogue<R, R, GPB, WALK>(acc, P, G, jb, j, y, rb, grp, t, target, tmask, inten_out, inten_by_env, partial,
+                                     red, rc_pending, rc_cache);
     if constexpr (WALK) {
       __syncthreads();   // every group is done with its scratch region: the decision's LDS
       walk_planes_arrive(wk, reinterpret_cast<char*>(scratch));
@@ -1062,8 +894,8 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_d(const JobDesc* __restrict__
 #pragma unroll
     for (int k = 0; k < R; ++k) tv[k] = trow[t + R * k];
     finish_plane(va, P - 1);
-    rowinv_epilogue<R, GPB, false, true>(acc, P, G, jb, j, y, rb, grp, t, target, tmask, inten_out, inten_by_env,
-                                         partial, red, rc_pending, rc_cache, tv);
+    rowinv_epilogue<R, R, GPB, false, true>(acc, P, G, jb, j, y, rb, grp, t, target, tmask, inten_out, inten_by_env,
+                                            partial, red, rc_pending, rc_cache, tv);
     return;
   } else {
 #pragma unroll 1
@@ -1072,8 +904,8 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_d(const JobDesc* __restrict__
       load_plane(va, p + 1 < P ? p + 1 : p);   // unconditional: the last round re-reads plane P - 1
     }
   }
-  rowinv_epilogue<R, GPB>(acc, P, G, jb, j, y, rb, grp, t, target, tmask, inten_out, inten_by_env, partial, red,
-                           rc_pending, rc_cache);
+  rowinv_epilogue<R, R, GPB>(acc, P, G, jb, j, y, rb, grp, t, target, tmask, inten_out, inten_by_env, partial, red,
+                              rc_pending, rc_cache);
 }
 
 template <int R, int NT>
@@ -1105,10 +937,7 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv(const JobDesc* __restri
   const int j = bid / RB;
   const JobDesc jb = jobs[j];
   if (jb.env < 0) {
-    if (threadIdx.x == 0) {
-      double* o = partial + ((size_t)j * RB + rb) * 3;
-      o[0] = 0.0; o[1] = 0.0; o[2] = 0.0;
-    }
+    rowinv_zero_partial(partial, j, RB, rb);
     return;
   }
   const int y0 = rb * GPB;
@@ -1119,9 +948,8 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv(const JobDesc* __restri
   float4 pre[PER];   // this thread's share of a plane tile, one plane ahead
 #pragma unroll
   for (int i = 0; i < PER; ++i) {
-    const int c = threadIdx.x + NT * i;
-    const int line = c / (GPB / 2), r2 = (c % (GPB / 2)) * 2;
-    pre[i] = ld_stream4(jbase + LayoutB<R>::at(line, y0 + r2));
+    const TileChunk ch = tile_chunk<NT, GPB>(i);
+    pre[i] = ld_stream4(jbase + LayoutB<R>::at(ch.line, y0 + ch.r2));
   }
   float acc[R];
 #pragma unroll
@@ -1132,18 +960,16 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv(const JobDesc* __restri
     lds_barrier();  // previous plane's scratch use is over (also publishes tw)
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
-      const int c = threadIdx.x + NT * i;
-      const int line = c / (GPB / 2), r2 = (c % (GPB / 2)) * 2;
-      tile[tile_pos<R, GPB>(line, r2)] = make_float2(pre[i].x, pre[i].y);
-      tile[tile_pos<R, GPB>(line, r2 + 1)] = make_float2(pre[i].z, pre[i].w);
+      const TileChunk ch = tile_chunk<NT, GPB>(i);
+      tile[tile_pos<R, GPB>(ch.line, ch.r2)] = make_float2(pre[i].x, pre[i].y);
+      tile[tile_pos<R, GPB>(ch.line, ch.r2 + 1)] = make_float2(pre[i].z, pre[i].w);
     }
     if (p + 1 < P) {  // next plane's tile in flight under this plane's FFT
       const float2* nb = jbase + (size_t)(p + 1) * PLB;
 #pragma unroll
       for (int i = 0; i < PER; ++i) {
-        const int c = threadIdx.x + NT * i;
-        const int line = c / (GPB / 2), r2 = (c % (GPB / 2)) * 2;
-        pre[i] = ld_stream4(nb + LayoutB<R>::at(line, y0 + r2));
+        const TileChunk ch = tile_chunk<NT, GPB>(i);
+        pre[i] = ld_stream4(nb + LayoutB<R>::at(ch.line, y0 + ch.r2));
       }
     }
     lds_barrier();
@@ -1161,15 +987,7 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv(const JobDesc* __restri
     }
   }
 
-  rowinv_epilogue<R, GPB>(acc, P, G, jb, j, y, rb, grp, t, target, tmask, inten_out, inten_by_env, partial, red);
-}
-
-// an invalid job's row block in the statistics form of the complex last pass: neutral partials
-__device__ __forceinline__ void rowinv_zero_partial(double* __restrict__ partial, int j, int RB, int rb) {
-  if (threadIdx.x == 0) {
-    double* o = partial + ((size_t)j * RB + rb) * 3;
-    o[0] = 0.0; o[1] = 0.0; o[2] = 0.0;
-  }
+  rowinv_epilogue<R, R, GPB>(acc, P, G, jb, j, y, rb, grp, t, target, tmask, inten_out, inten_by_env, partial, red);
 }
 
 // ---------------------------------------------------------------------------
@@ -1220,22 +1038,7 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_d_cplx(const JobDesc* __restr
   constexpr int PLB = N * N;                 // float2 per B plane
   const __amdgpu_buffer_rsrc_t rs = plane_rsrc(ws_b + (size_t)j * P * PLB, (unsigned)((size_t)P * PLB * 8));
   const RowinvLanes<R> ln(y, t);
-  auto load_pair = [&](pk2 (&v)[R], int q) {   // v = B[2q] + i B[2q + 1]
-    const int po = 2 * q * PLB * 8;
-#pragma unroll
-    for (int jj = 0; jj < R; ++jj) v[jj] = to_pk(ln.load(rs, po, jj));
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      float2 w[R / 2];
-#pragma unroll
-      for (int jj = 0; jj < R / 2; ++jj) w[jj] = ln.load(rs, po + PLB * 8, h * (R / 2) + jj);
-#pragma unroll
-      for (int jj = 0; jj < R / 2; ++jj) {
-        v[h * (R / 2) + jj].x -= w[jj].y;
-        v[h * (R / 2) + jj].y += w[jj].x;
-      }
-    }
-  };
+  auto load_pair = [&](pk2 (&v)[R], int q) { rowinv_load_pair(v, ln, rs, q); };
   const PaddedScratch<R> sc{scratch + grp * R * (R + 1)};
   const size_t row0 = (((size_t)jb.env * G + jb.group) * Q * N + y) * N + t;   // complex plane 0, pixel x = t
   float acc[ST ? R : 1];
@@ -1282,7 +1085,7 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_d_cplx(const JobDesc* __restr
   }
   if constexpr (ST) {
     __shared__ double red[GPB][3];
-    rowinv_epilogue<R, GPB>(acc, Q, G, jb, j, y, rb, grp, t, target, tmask, inten_out, 0, partial, red);
+    rowinv_epilogue<R, R, GPB>(acc, Q, G, jb, j, y, rb, grp, t, target, tmask, inten_out, 0, partial, red);
   }
 }
 
@@ -1330,10 +1133,9 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv_cplx(const JobDesc* __r
     const float2* a = jbase + (size_t)(2 * q) * PLB;
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
-      const int c = threadIdx.x + NT * i;
-      const int line = c / (GPB / 2), r2 = (c % (GPB / 2)) * 2;
-      pa[i] = ld_stream4(a + LayoutB<R>::at(line, y0 + r2));
-      pb[i] = ld_stream4(a + PLB + LayoutB<R>::at(line, y0 + r2));
+      const TileChunk ch = tile_chunk<NT, GPB>(i);
+      pa[i] = ld_stream4(a + LayoutB<R>::at(ch.line, y0 + ch.r2));
+      pb[i] = ld_stream4(a + PLB + LayoutB<R>::at(ch.line, y0 + ch.r2));
     }
   };
   load_pair(0);
@@ -1349,10 +1151,9 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv_cplx(const JobDesc* __r
     lds_barrier();  // previous plane's scratch use is over (also publishes tw)
 #pragma unroll
     for (int i = 0; i < PER; ++i) {   // B[2q] + i B[2q + 1]
-      const int c = threadIdx.x + NT * i;
-      const int line = c / (GPB / 2), r2 = (c % (GPB / 2)) * 2;
-      tile[tile_pos<R, GPB>(line, r2)] = make_float2(pa[i].x - pb[i].y, pa[i].y + pb[i].x);
-      tile[tile_pos<R, GPB>(line, r2 + 1)] = make_float2(pa[i].z - pb[i].w, pa[i].w + pb[i].z);
+      const TileChunk ch = tile_chunk<NT, GPB>(i);
+      tile[tile_pos<R, GPB>(ch.line, ch.r2)] = make_float2(pa[i].x - pb[i].y, pa[i].y + pb[i].x);
+      tile[tile_pos<R, GPB>(ch.line, ch.r2 + 1)] = make_float2(pa[i].z - pb[i].w, pa[i].w + pb[i].z);
     }
     if (q + 1 < Q) load_pair(q + 1);   // next pair's tiles in flight under this plane's FFT
     lds_barrier();
@@ -1377,7 +1178,7 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv_cplx(const JobDesc* __r
   }
   if constexpr (ST) {
     __shared__ double red[GPB][3];
-    rowinv_epilogue<R, GPB>(acc, Q, G, jb, j, y, rb, grp, t, target, tmask, inten_out, 0, partial, red);
+    rowinv_epilogue<R, R, GPB>(acc, Q, G, jb, j, y, rb, grp, t, target, tmask, inten_out, 0, partial, red);
   }
 }
 
@@ -1529,9 +1330,7 @@ static hipError_t launch_passes(const PlanDev& pd, const PassCall& c, hipStream_
   const int CH = pd.G * pd.P;
   PassTimer* tm = pd.timer;
   const int pair = c.plane_mode == kPlanesStep ? 1 : 0;
-  // no target: the last pass reads the plan's zero row, every row offset masked to 0
-  const float* tg = c.target ? c.target : pd.zero_row;
-  const size_t tmask = c.target ? ~(size_t)0 : (size_t)0;
+  const PassTarget tg = pass_target(pd, c);
   // Small batches (greedy DBS, a few candidates per launch): the walk-per-workgroup loops
   // (rowfwd_iters row blocks, col2_iters lines) trade parallelism for store overlap, which pays
   // only when the launch fills the chip many times over.  Below kSmallBlocks workgroups the
@@ -1584,7 +1383,6 @@ static hipError_t launch_passes(const PlanDev& pd, const PassCall& c, hipStream_
   if (tm) tm->end(1, n_jobs, st);
 
   const unsigned blocks = (unsigned)n_jobs * kRowBlocks;
-  bool reduce = !c.skip_reduce;
   if (tm) tm->begin(2, st);
   if (c.complex_values) {   // recombine each plane pair; ST (hbx_evaluate_complex): intensity and partials too
     const bool stats = c.complex_stats != 0;
@@ -1592,9 +1390,8 @@ static hipError_t launch_passes(const PlanDev& pd, const PassCall& c, hipStream_
       if constexpr (kTiledB<R>) return stats ? k_rowinv_d_cplx<R, true> : k_rowinv_d_cplx<R>;
       else return stats ? k_rowinv_cplx<R, NT, true> : k_rowinv_cplx<R, NT>;
     }();
-    launch_kernel(k, blocks, NT, st, jobs, pd.ws_b, pd.tw, P, pd.G, c.complex_field, c.real_part, tg, tmask,
+    launch_kernel(k, blocks, NT, st, jobs, pd.ws_b, pd.tw, P, pd.G, c.complex_field, c.real_part, tg.rows, tg.mask,
                   pd.partial, c.inten_out);
-    reduce = stats && c.target;   // only the statistics form with a target left partials to reduce
   } else if constexpr (kTiledB<R>) {
     // WALK (r05): a plane-cache walk batch, the last workgroup decides.  LEAN (r06): the plain
     // FFT-mode launch (the headline), its own instantiation without the plane cache / field /
@@ -1605,15 +1402,15 @@ static hipError_t launch_passes(const PlanDev& pd, const PassCall& c, hipStream_
     // the timings on record were taken with this layout -- tools/isa_cmp.py reports a reordering)
     auto k = k_rowinv_d<R, true>;
     if (!c.walk_planes) k = lean ? k_rowinv_d<R, false, true> : k_rowinv_d<R>;
-    launch_kernel(k, blocks, 256, st, jobs, pd.ws_b, tg, pd.tw, P, pd.G, pd.partial, c.inten_out, c.field_out, tmask,
-                  c.inten_by_env, c.plane_mode, c.plane_pool, c.plane_slot, c.plane_spares, c.spare_base,
+    launch_kernel(k, blocks, 256, st, jobs, pd.ws_b, tg.rows, pd.tw, P, pd.G, pd.partial, c.inten_out, c.field_out,
+                  tg.mask, c.inten_by_env, c.plane_mode, c.plane_pool, c.plane_slot, c.plane_spares, c.spare_base,
                   c.rc_pending, c.rc_cache, c.walk_planes ? *c.walk_planes : WalkPlanesArgs{});
   } else {
-    launch_kernel(k_rowinv<R, NT>, blocks, NT, st, jobs, pd.ws_b, tg, pd.tw, P, pd.G, pd.partial, c.inten_out,
-                  c.field_out, tmask, c.inten_by_env);
+    launch_kernel(k_rowinv<R, NT>, blocks, NT, st, jobs, pd.ws_b, tg.rows, pd.tw, P, pd.G, pd.partial, c.inten_out,
+                  c.field_out, tg.mask, c.inten_by_env);
   }
   if (tm) tm->end(2, n_jobs, st);
-  if (reduce)
+  if (pass_reduces(c))
     hipLaunchKernelGGL(k_reduce_partials, dim3(n_jobs), dim3(64), 0, st, pd.partial, n_jobs, kRowBlocks, pd.job_stats);
   return hipGetLastError();
 }

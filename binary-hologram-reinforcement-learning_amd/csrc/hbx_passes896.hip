@@ -30,6 +30,7 @@
 #include "hbx_fft.hpp"
 #include "hbx_internal.hpp"
 #include "hbx_rowcol.hpp"
+#include "hbx_rowinv.hpp"
 
 namespace hbx {
 
@@ -434,6 +435,8 @@ constexpr bool kInvScalar = false;   // packed DFTs (one line live)
 // the lane's slot-layout register k2 of the plane at byte offset po (wave-uniform)
 struct Rowinv896Lanes {
   static constexpr int TL = 8;                    // slots per tile (1-KB tiles, as N = 1024)
+  static constexpr int kRegs = 32;                // FFT inputs per lane (slot layout)
+  static constexpr int kPlaneBytes = (int)(kPlaneB * 8);   // B plane stride
   static constexpr int MS = 7 * 16 * TL * 8;      // bytes per m: 7 tiles
   int lo0, lo1, hi0, hi1, mid;
   __device__ __forceinline__ Rowinv896Lanes(int y, int t) {
@@ -451,47 +454,6 @@ struct Rowinv896Lanes {
     return buf_ld2s(rs, (q & 1) ? hi1 : hi0, po + (q >> 1) * MS);
   }
 };
-
-// the last pass's tail (hbx_passes.hip rowinv_epilogue at 28 values per lane): plane mean, f64
-// partials of (I*T, I^2, T^2) against the target row (tmask = 0: the plan's zero row), fixed-order
-// reduction over the group's lanes and the block's rows
-__device__ __forceinline__ void rowinv896_epilogue(float (&acc)[kL], int P, int G, const JobDesc& jb, int j, int y,
-                                                   int rb, int grp, int t, const float* __restrict__ target,
-                                                   size_t tmask, float* __restrict__ inten_out, int inten_by_env,
-                                                   double* __restrict__ partial, double (&red)[kGPB][3]) {
-  const float invp = 1.0f / (float)P;
-  const float* trow = target + ((((size_t)jb.env * G + jb.group) * kN + y) * kN & tmask);
-  double sxy = 0.0, sxx = 0.0, syy = 0.0;
-#pragma unroll
-  for (int k = 0; k < kL; ++k) {
-    const float I = acc[k] * invp;
-    const float T = trow[t + kR * k];
-    sxy = fma((double)I, (double)T, sxy);
-    sxx = fma((double)I, (double)I, sxx);
-    syy = fma((double)T, (double)T, syy);
-    acc[k] = I;
-  }
-  if (inten_out) {
-    const size_t slot = inten_by_env ? (size_t)jb.env * G + jb.group : (size_t)j;
-    float* orow = inten_out + (slot * kN + y) * kN;
-#pragma unroll
-    for (int k = 0; k < kL; ++k) orow[t + kR * k] = acc[k];
-  }
-#pragma unroll
-  for (int off = kR / 2; off >= 1; off >>= 1) {
-    sxy += __shfl_xor(sxy, off, 64);
-    sxx += __shfl_xor(sxx, off, 64);
-    syy += __shfl_xor(syy, off, 64);
-  }
-  if (t == 0) { red[grp][0] = sxy; red[grp][1] = sxx; red[grp][2] = syy; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double a = 0.0, b = 0.0, cc = 0.0;
-    for (int g = 0; g < kGPB; ++g) { a += red[g][0]; b += red[g][1]; cc += red[g][2]; }
-    double* o = partial + ((size_t)j * kRB + rb) * 3;
-    o[0] = a; o[1] = b; o[2] = cc;
-  }
-}
 
 template <bool LEAN>
 __global__ __launch_bounds__(256, 2) void k_rowinv896(const JobDesc* __restrict__ jobs,
@@ -521,71 +483,25 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896(const JobDesc* __restrict_
   const int j = bid / kRB;
   const JobDesc jb = jobs[j];
   if (jb.env < 0) {
-    if (threadIdx.x == 0) {
-      double* o = partial + ((size_t)j * kRB + rb) * 3;
-      o[0] = 0.0; o[1] = 0.0; o[2] = 0.0;
-    }
+    rowinv_zero_partial(partial, j, kRB, rb);
     return;
   }
   const int y = rb * kGPB + grp;
   const __amdgpu_buffer_rsrc_t rs = plane_rsrc(ws_b + (size_t)j * P * kPlaneB, (unsigned)((size_t)P * kPlaneB * 8));
   const Rowinv896Lanes ln(y, t);
-  auto load_plane = [&](float2 (&v)[32], int p) {
-    const int po = p * (int)(kPlaneB * 8);
-#pragma unroll
-    for (int k2 = 0; k2 < 32; ++k2) v[k2] = ln.load(rs, po, k2);
-  };
+  auto load_plane = [&](float2 (&v)[32], int p) { rowinv_load_plane(v, ln, rs, p); };
   float acc[kL];
 #pragma unroll
   for (int k = 0; k < kL; ++k) acc[k] = 0.0f;
   const PaddedScratch<kR> sc{scratch + grp * kR * (kR + 1)};
-  // (r06) plane cache, as k_rowinv_d (hbx_passes.hip): slots of this env's planes, pool rows of this
-  // lane group's row y; every plane's |U_p|^2 goes to its slot on a fill, the flipped pair's two to
-  // the job's spare pair on a step, and a step adds the cached planes in the FFT mode's plane order
-  const int CH = G * P;
-  const int CHS = CH + 2 * (plane_spares > 1 ? plane_spares : 1);
-  const int spare = CH + 2 * (plane_spares > 1 ? spare_base + j : 0);
-  const int32_t* slots = plane_slot ? plane_slot + (size_t)jb.env * CHS : nullptr;
-  auto pool_row = [&](int slot) { return plane_pool + (((size_t)jb.env * CHS + slot) * kN + y) * kN; };
+  const PlaneCache<kR, kL> pc(jb, j, y, G, P, plane_spares, spare_base, plane_pool, plane_slot);   // (r06)
   auto finish_plane = [&](float2 (&v)[32], int p) {
     fft896_sn<true, kInvScalar>(v, t, sc, tw);      // slot layout in, natural out: x = t + 32 j
-    float f[kL];
-#pragma unroll
-    for (int k = 0; k < kL; ++k) {
-      f[k] = fmaf(v[k].x, v[k].x, v[k].y * v[k].y);
-      acc[k] += f[k];
-    }
-    if (field_out) {  // exact field of this plane (incremental mode init / refresh)
-      float2* frow = field_out + (((size_t)jb.env * G * P + jb.group * P + p) * kN + y) * kN;
-#pragma unroll
-      for (int k = 0; k < kL; ++k) frow[t + kR * k] = v[k];
-    }
-    if (plane_mode != kPlanesOff) {
-      float* orow = pool_row(slots[plane_mode == kPlanesFill ? jb.group * P + p : spare + (p & 1)]);
-#pragma unroll
-      for (int k = 0; k < kL; ++k) __builtin_nontemporal_store(f[k], orow + t + kR * k);
-    }
-  };
-  auto add_cached = [&](int q) {
-    const float* crow = pool_row(slots[jb.group * P + q]);
-    float c[kL];
-#pragma unroll
-    for (int k = 0; k < kL; ++k) c[k] = __builtin_nontemporal_load(crow + t + kR * k);
-#pragma unroll
-    for (int k = 0; k < kL; ++k) acc[k] += c[k];
+    plane_out<kR, kL>(v, acc, pc, jb, G, P, p, t, field_out, plane_mode);
   };
   float2 v[32];
   if (plane_mode == kPlanesStep) {   // only the flipped plane's pair is in B
-    const int pa = jb.flip_plane & ~1;
-    load_plane(v, pa);
-    __syncthreads();  // tw visible
-#pragma unroll 1
-    for (int q = 0; q < pa; ++q) add_cached(q);
-    finish_plane(v, pa);
-    load_plane(v, pa + 1);
-    finish_plane(v, pa + 1);
-#pragma unroll 1
-    for (int q = pa + 2; q < P; ++q) add_cached(q);
+    rowinv_planes_step(v, acc, pc, jb, P, t, load_plane, finish_plane);
   } else {
     load_plane(v, 0);
     __syncthreads();  // tw visible
@@ -595,8 +511,10 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896(const JobDesc* __restrict_
       load_plane(v, p + 1 < P ? p + 1 : p);   // unconditional: the last round re-reads plane P - 1
     }
   }
-
-  rowinv896_epilogue(acc, P, G, jb, j, y, rb, grp, t, target, tmask, inten_out, inten_by_env, partial, red);
+  // the tail without the SC1, target-ahead and non-temporal forms (there is no walk batch, peeled last
+  // plane or fused reconcile at 896; the env-major intensity keeps the plain store it has had)
+  rowinv_epilogue<kR, kL, kGPB, false, false, false>(acc, P, G, jb, j, y, rb, grp, t, target, tmask, inten_out,
+                                                     inten_by_env, partial, red);
 }
 
 // Pass 3 on complex fields (hbx_simulate_complex): B planes 2q and 2q + 1 hold the column-pass
@@ -628,34 +546,14 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896_cplx(const JobDesc* __rest
   const int j = bid / kRB;
   const JobDesc jb = jobs[j];
   if (jb.env < 0) {  // uniform per block
-    if constexpr (ST) {
-      if (threadIdx.x == 0) {
-        double* o = partial + ((size_t)j * kRB + rb) * 3;
-        o[0] = 0.0; o[1] = 0.0; o[2] = 0.0;
-      }
-    }
+    if constexpr (ST) rowinv_zero_partial(partial, j, kRB, rb);
     return;
   }
   const int y = rb * kGPB + grp;
   const int Q = P / 2;                            // complex planes per group
   const __amdgpu_buffer_rsrc_t rs = plane_rsrc(ws_b + (size_t)j * P * kPlaneB, (unsigned)((size_t)P * kPlaneB * 8));
   const Rowinv896Lanes ln(y, t);
-  auto load_pair = [&](float2 (&v)[32], int q) {   // v = B[2q] + i B[2q + 1]
-    const int po = 2 * q * (int)(kPlaneB * 8);
-#pragma unroll
-    for (int k2 = 0; k2 < 32; ++k2) v[k2] = ln.load(rs, po, k2);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      float2 w[16];
-#pragma unroll
-      for (int k2 = 0; k2 < 16; ++k2) w[k2] = ln.load(rs, po + (int)(kPlaneB * 8), 16 * h + k2);
-#pragma unroll
-      for (int k2 = 0; k2 < 16; ++k2) {
-        v[16 * h + k2].x -= w[k2].y;
-        v[16 * h + k2].y += w[k2].x;
-      }
-    }
-  };
+  auto load_pair = [&](float2 (&v)[32], int q) { rowinv_load_pair(v, ln, rs, q); };
   const PaddedScratch<kR> sc{scratch + grp * kR * (kR + 1)};
   const size_t row0 = (((size_t)jb.env * G + jb.group) * Q * kN + y) * kN + t;   // complex plane 0, pixel x = t
   float acc[ST ? kL : 1];
@@ -686,7 +584,8 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896_cplx(const JobDesc* __rest
   }
   if constexpr (ST) {
     __shared__ double red[kGPB][3];
-    rowinv896_epilogue(acc, Q, G, jb, j, y, rb, grp, t, target, tmask, inten_out, 0, partial, red);
+    rowinv_epilogue<kR, kL, kGPB, false, false, false>(acc, Q, G, jb, j, y, rb, grp, t, target, tmask, inten_out, 0,
+                                                       partial, red);
   }
 }
 
@@ -702,9 +601,7 @@ hipError_t run_jobs_896(const PlanDev& pd, const PassCall& c, hipStream_t st) {
   // (r06) plane-cached mode at 896: a fill writes every plane's |U|^2, a step propagates the
   // flipped plane's pair only (the walk's decision runs in a launch of its own at 896)
   const int pair = c.plane_mode == kPlanesStep ? 1 : 0;
-  // no target: the last pass reads the plan's zero row, every row offset masked to 0
-  const float* tg = c.target ? c.target : pd.zero_row;
-  const size_t tmask = c.target ? ~(size_t)0 : (size_t)0;
+  const PassTarget tg = pass_target(pd, c);
   const unsigned blocks = (unsigned)n_jobs * kRB;   // one workgroup per row block of a job
 
   if (tm) tm->begin(0, st);
@@ -723,21 +620,19 @@ hipError_t run_jobs_896(const PlanDev& pd, const PassCall& c, hipStream_t st) {
                 pd.tw, P, pair);
   if (tm) tm->end(1, n_jobs, st);
 
-  bool reduce = true;
   if (tm) tm->begin(2, st);
   if (c.complex_values) {   // recombine each plane pair; ST (hbx_evaluate_complex): intensity and partials too
     launch_kernel(c.complex_stats ? k_rowinv896_cplx<true> : k_rowinv896_cplx<false>, blocks, 256, st, jobs, pd.ws_b,
-                  pd.tw, P, pd.G, c.complex_field, c.real_part, tg, tmask, pd.partial, c.inten_out);
-    reduce = c.complex_stats && c.target;   // only the statistics form with a target left partials to reduce
+                  pd.tw, P, pd.G, c.complex_field, c.real_part, tg.rows, tg.mask, pd.partial, c.inten_out);
   } else {
     // (r06) the plain FFT-mode launch gets the lean instantiation (profiles/r06/rowinv896_lean_ab_r06i.txt)
     const bool lean = c.plane_mode == kPlanesOff && !c.field_out;
-    launch_kernel(lean ? k_rowinv896<true> : k_rowinv896<false>, blocks, 256, st, jobs, pd.ws_b, tg, pd.tw, P, pd.G,
-                  pd.partial, c.inten_out, c.field_out, tmask, c.inten_by_env, c.plane_mode, c.plane_pool,
+    launch_kernel(lean ? k_rowinv896<true> : k_rowinv896<false>, blocks, 256, st, jobs, pd.ws_b, tg.rows, pd.tw, P,
+                  pd.G, pd.partial, c.inten_out, c.field_out, tg.mask, c.inten_by_env, c.plane_mode, c.plane_pool,
                   c.plane_slot, c.plane_spares, c.spare_base);
   }
   if (tm) tm->end(2, n_jobs, st);
-  if (reduce)
+  if (pass_reduces(c))   // (skip_reduce is refused at 896: check_pass_call)
     hipLaunchKernelGGL(k_reduce_partials, dim3(n_jobs), dim3(64), 0, st, pd.partial, n_jobs, kRB, pd.job_stats);
   return hipGetLastError();
 }

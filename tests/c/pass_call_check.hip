@@ -1,5 +1,6 @@
 // Host-side check of hbx::check_pass_call (csrc/hbx_internal.hpp): which PassCalls run_jobs takes.
-// One accepted call per shape the C-ABI layer (csrc/hbx_api.hip) builds, one rejected call per rule.
+// One accepted call per shape the C-ABI layer (csrc/hbx_api.hip) builds, one rejected call per rule; for some
+// of the accepted shapes also hbx::pass_reduces, the rule for when k_reduce_partials runs behind the last pass.
 // Built by tests/test_abi.py::test_pass_call_rules_under_asan with the host code under ASan + UBSan;
 // needs no GPU and no library: the validator only compares fields, no pointer is dereferenced.
 #include <stdio.h>
@@ -18,6 +19,15 @@ static void expect(bool accepted, const PlanDev& pd, const PassCall& c, int line
 }
 #define ACCEPT(pd, c) expect(true, pd, c, __LINE__)
 #define REJECT(pd, c) expect(false, pd, c, __LINE__)
+// pass_reduces: whether k_reduce_partials runs behind the last pass of this call
+static void expect_reduce(bool want, const PassCall& c, int line) {
+  if (pass_reduces(c) != want) {
+    printf("FAIL line %d: pass_reduces is %d, expected %d\n", line, !want, want);
+    fails++;
+  }
+}
+#define REDUCES(c) expect_reduce(true, c, __LINE__)
+#define NO_REDUCE(c) expect_reduce(false, c, __LINE__)
 
 static PlanDev plan(int R, int store_kind = HBX_PRECISION_F32) {
   PlanDev pd = {};
@@ -77,17 +87,21 @@ int main() {
   for (const PlanDev* pd : every) {
     PassCall c = bits();   // hbx_step, hbx_eval_flips
     ACCEPT(*pd, c);
+    REDUCES(c);
     c.field_out = buf<float2>(4);   // ensure_hpsf, hbx_simulate, hbx_field_refresh
     c.inten_out = buf<float>(3);
     ACCEPT(*pd, c);
     c = real();   // hbx_propagate_real, hbx_intensity_real, hbx_evaluate_real / hbx_simulate_real
     ACCEPT(*pd, c);
+    REDUCES(c);
     c.target = nullptr;
     ACCEPT(*pd, c);
+    REDUCES(c);   // (the zero row's partials: reduced all the same, as before)
     c.field_out = buf<float2>(4);
     ACCEPT(*pd, c);
     c = cplx();   // hbx_simulate_complex: the field, the real part, both
     ACCEPT(*pd, c);
+    NO_REDUCE(c);   // no statistics form: no partials
     c.real_part = buf<float>(7);
     ACCEPT(*pd, c);
     c.complex_field = nullptr;
@@ -100,9 +114,11 @@ int main() {
     c.target = buf<float>(2);
     c.inten_out = buf<float>(3);
     ACCEPT(*pd, c);
+    REDUCES(c);
     c.complex_field = nullptr;
     c.target = nullptr;
     ACCEPT(*pd, c);
+    NO_REDUCE(c);   // statistics without a target: the intensity alone
     c = bits();   // hbx_env_step into the recon buffer, jobs from k_jobs_from_actions
     c.inten_by_env = 1;
     c.inten_out = buf<float>(3);
@@ -131,6 +147,7 @@ int main() {
     c.rc_pending = buf<int32_t>(11);
     c.rc_cache = buf<float>(12);
     ACCEPT(*pd, c);
+    NO_REDUCE(c);   // skip_reduce: the finalize reads the partials
     c.plane_mode = kPlanesOff;   // ... without the plane cache
     c.plane_pool = nullptr;
     c.plane_slot = nullptr;

@@ -5,7 +5,7 @@ by HBX_LIB at import, so each build runs in its own process):
   python tools/lib_bitcmp.py cmp a.npz b.npz
 dump: seeded 1024x1024x24 RGB (4 envs), 256x256x8 mono (8 envs), 896 RGB, binary-phase fields and the
 bf16 / fp16 intermediate-storage study -> group intensities, per-channel statistics and PSNR of
-hbx_propagate."""
+hbx_propagate; then every form of the last pass at small shapes (third_pass: N = 64, 256, 896, 1024)."""
 import os
 import sys
 
@@ -39,17 +39,88 @@ def dump(path):
         out[name + "_stats"] = st.cpu().numpy()
         out[name + "_psnr"] = ps.cpu().numpy()
         plan.close()
+    third_pass(out)
     np.savez(path, **out)
     print("dumped", path, {k: v.shape for k, v in out.items()})
+
+
+def third_pass(out):
+    """Every instantiation of the last pass (k_rowinv, k_rowinv_d, k_rowinv896 and their _cplx forms) at
+    least once, through the entry points the tests of those paths use: bits with and without field_out,
+    candidate batches with an invalid flip (the neutral-partial exit; full re-propagation and plane-cached),
+    plane-cache fill and step, complex simulate / evaluate (statistics with and without a target), env steps
+    with the recon observation (the fused reconcile at 256, the env-major intensity at 896) and a device-decided
+    plane-cache walk at 256, 896 and 1024 that runs past the end of its order (invalid jobs in the walk batch).
+    The complex entry points build their jobs themselves and cannot carry an invalid one."""
+    import torch
+    from hbx import dbs, pack_bits
+    from hbx.env import OBS_KEYS, HologramVecEnv
+    from hbx.plan import Plan, mono_config, rgb_config
+
+    def put(name, *ts):
+        for i, t in enumerate(ts):
+            if t is not None:
+                out[f"{name}_{i}"] = (torch.view_as_real(t) if t.is_complex() else t).cpu().numpy()
+
+    def f64(*shape):
+        return torch.zeros(shape, dtype=torch.float64, device="cuda")
+
+    for name, cfg, B in (("tp64", mono_config(64), 3), ("tp256", mono_config(256), 2), ("tp896", rgb_config(896), 1),
+                         ("tp1024", rgb_config(1024), 1)):
+        n, ch, G = cfg.height, cfg.channels, cfg.groups
+        g = torch.Generator(device="cuda").manual_seed(23)
+        pre = torch.rand((B, ch, n, n), generator=g, device="cuda")
+        tgt = torch.rand((B, G, n, n), generator=g, device="cuda")
+        mask = pack_bits(pre >= 0.5)
+        plan = Plan(cfg, max_jobs=max(B * G, 8))
+        inten, st, ps = plan.propagate(mask, tgt)
+        put(name + "_prop", inten, st, ps)
+        put(name + "_sim", *plan.simulate(mask, want_intensity=True))
+        flips = torch.tensor([5, -1, ch * n * n - 7, n * n + 3], dtype=torch.int64, device="cuda")
+        fp, fs = f64(4), f64(4, 3)
+        plan.eval_flips(mask[0], tgt[0], st[0], flips, fp, fs)
+        put(name + "_flips", fp, fs)
+        if n != 64:
+            pool, slot = plan.plane_pool(4)
+            pool.zero_()    # the spare pairs no candidate writes stay comparable
+            put(name + "_fill", *plan.planes_fill(mask[0], tgt[0], pool, slot))
+            fp, fs = f64(4), f64(4, 3)
+            plan.eval_flips_planes(mask[0], tgt[0], st[0], pool, slot, flips, fp, fs)
+            put(name + "_step", fp, fs, pool, slot)
+        vals = torch.view_as_complex(torch.randn((B, ch // 2, n, n, 2), generator=g, device="cuda"))
+        put(name + "_csim", *plan.simulate_complex(vals, want_field=True, want_real=True))
+        put(name + "_cstat", *plan.evaluate_complex(vals, tgt))
+        put(name + "_cinten", *plan.evaluate_complex(vals, None, want_field=False))
+        if n != 64:   # the device-decided walk (N = 1024 / 256: in the batch's last pass; 896: a launch of its own)
+            order = np.random.default_rng(3).permutation(ch * n * n)[:300 if n == 256 else 60]
+            m = mask[0].clone()
+            res = dbs.greedy(plan, m, tgt[0], order=order, mode="fft", planes=True)
+            out[name + "_walk_pos"] = np.asarray(res.accepted_positions, np.int64)
+            out[name + "_walk_psnr"] = np.asarray(res.accepted_psnr + [res.final_psnr], np.float64)
+            put(name + "_walk_mask", m)
+        plan.close()
+        for mode in (("planes", "fft") if n == 256 else ("planes",) if n == 896 else ()):
+            env = HologramVecEnv(cfg, 2, lambda i: tgt[i % B], mode=mode, pre_model_source=lambda i: pre[i % B],
+                                 auto_reset=True, max_steps=10000, obs_keys=OBS_KEYS)
+            obs = env.reset()
+            put(f"{name}_env_{mode}_reset", obs["recon_image"], env.state.chan_stats)
+            acts = torch.randint(0, ch * n * n, (6, 2), generator=g, device="cuda")
+            for k in range(6):
+                obs = env.step(acts[k])[0]
+                out[f"{name}_env_{mode}_psnr{k}"] = np.asarray(env.last_step()["psnr"])
+                put(f"{name}_env_{mode}_step{k}", obs["recon_image"], env.state.chan_stats)
+            env.close()
+        torch.cuda.synchronize()
 
 
 def cmp(a, b):
     A, B = np.load(a), np.load(b)
     ok = True
     for k in A.files:
-        same = A[k].tobytes() == B[k].tobytes()
+        same = A[k].shape == B[k].shape and A[k].tobytes() == B[k].tobytes()
         ok &= same
-        print(f"{k:16s} bitwise {'EQUAL' if same else 'DIFFERENT'}  max|d| {np.abs(A[k] - B[k]).max():.3e}")
+        d = np.abs(A[k].astype(np.float64) - B[k]).max() if A[k].shape == B[k].shape and A[k].size else float("nan")
+        print(f"{k:28s} bitwise {'EQUAL' if same else 'DIFFERENT'}  max|d| {d:.3e}")
     sys.exit(0 if ok else 1)
 
 
