@@ -459,6 +459,7 @@ struct FullRequest {
   const float2* complex_values = nullptr;
   const float* weight = nullptr;
   float scale = 1.0f;
+  const float* phase_values = nullptr; // phase samples [n][G*P/2][N][N] f32, u = exp(i pi x): complex input from here on
   const float* target = nullptr;       // [n][G][N][N]; null: no statistics
   const int32_t* env_ids = nullptr;    // absolute env ids into every buffer (mask input only); null: 0 .. n - 1
   int n = 0;
@@ -471,6 +472,9 @@ struct FullRequest {
   float2* complex_field = nullptr;     // [n][G*P/2][N][N] complex64 (complex input)
   float* real_part = nullptr;          // [n][G*P/2][N][N] f32 (complex input)
   bool complex_stats = false;          // complex input: the last pass's intensity / statistics form
+  // complex input (hbx_phase_backward): the last pass's phase-gradient form, both or neither
+  const float* grad_samples = nullptr; // [n][G*P/2][N][N] f32 phase samples x of the leaf
+  float* grad_phase = nullptr;         // [n][G*P/2][N][N] f32 dL/dx
   // plane cache (ABI v9): identity slots, then every plane's |U|^2 into its slot
   float* plane_pool = nullptr;
   int32_t* plane_slot = nullptr;
@@ -483,7 +487,7 @@ int propagate_full(hbx_plan_t p, const FullRequest& r, void* stream) {
   const int G = pd.G, CH = pd.G * pd.P;
   const int CHs = CH + 2 * r.spares;   // plane-cache slots per env
   const int chunk = p->max_jobs / G;
-  const bool cplx = r.complex_values != nullptr;
+  const bool cplx = r.complex_values || r.phase_values;
   HBX_HIP(hipSetDevice(p->device));
   if (r.plane_pool) {
     if (pd.R != 32 && pd.R != 16 && pd.R != 0)
@@ -502,7 +506,7 @@ int propagate_full(hbx_plan_t p, const FullRequest& r, void* stream) {
   const size_t hw = (size_t)pd.N * pd.N;
   const size_t s_mask = (size_t)CH * pd.N * (pd.N / 64);   // mask words
   const size_t s_real = (size_t)CH * hw;                   // real samples, field planes
-  const size_t s_cplx = (size_t)(CH / 2) * hw;             // complex planes
+  const size_t s_cplx = (size_t)(CH / 2) * hw;             // complex planes (float2), phase planes (float)
   const size_t s_img = (size_t)G * hw;                     // images: target, intensity, weight
   const size_t s_stat = (size_t)G * 3;                     // statistics
   const size_t s_pool = (size_t)CHs * hw, s_slot = (size_t)CHs;
@@ -522,12 +526,15 @@ int propagate_full(hbx_plan_t p, const FullRequest& r, void* stream) {
     c.complex_values = at(r.complex_values, s_cplx);
     c.complex_weight = at(r.weight, s_img);
     c.complex_scale = r.scale;
+    c.phase_values = at(r.phase_values, s_cplx);
     c.target = at(r.target, s_img);
     c.inten_out = cplx ? at(r.intensity, s_img) : (r.intensity ? p->job_inten : nullptr);
     c.field_out = at(r.field, s_real);
     c.complex_field = at(r.complex_field, s_cplx);
     c.real_part = at(r.real_part, s_cplx);
     c.complex_stats = r.complex_stats;
+    c.grad_samples = at(r.grad_samples, s_cplx);
+    c.grad_phase = at(r.grad_phase, s_cplx);
     if (r.plane_pool) {
       c.plane_mode = hbx::kPlanesFill;
       c.plane_spares = r.spares;
@@ -647,6 +654,48 @@ int hbx_evaluate_complex(hbx_plan_t p, const float* values, const float* target,
   r.complex_values = reinterpret_cast<const float2*>(values); r.target = target; r.n = n_env;
   r.complex_field = reinterpret_cast<float2*>(field); r.complex_stats = true;
   r.intensity = intensity; r.chan_stats = chan_stats; r.psnr = psnr;
+  return propagate_full(p, r, stream);
+}
+
+// hbx_simulate_complex with exp(i pi phase) formed by the first pass
+int hbx_simulate_phase(hbx_plan_t p, const float* phase, int32_t n_env, float* field, float* real_part,
+                       void* stream) {
+  HBX_ENTER(p, n_env, "n_env");
+  if (!phase || (!field && !real_part)) return fail(HBX_ERR_INVALID, "null buffer");
+  if (int rc = check_real_plan(p, true)) return rc;
+  FullRequest r;
+  r.phase_values = phase; r.n = n_env;
+  r.complex_field = reinterpret_cast<float2*>(field); r.real_part = real_part;
+  return propagate_full(p, r, stream);
+}
+
+// hbx_evaluate_complex with exp(i pi phase) formed by the first pass
+int hbx_evaluate_phase(hbx_plan_t p, const float* phase, const float* target, int32_t n_env, float* field,
+                       float* intensity, double* chan_stats, double* psnr, void* stream) {
+  HBX_ENTER(p, n_env, "n_env");
+  if (!phase) return fail(HBX_ERR_INVALID, "null buffer");
+  if ((target == nullptr) != (chan_stats == nullptr))
+    return fail(HBX_ERR_INVALID, "target and chan_stats are given together or not at all");
+  if (!target && (!intensity || psnr))
+    return fail(HBX_ERR_INVALID, "without a target: intensity is the output, and there is no psnr");
+  if (int rc = check_real_plan(p, true)) return rc;
+  FullRequest r;
+  r.phase_values = phase; r.target = target; r.n = n_env;
+  r.complex_field = reinterpret_cast<float2*>(field); r.complex_stats = true;
+  r.intensity = intensity; r.chan_stats = chan_stats; r.psnr = psnr;
+  return propagate_full(p, r, stream);
+}
+
+// hbx_simulate_complex(_weighted)'s first pass, the phase-gradient last pass
+int hbx_phase_backward(hbx_plan_t p, const float* values, const float* weight, float scale, const float* phase,
+                       int32_t n_env, float* grad_phase, void* stream) {
+  HBX_ENTER(p, n_env, "n_env");
+  if (!values || !phase || !grad_phase) return fail(HBX_ERR_INVALID, "null buffer");
+  if (int rc = check_real_plan(p, true)) return rc;
+  FullRequest r;
+  r.complex_values = reinterpret_cast<const float2*>(values); r.weight = weight; r.n = n_env;
+  if (weight) r.scale = scale;
+  r.grad_samples = phase; r.grad_phase = grad_phase;
   return propagate_full(p, r, stream);
 }
 

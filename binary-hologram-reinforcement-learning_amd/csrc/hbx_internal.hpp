@@ -195,7 +195,7 @@ constexpr int kPlanesOff = 0, kPlanesFill = 1, kPlanesStep = 2;
 struct PassCall {
   const JobDesc* jobs = nullptr;
   int n_jobs = 0;
-  // the input, exactly one of three: the packed mask bits (u = va + vb * bit) ...
+  // the input, exactly one of four: the packed mask bits (u = va + vb * bit) ...
   const uint64_t* mask = nullptr;
   // ... (ABI v15) a real-valued field: [env][G*P][N][N] f32 samples the first pass reads instead of
   // the mask bits (u = value; va / vb are not applied).  f32 intermediates, no plane cache, no
@@ -211,6 +211,10 @@ struct PassCall {
   // complex_values; the first pass propagates (complex_scale * complex_weight[env][group]) * values
   const float* complex_weight = nullptr;
   float complex_scale = 1.0f;
+  // ... or (ABI v15, additive) a phase hologram (hbx_simulate_phase): [env][G*P/2][N][N] f32 samples x,
+  // u = exp(i pi x) formed by the first pass as it loads them, phase plane q into plane-pair slot q.
+  // Everything behind the load is complex_values' path: the same outputs and the same rules
+  const float* phase_values = nullptr;
   // env step at N = 1024 / 256: the first pass decodes the actions itself (no
   // k_jobs_from_actions launch) and one of its workgroups per job writes the JobDesc the later
   // passes read
@@ -229,6 +233,12 @@ struct PassCall {
   // intensity to inten_out [job][N][N] (job-major; nullable) and the partials against target (null:
   // the zero row, nothing reduced).  complex_field and real_part may then both be null
   int complex_stats = 0;
+  // (ABI v15, additive) hbx_phase_backward: with complex or phase input, both or neither.  The last
+  // pass takes each recombined plane as the gradient g with respect to u = exp(i pi x), x =
+  // grad_samples [env][G*P/2][N][N] f32, and writes grad_phase (same shape) = pi (Im g cos pi x -
+  // Re g sin pi x) and nothing else: no complex_field, real_part or complex_stats
+  const float* grad_samples = nullptr;
+  float* grad_phase = nullptr;
   // the plane cache (kPlanes* above)
   int plane_mode = kPlanesOff;
   float* plane_pool = nullptr;          // [env][CH + 2S][N][N] f32 per-plane |U|^2 (env ids as the jobs carry them)
@@ -247,6 +257,9 @@ struct PassCall {
                                                 // workgroup decides (hbx_walk_planes.hpp)
 };
 
+// The complex path: complex or phase samples in, the pair-recombining last pass out
+inline bool pass_complex(const PassCall& c) { return c.complex_values || c.phase_values; }
+
 // Which PassCalls the pass kernels of this plan can run: every field a selected kernel would not
 // read is refused, not ignored.  run_jobs calls it before a timer slot opens or a kernel is enqueued.
 inline hipError_t check_pass_call(const PlanDev& pd, const PassCall& c) {
@@ -255,17 +268,24 @@ inline hipError_t check_pass_call(const PlanDev& pd, const PassCall& c) {
   const bool planes = c.plane_mode != kPlanesOff;
   const bool walk = c.walk_phase || c.walk_planes;
   const bool complex_out = c.complex_field || c.real_part || c.complex_stats;
-  bool ok = (c.mask != nullptr) + (c.real_values != nullptr) + (c.complex_values != nullptr) == 1;
+  const bool grad_out = c.grad_samples || c.grad_phase;
+  bool ok = (c.mask != nullptr) + (c.real_values != nullptr) + (c.complex_values != nullptr) +
+            (c.phase_values != nullptr) == 1;
   ok = ok && (!planes || (c.plane_pool && c.plane_slot && (tiled || pd.R == 0)));
   ok = ok && (!c.walk_planes || (c.plane_mode == kPlanesStep && tiled));
   ok = ok && (!c.rc_pending == !c.rc_cache) && (!c.rc_pending || tiled);
   ok = ok && (c.actions || !c.act_err);
   if (pd.R == 0) ok = ok && !c.walk_phase && !c.actions && !c.skip_reduce;
-  // real and complex samples: the f32 product path alone
+  // real, complex and phase samples: the f32 product path alone
   if (!c.mask) ok = ok && f32 && !planes && !c.actions && !walk;
-  // complex in, complex out: the pair-recombining last pass writes these and nothing else
-  ok = ok && (c.complex_values ? complex_out && !c.field_out && !c.inten_by_env && !c.rc_pending && !c.skip_reduce
-                               : !complex_out && !c.complex_weight);
+  // complex or phase in, complex out: the pair-recombining last pass writes these and nothing else ...
+  ok = ok && (pass_complex(c) ? (complex_out || grad_out) && !c.field_out && !c.inten_by_env && !c.rc_pending &&
+                                    !c.skip_reduce
+                              : !complex_out && !grad_out);
+  // ... or the phase gradient alone, from its samples
+  ok = ok && (!grad_out || (c.grad_samples && c.grad_phase && !complex_out && !c.target && !c.inten_out));
+  // the weight rides on the complex load
+  ok = ok && (c.complex_values || !c.complex_weight);
   return ok ? hipSuccess : hipErrorInvalidValue;
 }
 // The target rows the last pass reads.  No target: the plan's zero row, every row offset masked to 0
@@ -276,10 +296,10 @@ struct PassTarget {
 inline PassTarget pass_target(const PlanDev& pd, const PassCall& c) {
   return c.target ? PassTarget{c.target, ~(size_t)0} : PassTarget{pd.zero_row, (size_t)0};
 }
-// Whether k_reduce_partials runs behind the last pass.  Complex samples: only the statistics form with
-// a target left partials to reduce; otherwise unless the caller reduces them itself
+// Whether k_reduce_partials runs behind the last pass.  Complex and phase samples: only the statistics
+// form with a target left partials to reduce; otherwise unless the caller reduces them itself
 inline bool pass_reduces(const PassCall& c) {
-  return c.complex_values ? c.complex_stats && c.target : !c.skip_reduce;
+  return pass_complex(c) ? c.complex_stats && c.target : !c.skip_reduce;
 }
 
 constexpr int kPsfBlocks = 128;   // blocks per job of the incremental-field kernels

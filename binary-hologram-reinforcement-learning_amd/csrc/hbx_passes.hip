@@ -20,7 +20,8 @@
 //             (k_rowfwd32 at N = 1024.  k_rowfwd_real / k_rowfwd32_real read f32 samples instead of
 //             bits; everything after the load -- FFT, split, tile, panel stores -- is one function
 //             per size class, rowfwd_emit / rowfwd32_emit, called by the bit and the real kernel;
-//             k_rowfwd_cplx / k_rowfwd32_cplx read complex64 samples, one complex plane per plane pair)
+//             k_rowfwd_cplx / k_rowfwd32_cplx read complex64 samples, one complex plane per plane pair,
+//             or f32 phase samples x that they turn into exp(i pi x) as they load them)
 //   k_col2    one lane group per half-spectrum line kx: FFT over y -> x H and
 //             x conj H (H is even in fx and ky) -> two IFFTs -> B lines kx
 //             and N - kx (N/2 for kx = 0); buffer loads / stores with one
@@ -32,7 +33,8 @@
 //             mean -> f64 partials of (I*T, I^2, T^2) vs the target row   [read 8 N^2 per plane + 4 N^2]
 //             (complex fields: k_rowinv_d_cplx / k_rowinv_cplx add B planes 2q and i * 2q + 1 on load,
 //             one IFFT per complex plane, and store the field / its real part; their statistics
-//             form, hbx_evaluate_complex, also sums |F_q|^2 and ends in the same plane mean and partials)
+//             form, hbx_evaluate_complex, also sums |F_q|^2 and ends in the same plane mean and partials;
+//             their gradient form, hbx_phase_backward, stores dL/dx of a phase leaf instead of the plane)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -527,15 +529,19 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd32_real(const JobDesc* __restr
 // samples into v as they are, and the shared tail does what it does for two real planes: the row
 // FFT of u = a + i b, split into the half spectra of a = Re u (A plane 2q) and b = Im u (2q + 1).
 // The real kernels' geometry: one row block per workgroup, wg.q = the complex plane.
-// WT (hbx_simulate_complex_weighted): complex_load_row_weighted multiplies the samples by scale *
+// LK = kLoadWeighted (hbx_simulate_complex_weighted): complex_load_row_weighted multiplies the samples by scale *
 // weight[env][group][y][x] as it loads them -- R more VGPRs live across the load (the weights), the
-// tail and the geometry unchanged; weight / scale are unused without WT.
-template <int R, int NT, bool WT = false>
+// tail and the geometry unchanged; weight / scale are unused without it.
+// LK = kLoadPhase (hbx_simulate_phase): phase[env][CH / 2][N][N] f32 instead of values, phase plane q
+// into plane-pair slot q as complex plane q; phase_load_row forms exp(i pi x) as it loads -- R floats
+// live across the load where the complex form holds R pairs.  phase is unused by the other kinds.
+template <int R, int NT, int LK = kLoadComplex>
 __global__ __launch_bounds__(NT, 512 / NT) void k_rowfwd_cplx(const JobDesc* __restrict__ jobs,
                                                         const float2* __restrict__ values,
                                                         float2* __restrict__ ws_a,
                                                         const float2* __restrict__ tw_glob, int P, int CH,
-                                                        const float* __restrict__ weight, float scale) {
+                                                        const float* __restrict__ weight, float scale,
+                                                        const float* __restrict__ phase) {
   constexpr int N = R * R;
   constexpr int GPB = NT / R;          // rows per row block
   __shared__ float2 tw[N];
@@ -554,25 +560,29 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowfwd_cplx(const JobDesc* __r
   const int y0 = wg.rbw * GPB;
   const int y = y0 + grp;
   pk2 v[R];
-  const float2* row = values + (((size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q) * N + y) * N;
-  if constexpr (WT)
-    complex_load_row_weighted<R>(v, row, weight + (((size_t)jb.env * (CH / P) + jb.group) * N + y) * N, scale, t);
+  const size_t row = (((size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q) * N + y) * N;
+  if constexpr (LK == kLoadWeighted)
+    complex_load_row_weighted<R>(v, values + row, weight + (((size_t)jb.env * (CH / P) + jb.group) * N + y) * N, scale, t);
+  else if constexpr (LK == kLoadPhase)
+    phase_load_row<R>(v, phase + row, t);
   else
-    complex_load_row<R>(v, row, t);
+    complex_load_row<R>(v, values + row, t);
   __syncthreads();  // tw visible
 
   float2* base = ws_a + ((size_t)j * P + 2 * wg.q) * plane_a_elems(R);
   rowfwd_emit<R, NT, HBX_PRECISION_F32>(v, t, grp, lane_base, y0, lds, tw, base);
 }
 
-// N = 1024: k_rowfwd32's three workgroups per CU (WT: 111 VGPRs against 112, the weights die before the
-// row FFT's temporaries are born; profiles/intensity_grad/resource_usage.txt)
-template <bool WT = false>
+// N = 1024: k_rowfwd32's three workgroups per CU (kLoadWeighted: 111 VGPRs against 112, the weights die before the
+// row FFT's temporaries are born; profiles/intensity_grad/resource_usage.txt; kLoadPhase:
+// profiles/phase_field/resource_usage.txt)
+template <int LK = kLoadComplex>
 __global__ __launch_bounds__(256, 3) void k_rowfwd32_cplx(const JobDesc* __restrict__ jobs,
                                                           const float2* __restrict__ values,
                                                           float2* __restrict__ ws_a,
                                                           const float2* __restrict__ tw_glob, int P, int CH,
-                                                          const float* __restrict__ weight, float scale) {
+                                                          const float* __restrict__ weight, float scale,
+                                                          const float* __restrict__ phase) {
   constexpr int R = 32, NT = 256, N = R * R;
   constexpr int GPB = NT / R;          // 8 rows per row block
   __shared__ float2 tw[N];
@@ -591,11 +601,13 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd32_cplx(const JobDesc* __restr
   const int y0 = wg.rbw * GPB;
   const int y = y0 + grp;
   pk2 v[R];
-  const float2* row = values + (((size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q) * N + y) * N;
-  if constexpr (WT)
-    complex_load_row_weighted<R>(v, row, weight + (((size_t)jb.env * (CH / P) + jb.group) * N + y) * N, scale, t);
+  const size_t row = (((size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q) * N + y) * N;
+  if constexpr (LK == kLoadWeighted)
+    complex_load_row_weighted<R>(v, values + row, weight + (((size_t)jb.env * (CH / P) + jb.group) * N + y) * N, scale, t);
+  else if constexpr (LK == kLoadPhase)
+    phase_load_row<R>(v, phase + row, t);
   else
-    complex_load_row<R>(v, row, t);
+    complex_load_row<R>(v, values + row, t);
   __syncthreads();  // tw visible
 
   float2* base = ws_a + ((size_t)j * P + 2 * wg.q) * plane_a_elems(R);
@@ -1003,13 +1015,17 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv(const JobDesc* __restri
 // k_rowinv's tail (rowinv_epilogue) runs with Q = P / 2 as the plane count: the plane-mean intensity
 // row to inten_out [job][N][N], the f64 partials against the target row (tmask = 0: the zero row).
 // field_out and real_out may then both be null.
+// PG (hbx_phase_backward; off by default, and the kernels without it compile as before): the plane out
+// of the inverse FFT is the gradient g with respect to the field u = exp(i pi x) of a phase leaf, and
+// the kernel writes grad[env][CH / 2][N][N] f32 = pi (Im g cos pi x - Re g sin pi x) from the samples
+// phase[env][CH / 2][N][N] (phase_grad_row) and nothing else: no complex field, no statistics.
 //
 // N = 1024 / 256: k_rowinv_d's direct loads from the tiled B (RowinvLanes).
 // Plane 2q + 1 arrives in two halves of R / 2 values that are folded into v as they land, so the
 // kernel never holds two whole lines (the second register set that cost k_rowinv_d its second
 // block per CU).  N = 256 has the registers for a second line and keeps the next pair in flight
 // under this one's FFT, as k_rowinv_d does with the next plane.
-template <int R, bool ST = false>
+template <int R, bool ST = false, bool PG = false>
 __global__ __launch_bounds__(256, 2) void k_rowinv_d_cplx(const JobDesc* __restrict__ jobs,
                                                           const float2* __restrict__ ws_b,
                                                           const float2* __restrict__ tw_glob, int P, int G,
@@ -1017,7 +1033,10 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_d_cplx(const JobDesc* __restr
                                                           float* __restrict__ real_out,
                                                           const float* __restrict__ target, size_t tmask,
                                                           double* __restrict__ partial,
-                                                          float* __restrict__ inten_out) {
+                                                          float* __restrict__ inten_out,
+                                                          const float* __restrict__ phase,
+                                                          float* __restrict__ grad) {
+  static_assert(!(ST && PG), "the gradient form runs no statistics");
   constexpr int N = R * R, GPB = 256 / R, RB = N / GPB;
   __shared__ float2 tw[N];
   __shared__ float2 scratch[GPB * R * (R + 1)];
@@ -1053,6 +1072,10 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_d_cplx(const JobDesc* __restr
       for (int k = 0; k < R; ++k) acc[k] += fmaf(v[k].x, v[k].x, v[k].y * v[k].y);
     }
     const size_t row = row0 + (size_t)q * N * N;
+    if constexpr (PG) {   // the samples are loaded behind the FFT: R = 32 never holds a second line
+      phase_grad_row<R, R>(v, phase + row, grad + row);
+      return;
+    }
     if (field_out) {
 #pragma unroll
       for (int k = 0; k < R; ++k) field_out[row + R * k] = from_pk(v[k]);
@@ -1091,7 +1114,7 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_d_cplx(const JobDesc* __restr
 
 // N = 64: k_rowinv's LDS tile transpose; both planes' shares of the tile are prefetched one pair
 // ahead and combined as they are written into the tile.
-template <int R, int NT, bool ST = false>
+template <int R, int NT, bool ST = false, bool PG = false>
 __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv_cplx(const JobDesc* __restrict__ jobs,
                                                         const float2* __restrict__ ws_b,
                                                         const float2* __restrict__ tw_glob, int P, int G,
@@ -1099,7 +1122,10 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv_cplx(const JobDesc* __r
                                                         float* __restrict__ real_out,
                                                         const float* __restrict__ target, size_t tmask,
                                                         double* __restrict__ partial,
-                                                        float* __restrict__ inten_out) {
+                                                        float* __restrict__ inten_out,
+                                                        const float* __restrict__ phase,
+                                                        float* __restrict__ grad) {
+  static_assert(!(ST && PG), "the gradient form runs no statistics");
   constexpr int N = R * R;
   constexpr int GPB = NT / R;          // rows per block
   constexpr int RB = N / GPB;
@@ -1167,6 +1193,10 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv_cplx(const JobDesc* __r
       for (int k = 0; k < R; ++k) acc[k] += fmaf(v[k].x, v[k].x, v[k].y * v[k].y);
     }
     const size_t row = row0 + (size_t)q * N * N;
+    if constexpr (PG) {
+      phase_grad_row<R, R>(v, phase + row, grad + row);
+      continue;
+    }
     if (field_out) {
 #pragma unroll
       for (int k = 0; k < R; ++k) field_out[row + R * k] = from_pk(v[k]);
@@ -1345,14 +1375,20 @@ static hipError_t launch_passes(const PlanDev& pd, const PassCall& c, hipStream_
   const unsigned sample_blocks = (unsigned)n_jobs * (P / 2) * kRowBlocks;
 
   if (tm) tm->begin(0, st);
-  if (c.complex_values) {   // WT (hbx_simulate_complex_weighted): u = (scale * weight) * values
-    const bool wt = c.complex_weight != nullptr;
+  if (pass_complex(c)) {   // the load kind: complex samples as they are, times scale * weight, or exp(i pi phase)
+    const int lk = c.phase_values ? kLoadPhase : c.complex_weight ? kLoadWeighted : kLoadComplex;
     auto k = [&] {
-      if constexpr (R == 32) return wt ? k_rowfwd32_cplx<true> : k_rowfwd32_cplx<false>;
-      else return wt ? k_rowfwd_cplx<R, NT, true> : k_rowfwd_cplx<R, NT, false>;
+      // (the two kernels that were here first stay first: first use fixes a kernel's place in the code object)
+      if constexpr (R == 32)
+        return lk == kLoadWeighted ? k_rowfwd32_cplx<kLoadWeighted>
+                                   : lk == kLoadComplex ? k_rowfwd32_cplx<kLoadComplex> : k_rowfwd32_cplx<kLoadPhase>;
+      else
+        return lk == kLoadWeighted ? k_rowfwd_cplx<R, NT, kLoadWeighted>
+                                   : lk == kLoadComplex ? k_rowfwd_cplx<R, NT, kLoadComplex>
+                                                        : k_rowfwd_cplx<R, NT, kLoadPhase>;
     }();
     launch_kernel(k, sample_blocks, NT, st, jobs, c.complex_values, pd.ws_a, pd.tw, P, CH, c.complex_weight,
-                  c.complex_scale);
+                  c.complex_scale, c.phase_values);
   } else if (c.real_values) {
     auto k = [&] {
       if constexpr (R == 32) return k_rowfwd32_real;
@@ -1384,14 +1420,17 @@ static hipError_t launch_passes(const PlanDev& pd, const PassCall& c, hipStream_
 
   const unsigned blocks = (unsigned)n_jobs * kRowBlocks;
   if (tm) tm->begin(2, st);
-  if (c.complex_values) {   // recombine each plane pair; ST (hbx_evaluate_complex): intensity and partials too
-    const bool stats = c.complex_stats != 0;
+  if (pass_complex(c)) {   // recombine each plane pair; ST (hbx_evaluate_complex): intensity and partials too;
+                           // PG (hbx_phase_backward): the phase gradient instead of the field
+    const bool stats = c.complex_stats != 0, pg = c.grad_phase != nullptr;
     auto k = [&] {
-      if constexpr (kTiledB<R>) return stats ? k_rowinv_d_cplx<R, true> : k_rowinv_d_cplx<R>;
-      else return stats ? k_rowinv_cplx<R, NT, true> : k_rowinv_cplx<R, NT>;
+      if constexpr (kTiledB<R>)
+        return !pg ? (stats ? k_rowinv_d_cplx<R, true> : k_rowinv_d_cplx<R>) : k_rowinv_d_cplx<R, false, true>;
+      else
+        return !pg ? (stats ? k_rowinv_cplx<R, NT, true> : k_rowinv_cplx<R, NT>) : k_rowinv_cplx<R, NT, false, true>;
     }();
     launch_kernel(k, blocks, NT, st, jobs, pd.ws_b, pd.tw, P, pd.G, c.complex_field, c.real_part, tg.rows, tg.mask,
-                  pd.partial, c.inten_out);
+                  pd.partial, c.inten_out, c.grad_samples, c.grad_phase);
   } else if constexpr (kTiledB<R>) {
     // WALK (r05): a plane-cache walk batch, the last workgroup decides.  LEAN (r06): the plain
     // FFT-mode launch (the headline), its own instantiation without the plane cache / field /

@@ -13,7 +13,7 @@
 //                LDS tile transpose -> A[kx][y0..y0+8)   [read N^2/8, write 4 N^2 B per plane]
 //                (k_rowfwd896_real reads f32 samples instead of bits; everything after the
 //                load is rowfwd896_emit, called by both and by k_rowfwd896_cplx, which reads
-//                complex64 samples; k_rowinv896_cplx is the last pass of that path)
+//                complex64 samples or f32 phase samples; k_rowinv896_cplx is the last pass of that path)
 //   k_col896     one lane group per half-spectrum line kx: FFT over y ->
 //                x H and x conj H (H even in fx and ky) -> two IFFTs -> B lines
 //                kx and N - kx (448 for kx = 0)           [read 4 N^2, write 8 N^2]
@@ -249,15 +249,17 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd896_real(const JobDesc* __rest
 // Pass 1 on complex fields (hbx_simulate_complex): values[env][CH / 2][896][896] complex64.
 // complex_load_row puts the complex sample of pixel x = t + 32 jj (jj < 28) into v[jj] as it is and
 // zeros above; rowfwd896_emit then leaves the half spectra of Re u_q and Im u_q in A planes 2q and
-// 2q + 1.  k_rowfwd896_real's geometry, wg.q = the complex plane.  WT (hbx_simulate_complex_weighted):
+// 2q + 1.  k_rowfwd896_real's geometry, wg.q = the complex plane.  LK = kLoadWeighted (hbx_simulate_complex_weighted):
 // complex_load_row_weighted scales the 28 loaded samples by scale * weight[env][group][y][x]; slots >= 28
-// stay zero.
-template <bool WT = false>
+// stay zero.  LK = kLoadPhase (hbx_simulate_phase): phase[env][CH / 2][896][896] f32 instead of values;
+// phase_load_row forms exp(i pi x) of the 28 loaded samples, and slots >= 28 are zero there too.
+template <int LK = kLoadComplex>
 __global__ __launch_bounds__(256, 3) void k_rowfwd896_cplx(const JobDesc* __restrict__ jobs,
                                                            const float2* __restrict__ values,
                                                            float2* __restrict__ ws_a,
                                                            const float2* __restrict__ tw_glob, int P, int CH,
-                                                           const float* __restrict__ weight, float scale) {
+                                                           const float* __restrict__ weight, float scale,
+                                                           const float* __restrict__ phase) {
   __shared__ float2 tw[kN];
   __shared__ __attribute__((aligned(16))) float lds[kRowfwd896Scr];
   stage_twiddles<kN, 256>(tw, tw_glob);
@@ -272,11 +274,13 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd896_cplx(const JobDesc* __rest
   const int y0 = wg.rbw * kGPB;
   const int y = y0 + grp;
   float2 v[32];
-  const float2* row = values + (((size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q) * kN + y) * kN;
-  if constexpr (WT)
-    complex_load_row_weighted<kR, kL>(v, row, weight + (((size_t)jb.env * (CH / P) + jb.group) * kN + y) * kN, scale, t);
+  const size_t row = (((size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q) * kN + y) * kN;
+  if constexpr (LK == kLoadWeighted)
+    complex_load_row_weighted<kR, kL>(v, values + row, weight + (((size_t)jb.env * (CH / P) + jb.group) * kN + y) * kN, scale, t);
+  else if constexpr (LK == kLoadPhase)
+    phase_load_row<kR, kL>(v, phase + row, t);
   else
-    complex_load_row<kR, kL>(v, row, t);
+    complex_load_row<kR, kL>(v, values + row, t);
   __syncthreads();  // tw visible
 
   float2* base = ws_a + ((size_t)j * P + 2 * wg.q) * kPlaneA;
@@ -526,7 +530,10 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896(const JobDesc* __restrict_
 // accumulated per pixel as k_rowinv896 does and its tail runs with Q = P / 2 as the plane count --
 // the plane-mean intensity row to inten_out [job][896][896] and the f64 partials against the target
 // row; field_out and real_out may then both be null.
-template <bool ST = false>
+// PG (hbx_phase_backward; off by default): the plane is the gradient with respect to u = exp(i pi x),
+// and grad[env][CH / 2][896][896] f32 = pi (Im g cos pi x - Re g sin pi x) from phase (same shape) is
+// the only output (phase_grad_row on the 28 pixels of a lane).
+template <bool ST = false, bool PG = false>
 __global__ __launch_bounds__(256, 2) void k_rowinv896_cplx(const JobDesc* __restrict__ jobs,
                                                            const float2* __restrict__ ws_b,
                                                            const float2* __restrict__ tw_glob, int P, int G,
@@ -534,7 +541,10 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896_cplx(const JobDesc* __rest
                                                            float* __restrict__ real_out,
                                                            const float* __restrict__ target, size_t tmask,
                                                            double* __restrict__ partial,
-                                                           float* __restrict__ inten_out) {
+                                                           float* __restrict__ inten_out,
+                                                           const float* __restrict__ phase,
+                                                           float* __restrict__ grad) {
+  static_assert(!(ST && PG), "the gradient form runs no statistics");
   __shared__ float2 tw[kN];
   __shared__ float2 scratch[kSCR];
   for (int i = threadIdx.x; i < kN; i += 256) tw[i] = tw_glob[i];
@@ -572,13 +582,17 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896_cplx(const JobDesc* __rest
       for (int k = 0; k < kL; ++k) acc[k] += fmaf(v[k].x, v[k].x, v[k].y * v[k].y);
     }
     const size_t row = row0 + (size_t)q * kN * kN;
-    if (field_out) {
+    if constexpr (PG) {
+      phase_grad_row<kR, kL>(v, phase + row, grad + row);
+    } else {
+      if (field_out) {
 #pragma unroll
-      for (int k = 0; k < kL; ++k) field_out[row + kR * k] = v[k];
-    }
-    if (real_out) {
+        for (int k = 0; k < kL; ++k) field_out[row + kR * k] = v[k];
+      }
+      if (real_out) {
 #pragma unroll
-      for (int k = 0; k < kL; ++k) real_out[row + kR * k] = v[k].x;
+        for (int k = 0; k < kL; ++k) real_out[row + kR * k] = v[k].x;
+      }
     }
     if (q + 1 < Q) load_pair(v, q + 1);   // uniform: no pair is read twice
   }
@@ -605,9 +619,11 @@ hipError_t run_jobs_896(const PlanDev& pd, const PassCall& c, hipStream_t st) {
   const unsigned blocks = (unsigned)n_jobs * kRB;   // one workgroup per row block of a job
 
   if (tm) tm->begin(0, st);
-  if (c.complex_values)   // WT (hbx_simulate_complex_weighted): u = (scale * weight) * values
-    launch_kernel(c.complex_weight ? k_rowfwd896_cplx<true> : k_rowfwd896_cplx<false>, blocks * (P / 2), 256, st, jobs,
-                  c.complex_values, pd.ws_a, pd.tw, P, CH, c.complex_weight, c.complex_scale);
+  if (pass_complex(c))   // the load kind: complex samples as they are, times scale * weight, or exp(i pi phase)
+    launch_kernel(c.complex_weight ? k_rowfwd896_cplx<kLoadWeighted>
+                                   : c.complex_values ? k_rowfwd896_cplx<kLoadComplex> : k_rowfwd896_cplx<kLoadPhase>,
+                  blocks * (P / 2), 256, st, jobs, c.complex_values, pd.ws_a, pd.tw, P, CH, c.complex_weight,
+                  c.complex_scale, c.phase_values);
   else if (c.real_values)
     launch_kernel(k_rowfwd896_real, blocks * (P / 2), 256, st, jobs, c.real_values, pd.ws_a, pd.tw, P, CH);
   else
@@ -621,9 +637,12 @@ hipError_t run_jobs_896(const PlanDev& pd, const PassCall& c, hipStream_t st) {
   if (tm) tm->end(1, n_jobs, st);
 
   if (tm) tm->begin(2, st);
-  if (c.complex_values) {   // recombine each plane pair; ST (hbx_evaluate_complex): intensity and partials too
-    launch_kernel(c.complex_stats ? k_rowinv896_cplx<true> : k_rowinv896_cplx<false>, blocks, 256, st, jobs, pd.ws_b,
-                  pd.tw, P, pd.G, c.complex_field, c.real_part, tg.rows, tg.mask, pd.partial, c.inten_out);
+  if (pass_complex(c)) {   // recombine each plane pair; ST (hbx_evaluate_complex): intensity and partials too;
+                           // PG (hbx_phase_backward): the phase gradient instead of the field
+    launch_kernel(!c.grad_phase ? (c.complex_stats ? k_rowinv896_cplx<true> : k_rowinv896_cplx<false>)
+                                : k_rowinv896_cplx<false, true>,
+                  blocks, 256, st, jobs, pd.ws_b, pd.tw, P, pd.G, c.complex_field, c.real_part, tg.rows, tg.mask,
+                  pd.partial, c.inten_out, c.grad_samples, c.grad_phase);
   } else {
     // (r06) the plain FFT-mode launch gets the lean instantiation (profiles/r06/rowinv896_lean_ab_r06i.txt)
     const bool lean = c.plane_mode == kPlanesOff && !c.field_out;

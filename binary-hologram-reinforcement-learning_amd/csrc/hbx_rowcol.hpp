@@ -197,6 +197,58 @@ __device__ __forceinline__ void complex_load_row_weighted(V (&v)[R], const float
   for (int jj = L; jj < R; ++jj) v[jj] = V{0.f, 0.f};
 }
 
+// What the complex first passes (k_rowfwd_cplx, k_rowfwd32_cplx, k_rowfwd896_cplx) load a row with:
+// complex_load_row, complex_load_row_weighted or phase_load_row
+constexpr int kLoadComplex = 0, kLoadWeighted = 1, kLoadPhase = 2;
+
+// Phase holograms (hbx_simulate_phase): u = exp(i pi x) from the float32 sample x.  sincospif reduces
+// the argument exactly (x mod 2 has no rounding in float32, unlike x * float32(pi)), so the error of
+// (c, s) does not grow with |x|: an unwrapped phase of thousands of turns is as good as a wrapped one.
+// The hardware sine / cosine on fract(x / 2) (their input is in revolutions) met the same accuracy
+// criteria and measured no shorter first pass, so the correctly reduced library form stays.
+__device__ __forceinline__ void phase_sincos(float x, float& c, float& s) { sincospif(x, &s, &c); }
+
+// Lane t loads the float32 phase sample of pixel x = t + R jj, jj < L, of the row at `row` -- one
+// 4-byte non-temporal load per element, a coalesced 4 R-byte run per lane group and jj, all L issued
+// before the first use (as real_load_row) -- and v[jj] = (cos pi x, sin pi x); v[L ..] = 0, not
+// exp(0) (N = 896: the padding is no sample).  The tail then sees complex_load_row's row.
+template <int R, int L = R, class V>
+__device__ __forceinline__ void phase_load_row(V (&v)[R], const float* __restrict__ row, int t) {
+  float a[L];
+#pragma unroll
+  for (int jj = 0; jj < L; ++jj) a[jj] = __builtin_nontemporal_load(row + t + R * jj);
+#pragma unroll
+  for (int jj = 0; jj < L; ++jj) {
+    float c, s;
+    phase_sincos(a[jj], c, s);
+    v[jj] = V{c, s};
+  }
+#pragma unroll
+  for (int jj = L; jj < R; ++jj) v[jj] = V{0.f, 0.f};
+}
+
+// The last pass of a phase leaf's backward (hbx_phase_backward): g = the inverse row FFT's output
+// (natural layout, pixel x = t + R k of the row), u = exp(i pi x) the leaf's field, du/dx = i pi u, so
+//   dL/dx = Re(conj(du/dx) g) = pi (Im g cos pi x - Re g sin pi x),
+// one float32 per pixel to g0[R k]; g0 / p0 = the lane's pixel x = t of the gradient row and of the
+// same row of the phase samples (read once, non-temporal, behind the FFT: no sample is live across
+// it -- at N = 256, where the registers are there, loading them ahead of the FFT measured no faster,
+// DESIGN.md 4q).  phase_load_row's sincos.
+template <int R, int L, class V, int NV>
+__device__ __forceinline__ void phase_grad_row(const V (&v)[NV], const float* __restrict__ p0,
+                                               float* __restrict__ g0) {
+  constexpr float kPiF = 3.14159265358979323846f;
+  float a[L];
+#pragma unroll
+  for (int k = 0; k < L; ++k) a[k] = __builtin_nontemporal_load(p0 + R * k);
+#pragma unroll
+  for (int k = 0; k < L; ++k) {
+    float c, s;
+    phase_sincos(a[k], c, s);
+    g0[R * k] = kPiF * fmaf(v[k].y, c, -(v[k].x * s));
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Staged slot-tile stores of the column passes (k_col2 at N = 1024 / 256, k_col896 since r04):
 // the output line sets of a block (TL lines: group g = slot g of slot tile st, TileB) go out

@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = (
     "hbx_simulate_real", "hbx_propagate_real", "hbx_simulate_complex",
     "hbx_simulate_complex_weighted", "hbx_intensity_real",
     "hbx_evaluate_real", "hbx_evaluate_complex", "hbx_loss", "hbx_loss_weight",
+    "hbx_simulate_phase", "hbx_evaluate_phase", "hbx_phase_backward",
 )
 NUM_PASSES = 5
 PASS_NAMES = ("k_rowfwd", "k_col", "k_rowinv", "k_psf_eval", "k_psf_commit")
@@ -136,6 +137,9 @@ def _declare(lib):
     lib.hbx_intensity_real.argtypes = [VP, VP, I32, VP, VP]
     lib.hbx_evaluate_real.argtypes = [VP, VP, VP, I32, VP, VP, VP, VP, VP]
     lib.hbx_evaluate_complex.argtypes = [VP, VP, VP, I32, VP, VP, VP, VP, VP]
+    lib.hbx_simulate_phase.argtypes = [VP, VP, I32, VP, VP, VP]
+    lib.hbx_evaluate_phase.argtypes = [VP, VP, VP, I32, VP, VP, VP, VP, VP]
+    lib.hbx_phase_backward.argtypes = [VP, VP, VP, C.c_float, VP, I32, VP, VP]
     lib.hbx_loss.argtypes = [VP, VP, I32, I32, I32, VP, VP]
     lib.hbx_loss_weight.argtypes = [VP, VP, VP, VP, VP, I32, I32, I32, VP, VP]
     lib.hbx_flip_map.argtypes = [VP, VP, VP, VP, VP, VP]

@@ -426,6 +426,75 @@ class Plan:
                                                  _ptr(stats), _ptr(psnr), _stream(stream)), "hbx_evaluate_complex")
         return (torch.view_as_complex(field) if want_field else None), inten, stats, psnr
 
+    def phase_shape(self, n: int):
+        c = self.cfg
+        return (n, c.channels // 2, c.height, c.width)
+
+    def simulate_phase(self, phase: torch.Tensor, want_field: bool = True, want_real: bool = False, stream=None):
+        """`simulate_complex` of u = exp(i pi phase) (hbx_simulate_phase): `phase` float32
+        [B, CH/2, H, W]; the first pass forms (cos, sin) as it loads the samples, with the argument
+        reduced exactly.  Returns (field complex64 [B, CH/2, H, W] | None, real_part | None)."""
+        if not (want_field or want_real):
+            raise ValueError("simulate_phase: want_field and want_real are both off")
+        n = phase.shape[0] if isinstance(phase, torch.Tensor) and phase.dim() else 0
+        shape = self.phase_shape(n)
+        _need(phase, "phase", torch.float32, shape, self.device)
+        phase = phase.resolve_neg()                # a lazily negated view shares the un-negated memory
+        field = torch.empty(shape + (2,), dtype=torch.float32, device=self.device) if want_field else None
+        real = torch.empty(shape, dtype=torch.float32, device=self.device) if want_real else None
+        _lib.check(self.lib.hbx_simulate_phase(self._h, _ptr(phase), n, _ptr(field), _ptr(real), _stream(stream)),
+                   "hbx_simulate_phase")
+        return (torch.view_as_complex(field) if want_field else None), real
+
+    def evaluate_phase(self, phase: torch.Tensor, target: Optional[torch.Tensor] = None, want_field: bool = True,
+                       want_intensity: bool = True, stream=None):
+        """`evaluate_complex` of u = exp(i pi phase) (hbx_evaluate_phase): `phase` float32
+        [B, CH/2, H, W] as `simulate_phase`; returns (field | None, intensity | None, chan_stats |
+        None, psnr | None) as `evaluate_complex`, the field `simulate_phase`'s bit for bit.  target
+        None: the intensity alone."""
+        n = phase.shape[0] if isinstance(phase, torch.Tensor) and phase.dim() else 0
+        c = self.cfg
+        shape = self.phase_shape(n)
+        _need(phase, "phase", torch.float32, shape, self.device)
+        phase = phase.resolve_neg()
+        if target is None:
+            if not want_intensity:
+                raise ValueError("evaluate_phase: without a target the intensity is the only output")
+        else:
+            _need(target, "target", torch.float32, self.target_shape(n), self.device)
+        field = torch.empty(shape + (2,), dtype=torch.float32, device=self.device) if want_field else None
+        inten = torch.empty(self.target_shape(n), dtype=torch.float32, device=self.device) if want_intensity else None
+        stats = psnr = None
+        if target is not None:
+            stats = torch.empty((n, c.groups, 3), dtype=torch.float64, device=self.device)
+            psnr = torch.empty((n,), dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.hbx_evaluate_phase(self._h, _ptr(phase), _ptr(target), n, _ptr(field), _ptr(inten),
+                                               _ptr(stats), _ptr(psnr), _stream(stream)), "hbx_evaluate_phase")
+        return (torch.view_as_complex(field) if want_field else None), inten, stats, psnr
+
+    def phase_backward(self, values: torch.Tensor, phase: torch.Tensor, weight: Optional[torch.Tensor] = None,
+                       scale: float = 1.0, stream=None) -> torch.Tensor:
+        """The backward pass of a phase leaf, on the plan for -z (hbx_phase_backward): `values`
+        complex64 [B, CH/2, H, W] and `weight` / `scale` are `simulate_complex`'s (weight None: the
+        samples as they are), `phase` float32 [B, CH/2, H, W] the leaf's samples x.  Returns
+        float32 [B, CH/2, H, W] = pi (Im g cos pi x - Re g sin pi x), g the field `simulate_complex`
+        would return -- which is not written.  With the saved field as values, the loss's or the
+        intensity's incoming gradient as weight and scale = 2 / planes this is dL/dx."""
+        n = values.shape[0] if isinstance(values, torch.Tensor) and values.dim() else 0
+        c = self.cfg
+        shape = self.phase_shape(n)
+        _need(values, "values", torch.complex64, shape, self.device)
+        values = values.resolve_conj().resolve_neg()   # as simulate_complex: the kernel reads the memory
+        _need(phase, "phase", torch.float32, shape, self.device)
+        phase = phase.resolve_neg()
+        if weight is not None:
+            _need(weight, "weight", torch.float32, (n, c.groups, c.height, c.width), self.device)
+            weight = weight.resolve_neg()
+        grad = torch.empty(shape, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.hbx_phase_backward(self._h, _ptr(values), _ptr(weight), float(scale), _ptr(phase), n,
+                                               _ptr(grad), _stream(stream)), "hbx_phase_backward")
+        return grad
+
     def loss(self, chan_stats: torch.Tensor, kind: int = _lib.LOSS_MSE, rel_scale: int = _lib.REL_LSQ,
              stream=None) -> torch.Tensor:
         """chan_stats [B, G, 3] -> the relative MSE or PSNR per env, float64 [B] on the device

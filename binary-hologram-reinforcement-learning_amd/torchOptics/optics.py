@@ -22,13 +22,17 @@ fallback on either):
   ``simulate(x, z, strict=True)`` waits and raises before returning.
 * ``binary=False`` (the continuous path, ABI v15): the samples are the field.  Real float
   input goes through hbx_simulate_real, whose first pass reads float32 samples instead of
-  bits; a complex field, or ``field="phase"`` on real input (u = exp(i pi x), formed with
-  torch ops), goes through hbx_simulate_complex, whose first pass reads complex64 samples and
-  whose last pass writes each complex plane once.  No pack kernel runs, the error word is
-  never set and ``strict`` has nothing to check.
+  bits; a complex field goes through hbx_simulate_complex, whose first pass reads complex64
+  samples and whose last pass writes each complex plane once; ``field="phase"`` on real input
+  (u = exp(i pi x)) goes through hbx_simulate_phase, the same with exp(i pi x) formed by the
+  first pass as it loads x.  No pack kernel runs, the error word is never set and ``strict``
+  has nothing to check.
   This path is differentiable: when the input requires grad the propagation runs as a
   torch.autograd.Function whose backward pass is hbx_simulate_complex of grad_output on the
-  plan for -z (the adjoint: H(-z) = conj H(z)); a real input receives the real part only.
+  plan for -z (the adjoint: H(-z) = conj H(z)); a real input receives the real part only, and
+  a phase leaf dL/dx = pi (Im g cos pi x - Re g sin pi x) from the last pass of
+  hbx_phase_backward (``intensity`` and ``loss`` likewise): no torch op forms u or walks back
+  through it.
   Without a gradient request the call is the plain one, with no graph.  Limits: the -z plan
   is a second workspace in the plan cache; there is no double backward; ``binary=True`` stays
   non-differentiable and builds no graph; ``relativeLoss(.., tm.get_PSNR)`` returns a float
@@ -187,7 +191,8 @@ def simulate(x, z: float, strict: bool = False, binary: bool = True, tf="asm", f
     binary=False: the continuous path; no binary check, `strict` is ignored.
       real x,    field="amplitude":  u = x (float64 is cast to float32), one real plane each;
       complex x, field="amplitude":  u = x (cast to complex64), through hbx_simulate_complex;
-      real x,    field="phase":      u = exp(i pi x) = cos(pi x) + i sin(pi x), the same route.
+      real x,    field="phase":      u = exp(i pi x), formed by the first pass of hbx_simulate_phase
+                                     (float64 is cast to float32; x and x + 2 are the same field).
     A complex plane takes the workspace of two real planes.  If x requires grad the result
     carries a grad_fn and loss.backward() reaches x (module docstring); otherwise it has none."""
     tf_kind = _switch(tf, _TF_NAMES, "tf")
@@ -291,14 +296,46 @@ class _Propagate(torch.autograd.Function):
         return grad.to(ctx.in_dtype), None
 
 
+def _phase_samples(t: torch.Tensor) -> torch.Tensor:
+    """The float32 contiguous samples of a real phase leaf, by torch ops: autograd carries a
+    float64 leaf's cast back."""
+    return t.to(torch.float32).resolve_neg().contiguous()
+
+
+class _PropagatePhase(torch.autograd.Function):
+    """x -> A exp(i pi x) through hbx_simulate_phase, x float32 [B, C, H, W].  Backward: one
+    hbx_phase_backward of grad_output on the plan for -z, whose last pass turns A^H g into
+    dL/dx = pi (Im cos pi x - Re sin pi x) from the saved samples.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, x, geom):
+        wl, dx, dy, z, dev, tf_kind = geom
+        b, c, h, w = x.shape
+        ctx.geom = geom
+        ctx.save_for_backward(x)
+        return _plan_for(h, w, 2 * c, wl, dx, dy, z, b, dev, tf_kind).simulate_phase(x)[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        wl, dx, dy, z, dev, tf_kind = ctx.geom
+        x, = ctx.saved_tensors
+        b, c, h, w = x.shape
+        g = grad_output.to(torch.complex64).resolve_conj().resolve_neg().contiguous()
+        return _plan_for(h, w, 2 * c, wl, dx, dy, -z, b, dev, tf_kind).phase_backward(g, x), None
+
+
 def _simulate_continuous(t: torch.Tensor, wl, dx, dy, z, dev: int, tf_kind: int, field_kind: int) -> torch.Tensor:
     """simulate's binary=False path on a device tensor [B, C, H, W]: real planes through
-    hbx_simulate_real, complex and phase fields through hbx_simulate_complex; through
-    _Propagate when a gradient is wanted."""
-    if field_kind == _lib.FIELD_PHASE and not t.is_complex():
-        ph = t.to(torch.float32) * np.float32(np.pi)
-        t = torch.complex(torch.cos(ph), torch.sin(ph))   # torch ops: autograd carries du/dx
+    hbx_simulate_real, complex fields through hbx_simulate_complex, phase samples through
+    hbx_simulate_phase; through _Propagate / _PropagatePhase when a gradient is wanted."""
     geom = (wl, dx, dy, z, dev, tf_kind)
+    if field_kind == _lib.FIELD_PHASE and not t.is_complex():
+        x = _phase_samples(t)
+        if x.requires_grad and torch.is_grad_enabled():
+            return _PropagatePhase.apply(x, geom)
+        b, c, h, w = x.shape
+        return _plan_for(h, w, 2 * c, wl, dx, dy, z, b, dev, tf_kind).simulate_phase(x)[0]
     if t.requires_grad and torch.is_grad_enabled():
         return _Propagate.apply(t, geom)
     if t.is_complex():
@@ -376,6 +413,32 @@ class _Intensity(torch.autograd.Function):
         return grad.to(ctx.in_dtype), None, None, None
 
 
+class _IntensityPhase(torch.autograd.Function):
+    """x -> I = mean_p |A exp(i pi x_p)|^2 per colour group, x float32 [B, C, H, W]: one
+    hbx_evaluate_phase that leaves the field F and I.  Backward: one hbx_phase_backward of F on
+    the plan for -z with (2 / P) gI applied in the first pass's load and dL/dx out of the last
+    pass.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, x, geom, groups):
+        wls, dx, dy, z, dev, tf_kind = geom
+        b, c, h, w = x.shape
+        ctx.geom, ctx.groups = geom, groups
+        field, inten, _, _ = _plan_for(h, w, 2 * c // groups, wls, dx, dy, z, b, dev, tf_kind).evaluate_phase(x)
+        ctx.save_for_backward(field, x)
+        return inten
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        wls, dx, dy, z, dev, tf_kind = ctx.geom
+        field, x = ctx.saved_tensors
+        b, c, h, w = x.shape
+        gi = grad_output.to(torch.float32).resolve_neg().contiguous()
+        adj = _plan_for(h, w, 2 * c // ctx.groups, wls, dx, dy, -z, b, dev, tf_kind)
+        return adj.phase_backward(field, x, weight=gi, scale=2.0 / (c // ctx.groups)), None, None
+
+
 def intensity(x, z: float, tf="asm", field="amplitude", save_field: bool = True) -> torch.Tensor:
     """Plane-mean intensity of the propagated field, the quantity every loss of the project goes
     through: float32 [B, G, H, W] (or [G, H, W] for a 3-D x) with
@@ -391,8 +454,9 @@ def intensity(x, z: float, tf="asm", field="amplitude", save_field: bool = True)
     odd C is padded with a zero plane and the mean is still over the C planes given.
 
     Without a gradient request no graph is built: real x goes through hbx_intensity_real, which
-    writes the intensity and no field; complex x, or field="phase" on real x (u = exp(i pi x),
-    formed with torch ops), through hbx_simulate_complex, with |.|^2 and the mean as torch ops.
+    writes the intensity and no field; complex x through hbx_simulate_complex, with |.|^2 and the
+    mean as torch ops; field="phase" on real x (u = exp(i pi x)) through hbx_evaluate_phase, which
+    writes the intensity and no field.
     If x requires grad the result carries a grad_fn whose backward pass is ONE
     hbx_simulate_complex_weighted on the plan for -z: the saved field is read with (2 / P) times
     the incoming gradient applied in the first pass's load, and a real x receives the real part
@@ -400,7 +464,9 @@ def intensity(x, z: float, tf="asm", field="amplitude", save_field: bool = True)
     last pass accumulates beside the field (hbx_simulate_real, one launch set).
     save_field=True keeps the complex field for the backward pass (8 bytes per pixel and plane);
     save_field=False (real x) keeps only x, writes no field in the forward pass and recomputes it
-    at the start of the backward pass.  No double backward."""
+    at the start of the backward pass.  field="phase" with a gradient request: the forward is one
+    hbx_evaluate_phase (field and intensity), the backward one hbx_phase_backward, which writes
+    dL/dx itself; the field is always saved.  No double backward."""
     tf_kind = _switch(tf, _TF_NAMES, "tf")
     field_kind = _switch(field, _FIELD_NAMES, "field")
     meta = _meta_of(x)
@@ -430,12 +496,16 @@ def intensity(x, z: float, tf="asm", field="amplitude", save_field: bool = True)
     else:
         dev = torch.cuda.current_device()
         t = t.to(f"cuda:{dev}")
-    if field_kind == _lib.FIELD_PHASE:
-        ph = t.to(torch.float32) * np.float32(np.pi)
-        t = torch.complex(torch.cos(ph), torch.sin(ph))   # torch ops: autograd carries du/dx
     geom = (wls, dx, dy, z, dev, tf_kind)
     b, _, h, w = t.shape
-    if t.requires_grad and torch.is_grad_enabled():
+    if field_kind == _lib.FIELD_PHASE:
+        xs = _phase_samples(t)
+        if xs.requires_grad and torch.is_grad_enabled():
+            out = _IntensityPhase.apply(xs, geom, groups)
+        else:
+            plan = _plan_for(h, w, 2 * c // groups, wls, dx, dy, z, b, dev, tf_kind)
+            out = plan.evaluate_phase(xs, want_field=False)[1]
+    elif t.requires_grad and torch.is_grad_enabled():
         out = _Intensity.apply(t, geom, groups, bool(save_field))
     elif t.is_complex():
         plan = _plan_for(h, w, 2 * c // groups, wls, dx, dy, z, b, dev, tf_kind)
@@ -453,13 +523,16 @@ def intensity(x, z: float, tf="asm", field="amplitude", save_field: bool = True)
 _METRIC_NAMES = {"mse": _lib.LOSS_MSE, "psnr": _lib.LOSS_PSNR}
 
 
-def _evaluate(t: torch.Tensor, target: torch.Tensor, geom, groups: int, want_field: bool):
+def _evaluate(t: torch.Tensor, target: torch.Tensor, geom, groups: int, want_field: bool, phase: bool = False):
     """One launch set on a device tensor [B, C, H, W] (real: hbx_evaluate_real, complex:
-    hbx_evaluate_complex) -> (plan, field | None, intensity | None, chan_stats); the intensity is
-    written only beside the field (the backward pass reads both)."""
+    hbx_evaluate_complex, phase samples: hbx_evaluate_phase) -> (plan, field | None, intensity |
+    None, chan_stats); the intensity is written only beside the field (the backward pass reads both)."""
     wls, dx, dy, z, dev, tf_kind = geom
     b, c, h, w = t.shape
-    if t.is_complex():
+    if phase:
+        plan = _plan_for(h, w, 2 * c // groups, wls, dx, dy, z, b, dev, tf_kind)
+        field, inten, stats, _ = plan.evaluate_phase(t, target, want_field=want_field, want_intensity=want_field)
+    elif t.is_complex():
         plan = _plan_for(h, w, 2 * c // groups, wls, dx, dy, z, b, dev, tf_kind)
         field, inten, stats, _ = plan.evaluate_complex(
             t.to(torch.complex64).resolve_conj().resolve_neg().contiguous(), target, want_field=want_field,
@@ -476,15 +549,16 @@ class _Loss(torch.autograd.Function):
     forward pass is one launch set that leaves the field F = A u, I and the statistics; with
     w = gL dL/dI = a I + c T (hbx_loss_weight: a, c per env from the statistics and the incoming
     gradient gL), dL/du = A^H((2 / P) w F): one hbx_simulate_complex_weighted of F on the plan for -z,
-    as tt.intensity's backward pass.  A real u receives the real part, a complex u the field.  No
-    double backward."""
+    as tt.intensity's backward pass.  A real u receives the real part, a complex u the field.
+    phase: t holds float32 phase samples x, u = exp(i pi x) (hbx_evaluate_phase), and the backward's
+    launch set is hbx_phase_backward, whose last pass writes dL/dx.  No double backward."""
 
     @staticmethod
-    def forward(ctx, t, target, geom, groups, kind, rel):
-        ctx.geom, ctx.groups, ctx.kind, ctx.rel = geom, groups, kind, rel
+    def forward(ctx, t, target, geom, groups, kind, rel, phase=False):
+        ctx.geom, ctx.groups, ctx.kind, ctx.rel, ctx.phase = geom, groups, kind, rel, phase
         ctx.in_dtype, ctx.planes = t.dtype, t.shape[1]
-        plan, field, inten, stats = _evaluate(t, target, geom, groups, True)
-        ctx.save_for_backward(field, inten, stats, target)
+        plan, field, inten, stats = _evaluate(t, target, geom, groups, True, phase)
+        ctx.save_for_backward(field, inten, stats, target, *((t,) if phase else ()))
         return plan.loss(stats, kind, rel)
 
     @staticmethod
@@ -492,15 +566,18 @@ class _Loss(torch.autograd.Function):
     def backward(ctx, grad_output):
         wls, dx, dy, z, dev, tf_kind = ctx.geom
         groups, c = ctx.groups, ctx.planes
-        field, inten, stats, target = ctx.saved_tensors
+        field, inten, stats, target = ctx.saved_tensors[:4]
         b, cf, h, w = field.shape
         cplx = ctx.in_dtype.is_complex
         adj = _plan_for(h, w, 2 * cf // groups, wls, dx, dy, -z, b, dev, tf_kind)
         gl = grad_output.to(torch.float64).resolve_neg().contiguous()
         wgt = adj.loss_weight(inten, target, stats, gl, ctx.kind, ctx.rel)   # the plan's G and N only
+        if ctx.phase:
+            grad = adj.phase_backward(field, ctx.saved_tensors[4], weight=wgt, scale=2.0 / (c // groups))
+            return grad, None, None, None, None, None, None
         gf, gr = adj.simulate_complex(field, want_field=cplx, want_real=not cplx, weight=wgt,
                                       scale=2.0 / (c // groups))
-        return (gf if cplx else gr).to(ctx.in_dtype), None, None, None, None, None
+        return (gf if cplx else gr).to(ctx.in_dtype), None, None, None, None, None, None
 
 
 def loss(x, target, z: float, metric="mse", rel_scale="lsq", tf="asm", field="amplitude") -> torch.Tensor:
@@ -523,8 +600,10 @@ def loss(x, target, z: float, metric="mse", rel_scale="lsq", tf="asm", field="am
     x requires grad the result carries a grad_fn: the forward pass also writes the field and the
     intensity, and the backward pass is hbx_loss_weight (the loss's gradient with respect to the
     intensity, a I + c T per env) followed by one hbx_simulate_complex_weighted on the plan for
-    -z.  A real x receives the real part, a complex x the field; field="phase" forms u =
-    exp(i pi x) with torch ops, which carry du/dx.  No double backward."""
+    -z.  A real x receives the real part, a complex x the field.  field="phase": the first pass
+    forms u = exp(i pi x) as it loads x (hbx_evaluate_phase), and the backward's launch set is
+    hbx_phase_backward, whose last pass writes dL/dx -- neither u nor the complex gradient is
+    written.  No double backward."""
     kind = _switch(metric, _METRIC_NAMES, "metric")
     rel = _switch(rel_scale, _REL_NAMES, "rel_scale")
     tf_kind = _switch(tf, _TF_NAMES, "tf")
@@ -562,14 +641,14 @@ def loss(x, target, z: float, metric="mse", rel_scale="lsq", tf="asm", field="am
         dev = torch.cuda.current_device()
         t = t.to(f"cuda:{dev}")
     tg = tg.to(device=t.device, dtype=torch.float32).contiguous()
-    if field_kind == _lib.FIELD_PHASE:
-        ph = t.to(torch.float32) * np.float32(np.pi)
-        t = torch.complex(torch.cos(ph), torch.sin(ph))   # torch ops: autograd carries du/dx
+    phase = field_kind == _lib.FIELD_PHASE
+    if phase:
+        t = _phase_samples(t)
     geom = (wls, dx, dy, z, dev, tf_kind)
     if t.requires_grad and torch.is_grad_enabled():
-        out = _Loss.apply(t, tg, geom, groups, kind, rel)
+        out = _Loss.apply(t, tg, geom, groups, kind, rel, phase)
     else:
-        plan, _, _, stats = _evaluate(t, tg, geom, groups, False)
+        plan, _, _, stats = _evaluate(t, tg, geom, groups, False, phase)
         out = plan.loss(stats, kind, rel)
     return out[0] if squeeze else out
 

@@ -341,6 +341,44 @@ int hbx_loss_weight(hbx_plan_t plan, const float* intensity, const float* target
                     const double* chan_stats, const double* grad_loss, int32_t n_env, int32_t kind,
                     int32_t rel_scale, float* weight, void* stream);
 
+/* (ABI v15, additive) Phase holograms: the leaf is the phase, u = exp(i pi x).
+ *   phase[B][G*P/2][H][W] float32 samples x, one per pixel of the plan's P/2 complex planes per
+ *   group; the phase is pi x, so x = 1 is half a turn and x and x + 2 are the same field.
+ * The first pass forms (cos pi x, sin pi x) as it loads x -- 4 N^2 bytes read per complex plane
+ * instead of 8 N^2, and no complex copy of the hologram is ever written -- with the argument
+ * reduced exactly (x mod 2 has no rounding in float32; x * float32(pi) has), so the field's error
+ * does not grow with |x|: unwrapped phases of thousands of turns are as good as wrapped ones.
+ *
+ * hbx_simulate_phase: field, real_part and every rule are hbx_simulate_complex's (at least one of
+ *   the two non-null; null phase: HBX_ERR_INVALID).
+ * hbx_evaluate_phase: field, intensity, chan_stats, psnr, their null-ability and the target /
+ *   chan_stats pairing are hbx_evaluate_complex's; only the first pass differs, and a written field
+ *   equals hbx_simulate_phase's bit for bit.
+ * hbx_phase_backward: the whole backward pass of a phase leaf, on the plan for -z.
+ *   values    [B][G*P/2][H][W][2] complex64, the gradient with respect to the propagated field (or,
+ *             with weight, the saved field itself)
+ *   weight    [B][G][H][W] float32, nullable: with it the first pass is
+ *             hbx_simulate_complex_weighted's (scale * weight applied on load); null: it is
+ *             hbx_simulate_complex's, scale is ignored and the samples are used as they are
+ *   phase     the leaf's samples x, as above
+ *   grad_phase[B][G*P/2][H][W] float32 = pi (Im g cos pi x - Re g sin pi x), g the complex plane
+ *             those two calls would write as field: Re(conj(du/dx) g) with du/dx = i pi u.
+ *   The last pass reads x (4 N^2 bytes) and writes the one float (4 N^2) where the complex call
+ *   stores g (8 N^2); g itself is never written.  With the saved field as values, hbx_loss_weight's
+ *   output (or the incoming intensity gradient) as weight and scale = 2 / (P/2), grad_phase is
+ *   dL/dx.  Null values, phase or grad_phase: HBX_ERR_INVALID.
+ * Chunking by max_jobs, n_env (0: OK, < 0: HBX_ERR_INVALID), HBX_PRECISION_F32 only (else
+ * HBX_ERR_UNSUPPORTED), the four built sizes and the pass-timer slots are hbx_simulate_complex's.
+ * No env, DBS, plane-cache or incremental mode runs on phase samples (the binary phase mask,
+ * HBX_FIELD_PHASE on bits, is the bit path and is not this). */
+int hbx_simulate_phase(hbx_plan_t plan, const float* phase, int32_t n_env, float* field,
+                       float* real_part, void* stream);
+int hbx_evaluate_phase(hbx_plan_t plan, const float* phase, const float* target, int32_t n_env,
+                       float* field, float* intensity, double* chan_stats, double* psnr,
+                       void* stream);
+int hbx_phase_backward(hbx_plan_t plan, const float* values, const float* weight, float scale,
+                       const float* phase, int32_t n_env, float* grad_phase, void* stream);
+
 /* PSNR from per-channel statistics (tt.relativeLoss(.., tm.get_PSNR),
  * env.py:174): chan_stats[B][G][3] -> psnr[B]. */
 int hbx_psnr(hbx_plan_t plan, const double* chan_stats, int32_t n_env, double* psnr,
