@@ -456,6 +456,8 @@ struct FullRequest {
   // complex samples [n][G*P/2][N][N] complex64, optionally times scale * weight[n][G][N][N]
   const uint64_t* mask = nullptr;
   const float* real_values = nullptr;
+  bool binarize = false;               // real input (hbx_evaluate_threshold): u = va + vb [x >= threshold]
+  float threshold = 0.0f;
   const float2* complex_values = nullptr;
   const float* weight = nullptr;
   float scale = 1.0f;
@@ -475,6 +477,9 @@ struct FullRequest {
   // complex input (hbx_phase_backward): the last pass's phase-gradient form, both or neither
   const float* grad_samples = nullptr; // [n][G*P/2][N][N] f32 phase samples x of the leaf
   float* grad_phase = nullptr;         // [n][G*P/2][N][N] f32 dL/dx
+  // (hbx_threshold_backward) grad_samples is a binary hologram's real leaf: hbx::kGradSteWindow / kGradSteSigmoid
+  int grad_kind = hbx::kGradPhase;
+  float grad_p0 = 0.0f, grad_p1 = 0.0f;
   // plane cache (ABI v9): identity slots, then every plane's |U|^2 into its slot
   float* plane_pool = nullptr;
   int32_t* plane_slot = nullptr;
@@ -523,6 +528,8 @@ int propagate_full(hbx_plan_t p, const FullRequest& r, void* stream) {
     c.n_jobs = n * G;
     c.mask = at(r.mask, s_mask);
     c.real_values = at(r.real_values, s_real);
+    c.real_binarize = r.binarize;
+    c.real_threshold = r.threshold;
     c.complex_values = at(r.complex_values, s_cplx);
     c.complex_weight = at(r.weight, s_img);
     c.complex_scale = r.scale;
@@ -535,6 +542,9 @@ int propagate_full(hbx_plan_t p, const FullRequest& r, void* stream) {
     c.complex_stats = r.complex_stats;
     c.grad_samples = at(r.grad_samples, s_cplx);
     c.grad_phase = at(r.grad_phase, s_cplx);
+    c.grad_kind = r.grad_kind;
+    c.grad_p0 = r.grad_p0;
+    c.grad_p1 = r.grad_p1;
     if (r.plane_pool) {
       c.plane_mode = hbx::kPlanesFill;
       c.plane_spares = r.spares;
@@ -696,6 +706,41 @@ int hbx_phase_backward(hbx_plan_t p, const float* values, const float* weight, f
   r.complex_values = reinterpret_cast<const float2*>(values); r.weight = weight; r.n = n_env;
   if (weight) r.scale = scale;
   r.grad_samples = phase; r.grad_phase = grad_phase;
+  return propagate_full(p, r, stream);
+}
+
+// hbx_evaluate_real with u = va + vb [values >= threshold] formed by the first pass; any subset of the
+// outputs (field alone: hbx_simulate_real's launch set, intensity alone: hbx_intensity_real's)
+int hbx_evaluate_threshold(hbx_plan_t p, const float* values, float threshold, const float* target, int32_t n_env,
+                           float* field, float* intensity, double* chan_stats, double* psnr, void* stream) {
+  HBX_ENTER(p, n_env, "n_env");
+  if (!values) return fail(HBX_ERR_INVALID, "null buffer");
+  if ((target == nullptr) != (chan_stats == nullptr))
+    return fail(HBX_ERR_INVALID, "target and chan_stats are given together or not at all");
+  if (!target && psnr) return fail(HBX_ERR_INVALID, "without a target there is no psnr");
+  if (!field && !intensity && !chan_stats) return fail(HBX_ERR_INVALID, "no output: field, intensity or chan_stats");
+  if (int rc = check_real_plan(p)) return rc;
+  FullRequest r;
+  r.real_values = values; r.binarize = true; r.threshold = threshold; r.target = target; r.n = n_env;
+  r.field = reinterpret_cast<float2*>(field); r.intensity = intensity; r.chan_stats = chan_stats; r.psnr = psnr;
+  return propagate_full(p, r, stream);
+}
+
+// hbx_phase_backward's launch set with the straight-through last pass: vb s(samples) Re g
+int hbx_threshold_backward(hbx_plan_t p, const float* values, const float* weight, float scale, const float* samples,
+                           int32_t surrogate, float p0, float p1, int32_t n_env, float* grad, void* stream) {
+  HBX_ENTER(p, n_env, "n_env");
+  if (!values || !samples || !grad) return fail(HBX_ERR_INVALID, "null buffer");
+  if (surrogate != HBX_STE_WINDOW && surrogate != HBX_STE_SIGMOID)
+    return fail(HBX_ERR_INVALID, "surrogate: HBX_STE_WINDOW or HBX_STE_SIGMOID");
+  if (surrogate == HBX_STE_SIGMOID && !(p1 > 0.0f)) return fail(HBX_ERR_INVALID, "HBX_STE_SIGMOID: p1 (the slope k) > 0");
+  if (int rc = check_real_plan(p, true)) return rc;
+  FullRequest r;
+  r.complex_values = reinterpret_cast<const float2*>(values); r.weight = weight; r.n = n_env;
+  if (weight) r.scale = scale;
+  r.grad_samples = samples; r.grad_phase = grad;
+  r.grad_kind = surrogate == HBX_STE_WINDOW ? hbx::kGradSteWindow : hbx::kGradSteSigmoid;
+  r.grad_p0 = p0; r.grad_p1 = p1;
   return propagate_full(p, r, stream);
 }
 

@@ -190,6 +190,12 @@ struct PlanDev {
 //                 |U|^2 go to the env's two spare slots (swapped in on accept)
 constexpr int kPlanesOff = 0, kPlanesFill = 1, kPlanesStep = 2;
 
+// What the complex last passes (k_rowinv_d_cplx, k_rowinv_cplx, k_rowinv896_cplx) write: the plane
+// (field, real part, statistics: kGradNone), or a real leaf's gradient instead of it --
+// phase_grad_row, or ste_grad_row with one of the two surrogate derivatives (hbx_rowcol.hpp).
+// PassCall::grad_kind is one of the last three
+constexpr int kGradNone = 0, kGradPhase = 1, kGradSteWindow = 2, kGradSteSigmoid = 3;
+
 // One three-pass propagation (run_jobs): everything a launch needs beyond the plan.  A call site
 // names what it sets; check_pass_call states which combinations mean something.
 struct PassCall {
@@ -201,6 +207,11 @@ struct PassCall {
   // the mask bits (u = value; va / vb are not applied).  f32 intermediates, no plane cache, no
   // actions, no walk ...
   const float* real_values = nullptr;
+  // (ABI v15, additive) hbx_evaluate_threshold: 1 with real_values = the samples are the real leaf of a
+  // binary hologram, and the first pass propagates u = va + vb [x >= real_threshold] (NaN: the bit is
+  // off), formed as it loads x.  Everything behind the load is real_values' path
+  int real_binarize = 0;
+  float real_threshold = 0.0f;
   // ... or (ABI v15, additive) a complex field (hbx_simulate_complex): [env][G*P/2][N][N] complex64
   // samples the first pass reads, complex plane q into plane-pair slot q; the last pass recombines
   // each pair and writes complex_field [env][G*P/2][N][N] complex64 and / or real_part
@@ -239,6 +250,13 @@ struct PassCall {
   // Re g sin pi x) and nothing else: no complex_field, real_part or complex_stats
   const float* grad_samples = nullptr;
   float* grad_phase = nullptr;
+  // (ABI v15, additive) hbx_threshold_backward: which gradient the pair above asks for.  kGradPhase is
+  // the one just described.  kGradSteWindow / kGradSteSigmoid: grad_samples is the real leaf x of a
+  // binary hologram u = va + vb [x >= thr], and grad_phase = vb s(x) Re g with the surrogate derivative
+  // s = [grad_p0 <= x <= grad_p1], or s = k sg (1 - sg), sg = sigmoid(k (x - grad_p0)), k = grad_p1 > 0.
+  // Any other kind than kGradPhase only with the pair
+  int grad_kind = kGradPhase;
+  float grad_p0 = 0.0f, grad_p1 = 0.0f;
   // the plane cache (kPlanes* above)
   int plane_mode = kPlanesOff;
   float* plane_pool = nullptr;          // [env][CH + 2S][N][N] f32 per-plane |U|^2 (env ids as the jobs carry them)
@@ -284,8 +302,12 @@ inline hipError_t check_pass_call(const PlanDev& pd, const PassCall& c) {
                               : !complex_out && !grad_out);
   // ... or the phase gradient alone, from its samples
   ok = ok && (!grad_out || (c.grad_samples && c.grad_phase && !complex_out && !c.target && !c.inten_out));
-  // the weight rides on the complex load
+  // its kind: the phase form unless the pair is there; the sigmoid's slope is positive (NaN is not)
+  ok = ok && (c.grad_kind == kGradPhase ||
+              (grad_out && (c.grad_kind == kGradSteWindow || (c.grad_kind == kGradSteSigmoid && c.grad_p1 > 0.0f))));
+  // the weight rides on the complex load, the threshold on the real one
   ok = ok && (c.complex_values || !c.complex_weight);
+  ok = ok && (c.real_values || !c.real_binarize);
   return ok ? hipSuccess : hipErrorInvalidValue;
 }
 // The target rows the last pass reads.  No target: the plan's zero row, every row offset masked to 0

@@ -34,7 +34,8 @@
 //             (complex fields: k_rowinv_d_cplx / k_rowinv_cplx add B planes 2q and i * 2q + 1 on load,
 //             one IFFT per complex plane, and store the field / its real part; their statistics
 //             form, hbx_evaluate_complex, also sums |F_q|^2 and ends in the same plane mean and partials;
-//             their gradient form, hbx_phase_backward, stores dL/dx of a phase leaf instead of the plane)
+//             their gradient forms, hbx_phase_backward and hbx_threshold_backward, store dL/dx of a
+//             phase leaf or of a binary hologram's real leaf instead of the plane)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -459,11 +460,15 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd32(const JobDesc* jobs,
 // block would be a second v (64 VGPRs at N = 1024), which does not fit three workgroups per
 // CU; the co-resident workgroups cover each other's loads instead.  This is the
 // bit kernels' RIT = 1 form with another load, at every launch size (no small / large switch).
-template <int R, int NT>
+// LK = kLoadThreshold (hbx_evaluate_threshold): threshold_load_row turns each sample into the field of
+// its mask bit, hi where x >= thr and lo elsewhere, as it loads it; the registers, the tail and the
+// geometry are unchanged, and thr / lo / hi are unused without it.
+template <int R, int NT, int LK = kLoadReal>
 __global__ __launch_bounds__(NT, 512 / NT) void k_rowfwd_real(const JobDesc* __restrict__ jobs,
                                                         const float* __restrict__ values,
                                                         float2* __restrict__ ws_a,
-                                                        const float2* __restrict__ tw_glob, int P, int CH) {
+                                                        const float2* __restrict__ tw_glob, int P, int CH,
+                                                        float thr, float lo, float hi) {
   constexpr int N = R * R;
   constexpr int GPB = NT / R;          // rows per row block
   __shared__ float2 tw[N];
@@ -483,18 +488,25 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowfwd_real(const JobDesc* __r
   const int y0 = wg.rbw * GPB;
   const int y = y0 + grp;
   pk2 v[R];
-  real_load_row<R>(v, values + (((size_t)jb.env * CH + jb.group * P + pa) * N + y) * N, (size_t)N * N, t);
+  const float* row = values + (((size_t)jb.env * CH + jb.group * P + pa) * N + y) * N;
+  if constexpr (LK == kLoadThreshold)
+    threshold_load_row<R>(v, row, (size_t)N * N, t, thr, lo, hi);
+  else
+    real_load_row<R>(v, row, (size_t)N * N, t);
   __syncthreads();  // tw visible
 
   float2* base = ws_a + ((size_t)j * P + pa) * plane_a_elems(R);
   rowfwd_emit<R, NT, HBX_PRECISION_F32>(v, t, grp, lane_base, y0, lds, tw, base);
 }
 
-// N = 1024: k_rowfwd32's three workgroups per CU (split FFT tiles, one plane's tile at a time)
+// N = 1024: k_rowfwd32's three workgroups per CU (split FFT tiles, one plane's tile at a time;
+// kLoadThreshold: profiles/binary_ste/resource_usage.txt)
+template <int LK = kLoadReal>
 __global__ __launch_bounds__(256, 3) void k_rowfwd32_real(const JobDesc* __restrict__ jobs,
                                                           const float* __restrict__ values,
                                                           float2* __restrict__ ws_a,
-                                                          const float2* __restrict__ tw_glob, int P, int CH) {
+                                                          const float2* __restrict__ tw_glob, int P, int CH,
+                                                          float thr, float lo, float hi) {
   constexpr int R = 32, NT = 256, N = R * R;
   constexpr int GPB = NT / R;          // 8 rows per row block
   __shared__ float2 tw[N];
@@ -514,7 +526,11 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd32_real(const JobDesc* __restr
   const int y0 = wg.rbw * GPB;
   const int y = y0 + grp;
   pk2 v[R];
-  real_load_row<R>(v, values + (((size_t)jb.env * CH + jb.group * P + pa) * N + y) * N, (size_t)N * N, t);
+  const float* row = values + (((size_t)jb.env * CH + jb.group * P + pa) * N + y) * N;
+  if constexpr (LK == kLoadThreshold)
+    threshold_load_row<R>(v, row, (size_t)N * N, t, thr, lo, hi);
+  else
+    real_load_row<R>(v, row, (size_t)N * N, t);
   __syncthreads();  // tw visible
 
   float2* base = ws_a + ((size_t)j * P + pa) * plane_a_elems(R);
@@ -1015,17 +1031,21 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv(const JobDesc* __restri
 // k_rowinv's tail (rowinv_epilogue) runs with Q = P / 2 as the plane count: the plane-mean intensity
 // row to inten_out [job][N][N], the f64 partials against the target row (tmask = 0: the zero row).
 // field_out and real_out may then both be null.
-// PG (hbx_phase_backward; off by default, and the kernels without it compile as before): the plane out
-// of the inverse FFT is the gradient g with respect to the field u = exp(i pi x) of a phase leaf, and
-// the kernel writes grad[env][CH / 2][N][N] f32 = pi (Im g cos pi x - Re g sin pi x) from the samples
-// phase[env][CH / 2][N][N] (phase_grad_row) and nothing else: no complex field, no statistics.
+// GK = kGradPhase (hbx_phase_backward; kGradNone by default, and the kernels without it compile as
+// before): the plane out of the inverse FFT is the gradient g with respect to the field u = exp(i pi x)
+// of a phase leaf, and the kernel writes grad[env][CH / 2][N][N] f32 = pi (Im g cos pi x - Re g sin pi x)
+// from the samples phase[env][CH / 2][N][N] (phase_grad_row) and nothing else: no complex field, no
+// statistics.
+// GK = kGradSteWindow / kGradSteSigmoid (hbx_threshold_backward): the same geometry for a binary
+// hologram's real leaf x (in `phase`): grad = gvb s(x) Re g with the surrogate derivative s of
+// ste_grad_row and its parameters (ga, gb); gvb / ga / gb are unused by the other kinds.
 //
 // N = 1024 / 256: k_rowinv_d's direct loads from the tiled B (RowinvLanes).
 // Plane 2q + 1 arrives in two halves of R / 2 values that are folded into v as they land, so the
 // kernel never holds two whole lines (the second register set that cost k_rowinv_d its second
 // block per CU).  N = 256 has the registers for a second line and keeps the next pair in flight
 // under this one's FFT, as k_rowinv_d does with the next plane.
-template <int R, bool ST = false, bool PG = false>
+template <int R, bool ST = false, int GK = kGradNone>
 __global__ __launch_bounds__(256, 2) void k_rowinv_d_cplx(const JobDesc* __restrict__ jobs,
                                                           const float2* __restrict__ ws_b,
                                                           const float2* __restrict__ tw_glob, int P, int G,
@@ -1035,8 +1055,9 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_d_cplx(const JobDesc* __restr
                                                           double* __restrict__ partial,
                                                           float* __restrict__ inten_out,
                                                           const float* __restrict__ phase,
-                                                          float* __restrict__ grad) {
-  static_assert(!(ST && PG), "the gradient form runs no statistics");
+                                                          float* __restrict__ grad, float gvb, float ga,
+                                                          float gb) {
+  static_assert(!(ST && GK != kGradNone), "the gradient forms run no statistics");
   constexpr int N = R * R, GPB = 256 / R, RB = N / GPB;
   __shared__ float2 tw[N];
   __shared__ float2 scratch[GPB * R * (R + 1)];
@@ -1072,8 +1093,11 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_d_cplx(const JobDesc* __restr
       for (int k = 0; k < R; ++k) acc[k] += fmaf(v[k].x, v[k].x, v[k].y * v[k].y);
     }
     const size_t row = row0 + (size_t)q * N * N;
-    if constexpr (PG) {   // the samples are loaded behind the FFT: R = 32 never holds a second line
+    if constexpr (GK == kGradPhase) {   // the samples are loaded behind the FFT: R = 32 never holds a second line
       phase_grad_row<R, R>(v, phase + row, grad + row);
+      return;
+    } else if constexpr (GK != kGradNone) {
+      ste_grad_row<R, R, GK>(v, phase + row, grad + row, gvb, ga, gb);
       return;
     }
     if (field_out) {
@@ -1114,7 +1138,7 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_d_cplx(const JobDesc* __restr
 
 // N = 64: k_rowinv's LDS tile transpose; both planes' shares of the tile are prefetched one pair
 // ahead and combined as they are written into the tile.
-template <int R, int NT, bool ST = false, bool PG = false>
+template <int R, int NT, bool ST = false, int GK = kGradNone>
 __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv_cplx(const JobDesc* __restrict__ jobs,
                                                         const float2* __restrict__ ws_b,
                                                         const float2* __restrict__ tw_glob, int P, int G,
@@ -1124,8 +1148,9 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv_cplx(const JobDesc* __r
                                                         double* __restrict__ partial,
                                                         float* __restrict__ inten_out,
                                                         const float* __restrict__ phase,
-                                                        float* __restrict__ grad) {
-  static_assert(!(ST && PG), "the gradient form runs no statistics");
+                                                        float* __restrict__ grad, float gvb, float ga,
+                                                        float gb) {
+  static_assert(!(ST && GK != kGradNone), "the gradient forms run no statistics");
   constexpr int N = R * R;
   constexpr int GPB = NT / R;          // rows per block
   constexpr int RB = N / GPB;
@@ -1193,8 +1218,11 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv_cplx(const JobDesc* __r
       for (int k = 0; k < R; ++k) acc[k] += fmaf(v[k].x, v[k].x, v[k].y * v[k].y);
     }
     const size_t row = row0 + (size_t)q * N * N;
-    if constexpr (PG) {
+    if constexpr (GK == kGradPhase) {
       phase_grad_row<R, R>(v, phase + row, grad + row);
+      continue;
+    } else if constexpr (GK != kGradNone) {
+      ste_grad_row<R, R, GK>(v, phase + row, grad + row, gvb, ga, gb);
       continue;
     }
     if (field_out) {
@@ -1390,11 +1418,14 @@ static hipError_t launch_passes(const PlanDev& pd, const PassCall& c, hipStream_
     launch_kernel(k, sample_blocks, NT, st, jobs, c.complex_values, pd.ws_a, pd.tw, P, CH, c.complex_weight,
                   c.complex_scale, c.phase_values);
   } else if (c.real_values) {
+    // the load kind: the samples as they are, or (hbx_evaluate_threshold) the field of the bit [x >= threshold]
+    const bool thr = c.real_binarize != 0;
     auto k = [&] {
-      if constexpr (R == 32) return k_rowfwd32_real;
-      else return k_rowfwd_real<R, NT>;
+      if constexpr (R == 32) return !thr ? k_rowfwd32_real<kLoadReal> : k_rowfwd32_real<kLoadThreshold>;
+      else return !thr ? k_rowfwd_real<R, NT, kLoadReal> : k_rowfwd_real<R, NT, kLoadThreshold>;
     }();
-    launch_kernel(k, sample_blocks, NT, st, jobs, c.real_values, pd.ws_a, pd.tw, P, CH);
+    launch_kernel(k, sample_blocks, NT, st, jobs, c.real_values, pd.ws_a, pd.tw, P, CH, c.real_threshold, pd.va,
+                  pd.va + pd.vb);
   } else {
     auto k = [&] {
       if constexpr (R == 32) return small ? k_rowfwd32<SK, 1> : k_rowfwd32<SK>;
@@ -1421,16 +1452,24 @@ static hipError_t launch_passes(const PlanDev& pd, const PassCall& c, hipStream_
   const unsigned blocks = (unsigned)n_jobs * kRowBlocks;
   if (tm) tm->begin(2, st);
   if (pass_complex(c)) {   // recombine each plane pair; ST (hbx_evaluate_complex): intensity and partials too;
-                           // PG (hbx_phase_backward): the phase gradient instead of the field
-    const bool stats = c.complex_stats != 0, pg = c.grad_phase != nullptr;
+                           // kGradPhase (hbx_phase_backward): the phase gradient instead of the field;
+    //                        kGradSte* (hbx_threshold_backward): a binary hologram's gated gradient
+    const bool stats = c.complex_stats != 0;
+    const int gk = c.grad_phase ? c.grad_kind : kGradNone;
     auto k = [&] {
       if constexpr (kTiledB<R>)
-        return !pg ? (stats ? k_rowinv_d_cplx<R, true> : k_rowinv_d_cplx<R>) : k_rowinv_d_cplx<R, false, true>;
+        return gk == kGradNone ? (stats ? k_rowinv_d_cplx<R, true> : k_rowinv_d_cplx<R>)
+               : gk == kGradPhase ? k_rowinv_d_cplx<R, false, kGradPhase>
+               : gk == kGradSteWindow ? k_rowinv_d_cplx<R, false, kGradSteWindow>
+                                      : k_rowinv_d_cplx<R, false, kGradSteSigmoid>;
       else
-        return !pg ? (stats ? k_rowinv_cplx<R, NT, true> : k_rowinv_cplx<R, NT>) : k_rowinv_cplx<R, NT, false, true>;
+        return gk == kGradNone ? (stats ? k_rowinv_cplx<R, NT, true> : k_rowinv_cplx<R, NT>)
+               : gk == kGradPhase ? k_rowinv_cplx<R, NT, false, kGradPhase>
+               : gk == kGradSteWindow ? k_rowinv_cplx<R, NT, false, kGradSteWindow>
+                                      : k_rowinv_cplx<R, NT, false, kGradSteSigmoid>;
     }();
     launch_kernel(k, blocks, NT, st, jobs, pd.ws_b, pd.tw, P, pd.G, c.complex_field, c.real_part, tg.rows, tg.mask,
-                  pd.partial, c.inten_out, c.grad_samples, c.grad_phase);
+                  pd.partial, c.inten_out, c.grad_samples, c.grad_phase, pd.vb, c.grad_p0, c.grad_p1);
   } else if constexpr (kTiledB<R>) {
     // WALK (r05): a plane-cache walk batch, the last workgroup decides.  LEAN (r06): the plain
     // FFT-mode launch (the headline), its own instantiation without the plane cache / field /

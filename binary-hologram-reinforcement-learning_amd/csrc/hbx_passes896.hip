@@ -219,11 +219,15 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd896(const JobDesc* __restrict_
 // of the row in planes pa, pb into the (re, im) of v[jj] and zeros above, and rowfwd896_emit --
 // k_rowfwd896's own FFT, split, tile and panel stores -- takes it from there.  One row block per
 // workgroup (no register room for a second row's samples at three workgroups per CU), in
-// blockIdx order; full propagations only.
+// blockIdx order; full propagations only.  LK = kLoadThreshold (hbx_evaluate_threshold):
+// threshold_load_row makes each of the 28 loaded samples hi where x >= thr and lo elsewhere; slots
+// >= 28 stay zero, not lo.  thr / lo / hi are unused by kLoadReal.
+template <int LK = kLoadReal>
 __global__ __launch_bounds__(256, 3) void k_rowfwd896_real(const JobDesc* __restrict__ jobs,
                                                            const float* __restrict__ values,
                                                            float2* __restrict__ ws_a,
-                                                           const float2* __restrict__ tw_glob, int P, int CH) {
+                                                           const float2* __restrict__ tw_glob, int P, int CH,
+                                                           float thr, float lo, float hi) {
   __shared__ float2 tw[kN];
   __shared__ __attribute__((aligned(16))) float lds[kRowfwd896Scr];
   stage_twiddles<kN, 256>(tw, tw_glob);
@@ -239,7 +243,11 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd896_real(const JobDesc* __rest
   const int y0 = wg.rbw * kGPB;
   const int y = y0 + grp;
   float2 v[32];
-  real_load_row<kR, kL>(v, values + (((size_t)jb.env * CH + jb.group * P + pa) * kN + y) * kN, (size_t)kN * kN, t);
+  const float* row = values + (((size_t)jb.env * CH + jb.group * P + pa) * kN + y) * kN;
+  if constexpr (LK == kLoadThreshold)
+    threshold_load_row<kR, kL>(v, row, (size_t)kN * kN, t, thr, lo, hi);
+  else
+    real_load_row<kR, kL>(v, row, (size_t)kN * kN, t);
   __syncthreads();  // tw visible
 
   float2* base = ws_a + ((size_t)j * P + pa) * kPlaneA;
@@ -530,10 +538,12 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896(const JobDesc* __restrict_
 // accumulated per pixel as k_rowinv896 does and its tail runs with Q = P / 2 as the plane count --
 // the plane-mean intensity row to inten_out [job][896][896] and the f64 partials against the target
 // row; field_out and real_out may then both be null.
-// PG (hbx_phase_backward; off by default): the plane is the gradient with respect to u = exp(i pi x),
-// and grad[env][CH / 2][896][896] f32 = pi (Im g cos pi x - Re g sin pi x) from phase (same shape) is
-// the only output (phase_grad_row on the 28 pixels of a lane).
-template <bool ST = false, bool PG = false>
+// GK = kGradPhase (hbx_phase_backward; kGradNone by default): the plane is the gradient with respect to
+// u = exp(i pi x), and grad[env][CH / 2][896][896] f32 = pi (Im g cos pi x - Re g sin pi x) from phase
+// (same shape) is the only output (phase_grad_row on the 28 pixels of a lane).
+// GK = kGradSteWindow / kGradSteSigmoid (hbx_threshold_backward): grad = gvb s(x) Re g for the real
+// leaf x of a binary hologram (in `phase`), s and (ga, gb) as ste_grad_row has them.
+template <bool ST = false, int GK = kGradNone>
 __global__ __launch_bounds__(256, 2) void k_rowinv896_cplx(const JobDesc* __restrict__ jobs,
                                                            const float2* __restrict__ ws_b,
                                                            const float2* __restrict__ tw_glob, int P, int G,
@@ -543,8 +553,9 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896_cplx(const JobDesc* __rest
                                                            double* __restrict__ partial,
                                                            float* __restrict__ inten_out,
                                                            const float* __restrict__ phase,
-                                                           float* __restrict__ grad) {
-  static_assert(!(ST && PG), "the gradient form runs no statistics");
+                                                           float* __restrict__ grad, float gvb, float ga,
+                                                           float gb) {
+  static_assert(!(ST && GK != kGradNone), "the gradient forms run no statistics");
   __shared__ float2 tw[kN];
   __shared__ float2 scratch[kSCR];
   for (int i = threadIdx.x; i < kN; i += 256) tw[i] = tw_glob[i];
@@ -582,8 +593,10 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896_cplx(const JobDesc* __rest
       for (int k = 0; k < kL; ++k) acc[k] += fmaf(v[k].x, v[k].x, v[k].y * v[k].y);
     }
     const size_t row = row0 + (size_t)q * kN * kN;
-    if constexpr (PG) {
+    if constexpr (GK == kGradPhase) {
       phase_grad_row<kR, kL>(v, phase + row, grad + row);
+    } else if constexpr (GK != kGradNone) {
+      ste_grad_row<kR, kL, GK>(v, phase + row, grad + row, gvb, ga, gb);
     } else {
       if (field_out) {
 #pragma unroll
@@ -625,7 +638,9 @@ hipError_t run_jobs_896(const PlanDev& pd, const PassCall& c, hipStream_t st) {
                   blocks * (P / 2), 256, st, jobs, c.complex_values, pd.ws_a, pd.tw, P, CH, c.complex_weight,
                   c.complex_scale, c.phase_values);
   else if (c.real_values)
-    launch_kernel(k_rowfwd896_real, blocks * (P / 2), 256, st, jobs, c.real_values, pd.ws_a, pd.tw, P, CH);
+    // the load kind: the samples as they are, or (hbx_evaluate_threshold) the field of the bit [x >= threshold]
+    launch_kernel(!c.real_binarize ? k_rowfwd896_real<kLoadReal> : k_rowfwd896_real<kLoadThreshold>, blocks * (P / 2),
+                  256, st, jobs, c.real_values, pd.ws_a, pd.tw, P, CH, c.real_threshold, pd.va, pd.va + pd.vb);
   else
     launch_kernel(k_rowfwd896, blocks / kRit896 * (pair ? 1 : P / 2), 256, st, jobs,
                   reinterpret_cast<const uint32_t*>(c.mask), pd.ws_a, pd.tw, P, CH, pd.va, pd.vb, pair);
@@ -638,11 +653,15 @@ hipError_t run_jobs_896(const PlanDev& pd, const PassCall& c, hipStream_t st) {
 
   if (tm) tm->begin(2, st);
   if (pass_complex(c)) {   // recombine each plane pair; ST (hbx_evaluate_complex): intensity and partials too;
-                           // PG (hbx_phase_backward): the phase gradient instead of the field
-    launch_kernel(!c.grad_phase ? (c.complex_stats ? k_rowinv896_cplx<true> : k_rowinv896_cplx<false>)
-                                : k_rowinv896_cplx<false, true>,
+                           // kGradPhase (hbx_phase_backward): the phase gradient instead of the field;
+                           // kGradSte* (hbx_threshold_backward): a binary hologram's gated gradient
+    const int gk = c.grad_phase ? c.grad_kind : kGradNone;
+    launch_kernel(gk == kGradNone ? (c.complex_stats ? k_rowinv896_cplx<true> : k_rowinv896_cplx<false>)
+                  : gk == kGradPhase ? k_rowinv896_cplx<false, kGradPhase>
+                  : gk == kGradSteWindow ? k_rowinv896_cplx<false, kGradSteWindow>
+                                         : k_rowinv896_cplx<false, kGradSteSigmoid>,
                   blocks, 256, st, jobs, pd.ws_b, pd.tw, P, pd.G, c.complex_field, c.real_part, tg.rows, tg.mask,
-                  pd.partial, c.inten_out, c.grad_samples, c.grad_phase);
+                  pd.partial, c.inten_out, c.grad_samples, c.grad_phase, pd.vb, c.grad_p0, c.grad_p1);
   } else {
     // (r06) the plain FFT-mode launch gets the lean instantiation (profiles/r06/rowinv896_lean_ab_r06i.txt)
     const bool lean = c.plane_mode == kPlanesOff && !c.field_out;

@@ -154,6 +154,30 @@ __device__ __forceinline__ void real_load_row(V (&v)[R], const float* __restrict
   for (int jj = L; jj < R; ++jj) v[jj] = V{0.f, 0.f};
 }
 
+// What the real first passes (k_rowfwd_real, k_rowfwd32_real, k_rowfwd896_real) load a row with:
+// real_load_row or threshold_load_row
+constexpr int kLoadReal = 0, kLoadThreshold = 1;
+
+// Binary holograms from a real leaf (hbx_evaluate_threshold): real_load_row's loads, in its order and
+// all issued before the first use, then each sample x becomes the field of its mask bit [x >= thr]:
+// hi = va + vb where the bit is set, lo = va where it is not -- NaN compares false and gives lo, as
+// HBX_PACK_THRESHOLD packs it.  v[L ..] = 0, not lo (N = 896: the padding is no sample).  The tail
+// then sees real_load_row's row of the materialised 0 / 1 (or 1 / -1) samples, which are never written.
+template <int R, int L = R, class V>
+__device__ __forceinline__ void threshold_load_row(V (&v)[R], const float* __restrict__ rowa, size_t plane, int t,
+                                                   float thr, float lo, float hi) {
+  const float* rowb = rowa + plane;
+  float a[L], b[L];
+#pragma unroll
+  for (int jj = 0; jj < L; ++jj) a[jj] = __builtin_nontemporal_load(rowa + t + R * jj);
+#pragma unroll
+  for (int jj = 0; jj < L; ++jj) b[jj] = __builtin_nontemporal_load(rowb + t + R * jj);
+#pragma unroll
+  for (int jj = 0; jj < L; ++jj) v[jj] = V{a[jj] >= thr ? hi : lo, b[jj] >= thr ? hi : lo};
+#pragma unroll
+  for (int jj = L; jj < R; ++jj) v[jj] = V{0.f, 0.f};
+}
+
 // Complex fields (hbx_simulate_complex): lane t loads the complex64 sample of pixel x = t + R jj,
 // jj < L, of the row at `row` straight into the (re, im) of v[jj] -- one 8-byte non-temporal load
 // per element, a coalesced 8 R-byte run per lane group and jj; v[L ..] = 0 (N = 896).  The row FFT
@@ -246,6 +270,36 @@ __device__ __forceinline__ void phase_grad_row(const V (&v)[NV], const float* __
     float c, s;
     phase_sincos(a[k], c, s);
     g0[R * k] = kPiF * fmaf(v[k].y, c, -(v[k].x * s));
+  }
+}
+
+// The last pass of a binary hologram's backward (hbx_threshold_backward): the leaf x is real, its
+// field u = va + vb [x >= thr], g = the inverse row FFT's output = dL/du, and the straight-through
+// estimator hands Re g to x through a surrogate derivative s(x) of the step:
+//   dL/dx = vb s(x) Re g,
+// one float32 per pixel to g0[R k] from the samples at p0 (phase_grad_row's geometry and loads: read
+// once, non-temporal, behind the FFT).
+//   kGradSteWindow  (a = lo, b = hi): s = 1 on lo <= x <= hi, else 0 -- a select, so a closed gate
+//                   stores +0.0f whatever g holds (inf, NaN), and a NaN sample closes it
+//   kGradSteSigmoid (a = thr, b = k > 0): s = k sg (1 - sg), sg = 1 / (1 + exp(-k (x - thr))), formed
+//                   as k e / (1 + e)^2 with e = exp(-|k (x - thr)|) <= 1: the same value without the
+//                   cancellation in 1 - sg, and no overflow for any x
+template <int R, int L, int GK, class V, int NV>
+__device__ __forceinline__ void ste_grad_row(const V (&v)[NV], const float* __restrict__ p0, float* __restrict__ g0,
+                                             float vb, float a, float b) {
+  static_assert(GK == kGradSteWindow || GK == kGradSteSigmoid, "a surrogate kind");
+  float x[L];
+#pragma unroll
+  for (int k = 0; k < L; ++k) x[k] = __builtin_nontemporal_load(p0 + R * k);
+#pragma unroll
+  for (int k = 0; k < L; ++k) {
+    if constexpr (GK == kGradSteWindow) {
+      g0[R * k] = (x[k] >= a && x[k] <= b) ? vb * v[k].x : 0.0f;
+    } else {
+      const float e = expf(-fabsf(b * (x[k] - a)));
+      const float d = 1.0f + e;
+      g0[R * k] = vb * (b * e / (d * d)) * v[k].x;
+    }
   }
 }
 

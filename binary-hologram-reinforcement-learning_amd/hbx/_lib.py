@@ -30,6 +30,7 @@ SRC_U8, SRC_F32, SRC_F64 = 0, 1, 2             # hbx_pack_mask / hbx_rel_stats v
 PACK_BINARY, PACK_THRESHOLD = 0, 1
 REL_WORKSPACE_DOUBLES = 3072
 LOSS_MSE, LOSS_PSNR = 0, 1                      # hbx_loss / hbx_loss_weight kinds
+STE_WINDOW, STE_SIGMOID = 0, 1                  # hbx_threshold_backward surrogates
 
 EXPORTED_SYMBOLS = (
     "hbx_abi_version", "hbx_last_error", "hbx_plan_create", "hbx_plan_destroy",
@@ -44,6 +45,7 @@ EXPORTED_SYMBOLS = (
     "hbx_simulate_complex_weighted", "hbx_intensity_real",
     "hbx_evaluate_real", "hbx_evaluate_complex", "hbx_loss", "hbx_loss_weight",
     "hbx_simulate_phase", "hbx_evaluate_phase", "hbx_phase_backward",
+    "hbx_evaluate_threshold", "hbx_threshold_backward",
 )
 NUM_PASSES = 5
 PASS_NAMES = ("k_rowfwd", "k_col", "k_rowinv", "k_psf_eval", "k_psf_commit")
@@ -140,6 +142,8 @@ def _declare(lib):
     lib.hbx_simulate_phase.argtypes = [VP, VP, I32, VP, VP, VP]
     lib.hbx_evaluate_phase.argtypes = [VP, VP, VP, I32, VP, VP, VP, VP, VP]
     lib.hbx_phase_backward.argtypes = [VP, VP, VP, C.c_float, VP, I32, VP, VP]
+    lib.hbx_evaluate_threshold.argtypes = [VP, VP, C.c_float, VP, I32, VP, VP, VP, VP, VP]
+    lib.hbx_threshold_backward.argtypes = [VP, VP, VP, C.c_float, VP, I32, C.c_float, C.c_float, I32, VP, VP]
     lib.hbx_loss.argtypes = [VP, VP, I32, I32, I32, VP, VP]
     lib.hbx_loss_weight.argtypes = [VP, VP, VP, VP, VP, I32, I32, I32, VP, VP]
     lib.hbx_flip_map.argtypes = [VP, VP, VP, VP, VP, VP]

@@ -8,6 +8,7 @@ batch of bit-packed masks at once, entirely on the device.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass, field
 from typing import Optional, Sequence
 
@@ -493,6 +494,60 @@ class Plan:
         grad = torch.empty(shape, dtype=torch.float32, device=self.device)
         _lib.check(self.lib.hbx_phase_backward(self._h, _ptr(values), _ptr(weight), float(scale), _ptr(phase), n,
                                                _ptr(grad), _stream(stream)), "hbx_phase_backward")
+        return grad
+
+    def evaluate_threshold(self, values: torch.Tensor, threshold: float, target: Optional[torch.Tensor] = None,
+                           want_field: bool = True, want_intensity: bool = True, stream=None):
+        """`evaluate_real` of the binary hologram m = [values >= threshold], u = va + vb m with the
+        plan's field_kind (hbx_evaluate_threshold): `values` float32 [B, CH, H, W] is the real leaf;
+        the first pass thresholds it as it loads it and no 0 / 1 copy is written.  Returns (field
+        complex64 [B, CH, H, W] | None, intensity | None, chan_stats | None, psnr | None), each
+        `evaluate_real`'s on the materialised samples bit for bit; chan_stats and psnr come with a
+        target.  At least one of want_field, want_intensity and target is needed."""
+        n = values.shape[0] if isinstance(values, torch.Tensor) and values.dim() else 0
+        c = self.cfg
+        _need(values, "values", torch.float32, self.values_shape(n), self.device)
+        values = values.resolve_neg()              # a lazily negated view shares the un-negated memory
+        if target is not None:
+            _need(target, "target", torch.float32, self.target_shape(n), self.device)
+        elif not (want_field or want_intensity):
+            raise ValueError("evaluate_threshold: no target, and want_field and want_intensity are both off")
+        field = torch.empty((n, c.channels, c.height, c.width, 2), dtype=torch.float32,
+                            device=self.device) if want_field else None
+        inten = torch.empty(self.target_shape(n), dtype=torch.float32, device=self.device) if want_intensity else None
+        stats = psnr = None
+        if target is not None:
+            stats = torch.empty((n, c.groups, 3), dtype=torch.float64, device=self.device)
+            psnr = torch.empty((n,), dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.hbx_evaluate_threshold(self._h, _ptr(values), float(threshold), _ptr(target), n,
+                                                   _ptr(field), _ptr(inten), _ptr(stats), _ptr(psnr),
+                                                   _stream(stream)), "hbx_evaluate_threshold")
+        return (torch.view_as_complex(field) if want_field else None), inten, stats, psnr
+
+    def threshold_backward(self, values: torch.Tensor, samples: torch.Tensor, weight: Optional[torch.Tensor] = None,
+                           scale: float = 1.0, surrogate: int = _lib.STE_WINDOW, p0: float = -math.inf,
+                           p1: float = math.inf, stream=None) -> torch.Tensor:
+        """The backward pass of a binary hologram's real leaf under the straight-through estimator,
+        on the plan for -z (hbx_threshold_backward): `values` complex64 [B, CH/2, H, W] and `weight`
+        / `scale` are `phase_backward`'s, `samples` float32 [B, CH/2, H, W] the leaf's samples x
+        (real plane q of the leaf is complex plane q here).  Returns float32 [B, CH/2, H, W] =
+        vb s(x) Re g, vb this plan's (1 or -2) and g the field `simulate_complex` would return --
+        which is not written.  STE_WINDOW: s = [p0 <= x <= p1] (the default is the plain estimator);
+        STE_SIGMOID: s = k sg (1 - sg), sg = sigmoid(k (x - p0)), k = p1 > 0."""
+        n = values.shape[0] if isinstance(values, torch.Tensor) and values.dim() else 0
+        c = self.cfg
+        shape = self.phase_shape(n)
+        _need(values, "values", torch.complex64, shape, self.device)
+        values = values.resolve_conj().resolve_neg()   # as simulate_complex: the kernel reads the memory
+        _need(samples, "samples", torch.float32, shape, self.device)
+        samples = samples.resolve_neg()
+        if weight is not None:
+            _need(weight, "weight", torch.float32, (n, c.groups, c.height, c.width), self.device)
+            weight = weight.resolve_neg()
+        grad = torch.empty(shape, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.hbx_threshold_backward(self._h, _ptr(values), _ptr(weight), float(scale), _ptr(samples),
+                                                   int(surrogate), float(p0), float(p1), n, _ptr(grad),
+                                                   _stream(stream)), "hbx_threshold_backward")
         return grad
 
     def loss(self, chan_stats: torch.Tensor, kind: int = _lib.LOSS_MSE, rel_scale: int = _lib.REL_LSQ,

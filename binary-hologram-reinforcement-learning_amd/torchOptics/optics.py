@@ -37,6 +37,12 @@ fallback on either):
   is a second workspace in the plan cache; there is no double backward; ``binary=True`` stays
   non-differentiable and builds no graph; ``relativeLoss(.., tm.get_PSNR)`` returns a float
   (its ``F.mse_loss`` form is torch ops and differentiates by itself).
+* ``threshold=tau`` on that path (``simulate``, ``intensity`` and ``loss``; real input only): x is
+  the leaf of the binary hologram m = [x >= tau], the field is the mask's (amplitude m, phase
+  1 - 2 m), thresholded by the first pass of hbx_evaluate_threshold as it loads x, and the
+  backward pass is the straight-through estimator: the last pass of hbx_threshold_backward
+  writes vb s(x) Re g with the surrogate derivative s chosen by ``ste`` / ``ste_width``.  No
+  0 / 1 copy of x is written in either direction.
 
 ``intensity`` returns the plane-mean intensity mean_p |A u_p|^2 per colour group -- what every loss
 of the project is built on -- on the continuous path: several wavelengths in one call, no field
@@ -175,8 +181,37 @@ def check_binary(device: Optional[int] = None):
         _raise_pending(sc)
 
 
+_STE_NAMES = {"window": _lib.STE_WINDOW, "sigmoid": _lib.STE_SIGMOID}
+
+
+def _ste_args(threshold, ste, ste_width, what: str):
+    """threshold / ste / ste_width of simulate, intensity and loss -> None without a threshold,
+    else (threshold, surrogate, p0, p1) as hbx_threshold_backward takes them, every number a
+    float32 value formed here: the window's ends are float32(tau - w) and float32(tau + w)
+    (w = inf: the plain straight-through estimator), the sigmoid's slope float32(1 / w)."""
+    if threshold is None:
+        return None
+    kind = _switch(ste, _STE_NAMES, "ste")
+    try:
+        tau, w = np.float32(threshold), np.float32(ste_width)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: threshold and ste_width are numbers, got {threshold!r}, {ste_width!r}") from None
+    if not np.isfinite(tau):
+        raise ValueError(f"{what}: threshold must be finite, got {threshold!r}")
+    if kind == _lib.STE_WINDOW:
+        if not w >= 0:
+            raise ValueError(f"{what}: ste_width must be >= 0 (math.inf: no window), got {ste_width!r}")
+        return float(tau), kind, float(np.float32(tau - w)), float(np.float32(tau + w))
+    if not (w > 0 and np.isfinite(w)):
+        raise ValueError(f"{what}: ste=\"sigmoid\" needs a finite ste_width > 0, got {ste_width!r}")
+    k = np.float32(1.0) / w
+    if not (k > 0 and np.isfinite(k)):
+        raise ValueError(f"{what}: 1 / ste_width is not a positive float32, got {ste_width!r}")
+    return float(tau), kind, float(tau), float(k)
+
+
 def simulate(x, z: float, strict: bool = False, binary: bool = True, tf="asm", field="amplitude",
-             **_) -> torch.Tensor:
+             threshold=None, ste="window", ste_width=0.5, **_) -> torch.Tensor:
     """Free-space propagation of a tensor [B, C, H, W] (or [C, H, W]) by z metres: the
     complex field of every plane, complex64, on the GPU.
 
@@ -194,9 +229,21 @@ def simulate(x, z: float, strict: bool = False, binary: bool = True, tf="asm", f
       real x,    field="phase":      u = exp(i pi x), formed by the first pass of hbx_simulate_phase
                                      (float64 is cast to float32; x and x + 2 are the same field).
     A complex plane takes the workspace of two real planes.  If x requires grad the result
-    carries a grad_fn and loss.backward() reaches x (module docstring); otherwise it has none."""
+    carries a grad_fn and loss.backward() reaches x (module docstring); otherwise it has none.
+
+    binary=False with threshold=tau: real x is the leaf of a binary hologram m = [x >= tau], and
+    the field is that of the mask, amplitude u = m or phase u = 1 - 2 m (what binary=True gives
+    for m), thresholded by the first pass of hbx_evaluate_threshold as it loads x -- no 0 / 1 copy
+    is written.  If x requires grad the backward pass is the straight-through estimator, one
+    hbx_threshold_backward on the plan for -z: dL/dx = vb s(x) Re(A^H g) with vb = 1 or -2 and
+    the surrogate derivative s of the step, ste="window": s = 1 on [tau - ste_width, tau +
+    ste_width] (math.inf: everywhere), else 0; ste="sigmoid": the derivative of
+    sigmoid((x - tau) / ste_width).  Complex x, or binary=True, with a threshold raises ValueError."""
     tf_kind = _switch(tf, _TF_NAMES, "tf")
     field_kind = _switch(field, _FIELD_NAMES, "field")
+    ste_args = _ste_args(threshold, ste, ste_width, "simulate")
+    if ste_args is not None and binary:
+        raise ValueError("simulate: threshold= binarizes a real leaf on the continuous path (binary=False)")
     meta = _meta_of(x)
     wl = meta["wl"]
     if isinstance(wl, (tuple, list)):
@@ -216,6 +263,8 @@ def simulate(x, z: float, strict: bool = False, binary: bool = True, tf="asm", f
             raise ValueError("tt.simulate (hbx) propagates binary {0,1} masks only, as the reference does")
         if field_kind != _lib.FIELD_AMPLITUDE:
             raise ValueError("tt.simulate: a complex field is used as it is (field=\"amplitude\")")
+        if ste_args is not None:
+            raise ValueError("tt.simulate: threshold= needs a real leaf, got a complex field")
     if not torch.cuda.is_available():
         raise RuntimeError("tt.simulate needs a ROCm GPU (libhbx.so)")
     if t.is_cuda:
@@ -223,6 +272,14 @@ def simulate(x, z: float, strict: bool = False, binary: bool = True, tf="asm", f
     else:
         dev = torch.cuda.current_device()
         t = t.to(f"cuda:{dev}")
+    if ste_args is not None:
+        xs = _phase_samples(t)
+        geom = (wl, dx, dy, z, dev, tf_kind)
+        if xs.requires_grad and torch.is_grad_enabled():
+            out = _PropagateThreshold.apply(xs, geom, field_kind, ste_args)
+        else:
+            out = _propagate_threshold(xs, geom, field_kind, ste_args[0])
+        return out[0] if squeeze else out
     if not binary:
         out = _simulate_continuous(t, wl, dx, dy, z, dev, tf_kind, field_kind)
         return out[0] if squeeze else out
@@ -323,6 +380,48 @@ class _PropagatePhase(torch.autograd.Function):
         b, c, h, w = x.shape
         g = grad_output.to(torch.complex64).resolve_conj().resolve_neg().contiguous()
         return _plan_for(h, w, 2 * c, wl, dx, dy, -z, b, dev, tf_kind).phase_backward(g, x), None
+
+
+def _propagate_threshold(x: torch.Tensor, geom, field_kind: int, tau: float) -> torch.Tensor:
+    """The field of the binary hologram [x >= tau] of float32 samples [B, C, H, W], every plane,
+    through hbx_evaluate_threshold; an odd C is padded with a plane that is sliced off again."""
+    wl, dx, dy, z, dev, tf_kind = geom
+    b, c, h, w = x.shape
+    cp = c + (c % 2)
+    plan = _plan_for(h, w, cp, wl, dx, dy, z, b, dev, tf_kind, field_kind)
+    out = plan.evaluate_threshold(_pad_real(x, cp), tau, want_intensity=False)[0]
+    return out[:, :c] if cp != c else out
+
+
+def _threshold_backward(values: torch.Tensor, x: torch.Tensor, geom, groups: int, field_kind: int, ste_args,
+                        weight: Optional[torch.Tensor] = None, scale: float = 1.0) -> torch.Tensor:
+    """One hbx_threshold_backward on the plan for -z with the leaf's field kind (its vb): values
+    complex64 and x float32, both [B, C, H, W] -- real plane q of the leaf is complex plane q of
+    that plan, so nothing is padded."""
+    wls, dx, dy, z, dev, tf_kind = geom
+    b, c, h, w = x.shape
+    _, kind, p0, p1 = ste_args
+    adj = _plan_for(h, w, 2 * c // groups, wls, dx, dy, -z, b, dev, tf_kind, field_kind)
+    return adj.threshold_backward(values, x, weight=weight, scale=scale, surrogate=kind, p0=p0, p1=p1)
+
+
+class _PropagateThreshold(torch.autograd.Function):
+    """x -> A (va + vb [x >= tau]) through hbx_evaluate_threshold, x float32 [B, C, H, W].
+    Backward, the straight-through estimator: one hbx_threshold_backward of grad_output on the plan
+    for -z, whose last pass writes vb s(x) Re(A^H g) from the saved samples.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, x, geom, field_kind, ste_args):
+        ctx.geom, ctx.field_kind, ctx.ste_args = geom, field_kind, ste_args
+        ctx.save_for_backward(x)
+        return _propagate_threshold(x, geom, field_kind, ste_args[0])
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        x, = ctx.saved_tensors
+        g = grad_output.to(torch.complex64).resolve_conj().resolve_neg().contiguous()
+        return _threshold_backward(g, x, ctx.geom, 1, ctx.field_kind, ctx.ste_args), None, None, None
 
 
 def _simulate_continuous(t: torch.Tensor, wl, dx, dy, z, dev: int, tf_kind: int, field_kind: int) -> torch.Tensor:
@@ -439,7 +538,34 @@ class _IntensityPhase(torch.autograd.Function):
         return adj.phase_backward(field, x, weight=gi, scale=2.0 / (c // ctx.groups)), None, None
 
 
-def intensity(x, z: float, tf="asm", field="amplitude", save_field: bool = True) -> torch.Tensor:
+class _IntensityThreshold(torch.autograd.Function):
+    """x -> I = mean_p |A (va + vb [x_p >= tau])|^2 per colour group, x float32 [B, C, H, W]: one
+    hbx_evaluate_threshold that leaves the field F and I.  Backward, the straight-through
+    estimator: one hbx_threshold_backward of F on the plan for -z with (2 / P) gI applied in the
+    first pass's load and vb s(x) Re(.) out of the last pass.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, x, geom, groups, field_kind, ste_args):
+        wls, dx, dy, z, dev, tf_kind = geom
+        b, c, h, w = x.shape
+        ctx.geom, ctx.groups, ctx.field_kind, ctx.ste_args = geom, groups, field_kind, ste_args
+        plan = _plan_for(h, w, c // groups, wls, dx, dy, z, b, dev, tf_kind, field_kind)
+        field, inten, _, _ = plan.evaluate_threshold(x, ste_args[0])
+        ctx.save_for_backward(field, x)
+        return inten
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        field, x = ctx.saved_tensors
+        gi = grad_output.to(torch.float32).resolve_neg().contiguous()
+        grad = _threshold_backward(field, x, ctx.geom, ctx.groups, ctx.field_kind, ctx.ste_args, weight=gi,
+                                   scale=2.0 / (x.shape[1] // ctx.groups))
+        return grad, None, None, None, None
+
+
+def intensity(x, z: float, tf="asm", field="amplitude", save_field: bool = True, threshold=None, ste="window",
+              ste_width=0.5) -> torch.Tensor:
     """Plane-mean intensity of the propagated field, the quantity every loss of the project goes
     through: float32 [B, G, H, W] (or [G, H, W] for a 3-D x) with
         I[b, g] = mean over the planes p of group g of |IFFT2(FFT2(u[b, p]) H_g(z))|^2,
@@ -466,9 +592,17 @@ def intensity(x, z: float, tf="asm", field="amplitude", save_field: bool = True)
     save_field=False (real x) keeps only x, writes no field in the forward pass and recomputes it
     at the start of the backward pass.  field="phase" with a gradient request: the forward is one
     hbx_evaluate_phase (field and intensity), the backward one hbx_phase_backward, which writes
-    dL/dx itself; the field is always saved.  No double backward."""
+    dL/dx itself; the field is always saved.  No double backward.
+
+    threshold=tau (real x only; complex x raises ValueError): x is the leaf of a binary hologram
+    m = [x >= tau] and I is the intensity of its field, amplitude u = m or phase u = 1 - 2 m,
+    through hbx_evaluate_threshold; ste and ste_width choose the straight-through backward pass
+    (hbx_threshold_backward) as in simulate.  C / G must be even: a padded plane would be
+    thresholded too, and its `off` value is 1, not 0, under field="phase".  The field is always
+    saved."""
     tf_kind = _switch(tf, _TF_NAMES, "tf")
     field_kind = _switch(field, _FIELD_NAMES, "field")
+    ste_args = _ste_args(threshold, ste, ste_width, "intensity")
     meta = _meta_of(x)
     wl = meta["wl"]
     wls = tuple(float(v) for v in wl) if isinstance(wl, (tuple, list)) else (float(wl),)
@@ -489,6 +623,11 @@ def intensity(x, z: float, tf="asm", field="amplitude", save_field: bool = True)
         raise ValueError(f"intensity: {groups} colour groups need an even number of planes each, got {c // groups}")
     if t.is_complex() and field_kind != _lib.FIELD_AMPLITUDE:
         raise ValueError("tt.intensity: a complex field is used as it is (field=\"amplitude\")")
+    if ste_args is not None:
+        if t.is_complex():
+            raise ValueError("tt.intensity: threshold= needs a real leaf, got a complex field")
+        if (c // groups) % 2:
+            raise ValueError(f"intensity: threshold= needs an even number of planes per colour group, got {c // groups}")
     if not torch.cuda.is_available():
         raise RuntimeError("tt.intensity needs a ROCm GPU (libhbx.so)")
     if t.is_cuda:
@@ -498,7 +637,14 @@ def intensity(x, z: float, tf="asm", field="amplitude", save_field: bool = True)
         t = t.to(f"cuda:{dev}")
     geom = (wls, dx, dy, z, dev, tf_kind)
     b, _, h, w = t.shape
-    if field_kind == _lib.FIELD_PHASE:
+    if ste_args is not None:
+        xs = _phase_samples(t)
+        if xs.requires_grad and torch.is_grad_enabled():
+            out = _IntensityThreshold.apply(xs, geom, groups, field_kind, ste_args)
+        else:
+            plan = _plan_for(h, w, c // groups, wls, dx, dy, z, b, dev, tf_kind, field_kind)
+            out = plan.evaluate_threshold(xs, ste_args[0], want_field=False)[1]
+    elif field_kind == _lib.FIELD_PHASE:
         xs = _phase_samples(t)
         if xs.requires_grad and torch.is_grad_enabled():
             out = _IntensityPhase.apply(xs, geom, groups)
@@ -580,7 +726,41 @@ class _Loss(torch.autograd.Function):
         return (gf if cplx else gr).to(ctx.in_dtype), None, None, None, None, None, None
 
 
-def loss(x, target, z: float, metric="mse", rel_scale="lsq", tf="asm", field="amplitude") -> torch.Tensor:
+class _LossThreshold(torch.autograd.Function):
+    """x -> the relative MSE or PSNR per env of I = mean_p |A (va + vb [x_p >= tau])|^2 against a
+    constant target, x float32 [B, C, H, W]: one hbx_evaluate_threshold that leaves the field, I
+    and the statistics.  Backward, the straight-through estimator: hbx_loss_weight as _Loss, then
+    one hbx_threshold_backward of the field on the plan for -z, whose last pass writes
+    vb s(x) Re(A^H((2 / P) w F)).  No double backward."""
+
+    @staticmethod
+    def forward(ctx, x, target, geom, groups, kind, rel, field_kind, ste_args):
+        wls, dx, dy, z, dev, tf_kind = geom
+        b, c, h, w = x.shape
+        ctx.geom, ctx.groups, ctx.kind, ctx.rel = geom, groups, kind, rel
+        ctx.field_kind, ctx.ste_args = field_kind, ste_args
+        plan = _plan_for(h, w, c // groups, wls, dx, dy, z, b, dev, tf_kind, field_kind)
+        field, inten, stats, _ = plan.evaluate_threshold(x, ste_args[0], target)
+        ctx.save_for_backward(field, inten, stats, target, x)
+        return plan.loss(stats, kind, rel)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        wls, dx, dy, z, dev, tf_kind = ctx.geom
+        field, inten, stats, target, x = ctx.saved_tensors
+        b, c, h, w = x.shape
+        groups = ctx.groups
+        adj = _plan_for(h, w, 2 * c // groups, wls, dx, dy, -z, b, dev, tf_kind, ctx.field_kind)
+        gl = grad_output.to(torch.float64).resolve_neg().contiguous()
+        wgt = adj.loss_weight(inten, target, stats, gl, ctx.kind, ctx.rel)   # the plan's G and N only
+        grad = _threshold_backward(field, x, ctx.geom, groups, ctx.field_kind, ctx.ste_args, weight=wgt,
+                                   scale=2.0 / (c // groups))
+        return grad, None, None, None, None, None, None, None
+
+
+def loss(x, target, z: float, metric="mse", rel_scale="lsq", tf="asm", field="amplitude", threshold=None,
+         ste="window", ste_width=0.5) -> torch.Tensor:
     """The relative loss of a continuous hologram against a target, one value per env, without
     leaving the HIP path and without a host wait: float64 [B] on the device (0-dim for a 3-D x),
         metric="mse"   what tt.relativeLoss(I[b], target[b], F.mse_loss) gives (env.py:131),
@@ -603,11 +783,20 @@ def loss(x, target, z: float, metric="mse", rel_scale="lsq", tf="asm", field="am
     -z.  A real x receives the real part, a complex x the field.  field="phase": the first pass
     forms u = exp(i pi x) as it loads x (hbx_evaluate_phase), and the backward's launch set is
     hbx_phase_backward, whose last pass writes dL/dx -- neither u nor the complex gradient is
-    written.  No double backward."""
+    written.  No double backward.
+
+    threshold=tau (real x only; complex x raises ValueError, and so does an odd C / G): the loss of
+    the binary hologram m = [x >= tau] itself -- the mask hbx.pack_mask(x, threshold=tau) hands to
+    the env, the DBS walk and the display -- with field="amplitude" u = m or field="phase"
+    u = 1 - 2 m, thresholded by the first pass of hbx_evaluate_threshold as it loads x.  If x
+    requires grad the backward pass is the straight-through estimator: hbx_loss_weight, then one
+    hbx_threshold_backward on the plan for -z, dL/dx = vb s(x) Re(A^H((2 / P) w F)) with ste and
+    ste_width as in simulate.  Neither a 0 / 1 copy of x nor the field's gradient is written."""
     kind = _switch(metric, _METRIC_NAMES, "metric")
     rel = _switch(rel_scale, _REL_NAMES, "rel_scale")
     tf_kind = _switch(tf, _TF_NAMES, "tf")
     field_kind = _switch(field, _FIELD_NAMES, "field")
+    ste_args = _ste_args(threshold, ste, ste_width, "loss")
     meta = _meta_of(x)
     wl = meta["wl"]
     wls = tuple(float(v) for v in wl) if isinstance(wl, (tuple, list)) else (float(wl),)
@@ -629,6 +818,11 @@ def loss(x, target, z: float, metric="mse", rel_scale="lsq", tf="asm", field="am
         raise ValueError("tt.loss: a complex field is used as it is (field=\"amplitude\")")
     if not t.is_complex() and field_kind == _lib.FIELD_AMPLITUDE and (c // groups) % 2:
         raise ValueError(f"loss: a real field needs an even number of planes per colour group, got {c // groups}")
+    if ste_args is not None:
+        if t.is_complex():
+            raise ValueError("tt.loss: threshold= needs a real leaf, got a complex field")
+        if (c // groups) % 2:
+            raise ValueError(f"loss: threshold= needs an even number of planes per colour group, got {c // groups}")
     if tg.requires_grad:
         raise ValueError("loss: the target is a constant (it requires grad)")
     if tg.is_complex() or tuple(tg.shape) != (b, groups, h, w):
@@ -641,10 +835,19 @@ def loss(x, target, z: float, metric="mse", rel_scale="lsq", tf="asm", field="am
         dev = torch.cuda.current_device()
         t = t.to(f"cuda:{dev}")
     tg = tg.to(device=t.device, dtype=torch.float32).contiguous()
+    geom = (wls, dx, dy, z, dev, tf_kind)
+    if ste_args is not None:
+        xs = _phase_samples(t)
+        if xs.requires_grad and torch.is_grad_enabled():
+            out = _LossThreshold.apply(xs, tg, geom, groups, kind, rel, field_kind, ste_args)
+        else:
+            plan = _plan_for(h, w, c // groups, wls, dx, dy, z, b, dev, tf_kind, field_kind)
+            stats = plan.evaluate_threshold(xs, ste_args[0], tg, want_field=False, want_intensity=False)[2]
+            out = plan.loss(stats, kind, rel)
+        return out[0] if squeeze else out
     phase = field_kind == _lib.FIELD_PHASE
     if phase:
         t = _phase_samples(t)
-    geom = (wls, dx, dy, z, dev, tf_kind)
     if t.requires_grad and torch.is_grad_enabled():
         out = _Loss.apply(t, tg, geom, groups, kind, rel, phase)
     else:

@@ -379,6 +379,49 @@ int hbx_evaluate_phase(hbx_plan_t plan, const float* phase, const float* target,
 int hbx_phase_backward(hbx_plan_t plan, const float* values, const float* weight, float scale,
                        const float* phase, int32_t n_env, float* grad_phase, void* stream);
 
+/* (ABI v15, additive) Binary holograms from a real leaf: m = [x >= threshold], u = va + vb m with
+ * the plan's field_kind (HBX_FIELD_AMPLITUDE: 0 / 1; HBX_FIELD_PHASE: 1 / -1, vb = -2) -- the field
+ * of the mask HBX_PACK_THRESHOLD packs from the same samples (NaN: the bit is off).
+ *   values[B][G*P][H][W] float32 samples x, one per pixel of every plane, as hbx_evaluate_real's.
+ * The first pass thresholds x as it loads it: no 0 / 1 copy of the hologram is ever written, and
+ * everything behind the load is hbx_evaluate_real's, so every output equals hbx_evaluate_real's on
+ * the materialised samples (x >= threshold ? va + vb : va) bit for bit.
+ *
+ * hbx_evaluate_threshold: field [B][G*P][H][W][2] complex64, intensity [B][G][H][W], chan_stats
+ *   [B][G][3] and psnr [B] are hbx_evaluate_real's, each nullable: target and chan_stats are given
+ *   together or not at all, psnr only with a target, and at least one of field, intensity and
+ *   chan_stats is non-null (else, or with null values: HBX_ERR_INVALID).  With the intensity alone
+ *   the last pass is hbx_intensity_real's lean form.
+ * hbx_threshold_backward: the whole backward pass of such a leaf under the straight-through
+ *   estimator, on the plan for -z.  The forward pass ran on the thresholded field; the gradient
+ *   with respect to that field reaches x through a surrogate derivative s(x) of the step.
+ *   values    [B][G*P/2][H][W][2] complex64, weight [B][G][H][W] float32 (nullable) and scale are
+ *             hbx_phase_backward's: the first pass is hbx_simulate_complex(_weighted)'s
+ *   samples   [B][G*P/2][H][W] float32, the leaf's samples x: complex plane q of this plan is real
+ *             plane q of the leaf (a leaf of C real planes runs on the -z plan of 2 C channels)
+ *   surrogate HBX_STE_WINDOW   (p0 = lo, p1 = hi): s = 1 for lo <= x <= hi, else 0.  A closed gate
+ *                              stores +0.0f whatever g holds; a NaN sample closes it; lo = -inf,
+ *                              hi = +inf is the plain straight-through estimator
+ *             HBX_STE_SIGMOID  (p0 = the threshold, p1 = k > 0): s = k sg (1 - sg) with
+ *                              sg = 1 / (1 + exp(-k (x - p0))), the derivative of the soft step,
+ *                              evaluated in float32
+ *   grad      [B][G*P/2][H][W] float32 = vb s(x) Re g, g the complex plane hbx_simulate_complex
+ *             (_weighted) would write as field, vb the plan's own (1 or -2).  The last pass reads x
+ *             and writes the one float; neither g nor its real part is written.
+ *   An unknown surrogate, p1 <= 0 for HBX_STE_SIGMOID, or null values, samples or grad:
+ *   HBX_ERR_INVALID before anything is enqueued.
+ * Chunking by max_jobs, n_env (0: OK, < 0: HBX_ERR_INVALID), HBX_PRECISION_F32 only (else
+ * HBX_ERR_UNSUPPORTED), the four built sizes and the pass-timer slots are hbx_evaluate_real's and
+ * hbx_phase_backward's. */
+#define HBX_STE_WINDOW 0
+#define HBX_STE_SIGMOID 1
+int hbx_evaluate_threshold(hbx_plan_t plan, const float* values, float threshold,
+                           const float* target, int32_t n_env, float* field, float* intensity,
+                           double* chan_stats, double* psnr, void* stream);
+int hbx_threshold_backward(hbx_plan_t plan, const float* values, const float* weight, float scale,
+                           const float* samples, int32_t surrogate, float p0, float p1,
+                           int32_t n_env, float* grad, void* stream);
+
 /* PSNR from per-channel statistics (tt.relativeLoss(.., tm.get_PSNR),
  * env.py:174): chan_stats[B][G][3] -> psnr[B]. */
 int hbx_psnr(hbx_plan_t plan, const double* chan_stats, int32_t n_env, double* psnr,
