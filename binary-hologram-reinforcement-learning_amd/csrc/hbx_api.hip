@@ -480,6 +480,11 @@ struct FullRequest {
   // (hbx_threshold_backward) grad_samples is a binary hologram's real leaf: hbx::kGradSteWindow / kGradSteSigmoid
   int grad_kind = hbx::kGradPhase;
   float grad_p0 = 0.0f, grad_p1 = 0.0f;
+  // (hbx_*_window) real or complex input: the input arrays (real_values, or complex_values and weight) are
+  // compact over in_win, the output arrays (target, intensity, field, or real_part, or grad_samples and
+  // grad_phase) compact over out_win, and the statistics and the pixel count are out_win's
+  bool windowed = false;
+  hbx_window_t in_win = {0, 0, 0, 0}, out_win = {0, 0, 0, 0};
   // plane cache (ABI v9): identity slots, then every plane's |U|^2 into its slot
   float* plane_pool = nullptr;
   int32_t* plane_slot = nullptr;
@@ -502,17 +507,26 @@ int propagate_full(hbx_plan_t p, const FullRequest& r, void* stream) {
   // Complex input: the jobs are the plan's constant table (job j = env j / G, group j % G), so the
   // job-major intensity rows are the caller's [env][G][N][N] of the chunk and the last pass writes
   // them in place.  Mask and real input: through job_inten and a scatter (jobs may carry env ids)
-  const bool scatter = r.intensity && !cplx;
+  // (windows: the constant table too, and the compact rows have no 16-byte pieces for the scatter to move)
+  const bool direct = cplx || r.windowed;
+  const bool scatter = r.intensity && !direct;
   if (scatter) {
     int rc = ensure_job_inten(p);
     if (rc) return rc;
   }
   // per-env strides of the caller's buffers, in elements
   const size_t hw = (size_t)pd.N * pd.N;
+  // pixels per input and per output plane: the grid's, or the windows'
+  const size_t hw_i = r.windowed ? (size_t)r.in_win.h * r.in_win.w : hw;
+  const size_t hw_o = r.windowed ? (size_t)r.out_win.h * r.out_win.w : hw;
+  const double count = r.windowed ? (double)G * (double)hw_o : pixel_count(p);
   const size_t s_mask = (size_t)CH * pd.N * (pd.N / 64);   // mask words
-  const size_t s_real = (size_t)CH * hw;                   // real samples, field planes
-  const size_t s_cplx = (size_t)(CH / 2) * hw;             // complex planes (float2), phase planes (float)
-  const size_t s_img = (size_t)G * hw;                     // images: target, intensity, weight
+  const size_t s_real = (size_t)CH * hw_i;                 // real samples
+  const size_t s_field = (size_t)CH * hw_o;                // field planes
+  const size_t s_cplx = (size_t)(CH / 2) * hw_i;           // complex planes (float2), phase planes (float)
+  const size_t s_cout = (size_t)(CH / 2) * hw_o;           // the complex path's outputs and gradient samples
+  const size_t s_wgt = (size_t)G * hw_i;                   // images in: weight
+  const size_t s_img = (size_t)G * hw_o;                   // images out: target, intensity
   const size_t s_stat = (size_t)G * 3;                     // statistics
   const size_t s_pool = (size_t)CHs * hw, s_slot = (size_t)CHs;
   for (int i0 = 0; i0 < r.n; i0 += chunk) {
@@ -531,20 +545,23 @@ int propagate_full(hbx_plan_t p, const FullRequest& r, void* stream) {
     c.real_binarize = r.binarize;
     c.real_threshold = r.threshold;
     c.complex_values = at(r.complex_values, s_cplx);
-    c.complex_weight = at(r.weight, s_img);
+    c.complex_weight = at(r.weight, s_wgt);
     c.complex_scale = r.scale;
     c.phase_values = at(r.phase_values, s_cplx);
     c.target = at(r.target, s_img);
-    c.inten_out = cplx ? at(r.intensity, s_img) : (r.intensity ? p->job_inten : nullptr);
-    c.field_out = at(r.field, s_real);
-    c.complex_field = at(r.complex_field, s_cplx);
-    c.real_part = at(r.real_part, s_cplx);
+    c.inten_out = direct ? at(r.intensity, s_img) : (r.intensity ? p->job_inten : nullptr);
+    c.field_out = at(r.field, s_field);
+    c.complex_field = at(r.complex_field, s_cout);
+    c.real_part = at(r.real_part, s_cout);
     c.complex_stats = r.complex_stats;
-    c.grad_samples = at(r.grad_samples, s_cplx);
-    c.grad_phase = at(r.grad_phase, s_cplx);
+    c.grad_samples = at(r.grad_samples, s_cout);
+    c.grad_phase = at(r.grad_phase, s_cout);
     c.grad_kind = r.grad_kind;
     c.grad_p0 = r.grad_p0;
     c.grad_p1 = r.grad_p1;
+    c.windowed = r.windowed;
+    c.in_win = r.in_win;
+    c.out_win = r.out_win;
     if (r.plane_pool) {
       c.plane_mode = hbx::kPlanesFill;
       c.plane_spares = r.spares;
@@ -555,10 +572,10 @@ int propagate_full(hbx_plan_t p, const FullRequest& r, void* stream) {
     // fields or intensity alone have nothing to finalize (complex input: psnr comes with chan_stats)
     if (r.chan_stats || r.psnr || r.env)
       HBX_HIP(hbx::launch_full_finalize(jobs, pd.job_stats, n, G, at(r.chan_stats, s_stat), at(r.psnr, 1),
-                                        pixel_count(p), p->optics.rel_scale, p->optics.peak,
+                                        count, p->optics.rel_scale, p->optics.peak,
                                         r.env ? env_offset(*r.env, e0, CH, G, pd.N) : EnvDev{}, r.env ? 1 : 0, st));
     if (scatter)
-      HBX_HIP(hbx::launch_scatter_intensity(jobs, n * G, p->job_inten, at(r.intensity, s_img), G, hw, nullptr, st));
+      HBX_HIP(hbx::launch_scatter_intensity(jobs, n * G, p->job_inten, at(r.intensity, s_img), G, hw_o, nullptr, st));
   }
   return HBX_OK;
 }
@@ -745,6 +762,81 @@ int hbx_threshold_backward(hbx_plan_t p, const float* values, const float* weigh
 }
 
 namespace {
+// a window argument of the hbx_*_window calls: null = the full grid; else a non-empty rectangle of it
+int resolve_window(hbx_plan_t p, const hbx_window_t* w, const char* name, hbx_window_t* out) {
+  const hbx_window_t full = {0, 0, p->pd.N, p->pd.N};
+  *out = w ? *w : full;
+  if (!hbx::window_in_grid(*out, p->pd.N))
+    return fail(HBX_ERR_INVALID, std::string(name) + ": a window is a non-empty rectangle inside the plan's grid");
+  return HBX_OK;
+}
+
+// hbx_evaluate_real / hbx_evaluate_threshold (binarize) over windows
+int evaluate_window(hbx_plan_t p, const float* values, bool binarize, float threshold, const hbx_window_t* in_win,
+                    const float* target, const hbx_window_t* out_win, int32_t n_env, float* field, float* intensity,
+                    double* chan_stats, double* psnr, void* stream) {
+  HBX_ENTER(p, n_env, "n_env");
+  if (!values) return fail(HBX_ERR_INVALID, "null buffer");
+  if ((target == nullptr) != (chan_stats == nullptr))
+    return fail(HBX_ERR_INVALID, "target and chan_stats are given together or not at all");
+  if (!target && psnr) return fail(HBX_ERR_INVALID, "without a target there is no psnr");
+  if (!field && !intensity && !chan_stats) return fail(HBX_ERR_INVALID, "no output: field, intensity or chan_stats");
+  FullRequest r;
+  if (int rc = resolve_window(p, in_win, "in_win", &r.in_win)) return rc;
+  if (int rc = resolve_window(p, out_win, "out_win", &r.out_win)) return rc;
+  if (int rc = check_real_plan(p)) return rc;
+  r.windowed = true;
+  r.real_values = values; r.binarize = binarize; r.threshold = threshold; r.target = target; r.n = n_env;
+  r.field = reinterpret_cast<float2*>(field); r.intensity = intensity; r.chan_stats = chan_stats; r.psnr = psnr;
+  return propagate_full(p, r, stream);
+}
+}  // namespace
+
+int hbx_evaluate_real_window(hbx_plan_t p, const float* values, const hbx_window_t* in_win, const float* target,
+                             const hbx_window_t* out_win, int32_t n_env, float* field, float* intensity,
+                             double* chan_stats, double* psnr, void* stream) {
+  return evaluate_window(p, values, false, 0.0f, in_win, target, out_win, n_env, field, intensity, chan_stats, psnr,
+                         stream);
+}
+
+int hbx_evaluate_threshold_window(hbx_plan_t p, const float* values, float threshold, const hbx_window_t* in_win,
+                                  const float* target, const hbx_window_t* out_win, int32_t n_env, float* field,
+                                  float* intensity, double* chan_stats, double* psnr, void* stream) {
+  return evaluate_window(p, values, true, threshold, in_win, target, out_win, n_env, field, intensity, chan_stats, psnr,
+                         stream);
+}
+
+// hbx_simulate_complex(_weighted)'s first pass on values embedded at val_win; the last pass writes the real
+// part (samples null) or hbx_threshold_backward's gated gradient over grad_win
+int hbx_backward_window(hbx_plan_t p, const float* values, const float* weight, float scale, const hbx_window_t* val_win,
+                        const float* samples, int32_t surrogate, float p0, float p1, const hbx_window_t* grad_win,
+                        int32_t n_env, float* grad, void* stream) {
+  HBX_ENTER(p, n_env, "n_env");
+  if (!values || !grad) return fail(HBX_ERR_INVALID, "null buffer");
+  if (samples) {
+    if (surrogate != HBX_STE_WINDOW && surrogate != HBX_STE_SIGMOID)
+      return fail(HBX_ERR_INVALID, "surrogate: HBX_STE_WINDOW or HBX_STE_SIGMOID");
+    if (surrogate == HBX_STE_SIGMOID && !(p1 > 0.0f))
+      return fail(HBX_ERR_INVALID, "HBX_STE_SIGMOID: p1 (the slope k) > 0");
+  }
+  FullRequest r;
+  if (int rc = resolve_window(p, val_win, "val_win", &r.in_win)) return rc;
+  if (int rc = resolve_window(p, grad_win, "grad_win", &r.out_win)) return rc;
+  if (int rc = check_real_plan(p, true)) return rc;
+  r.windowed = true;
+  r.complex_values = reinterpret_cast<const float2*>(values); r.weight = weight; r.n = n_env;
+  if (weight) r.scale = scale;
+  if (samples) {
+    r.grad_samples = samples; r.grad_phase = grad;
+    r.grad_kind = surrogate == HBX_STE_WINDOW ? hbx::kGradSteWindow : hbx::kGradSteSigmoid;
+    r.grad_p0 = p0; r.grad_p1 = p1;
+  } else {
+    r.real_part = grad;
+  }
+  return propagate_full(p, r, stream);
+}
+
+namespace {
 int check_loss_kind(int32_t kind, int32_t rel_scale) {
   if (kind != HBX_LOSS_MSE && kind != HBX_LOSS_PSNR) return fail(HBX_ERR_INVALID, "kind: HBX_LOSS_MSE or HBX_LOSS_PSNR");
   if (rel_scale != HBX_REL_NONE && rel_scale != HBX_REL_LSQ)
@@ -778,6 +870,37 @@ int hbx_loss_weight(hbx_plan_t p, const float* intensity, const float* target, c
   HBX_HIP(hbx::launch_loss_weight(intensity, target, chan_stats, grad_loss, n_env, p->pd.G,
                                   (size_t)p->pd.N * p->pd.N, kind, rel_scale, pixel_count(p), weight,
                                   (hipStream_t)stream));
+  return HBX_OK;
+}
+
+int hbx_loss_window(hbx_plan_t p, const double* chan_stats, const hbx_window_t* out_win, int32_t n_env, int32_t kind,
+                    int32_t rel_scale, double* loss, void* stream) {
+  int rc = check_plan(p);
+  if (rc) return rc;
+  if ((rc = check_loss_kind(kind, rel_scale))) return rc;
+  hbx_window_t w;
+  if ((rc = resolve_window(p, out_win, "out_win", &w))) return rc;
+  if (n_env <= 0) return n_env == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "n_env");
+  if (!chan_stats || !loss) return fail(HBX_ERR_INVALID, "null buffer");
+  HBX_HIP(hipSetDevice(p->device));
+  HBX_HIP(hbx::launch_loss(chan_stats, n_env, p->pd.G, kind, rel_scale, (double)p->pd.G * w.h * w.w, p->optics.peak,
+                           loss, (hipStream_t)stream));
+  return HBX_OK;
+}
+
+int hbx_loss_weight_window(hbx_plan_t p, const float* intensity, const float* target, const double* chan_stats,
+                           const double* grad_loss, const hbx_window_t* out_win, int32_t n_env, int32_t kind,
+                           int32_t rel_scale, float* weight, void* stream) {
+  int rc = check_plan(p);
+  if (rc) return rc;
+  if ((rc = check_loss_kind(kind, rel_scale))) return rc;
+  hbx_window_t w;
+  if ((rc = resolve_window(p, out_win, "out_win", &w))) return rc;
+  if (n_env <= 0) return n_env == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "n_env");
+  if (!intensity || !target || !chan_stats || !weight) return fail(HBX_ERR_INVALID, "null buffer");
+  HBX_HIP(hipSetDevice(p->device));
+  HBX_HIP(hbx::launch_loss_weight(intensity, target, chan_stats, grad_loss, n_env, p->pd.G, (size_t)w.h * w.w, kind,
+                                  rel_scale, (double)p->pd.G * w.h * w.w, weight, (hipStream_t)stream));
   return HBX_OK;
 }
 

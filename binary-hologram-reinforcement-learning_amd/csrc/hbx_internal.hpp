@@ -257,6 +257,13 @@ struct PassCall {
   // Any other kind than kGradPhase only with the pair
   int grad_kind = kGradPhase;
   float grad_p0 = 0.0f, grad_p1 = 0.0f;
+  // (ABI v15, additive) hbx_*_window: 1 = the input sits in in_win of the grid and is 0 elsewhere, the
+  // outputs are taken over out_win, and every array that belongs to a window is compact ([..][h][w], row
+  // pitch w).  in_win: real_values, or complex_values and complex_weight; out_win: target, inten_out
+  // (job-major) and field_out, or real_part, or grad_samples and grad_phase (the two STE kinds).  Both are
+  // whole rectangles of the grid (a full-grid window is the unwindowed layout), never read with windowed = 0
+  int windowed = 0;
+  hbx_window_t in_win = {0, 0, 0, 0}, out_win = {0, 0, 0, 0};
   // the plane cache (kPlanes* above)
   int plane_mode = kPlanesOff;
   float* plane_pool = nullptr;          // [env][CH + 2S][N][N] f32 per-plane |U|^2 (env ids as the jobs carry them)
@@ -274,6 +281,17 @@ struct PassCall {
   const WalkPlanesArgs* walk_planes = nullptr;  // (r05) plane-cache walk batch: the last k_rowinv_d
                                                 // workgroup decides (hbx_walk_planes.hpp)
 };
+
+// a window (hbx_window_t) that is a non-empty rectangle of the N x N grid
+inline bool window_in_grid(const hbx_window_t& w, int N) {
+  return w.y0 >= 0 && w.x0 >= 0 && w.h >= 1 && w.w >= 1 && w.y0 <= N - w.h && w.x0 <= N - w.w;
+}
+
+// Whether the first pass takes its predicated loads: an input window that is the whole grid is the
+// unwindowed layout, and the plain loads measured 3 % faster there
+inline bool pass_window_in(const PassCall& c, int N) {
+  return c.windowed && !(c.in_win.y0 == 0 && c.in_win.x0 == 0 && c.in_win.h == N && c.in_win.w == N);
+}
 
 // The complex path: complex or phase samples in, the pair-recombining last pass out
 inline bool pass_complex(const PassCall& c) { return c.complex_values || c.phase_values; }
@@ -308,6 +326,14 @@ inline hipError_t check_pass_call(const PlanDev& pd, const PassCall& c) {
   // the weight rides on the complex load, the threshold on the real one
   ok = ok && (c.complex_values || !c.complex_weight);
   ok = ok && (c.real_values || !c.real_binarize);
+  // windows: whole rectangles of the grid; real samples in, or complex samples in and the real part or an
+  // STE gradient out; no plane cache, actions, walk or reconcile, and nothing env-major
+  if (c.windowed) {
+    ok = ok && window_in_grid(c.in_win, pd.N) && window_in_grid(c.out_win, pd.N);
+    ok = ok && (c.real_values || (c.complex_values && !c.complex_field && !c.complex_stats &&
+                                  (c.real_part || (grad_out && c.grad_kind != kGradPhase))));
+    ok = ok && !planes && !c.actions && !walk && !c.rc_pending && !c.inten_by_env && !c.skip_reduce;
+  }
   return ok ? hipSuccess : hipErrorInvalidValue;
 }
 // The target rows the last pass reads.  No target: the plan's zero row, every row offset masked to 0

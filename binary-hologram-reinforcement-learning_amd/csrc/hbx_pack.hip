@@ -197,12 +197,10 @@ __global__ void k_loss(const double* __restrict__ chan_stats, int n, int G, int 
 // coefficients in f64 from 3 G statistics -- uniform per workgroup, so scalar loads and no LDS --
 // rounds them to f32 once and streams kLossPer 16-byte pieces per thread
 constexpr int kLossPer = 4;
-__global__ __launch_bounds__(256) void k_loss_weight(const float4* __restrict__ inten, const float4* __restrict__ target,
-                                                     const double* __restrict__ chan_stats,
-                                                     const double* __restrict__ grad_loss, int G, int64_t n4,
-                                                     unsigned bx, int kind, int rel_scale, double count,
-                                                     float4* __restrict__ weight) {
-  const int b = blockIdx.x / bx;
+// env b's two coefficients, rounded to f32 once
+__device__ __forceinline__ void loss_weight_coeffs(const double* __restrict__ chan_stats,
+                                                   const double* __restrict__ grad_loss, int b, int G, int kind,
+                                                   int rel_scale, double count, float& af, float& cf) {
   double sxy, sxx, syy;
   env_sums(chan_stats, b, G, sxy, sxx, syy);
   double a, c;   // dMSE/dI = a I + c T
@@ -221,7 +219,17 @@ __global__ __launch_bounds__(256) void k_loss_weight(const float4* __restrict__ 
     c *= f;
   }
   const double up = grad_loss ? grad_loss[b] : 1.0;
-  const float af = (float)(a * up), cf = (float)(c * up);
+  af = (float)(a * up), cf = (float)(c * up);
+}
+
+__global__ __launch_bounds__(256) void k_loss_weight(const float4* __restrict__ inten, const float4* __restrict__ target,
+                                                     const double* __restrict__ chan_stats,
+                                                     const double* __restrict__ grad_loss, int G, int64_t n4,
+                                                     unsigned bx, int kind, int rel_scale, double count,
+                                                     float4* __restrict__ weight) {
+  const int b = blockIdx.x / bx;
+  float af, cf;
+  loss_weight_coeffs(chan_stats, grad_loss, b, G, kind, rel_scale, count, af, cf);
   const int64_t base = (int64_t)b * n4;
   const int64_t i0 = (int64_t)(blockIdx.x % bx) * (256 * kLossPer) + threadIdx.x;
   float4 I[kLossPer], T[kLossPer];
@@ -242,6 +250,26 @@ __global__ __launch_bounds__(256) void k_loss_weight(const float4* __restrict__ 
   }
 }
 
+// k_loss_weight one float at a time (hbx_loss_weight_window): the images of an output window are compact,
+// so an env's G h w floats are neither a multiple of four nor 16-byte aligned in general.  The same
+// coefficients and the same fmaf per pixel: on a full-grid window it is k_loss_weight's weight bit for bit
+__global__ __launch_bounds__(256) void k_loss_weight1(const float* __restrict__ inten, const float* __restrict__ target,
+                                                      const double* __restrict__ chan_stats,
+                                                      const double* __restrict__ grad_loss, int G, int64_t n1,
+                                                      unsigned bx, int kind, int rel_scale, double count,
+                                                      float* __restrict__ weight) {
+  const int b = blockIdx.x / bx;
+  float af, cf;
+  loss_weight_coeffs(chan_stats, grad_loss, b, G, kind, rel_scale, count, af, cf);
+  const int64_t base = (int64_t)b * n1;
+  const int64_t i0 = (int64_t)(blockIdx.x % bx) * (256 * kLossPer) + threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < kLossPer; ++k) {
+    const int64_t i = i0 + 256 * k;
+    if (i < n1) weight[base + i] = fmaf(af, inten[base + i], cf * target[base + i]);
+  }
+}
+
 }  // namespace
 
 hipError_t launch_loss(const double* chan_stats, int n, int G, int kind, int rel_scale, double count, double peak,
@@ -254,7 +282,15 @@ hipError_t launch_loss(const double* chan_stats, int n, int G, int kind, int rel
 hipError_t launch_loss_weight(const float* inten, const float* target, const double* chan_stats,
                               const double* grad_loss, int n, int G, size_t hw, int kind, int rel_scale, double count,
                               float* weight, hipStream_t st) {
-  const int64_t n4 = (int64_t)G * (int64_t)hw / 4;   // 16-byte pieces per env (N^2 is a multiple of 4)
+  const int64_t n1 = (int64_t)G * (int64_t)hw;
+  const auto misaligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) != 0; };
+  if (n1 % 4 != 0 || misaligned(inten) || misaligned(target) || misaligned(weight)) {   // a window's compact images
+    const unsigned bx1 = (unsigned)((n1 + 256 * kLossPer - 1) / (256 * kLossPer));
+    hipLaunchKernelGGL(k_loss_weight1, dim3(bx1 * (unsigned)n), dim3(256), 0, st, inten, target, chan_stats, grad_loss,
+                       G, n1, bx1, kind, rel_scale, count, weight);
+    return hipGetLastError();
+  }
+  const int64_t n4 = n1 / 4;   // 16-byte pieces per env (N^2 is a multiple of 4)
   const unsigned bx = (unsigned)((n4 + 256 * kLossPer - 1) / (256 * kLossPer));
   hipLaunchKernelGGL(k_loss_weight, dim3(bx * (unsigned)n), dim3(256), 0, st,
                      reinterpret_cast<const float4*>(inten), reinterpret_cast<const float4*>(target), chan_stats,

@@ -463,12 +463,15 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd32(const JobDesc* jobs,
 // LK = kLoadThreshold (hbx_evaluate_threshold): threshold_load_row turns each sample into the field of
 // its mask bit, hi where x >= thr and lo elsewhere, as it loads it; the registers, the tail and the
 // geometry are unchanged, and thr / lo / hi are unused without it.
-template <int R, int NT, int LK = kLoadReal>
+// WIN (hbx_evaluate_real_window / _threshold_window; off by default, and the kernels without it compile
+// as before): values is compact, [env][CH][win.h][win.w], and sits at win of the grid, which is 0
+// elsewhere -- real_load_row_win loads a pixel only inside it; the A panel of every row is written.
+template <int R, int NT, int LK = kLoadReal, bool WIN = false>
 __global__ __launch_bounds__(NT, 512 / NT) void k_rowfwd_real(const JobDesc* __restrict__ jobs,
                                                         const float* __restrict__ values,
                                                         float2* __restrict__ ws_a,
                                                         const float2* __restrict__ tw_glob, int P, int CH,
-                                                        float thr, float lo, float hi) {
+                                                        float thr, float lo, float hi, hbx_window_t win) {
   constexpr int N = R * R;
   constexpr int GPB = NT / R;          // rows per row block
   __shared__ float2 tw[N];
@@ -488,11 +491,17 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowfwd_real(const JobDesc* __r
   const int y0 = wg.rbw * GPB;
   const int y = y0 + grp;
   pk2 v[R];
-  const float* row = values + (((size_t)jb.env * CH + jb.group * P + pa) * N + y) * N;
-  if constexpr (LK == kLoadThreshold)
-    threshold_load_row<R>(v, row, (size_t)N * N, t, thr, lo, hi);
-  else
-    real_load_row<R>(v, row, (size_t)N * N, t);
+  if constexpr (WIN) {
+    const WinRow wr(win, y, t);
+    const size_t ro = wr.in ? WinRow::row_of(win, (size_t)jb.env * CH + jb.group * P + pa, y) : 0;
+    real_load_row_win<R, R, LK>(v, values + ro, (size_t)win.h * win.w, wr, thr, lo, hi);
+  } else {
+    const float* row = values + (((size_t)jb.env * CH + jb.group * P + pa) * N + y) * N;
+    if constexpr (LK == kLoadThreshold)
+      threshold_load_row<R>(v, row, (size_t)N * N, t, thr, lo, hi);
+    else
+      real_load_row<R>(v, row, (size_t)N * N, t);
+  }
   __syncthreads();  // tw visible
 
   float2* base = ws_a + ((size_t)j * P + pa) * plane_a_elems(R);
@@ -501,12 +510,12 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowfwd_real(const JobDesc* __r
 
 // N = 1024: k_rowfwd32's three workgroups per CU (split FFT tiles, one plane's tile at a time;
 // kLoadThreshold: profiles/binary_ste/resource_usage.txt)
-template <int LK = kLoadReal>
+template <int LK = kLoadReal, bool WIN = false>
 __global__ __launch_bounds__(256, 3) void k_rowfwd32_real(const JobDesc* __restrict__ jobs,
                                                           const float* __restrict__ values,
                                                           float2* __restrict__ ws_a,
                                                           const float2* __restrict__ tw_glob, int P, int CH,
-                                                          float thr, float lo, float hi) {
+                                                          float thr, float lo, float hi, hbx_window_t win) {
   constexpr int R = 32, NT = 256, N = R * R;
   constexpr int GPB = NT / R;          // 8 rows per row block
   __shared__ float2 tw[N];
@@ -526,11 +535,17 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd32_real(const JobDesc* __restr
   const int y0 = wg.rbw * GPB;
   const int y = y0 + grp;
   pk2 v[R];
-  const float* row = values + (((size_t)jb.env * CH + jb.group * P + pa) * N + y) * N;
-  if constexpr (LK == kLoadThreshold)
-    threshold_load_row<R>(v, row, (size_t)N * N, t, thr, lo, hi);
-  else
-    real_load_row<R>(v, row, (size_t)N * N, t);
+  if constexpr (WIN) {
+    const WinRow wr(win, y, t);
+    const size_t ro = wr.in ? WinRow::row_of(win, (size_t)jb.env * CH + jb.group * P + pa, y) : 0;
+    real_load_row_win<R, R, LK>(v, values + ro, (size_t)win.h * win.w, wr, thr, lo, hi);
+  } else {
+    const float* row = values + (((size_t)jb.env * CH + jb.group * P + pa) * N + y) * N;
+    if constexpr (LK == kLoadThreshold)
+      threshold_load_row<R>(v, row, (size_t)N * N, t, thr, lo, hi);
+    else
+      real_load_row<R>(v, row, (size_t)N * N, t);
+  }
   __syncthreads();  // tw visible
 
   float2* base = ws_a + ((size_t)j * P + pa) * plane_a_elems(R);
@@ -551,13 +566,15 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd32_real(const JobDesc* __restr
 // LK = kLoadPhase (hbx_simulate_phase): phase[env][CH / 2][N][N] f32 instead of values, phase plane q
 // into plane-pair slot q as complex plane q; phase_load_row forms exp(i pi x) as it loads -- R floats
 // live across the load where the complex form holds R pairs.  phase is unused by the other kinds.
-template <int R, int NT, int LK = kLoadComplex>
+// WIN (hbx_backward_window; kLoadComplex and kLoadWeighted): values [env][CH / 2][win.h][win.w] and weight
+// [env][G][win.h][win.w] are compact and sit at win of the grid, 0 elsewhere (complex_load_row_win).
+template <int R, int NT, int LK = kLoadComplex, bool WIN = false>
 __global__ __launch_bounds__(NT, 512 / NT) void k_rowfwd_cplx(const JobDesc* __restrict__ jobs,
                                                         const float2* __restrict__ values,
                                                         float2* __restrict__ ws_a,
                                                         const float2* __restrict__ tw_glob, int P, int CH,
                                                         const float* __restrict__ weight, float scale,
-                                                        const float* __restrict__ phase) {
+                                                        const float* __restrict__ phase, hbx_window_t win) {
   constexpr int N = R * R;
   constexpr int GPB = NT / R;          // rows per row block
   __shared__ float2 tw[N];
@@ -576,13 +593,21 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowfwd_cplx(const JobDesc* __r
   const int y0 = wg.rbw * GPB;
   const int y = y0 + grp;
   pk2 v[R];
-  const size_t row = (((size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q) * N + y) * N;
-  if constexpr (LK == kLoadWeighted)
-    complex_load_row_weighted<R>(v, values + row, weight + (((size_t)jb.env * (CH / P) + jb.group) * N + y) * N, scale, t);
-  else if constexpr (LK == kLoadPhase)
-    phase_load_row<R>(v, phase + row, t);
-  else
-    complex_load_row<R>(v, values + row, t);
+  if constexpr (WIN) {
+    static_assert(LK != kLoadPhase, "phase leaves are not windowed");
+    const WinRow wr(win, y, t);
+    const size_t ro = wr.in ? WinRow::row_of(win, (size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q, y) : 0;
+    const size_t wo = wr.in ? WinRow::row_of(win, (size_t)jb.env * (CH / P) + jb.group, y) : 0;
+    complex_load_row_win<R, R, LK>(v, values + ro, LK == kLoadWeighted ? weight + wo : nullptr, scale, wr);
+  } else {
+    const size_t row = (((size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q) * N + y) * N;
+    if constexpr (LK == kLoadWeighted)
+      complex_load_row_weighted<R>(v, values + row, weight + (((size_t)jb.env * (CH / P) + jb.group) * N + y) * N, scale, t);
+    else if constexpr (LK == kLoadPhase)
+      phase_load_row<R>(v, phase + row, t);
+    else
+      complex_load_row<R>(v, values + row, t);
+  }
   __syncthreads();  // tw visible
 
   float2* base = ws_a + ((size_t)j * P + 2 * wg.q) * plane_a_elems(R);
@@ -592,13 +617,13 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowfwd_cplx(const JobDesc* __r
 // N = 1024: k_rowfwd32's three workgroups per CU (kLoadWeighted: 111 VGPRs against 112, the weights die before the
 // row FFT's temporaries are born; profiles/intensity_grad/resource_usage.txt; kLoadPhase:
 // profiles/phase_field/resource_usage.txt)
-template <int LK = kLoadComplex>
+template <int LK = kLoadComplex, bool WIN = false>
 __global__ __launch_bounds__(256, 3) void k_rowfwd32_cplx(const JobDesc* __restrict__ jobs,
                                                           const float2* __restrict__ values,
                                                           float2* __restrict__ ws_a,
                                                           const float2* __restrict__ tw_glob, int P, int CH,
                                                           const float* __restrict__ weight, float scale,
-                                                          const float* __restrict__ phase) {
+                                                          const float* __restrict__ phase, hbx_window_t win) {
   constexpr int R = 32, NT = 256, N = R * R;
   constexpr int GPB = NT / R;          // 8 rows per row block
   __shared__ float2 tw[N];
@@ -617,13 +642,21 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd32_cplx(const JobDesc* __restr
   const int y0 = wg.rbw * GPB;
   const int y = y0 + grp;
   pk2 v[R];
-  const size_t row = (((size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q) * N + y) * N;
-  if constexpr (LK == kLoadWeighted)
-    complex_load_row_weighted<R>(v, values + row, weight + (((size_t)jb.env * (CH / P) + jb.group) * N + y) * N, scale, t);
-  else if constexpr (LK == kLoadPhase)
-    phase_load_row<R>(v, phase + row, t);
-  else
-    complex_load_row<R>(v, values + row, t);
+  if constexpr (WIN) {
+    static_assert(LK != kLoadPhase, "phase leaves are not windowed");
+    const WinRow wr(win, y, t);
+    const size_t ro = wr.in ? WinRow::row_of(win, (size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q, y) : 0;
+    const size_t wo = wr.in ? WinRow::row_of(win, (size_t)jb.env * (CH / P) + jb.group, y) : 0;
+    complex_load_row_win<R, R, LK>(v, values + ro, LK == kLoadWeighted ? weight + wo : nullptr, scale, wr);
+  } else {
+    const size_t row = (((size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q) * N + y) * N;
+    if constexpr (LK == kLoadWeighted)
+      complex_load_row_weighted<R>(v, values + row, weight + (((size_t)jb.env * (CH / P) + jb.group) * N + y) * N, scale, t);
+    else if constexpr (LK == kLoadPhase)
+      phase_load_row<R>(v, phase + row, t);
+    else
+      complex_load_row<R>(v, values + row, t);
+  }
   __syncthreads();  // tw visible
 
   float2* base = ws_a + ((size_t)j * P + 2 * wg.q) * plane_a_elems(R);
@@ -832,7 +865,12 @@ __global__ __launch_bounds__(256, 2) void k_col2(const JobDesc* __restrict__ job
 // The tail (rowinv_epilogue), the lane bases of the direct loads (RowinvLanes), the plane cache and the
 // other pieces shared with the N = 896 kernels are in hbx_rowinv.hpp.
 
-template <int R, bool WALK = false, bool LEAN = false>
+// WIN (hbx_evaluate_real_window / _threshold_window; off by default, and the kernels without it compile as
+// before): target [env][G][h][w], inten_out [job][h][w] and field_out [env][G*P][h][w] are compact arrays
+// over the output window win.  A row block that shares no row with it writes neutral partials and reads
+// nothing from B; the others run every row's FFTs and store, reduce and load the target only inside
+// (plane_out_win, rowinv_epilogue_win).  No plane cache, reconcile or walk; LEAN: no field code.
+template <int R, bool WALK = false, bool LEAN = false, bool WIN = false>
 __global__ __launch_bounds__(256, 2) void k_rowinv_d(const JobDesc* __restrict__ jobs,
                                                      const float2* __restrict__ ws_b,
                                                      const float* __restrict__ target,
@@ -842,8 +880,10 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_d(const JobDesc* __restrict__
                                                      int plane_mode, float* __restrict__ plane_pool,
                                                      const int32_t* __restrict__ plane_slot, int plane_spares,
                                                      int spare_base, const int32_t* __restrict__ rc_pending,
-                                                     float* __restrict__ rc_cache, WalkPlanesArgs wk) {
+                                                     float* __restrict__ rc_cache, WalkPlanesArgs wk,
+                                                     hbx_window_t win) {
   constexpr int N = R * R, GPB = 256 / R, RB = N / GPB;
+  static_assert(!(WIN && WALK), "a walk batch is not windowed");
   static_assert(!WALK || walk_planes_lds_bytes(RB) <= GPB * R * (R + 1) * 8, "the decision's LDS fits the scratch");
   __shared__ float2 tw[N];
   __shared__ float2 scratch[GPB * R * (R + 1)];
@@ -873,6 +913,15 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_d(const JobDesc* __restrict__
     rc_pending = nullptr;
     rc_cache = nullptr;
   }
+  if constexpr (WIN) {
+    if (rowinv_block_outside(win, rb * GPB, GPB)) {   // uniform per block
+      rowinv_zero_partial(partial, j, RB, rb);
+      return;
+    }
+    plane_mode = kPlanesOff;
+    rc_pending = nullptr;
+    rc_cache = nullptr;
+  }
   const int y = rb * GPB + grp;
   constexpr int PLB = N * N;                 // float2 per B plane
   const __amdgpu_buffer_rsrc_t rs = plane_rsrc(ws_b + (size_t)j * P * PLB, (unsigned)((size_t)P * PLB * 8));
@@ -883,9 +932,11 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_d(const JobDesc* __restrict__
   for (int k = 0; k < R; ++k) acc[k] = 0.0f;
   const PaddedScratch<R> sc{scratch + grp * R * (R + 1)};
   const PlaneCache<R> pc(jb, j, y, G, P, plane_spares, spare_base, plane_pool, plane_slot);
+  const WinRow wr(win, y, t);   // (WIN alone reads it)
   auto finish_plane = [&](pk2 (&v)[R], int p) {
     fft_group<R, true>(v, t, sc, tw);
-    plane_out<R, R>(v, acc, pc, jb, G, P, p, t, field_out, plane_mode);
+    if constexpr (WIN) plane_out_win<R, R>(v, acc, jb, G, P, p, y, win, wr, field_out);
+    else plane_out<R, R>(v, acc, pc, jb, G, P, p, t, field_out, plane_mode);
   };
   pk2 va[R];
   if (plane_mode == kPlanesStep) {   // only the flipped plane's pair is in B
@@ -909,7 +960,7 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_d(const JobDesc* __restrict__
       load_plane(va, p + 2 < P ? p + 2 : p + 1);
       finish_plane(vb, p + 1);
     }
-  } else if constexpr (LEAN) {
+  } else if constexpr (LEAN && !WIN) {
     // (r06) the last plane peeled: its FFT runs with the target row's loads in flight instead of a
     // re-read of plane P - 1 (the loads the tail waited for; 32 more VGPRs fit the lean kernel)
 #pragma unroll 1
@@ -932,11 +983,15 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_d(const JobDesc* __restrict__
       load_plane(va, p + 1 < P ? p + 1 : p);   // unconditional: the last round re-reads plane P - 1
     }
   }
-  rowinv_epilogue<R, R, GPB>(acc, P, G, jb, j, y, rb, grp, t, target, tmask, inten_out, inten_by_env, partial, red,
-                              rc_pending, rc_cache);
+  if constexpr (WIN)
+    rowinv_epilogue_win<R, R, GPB>(acc, P, G, jb, j, y, rb, grp, t, target, tmask, inten_out, partial, red, win, wr);
+  else
+    rowinv_epilogue<R, R, GPB>(acc, P, G, jb, j, y, rb, grp, t, target, tmask, inten_out, inten_by_env, partial, red,
+                                rc_pending, rc_cache);
 }
 
-template <int R, int NT>
+// WIN: as k_rowinv_d's
+template <int R, int NT, bool WIN = false>
 __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv(const JobDesc* __restrict__ jobs,
                                                    const float2* __restrict__ ws_b,
                                                    const float* __restrict__ target,
@@ -944,7 +999,7 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv(const JobDesc* __restri
                                                    int G, double* __restrict__ partial,
                                                    float* __restrict__ inten_out,
                                                    float2* __restrict__ field_out,
-                                                   size_t tmask, int inten_by_env) {
+                                                   size_t tmask, int inten_by_env, hbx_window_t win) {
   constexpr int N = R * R;
   constexpr int GPB = NT / R;          // rows per block
   constexpr int RB = N / GPB;
@@ -970,6 +1025,13 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv(const JobDesc* __restri
   }
   const int y0 = rb * GPB;
   const int y = y0 + grp;
+  if constexpr (WIN) {
+    if (rowinv_block_outside(win, y0, GPB)) {   // uniform per block
+      rowinv_zero_partial(partial, j, RB, rb);
+      return;
+    }
+  }
+  const WinRow wr(win, y, t);   // (WIN alone reads it)
   constexpr size_t PLB = plane_b_elems(R);
   const float2* jbase = ws_b + (size_t)j * P * PLB;
 
@@ -1006,6 +1068,10 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv(const JobDesc* __restri
     for (int jj = 0; jj < R; ++jj) v[jj] = to_pk(tile[tile_pos<R, GPB>(t + R * jj, grp)]);
     lds_barrier();  // tile consumed: reuse it as transpose scratch
     fft_group<R, true>(v, t, PaddedScratch<R>{tile + grp * R * (R + 1)}, tw);
+    if constexpr (WIN) {
+      plane_out_win<R, R>(v, acc, jb, G, P, p, y, win, wr, field_out);
+      continue;
+    }
 #pragma unroll
     for (int k = 0; k < R; ++k) acc[k] += fmaf(v[k].x, v[k].x, v[k].y * v[k].y);
     if (field_out) {  // exact field of this plane (incremental mode init / refresh)
@@ -1015,7 +1081,10 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv(const JobDesc* __restri
     }
   }
 
-  rowinv_epilogue<R, R, GPB>(acc, P, G, jb, j, y, rb, grp, t, target, tmask, inten_out, inten_by_env, partial, red);
+  if constexpr (WIN)
+    rowinv_epilogue_win<R, R, GPB>(acc, P, G, jb, j, y, rb, grp, t, target, tmask, inten_out, partial, red, win, wr);
+  else
+    rowinv_epilogue<R, R, GPB>(acc, P, G, jb, j, y, rb, grp, t, target, tmask, inten_out, inten_by_env, partial, red);
 }
 
 // ---------------------------------------------------------------------------
@@ -1045,7 +1114,11 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv(const JobDesc* __restri
 // kernel never holds two whole lines (the second register set that cost k_rowinv_d its second
 // block per CU).  N = 256 has the registers for a second line and keeps the next pair in flight
 // under this one's FFT, as k_rowinv_d does with the next plane.
-template <int R, bool ST = false, int GK = kGradNone>
+// WIN (hbx_backward_window; off by default, and the kernels without it compile as before; kGradNone and the
+// two STE kinds, never ST): the one output is a compact array over the window win -- real_out
+// [env][CH / 2][h][w] = Re F_q (kGradNone; field_out is not written), or grad from the leaf's samples
+// in `phase`, both of that shape (grad_row_win).  A row block that shares no row with win reads nothing.
+template <int R, bool ST = false, int GK = kGradNone, bool WIN = false>
 __global__ __launch_bounds__(256, 2) void k_rowinv_d_cplx(const JobDesc* __restrict__ jobs,
                                                           const float2* __restrict__ ws_b,
                                                           const float2* __restrict__ tw_glob, int P, int G,
@@ -1056,8 +1129,9 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_d_cplx(const JobDesc* __restr
                                                           float* __restrict__ inten_out,
                                                           const float* __restrict__ phase,
                                                           float* __restrict__ grad, float gvb, float ga,
-                                                          float gb) {
+                                                          float gb, hbx_window_t win) {
   static_assert(!(ST && GK != kGradNone), "the gradient forms run no statistics");
+  static_assert(!(WIN && (ST || GK == kGradPhase)), "windows: the real part or an STE gradient");
   constexpr int N = R * R, GPB = 256 / R, RB = N / GPB;
   __shared__ float2 tw[N];
   __shared__ float2 scratch[GPB * R * (R + 1)];
@@ -1073,7 +1147,11 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_d_cplx(const JobDesc* __restr
     if constexpr (ST) rowinv_zero_partial(partial, j, RB, rb);
     return;
   }
+  if constexpr (WIN) {
+    if (rowinv_block_outside(win, rb * GPB, GPB)) return;   // uniform per block
+  }
   const int y = rb * GPB + grp;
+  const WinRow wr(win, y, t);   // (WIN alone reads it)
   const int Q = P / 2;                        // complex planes per group
   constexpr int PLB = N * N;                 // float2 per B plane
   const __amdgpu_buffer_rsrc_t rs = plane_rsrc(ws_b + (size_t)j * P * PLB, (unsigned)((size_t)P * PLB * 8));
@@ -1091,6 +1169,11 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_d_cplx(const JobDesc* __restr
     if constexpr (ST) {
 #pragma unroll
       for (int k = 0; k < R; ++k) acc[k] += fmaf(v[k].x, v[k].x, v[k].y * v[k].y);
+    }
+    if constexpr (WIN) {
+      const size_t ro = wr.in ? WinRow::row_of(win, ((size_t)jb.env * G + jb.group) * Q + q, y) : 0;
+      grad_row_win<R, R, GK>(v, phase + ro, (GK == kGradNone ? real_out : grad) + ro, wr, gvb, ga, gb);
+      return;
     }
     const size_t row = row0 + (size_t)q * N * N;
     if constexpr (GK == kGradPhase) {   // the samples are loaded behind the FFT: R = 32 never holds a second line
@@ -1138,7 +1221,7 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_d_cplx(const JobDesc* __restr
 
 // N = 64: k_rowinv's LDS tile transpose; both planes' shares of the tile are prefetched one pair
 // ahead and combined as they are written into the tile.
-template <int R, int NT, bool ST = false, int GK = kGradNone>
+template <int R, int NT, bool ST = false, int GK = kGradNone, bool WIN = false>
 __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv_cplx(const JobDesc* __restrict__ jobs,
                                                         const float2* __restrict__ ws_b,
                                                         const float2* __restrict__ tw_glob, int P, int G,
@@ -1149,8 +1232,9 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv_cplx(const JobDesc* __r
                                                         float* __restrict__ inten_out,
                                                         const float* __restrict__ phase,
                                                         float* __restrict__ grad, float gvb, float ga,
-                                                        float gb) {
+                                                        float gb, hbx_window_t win) {
   static_assert(!(ST && GK != kGradNone), "the gradient forms run no statistics");
+  static_assert(!(WIN && (ST || GK == kGradPhase)), "windows: the real part or an STE gradient");
   constexpr int N = R * R;
   constexpr int GPB = NT / R;          // rows per block
   constexpr int RB = N / GPB;
@@ -1175,6 +1259,10 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv_cplx(const JobDesc* __r
   }
   const int y0 = rb * GPB;
   const int y = y0 + grp;
+  if constexpr (WIN) {
+    if (rowinv_block_outside(win, y0, GPB)) return;   // uniform per block
+  }
+  const WinRow wr(win, y, t);   // (WIN alone reads it)
   const int Q = P / 2;
   constexpr size_t PLB = plane_b_elems(R);
   const float2* jbase = ws_b + (size_t)j * P * PLB;
@@ -1216,6 +1304,11 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv_cplx(const JobDesc* __r
     if constexpr (ST) {
 #pragma unroll
       for (int k = 0; k < R; ++k) acc[k] += fmaf(v[k].x, v[k].x, v[k].y * v[k].y);
+    }
+    if constexpr (WIN) {
+      const size_t ro = wr.in ? WinRow::row_of(win, ((size_t)jb.env * G + jb.group) * Q + q, y) : 0;
+      grad_row_win<R, R, GK>(v, phase + ro, (GK == kGradNone ? real_out : grad) + ro, wr, gvb, ga, gb);
+      continue;
     }
     const size_t row = row0 + (size_t)q * N * N;
     if constexpr (GK == kGradPhase) {
@@ -1415,8 +1508,15 @@ static hipError_t launch_passes(const PlanDev& pd, const PassCall& c, hipStream_
                                    : lk == kLoadComplex ? k_rowfwd_cplx<R, NT, kLoadComplex>
                                                         : k_rowfwd_cplx<R, NT, kLoadPhase>;
     }();
+    // (the windowed forms are named behind the others, here and below: they come last in the code object)
+    if (pass_window_in(c, N)) {
+      if constexpr (R == 32)
+        k = lk == kLoadWeighted ? k_rowfwd32_cplx<kLoadWeighted, true> : k_rowfwd32_cplx<kLoadComplex, true>;
+      else
+        k = lk == kLoadWeighted ? k_rowfwd_cplx<R, NT, kLoadWeighted, true> : k_rowfwd_cplx<R, NT, kLoadComplex, true>;
+    }
     launch_kernel(k, sample_blocks, NT, st, jobs, c.complex_values, pd.ws_a, pd.tw, P, CH, c.complex_weight,
-                  c.complex_scale, c.phase_values);
+                  c.complex_scale, c.phase_values, c.in_win);
   } else if (c.real_values) {
     // the load kind: the samples as they are, or (hbx_evaluate_threshold) the field of the bit [x >= threshold]
     const bool thr = c.real_binarize != 0;
@@ -1424,8 +1524,12 @@ static hipError_t launch_passes(const PlanDev& pd, const PassCall& c, hipStream_
       if constexpr (R == 32) return !thr ? k_rowfwd32_real<kLoadReal> : k_rowfwd32_real<kLoadThreshold>;
       else return !thr ? k_rowfwd_real<R, NT, kLoadReal> : k_rowfwd_real<R, NT, kLoadThreshold>;
     }();
+    if (pass_window_in(c, N)) {
+      if constexpr (R == 32) k = !thr ? k_rowfwd32_real<kLoadReal, true> : k_rowfwd32_real<kLoadThreshold, true>;
+      else k = !thr ? k_rowfwd_real<R, NT, kLoadReal, true> : k_rowfwd_real<R, NT, kLoadThreshold, true>;
+    }
     launch_kernel(k, sample_blocks, NT, st, jobs, c.real_values, pd.ws_a, pd.tw, P, CH, c.real_threshold, pd.va,
-                  pd.va + pd.vb);
+                  pd.va + pd.vb, c.in_win);
   } else {
     auto k = [&] {
       if constexpr (R == 32) return small ? k_rowfwd32<SK, 1> : k_rowfwd32<SK>;
@@ -1468,8 +1572,18 @@ static hipError_t launch_passes(const PlanDev& pd, const PassCall& c, hipStream_
                : gk == kGradSteWindow ? k_rowinv_cplx<R, NT, false, kGradSteWindow>
                                       : k_rowinv_cplx<R, NT, false, kGradSteSigmoid>;
     }();
+    if (c.windowed) {   // the real part or an STE gradient over out_win (check_pass_call)
+      if constexpr (kTiledB<R>)
+        k = gk == kGradNone ? k_rowinv_d_cplx<R, false, kGradNone, true>
+            : gk == kGradSteWindow ? k_rowinv_d_cplx<R, false, kGradSteWindow, true>
+                                   : k_rowinv_d_cplx<R, false, kGradSteSigmoid, true>;
+      else
+        k = gk == kGradNone ? k_rowinv_cplx<R, NT, false, kGradNone, true>
+            : gk == kGradSteWindow ? k_rowinv_cplx<R, NT, false, kGradSteWindow, true>
+                                   : k_rowinv_cplx<R, NT, false, kGradSteSigmoid, true>;
+    }
     launch_kernel(k, blocks, NT, st, jobs, pd.ws_b, pd.tw, P, pd.G, c.complex_field, c.real_part, tg.rows, tg.mask,
-                  pd.partial, c.inten_out, c.grad_samples, c.grad_phase, pd.vb, c.grad_p0, c.grad_p1);
+                  pd.partial, c.inten_out, c.grad_samples, c.grad_phase, pd.vb, c.grad_p0, c.grad_p1, c.out_win);
   } else if constexpr (kTiledB<R>) {
     // WALK (r05): a plane-cache walk batch, the last workgroup decides.  LEAN (r06): the plain
     // FFT-mode launch (the headline), its own instantiation without the plane cache / field /
@@ -1480,12 +1594,13 @@ static hipError_t launch_passes(const PlanDev& pd, const PassCall& c, hipStream_
     // the timings on record were taken with this layout -- tools/isa_cmp.py reports a reordering)
     auto k = k_rowinv_d<R, true>;
     if (!c.walk_planes) k = lean ? k_rowinv_d<R, false, true> : k_rowinv_d<R>;
+    if (c.windowed) k = lean ? k_rowinv_d<R, false, true, true> : k_rowinv_d<R, false, false, true>;
     launch_kernel(k, blocks, 256, st, jobs, pd.ws_b, tg.rows, pd.tw, P, pd.G, pd.partial, c.inten_out, c.field_out,
                   tg.mask, c.inten_by_env, c.plane_mode, c.plane_pool, c.plane_slot, c.plane_spares, c.spare_base,
-                  c.rc_pending, c.rc_cache, c.walk_planes ? *c.walk_planes : WalkPlanesArgs{});
+                  c.rc_pending, c.rc_cache, c.walk_planes ? *c.walk_planes : WalkPlanesArgs{}, c.out_win);
   } else {
-    launch_kernel(k_rowinv<R, NT>, blocks, NT, st, jobs, pd.ws_b, tg.rows, pd.tw, P, pd.G, pd.partial, c.inten_out,
-                  c.field_out, tg.mask, c.inten_by_env);
+    launch_kernel(!c.windowed ? k_rowinv<R, NT> : k_rowinv<R, NT, true>, blocks, NT, st, jobs, pd.ws_b, tg.rows, pd.tw,
+                  P, pd.G, pd.partial, c.inten_out, c.field_out, tg.mask, c.inten_by_env, c.out_win);
   }
   if (tm) tm->end(2, n_jobs, st);
   if (pass_reduces(c))

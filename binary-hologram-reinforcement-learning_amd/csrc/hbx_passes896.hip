@@ -222,12 +222,14 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd896(const JobDesc* __restrict_
 // blockIdx order; full propagations only.  LK = kLoadThreshold (hbx_evaluate_threshold):
 // threshold_load_row makes each of the 28 loaded samples hi where x >= thr and lo elsewhere; slots
 // >= 28 stay zero, not lo.  thr / lo / hi are unused by kLoadReal.
-template <int LK = kLoadReal>
+// WIN (hbx_evaluate_real_window / _threshold_window; off by default): values is compact,
+// [env][CH][win.h][win.w], and sits at win of the grid, which is 0 elsewhere (real_load_row_win).
+template <int LK = kLoadReal, bool WIN = false>
 __global__ __launch_bounds__(256, 3) void k_rowfwd896_real(const JobDesc* __restrict__ jobs,
                                                            const float* __restrict__ values,
                                                            float2* __restrict__ ws_a,
                                                            const float2* __restrict__ tw_glob, int P, int CH,
-                                                           float thr, float lo, float hi) {
+                                                           float thr, float lo, float hi, hbx_window_t win) {
   __shared__ float2 tw[kN];
   __shared__ __attribute__((aligned(16))) float lds[kRowfwd896Scr];
   stage_twiddles<kN, 256>(tw, tw_glob);
@@ -243,11 +245,17 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd896_real(const JobDesc* __rest
   const int y0 = wg.rbw * kGPB;
   const int y = y0 + grp;
   float2 v[32];
-  const float* row = values + (((size_t)jb.env * CH + jb.group * P + pa) * kN + y) * kN;
-  if constexpr (LK == kLoadThreshold)
-    threshold_load_row<kR, kL>(v, row, (size_t)kN * kN, t, thr, lo, hi);
-  else
-    real_load_row<kR, kL>(v, row, (size_t)kN * kN, t);
+  if constexpr (WIN) {
+    const WinRow wr(win, y, t);
+    const size_t ro = wr.in ? WinRow::row_of(win, (size_t)jb.env * CH + jb.group * P + pa, y) : 0;
+    real_load_row_win<kR, kL, LK>(v, values + ro, (size_t)win.h * win.w, wr, thr, lo, hi);
+  } else {
+    const float* row = values + (((size_t)jb.env * CH + jb.group * P + pa) * kN + y) * kN;
+    if constexpr (LK == kLoadThreshold)
+      threshold_load_row<kR, kL>(v, row, (size_t)kN * kN, t, thr, lo, hi);
+    else
+      real_load_row<kR, kL>(v, row, (size_t)kN * kN, t);
+  }
   __syncthreads();  // tw visible
 
   float2* base = ws_a + ((size_t)j * P + pa) * kPlaneA;
@@ -261,13 +269,14 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd896_real(const JobDesc* __rest
 // complex_load_row_weighted scales the 28 loaded samples by scale * weight[env][group][y][x]; slots >= 28
 // stay zero.  LK = kLoadPhase (hbx_simulate_phase): phase[env][CH / 2][896][896] f32 instead of values;
 // phase_load_row forms exp(i pi x) of the 28 loaded samples, and slots >= 28 are zero there too.
-template <int LK = kLoadComplex>
+// WIN (hbx_backward_window; kLoadComplex and kLoadWeighted): compact values and weight at win, 0 elsewhere.
+template <int LK = kLoadComplex, bool WIN = false>
 __global__ __launch_bounds__(256, 3) void k_rowfwd896_cplx(const JobDesc* __restrict__ jobs,
                                                            const float2* __restrict__ values,
                                                            float2* __restrict__ ws_a,
                                                            const float2* __restrict__ tw_glob, int P, int CH,
                                                            const float* __restrict__ weight, float scale,
-                                                           const float* __restrict__ phase) {
+                                                           const float* __restrict__ phase, hbx_window_t win) {
   __shared__ float2 tw[kN];
   __shared__ __attribute__((aligned(16))) float lds[kRowfwd896Scr];
   stage_twiddles<kN, 256>(tw, tw_glob);
@@ -282,13 +291,21 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd896_cplx(const JobDesc* __rest
   const int y0 = wg.rbw * kGPB;
   const int y = y0 + grp;
   float2 v[32];
-  const size_t row = (((size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q) * kN + y) * kN;
-  if constexpr (LK == kLoadWeighted)
-    complex_load_row_weighted<kR, kL>(v, values + row, weight + (((size_t)jb.env * (CH / P) + jb.group) * kN + y) * kN, scale, t);
-  else if constexpr (LK == kLoadPhase)
-    phase_load_row<kR, kL>(v, phase + row, t);
-  else
-    complex_load_row<kR, kL>(v, values + row, t);
+  if constexpr (WIN) {
+    static_assert(LK != kLoadPhase, "phase leaves are not windowed");
+    const WinRow wr(win, y, t);
+    const size_t ro = wr.in ? WinRow::row_of(win, (size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q, y) : 0;
+    const size_t wo = wr.in ? WinRow::row_of(win, (size_t)jb.env * (CH / P) + jb.group, y) : 0;
+    complex_load_row_win<kR, kL, LK>(v, values + ro, LK == kLoadWeighted ? weight + wo : nullptr, scale, wr);
+  } else {
+    const size_t row = (((size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q) * kN + y) * kN;
+    if constexpr (LK == kLoadWeighted)
+      complex_load_row_weighted<kR, kL>(v, values + row, weight + (((size_t)jb.env * (CH / P) + jb.group) * kN + y) * kN, scale, t);
+    else if constexpr (LK == kLoadPhase)
+      phase_load_row<kR, kL>(v, phase + row, t);
+    else
+      complex_load_row<kR, kL>(v, values + row, t);
+  }
   __syncthreads();  // tw visible
 
   float2* base = ws_a + ((size_t)j * P + 2 * wg.q) * kPlaneA;
@@ -467,7 +484,9 @@ struct Rowinv896Lanes {
   }
 };
 
-template <bool LEAN>
+// WIN (hbx_evaluate_real_window / _threshold_window): k_rowinv_d's -- compact target, intensity and field
+// over the output window win, a row block outside it reads nothing from B, no plane cache.
+template <bool LEAN, bool WIN = false>
 __global__ __launch_bounds__(256, 2) void k_rowinv896(const JobDesc* __restrict__ jobs,
                                                       const float2* __restrict__ ws_b,
                                                       const float* __restrict__ target,
@@ -478,11 +497,12 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896(const JobDesc* __restrict_
                                                       int inten_by_env, int plane_mode,
                                                       float* __restrict__ plane_pool,
                                                       const int32_t* __restrict__ plane_slot, int plane_spares,
-                                                      int spare_base) {
+                                                      int spare_base, hbx_window_t win) {
   if constexpr (LEAN) {   // (r06) the plain FFT-mode launch: no plane-cache / field code (as k_rowinv_d)
     plane_mode = kPlanesOff;
     field_out = nullptr;
   }
+  if constexpr (WIN) plane_mode = kPlanesOff;
   __shared__ float2 tw[kN];
   __shared__ float2 scratch[kSCR];
   __shared__ double red[kGPB][3];
@@ -498,7 +518,14 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896(const JobDesc* __restrict_
     rowinv_zero_partial(partial, j, kRB, rb);
     return;
   }
+  if constexpr (WIN) {
+    if (rowinv_block_outside(win, rb * kGPB, kGPB)) {   // uniform per block
+      rowinv_zero_partial(partial, j, kRB, rb);
+      return;
+    }
+  }
   const int y = rb * kGPB + grp;
+  const WinRow wr(win, y, t);   // (WIN alone reads it)
   const __amdgpu_buffer_rsrc_t rs = plane_rsrc(ws_b + (size_t)j * P * kPlaneB, (unsigned)((size_t)P * kPlaneB * 8));
   const Rowinv896Lanes ln(y, t);
   auto load_plane = [&](float2 (&v)[32], int p) { rowinv_load_plane(v, ln, rs, p); };
@@ -509,7 +536,8 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896(const JobDesc* __restrict_
   const PlaneCache<kR, kL> pc(jb, j, y, G, P, plane_spares, spare_base, plane_pool, plane_slot);   // (r06)
   auto finish_plane = [&](float2 (&v)[32], int p) {
     fft896_sn<true, kInvScalar>(v, t, sc, tw);      // slot layout in, natural out: x = t + 32 j
-    plane_out<kR, kL>(v, acc, pc, jb, G, P, p, t, field_out, plane_mode);
+    if constexpr (WIN) plane_out_win<kR, kL>(v, acc, jb, G, P, p, y, win, wr, field_out);
+    else plane_out<kR, kL>(v, acc, pc, jb, G, P, p, t, field_out, plane_mode);
   };
   float2 v[32];
   if (plane_mode == kPlanesStep) {   // only the flipped plane's pair is in B
@@ -525,8 +553,11 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896(const JobDesc* __restrict_
   }
   // the tail without the SC1, target-ahead and non-temporal forms (there is no walk batch, peeled last
   // plane or fused reconcile at 896; the env-major intensity keeps the plain store it has had)
-  rowinv_epilogue<kR, kL, kGPB, false, false, false>(acc, P, G, jb, j, y, rb, grp, t, target, tmask, inten_out,
-                                                     inten_by_env, partial, red);
+  if constexpr (WIN)
+    rowinv_epilogue_win<kR, kL, kGPB>(acc, P, G, jb, j, y, rb, grp, t, target, tmask, inten_out, partial, red, win, wr);
+  else
+    rowinv_epilogue<kR, kL, kGPB, false, false, false>(acc, P, G, jb, j, y, rb, grp, t, target, tmask, inten_out,
+                                                       inten_by_env, partial, red);
 }
 
 // Pass 3 on complex fields (hbx_simulate_complex): B planes 2q and 2q + 1 hold the column-pass
@@ -543,7 +574,9 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896(const JobDesc* __restrict_
 // (same shape) is the only output (phase_grad_row on the 28 pixels of a lane).
 // GK = kGradSteWindow / kGradSteSigmoid (hbx_threshold_backward): grad = gvb s(x) Re g for the real
 // leaf x of a binary hologram (in `phase`), s and (ga, gb) as ste_grad_row has them.
-template <bool ST = false, int GK = kGradNone>
+// WIN (hbx_backward_window; kGradNone and the two STE kinds, never ST): the one output, real_out or grad,
+// is compact over the window win, as are the leaf's samples (grad_row_win); a row block outside it reads nothing.
+template <bool ST = false, int GK = kGradNone, bool WIN = false>
 __global__ __launch_bounds__(256, 2) void k_rowinv896_cplx(const JobDesc* __restrict__ jobs,
                                                            const float2* __restrict__ ws_b,
                                                            const float2* __restrict__ tw_glob, int P, int G,
@@ -554,8 +587,9 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896_cplx(const JobDesc* __rest
                                                            float* __restrict__ inten_out,
                                                            const float* __restrict__ phase,
                                                            float* __restrict__ grad, float gvb, float ga,
-                                                           float gb) {
+                                                           float gb, hbx_window_t win) {
   static_assert(!(ST && GK != kGradNone), "the gradient forms run no statistics");
+  static_assert(!(WIN && (ST || GK == kGradPhase)), "windows: the real part or an STE gradient");
   __shared__ float2 tw[kN];
   __shared__ float2 scratch[kSCR];
   for (int i = threadIdx.x; i < kN; i += 256) tw[i] = tw_glob[i];
@@ -570,7 +604,11 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896_cplx(const JobDesc* __rest
     if constexpr (ST) rowinv_zero_partial(partial, j, kRB, rb);
     return;
   }
+  if constexpr (WIN) {
+    if (rowinv_block_outside(win, rb * kGPB, kGPB)) return;   // uniform per block
+  }
   const int y = rb * kGPB + grp;
+  const WinRow wr(win, y, t);   // (WIN alone reads it)
   const int Q = P / 2;                            // complex planes per group
   const __amdgpu_buffer_rsrc_t rs = plane_rsrc(ws_b + (size_t)j * P * kPlaneB, (unsigned)((size_t)P * kPlaneB * 8));
   const Rowinv896Lanes ln(y, t);
@@ -593,7 +631,10 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896_cplx(const JobDesc* __rest
       for (int k = 0; k < kL; ++k) acc[k] += fmaf(v[k].x, v[k].x, v[k].y * v[k].y);
     }
     const size_t row = row0 + (size_t)q * kN * kN;
-    if constexpr (GK == kGradPhase) {
+    if constexpr (WIN) {
+      const size_t ro = wr.in ? WinRow::row_of(win, ((size_t)jb.env * G + jb.group) * Q + q, y) : 0;
+      grad_row_win<kR, kL, GK>(v, phase + ro, (GK == kGradNone ? real_out : grad) + ro, wr, gvb, ga, gb);
+    } else if constexpr (GK == kGradPhase) {
       phase_grad_row<kR, kL>(v, phase + row, grad + row);
     } else if constexpr (GK != kGradNone) {
       ste_grad_row<kR, kL, GK>(v, phase + row, grad + row, gvb, ga, gb);
@@ -632,15 +673,22 @@ hipError_t run_jobs_896(const PlanDev& pd, const PassCall& c, hipStream_t st) {
   const unsigned blocks = (unsigned)n_jobs * kRB;   // one workgroup per row block of a job
 
   if (tm) tm->begin(0, st);
+  // (the windowed forms are named behind the others, here and below: they come last in the code object)
+  const bool win_in = pass_window_in(c, kN);
   if (pass_complex(c))   // the load kind: complex samples as they are, times scale * weight, or exp(i pi phase)
-    launch_kernel(c.complex_weight ? k_rowfwd896_cplx<kLoadWeighted>
-                                   : c.complex_values ? k_rowfwd896_cplx<kLoadComplex> : k_rowfwd896_cplx<kLoadPhase>,
+    launch_kernel(!win_in ? (c.complex_weight ? k_rowfwd896_cplx<kLoadWeighted>
+                                 : c.complex_values ? k_rowfwd896_cplx<kLoadComplex> : k_rowfwd896_cplx<kLoadPhase>)
+                              : (c.complex_weight ? k_rowfwd896_cplx<kLoadWeighted, true>
+                                                  : k_rowfwd896_cplx<kLoadComplex, true>),
                   blocks * (P / 2), 256, st, jobs, c.complex_values, pd.ws_a, pd.tw, P, CH, c.complex_weight,
-                  c.complex_scale, c.phase_values);
+                  c.complex_scale, c.phase_values, c.in_win);
   else if (c.real_values)
     // the load kind: the samples as they are, or (hbx_evaluate_threshold) the field of the bit [x >= threshold]
-    launch_kernel(!c.real_binarize ? k_rowfwd896_real<kLoadReal> : k_rowfwd896_real<kLoadThreshold>, blocks * (P / 2),
-                  256, st, jobs, c.real_values, pd.ws_a, pd.tw, P, CH, c.real_threshold, pd.va, pd.va + pd.vb);
+    launch_kernel(!win_in ? (!c.real_binarize ? k_rowfwd896_real<kLoadReal> : k_rowfwd896_real<kLoadThreshold>)
+                              : (!c.real_binarize ? k_rowfwd896_real<kLoadReal, true>
+                                                  : k_rowfwd896_real<kLoadThreshold, true>),
+                  blocks * (P / 2), 256, st, jobs, c.real_values, pd.ws_a, pd.tw, P, CH, c.real_threshold, pd.va,
+                  pd.va + pd.vb, c.in_win);
   else
     launch_kernel(k_rowfwd896, blocks / kRit896 * (pair ? 1 : P / 2), 256, st, jobs,
                   reinterpret_cast<const uint32_t*>(c.mask), pd.ws_a, pd.tw, P, CH, pd.va, pd.vb, pair);
@@ -656,18 +704,23 @@ hipError_t run_jobs_896(const PlanDev& pd, const PassCall& c, hipStream_t st) {
                            // kGradPhase (hbx_phase_backward): the phase gradient instead of the field;
                            // kGradSte* (hbx_threshold_backward): a binary hologram's gated gradient
     const int gk = c.grad_phase ? c.grad_kind : kGradNone;
-    launch_kernel(gk == kGradNone ? (c.complex_stats ? k_rowinv896_cplx<true> : k_rowinv896_cplx<false>)
-                  : gk == kGradPhase ? k_rowinv896_cplx<false, kGradPhase>
-                  : gk == kGradSteWindow ? k_rowinv896_cplx<false, kGradSteWindow>
-                                         : k_rowinv896_cplx<false, kGradSteSigmoid>,
-                  blocks, 256, st, jobs, pd.ws_b, pd.tw, P, pd.G, c.complex_field, c.real_part, tg.rows, tg.mask,
-                  pd.partial, c.inten_out, c.grad_samples, c.grad_phase, pd.vb, c.grad_p0, c.grad_p1);
+    auto k = gk == kGradNone ? (c.complex_stats ? k_rowinv896_cplx<true> : k_rowinv896_cplx<false>)
+             : gk == kGradPhase ? k_rowinv896_cplx<false, kGradPhase>
+             : gk == kGradSteWindow ? k_rowinv896_cplx<false, kGradSteWindow>
+                                    : k_rowinv896_cplx<false, kGradSteSigmoid>;
+    if (c.windowed)   // the real part or an STE gradient over out_win (check_pass_call)
+      k = gk == kGradNone ? k_rowinv896_cplx<false, kGradNone, true>
+          : gk == kGradSteWindow ? k_rowinv896_cplx<false, kGradSteWindow, true>
+                                 : k_rowinv896_cplx<false, kGradSteSigmoid, true>;
+    launch_kernel(k, blocks, 256, st, jobs, pd.ws_b, pd.tw, P, pd.G, c.complex_field, c.real_part, tg.rows, tg.mask,
+                  pd.partial, c.inten_out, c.grad_samples, c.grad_phase, pd.vb, c.grad_p0, c.grad_p1, c.out_win);
   } else {
     // (r06) the plain FFT-mode launch gets the lean instantiation (profiles/r06/rowinv896_lean_ab_r06i.txt)
     const bool lean = c.plane_mode == kPlanesOff && !c.field_out;
-    launch_kernel(lean ? k_rowinv896<true> : k_rowinv896<false>, blocks, 256, st, jobs, pd.ws_b, tg.rows, pd.tw, P,
-                  pd.G, pd.partial, c.inten_out, c.field_out, tg.mask, c.inten_by_env, c.plane_mode, c.plane_pool,
-                  c.plane_slot, c.plane_spares, c.spare_base);
+    launch_kernel(!c.windowed ? (lean ? k_rowinv896<true> : k_rowinv896<false>)
+                              : (lean ? k_rowinv896<true, true> : k_rowinv896<false, true>),
+                  blocks, 256, st, jobs, pd.ws_b, tg.rows, pd.tw, P, pd.G, pd.partial, c.inten_out, c.field_out, tg.mask,
+                  c.inten_by_env, c.plane_mode, c.plane_pool, c.plane_slot, c.plane_spares, c.spare_base, c.out_win);
   }
   if (tm) tm->end(2, n_jobs, st);
   if (pass_reduces(c))   // (skip_reduce is refused at 896: check_pass_call)

@@ -304,6 +304,105 @@ __device__ __forceinline__ void ste_grad_row(const V (&v)[NV], const float* __re
 }
 
 // ---------------------------------------------------------------------------
+// Windows (hbx_*_window): an array that belongs to a window of the grid is compact, [..][h][w] with
+// row pitch w, and the row passes reach it through a predicate on their per-element loads and stores.
+// WinRow is row y of such an array as lane t sees it: whether the row is inside, and for pixel
+// x = t + R k its index x - x0 in the compact row -- unsigned, so one compare tells 0 <= x - x0 < w.
+struct WinRow {
+  bool in;        // y0 <= y < y0 + h: no load or store of any lane otherwise
+  unsigned w;
+  int xo;         // t - x0
+  __device__ __forceinline__ WinRow(const hbx_window_t& win, int y, int t)
+      : in((unsigned)(y - win.y0) < (unsigned)win.h), w((unsigned)win.w), xo(t - win.x0) {}
+  __device__ __forceinline__ bool has(int xk) const { return in && (unsigned)(xo + xk) < w; }
+  // element offset of row y of plane `plane` of a compact [planes][h][w] array
+  __device__ __forceinline__ static size_t row_of(const hbx_window_t& win, size_t plane, int y) {
+    return (plane * (size_t)win.h + (size_t)(y - win.y0)) * (size_t)win.w;
+  }
+};
+
+// real_load_row / threshold_load_row (LK) on a hologram zero-filled into the grid: rowa = the compact
+// row of plane pa (dereferenced only where wr.has), the same row of plane pb one compact plane further.
+// A pixel outside the window is 0 -- no light, not the field `lo` of an unset bit -- and issues no load.
+template <int R, int L, int LK, class V>
+__device__ __forceinline__ void real_load_row_win(V (&v)[R], const float* __restrict__ rowa, size_t plane,
+                                                  const WinRow& wr, float thr, float lo, float hi) {
+  const float* rowb = rowa + plane;
+  float a[L], b[L];
+#pragma unroll
+  for (int jj = 0; jj < L; ++jj) a[jj] = wr.has(R * jj) ? __builtin_nontemporal_load(rowa + wr.xo + R * jj) : 0.0f;
+#pragma unroll
+  for (int jj = 0; jj < L; ++jj) b[jj] = wr.has(R * jj) ? __builtin_nontemporal_load(rowb + wr.xo + R * jj) : 0.0f;
+#pragma unroll
+  for (int jj = 0; jj < L; ++jj) {
+    if constexpr (LK == kLoadThreshold)
+      v[jj] = wr.has(R * jj) ? V{a[jj] >= thr ? hi : lo, b[jj] >= thr ? hi : lo} : V{0.f, 0.f};
+    else
+      v[jj] = V{a[jj], b[jj]};
+  }
+#pragma unroll
+  for (int jj = L; jj < R; ++jj) v[jj] = V{0.f, 0.f};
+}
+
+// complex_load_row / complex_load_row_weighted (LK) on compact rows embedded at the window: row and wrow
+// = the compact rows of the samples and of the group's weight (the same window); the weighted form's
+// three multiplies, in its order.  0 outside the window, and no load there.
+template <int R, int L, int LK, class V>
+__device__ __forceinline__ void complex_load_row_win(V (&v)[R], const float2* __restrict__ row,
+                                                     const float* __restrict__ wrow, float scale, const WinRow& wr) {
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  const f32x2* r2 = reinterpret_cast<const f32x2*>(row);
+  f32x2 s[L];
+#pragma unroll
+  for (int jj = 0; jj < L; ++jj)
+    s[jj] = wr.has(R * jj) ? __builtin_nontemporal_load(r2 + wr.xo + R * jj) : f32x2{0.f, 0.f};
+  if constexpr (LK == kLoadWeighted) {
+    float w[L];
+#pragma unroll
+    for (int jj = 0; jj < L; ++jj) w[jj] = wr.has(R * jj) ? wrow[wr.xo + R * jj] : 0.0f;
+#pragma unroll
+    for (int jj = 0; jj < L; ++jj) {
+      const float m = scale * w[jj];
+      v[jj] = wr.has(R * jj) ? V{s[jj].x * m, s[jj].y * m} : V{0.f, 0.f};
+    }
+  } else {
+#pragma unroll
+    for (int jj = 0; jj < L; ++jj) v[jj] = V{s[jj].x, s[jj].y};
+  }
+#pragma unroll
+  for (int jj = L; jj < R; ++jj) v[jj] = V{0.f, 0.f};
+}
+
+// The complex last passes' stores over an output window: g0 / p0 = the compact rows of the output and
+// of the leaf's samples (dereferenced only where wr.has).  GK = kGradNone: the real part of the plane
+// (the gradient of a real leaf); the two STE kinds: ste_grad_row's expressions on the pixels inside.
+template <int R, int L, int GK, class V, int NV>
+__device__ __forceinline__ void grad_row_win(const V (&v)[NV], const float* __restrict__ p0, float* __restrict__ g0,
+                                             const WinRow& wr, float vb, float a, float b) {
+  static_assert(GK == kGradNone || GK == kGradSteWindow || GK == kGradSteSigmoid, "real part or a surrogate kind");
+  if constexpr (GK == kGradNone) {
+#pragma unroll
+    for (int k = 0; k < L; ++k)
+      if (wr.has(R * k)) g0[wr.xo + R * k] = v[k].x;
+  } else {
+    float x[L];
+#pragma unroll
+    for (int k = 0; k < L; ++k) x[k] = wr.has(R * k) ? __builtin_nontemporal_load(p0 + wr.xo + R * k) : 0.0f;
+#pragma unroll
+    for (int k = 0; k < L; ++k) {
+      if (!wr.has(R * k)) continue;
+      if constexpr (GK == kGradSteWindow) {
+        g0[wr.xo + R * k] = (x[k] >= a && x[k] <= b) ? vb * v[k].x : 0.0f;
+      } else {
+        const float e = expf(-fabsf(b * (x[k] - a)));
+        const float d = 1.0f + e;
+        g0[wr.xo + R * k] = vb * (b * e / (d * d)) * v[k].x;
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Staged slot-tile stores of the column passes (k_col2 at N = 1024 / 256, k_col896 since r04):
 // the output line sets of a block (TL lines: group g = slot g of slot tile st, TileB) go out
 // through the groups' FFT scratch regions.  The writer puts row y of its line at col2_pos(g / 2,

@@ -283,4 +283,79 @@ __device__ __forceinline__ void rowinv_epilogue(float (&acc)[L], int P, int G, c
   }
 }
 
+// ---------------------------------------------------------------------------
+// The last pass over an output window (hbx_*_window; WinRow, hbx_rowcol.hpp)
+// ---------------------------------------------------------------------------
+// a row block [y0, y0 + rows) that shares no row with the window: it has nothing to read from B
+__device__ __forceinline__ bool rowinv_block_outside(const hbx_window_t& win, int y0, int rows) {
+  return y0 + rows <= win.y0 || y0 >= win.y0 + win.h;
+}
+
+// plane_out without the plane cache: |U_p|^2 of every pixel into acc (the lanes outside the window carry
+// theirs along unused), the field only inside the window, to the compact [env][G*P][h][w] field_out
+template <int R, int L, class V, int NV>
+__device__ __forceinline__ void plane_out_win(const V (&v)[NV], float (&acc)[L], const JobDesc& jb, int G, int P,
+                                              int p, int y, const hbx_window_t& win, const WinRow& wr,
+                                              float2* field_out) {
+#pragma unroll
+  for (int k = 0; k < L; ++k) acc[k] += fmaf(v[k].x, v[k].x, v[k].y * v[k].y);
+  if (field_out) {
+    float2* frow = field_out + WinRow::row_of(win, (size_t)jb.env * G * P + jb.group * P + p, y);
+#pragma unroll
+    for (int k = 0; k < L; ++k)
+      if (wr.has(R * k)) frow[wr.xo + R * k] = make_float2(v[k].x, v[k].y);
+  }
+}
+
+// rowinv_epilogue over the window: the plane mean, the target row's loads, the job-major intensity
+// stores and the f64 terms only for the pixels inside, in rowinv_epilogue's order -- over the lane's k,
+// the group's lanes, the block's rows -- so the partials are its sums without the terms outside.  target
+// and inten_out are compact, [env][G][h][w] and [job][h][w]; tmask = 0: the plan's zero row (w <= N).
+template <int R, int L, int GPB>
+__device__ __forceinline__ void rowinv_epilogue_win(float (&acc)[L], int P, int G, const JobDesc& jb, int j, int y,
+                                                    int rb, int grp, int t, const float* __restrict__ target,
+                                                    size_t tmask, float* __restrict__ inten_out,
+                                                    double* __restrict__ partial, double (&red)[GPB][3],
+                                                    const hbx_window_t& win, const WinRow& wr) {
+  constexpr int N = R * L;
+  constexpr int RB = N / GPB;
+  const float invp = 1.0f / (float)P;
+  const float* trow = target + ((wr.in ? WinRow::row_of(win, (size_t)jb.env * G + jb.group, y) : (size_t)0) & tmask);
+  double sxy = 0.0, sxx = 0.0, syy = 0.0;
+  float T[L];
+#pragma unroll
+  for (int k = 0; k < L; ++k) T[k] = wr.has(R * k) ? trow[wr.xo + R * k] : 0.0f;
+#pragma unroll
+  for (int k = 0; k < L; ++k) {
+    const float I = acc[k] * invp;
+    acc[k] = I;
+    if (wr.has(R * k)) {
+      sxy = fma((double)I, (double)T[k], sxy);
+      sxx = fma((double)I, (double)I, sxx);
+      syy = fma((double)T[k], (double)T[k], syy);
+    }
+  }
+  if (inten_out && wr.in) {
+    float* orow = inten_out + WinRow::row_of(win, (size_t)j, y);
+#pragma unroll
+    for (int k = 0; k < L; ++k)
+      if (wr.has(R * k)) orow[wr.xo + R * k] = acc[k];
+  }
+  // reduce over the R lanes of the group, fixed order -> bitwise reproducible
+#pragma unroll
+  for (int off = R / 2; off >= 1; off >>= 1) {
+    sxy += __shfl_xor(sxy, off, 64);
+    sxx += __shfl_xor(sxx, off, 64);
+    syy += __shfl_xor(syy, off, 64);
+  }
+  if (t == 0) { red[grp][0] = sxy; red[grp][1] = sxx; red[grp][2] = syy; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double a = 0.0, b = 0.0, cc = 0.0;
+    for (int g = 0; g < GPB; ++g) { a += red[g][0]; b += red[g][1]; cc += red[g][2]; }
+    double* o = partial + ((size_t)j * RB + rb) * 3;
+    o[0] = a; o[1] = b; o[2] = cc;
+  }
+}
+
 }  // namespace hbx

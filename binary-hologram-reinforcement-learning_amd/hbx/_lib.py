@@ -46,6 +46,8 @@ EXPORTED_SYMBOLS = (
     "hbx_evaluate_real", "hbx_evaluate_complex", "hbx_loss", "hbx_loss_weight",
     "hbx_simulate_phase", "hbx_evaluate_phase", "hbx_phase_backward",
     "hbx_evaluate_threshold", "hbx_threshold_backward",
+    "hbx_evaluate_real_window", "hbx_evaluate_threshold_window", "hbx_backward_window",
+    "hbx_loss_window", "hbx_loss_weight_window",
 )
 NUM_PASSES = 5
 PASS_NAMES = ("k_rowfwd", "k_col", "k_rowinv", "k_psf_eval", "k_psf_commit")
@@ -69,6 +71,11 @@ class Optics(C.Structure):
         ("tf_kind", C.c_int32), ("field_kind", C.c_int32), ("rel_scale", C.c_int32),
         ("reserved", C.c_int32), ("peak", C.c_double),
     ]
+
+
+class Window(C.Structure):
+    """hbx_window_t (include/hbx.h): a rectangle (y0, x0, h, w) of the plan's N x N grid."""
+    _fields_ = [("y0", C.c_int32), ("x0", C.c_int32), ("h", C.c_int32), ("w", C.c_int32)]
 
 
 class DbsWalk(C.Structure):
@@ -144,6 +151,12 @@ def _declare(lib):
     lib.hbx_phase_backward.argtypes = [VP, VP, VP, C.c_float, VP, I32, VP, VP]
     lib.hbx_evaluate_threshold.argtypes = [VP, VP, C.c_float, VP, I32, VP, VP, VP, VP, VP]
     lib.hbx_threshold_backward.argtypes = [VP, VP, VP, C.c_float, VP, I32, C.c_float, C.c_float, I32, VP, VP]
+    WP = C.POINTER(Window)
+    lib.hbx_evaluate_real_window.argtypes = [VP, VP, WP, VP, WP, I32, VP, VP, VP, VP, VP]
+    lib.hbx_evaluate_threshold_window.argtypes = [VP, VP, C.c_float, WP, VP, WP, I32, VP, VP, VP, VP, VP]
+    lib.hbx_backward_window.argtypes = [VP, VP, VP, C.c_float, WP, VP, I32, C.c_float, C.c_float, WP, I32, VP, VP]
+    lib.hbx_loss_window.argtypes = [VP, VP, WP, I32, I32, I32, VP, VP]
+    lib.hbx_loss_weight_window.argtypes = [VP, VP, VP, VP, VP, WP, I32, I32, I32, VP, VP]
     lib.hbx_loss.argtypes = [VP, VP, I32, I32, I32, VP, VP]
     lib.hbx_loss_weight.argtypes = [VP, VP, VP, VP, VP, I32, I32, I32, VP, VP]
     lib.hbx_flip_map.argtypes = [VP, VP, VP, VP, VP, VP]

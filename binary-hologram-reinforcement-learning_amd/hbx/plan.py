@@ -580,6 +580,129 @@ class Plan:
                                             _stream(stream)), "hbx_loss_weight")
         return weight
 
+    # --- windows (hbx_*_window): holograms of any size zero-filled into the grid, outputs over a rectangle ---
+    def window(self, win):
+        """(y0, x0, h, w) | None -> (the _lib.Window to pass, or None for the full grid, and its
+        (h, w)).  A window outside the grid or empty raises ValueError before any device work."""
+        c = self.cfg
+        if win is None:
+            return None, (c.height, c.width)
+        y0, x0, h, w = (int(v) for v in win)
+        if y0 < 0 or x0 < 0 or h < 1 or w < 1 or y0 + h > c.height or x0 + w > c.width:
+            raise ValueError(f"window {(y0, x0, h, w)}: not a non-empty rectangle of the {c.height} x {c.width} grid")
+        return _lib.Window(y0, x0, h, w), (h, w)
+
+    def _evaluate_window(self, name, values, threshold, in_win, target, out_win, want_field, want_intensity, stream):
+        n = values.shape[0] if isinstance(values, torch.Tensor) and values.dim() else 0
+        c = self.cfg
+        wi, (hi, wd_i) = self.window(in_win)
+        wo, (ho, wd_o) = self.window(out_win)
+        _need(values, "values", torch.float32, (n, c.channels, hi, wd_i), self.device)
+        values = values.resolve_neg()              # a lazily negated view shares the un-negated memory
+        if target is not None:
+            _need(target, "target", torch.float32, (n, c.groups, ho, wd_o), self.device)
+        elif not (want_field or want_intensity):
+            raise ValueError(f"{name}: no target, and want_field and want_intensity are both off")
+        field = torch.empty((n, c.channels, ho, wd_o, 2), dtype=torch.float32,
+                            device=self.device) if want_field else None
+        inten = torch.empty((n, c.groups, ho, wd_o), dtype=torch.float32, device=self.device) if want_intensity else None
+        stats = psnr = None
+        if target is not None:
+            stats = torch.empty((n, c.groups, 3), dtype=torch.float64, device=self.device)
+            psnr = torch.empty((n,), dtype=torch.float64, device=self.device)
+        pi, po = (C.byref(wi) if wi is not None else None), (C.byref(wo) if wo is not None else None)
+        if threshold is None:
+            rc = self.lib.hbx_evaluate_real_window(self._h, _ptr(values), pi, _ptr(target), po, n, _ptr(field),
+                                                   _ptr(inten), _ptr(stats), _ptr(psnr), _stream(stream))
+        else:
+            rc = self.lib.hbx_evaluate_threshold_window(self._h, _ptr(values), float(threshold), pi, _ptr(target), po,
+                                                        n, _ptr(field), _ptr(inten), _ptr(stats), _ptr(psnr),
+                                                        _stream(stream))
+        _lib.check(rc, "hbx_" + name)
+        return (torch.view_as_complex(field) if want_field else None), inten, stats, psnr
+
+    def evaluate_real_window(self, values: torch.Tensor, in_win=None, target: Optional[torch.Tensor] = None,
+                             out_win=None, want_field: bool = True, want_intensity: bool = True, stream=None):
+        """`evaluate_real` of a hologram of any size (hbx_evaluate_real_window): `values` float32
+        [B, CH, h_i, w_i] sits at in_win = (y0, x0, h_i, w_i) of the grid, which is 0 elsewhere; the
+        outputs are taken over out_win = (y0, x0, h_o, w_o).  Windows are compact arrays: target and
+        intensity [B, G, h_o, w_o], field [B, CH, h_o, w_o]; chan_stats and psnr (with a target) are
+        over out_win, n = G h_o w_o.  None is the full grid.  Returns (field | None, intensity |
+        None, chan_stats | None, psnr | None): `evaluate_real` on the zero-embedded values, sliced."""
+        return self._evaluate_window("evaluate_real_window", values, None, in_win, target, out_win, want_field,
+                                     want_intensity, stream)
+
+    def evaluate_threshold_window(self, values: torch.Tensor, threshold: float, in_win=None,
+                                  target: Optional[torch.Tensor] = None, out_win=None, want_field: bool = True,
+                                  want_intensity: bool = True, stream=None):
+        """`evaluate_real_window` of the binary hologram m = [values >= threshold], u = va + vb m
+        inside in_win and 0 (no light) outside it, under either field kind
+        (hbx_evaluate_threshold_window)."""
+        return self._evaluate_window("evaluate_threshold_window", values, threshold, in_win, target, out_win,
+                                     want_field, want_intensity, stream)
+
+    def backward_window(self, values: torch.Tensor, val_win=None, grad_win=None,
+                        samples: Optional[torch.Tensor] = None, weight: Optional[torch.Tensor] = None,
+                        scale: float = 1.0, surrogate: int = _lib.STE_WINDOW, p0: float = -math.inf,
+                        p1: float = math.inf, stream=None) -> torch.Tensor:
+        """The backward pass of a windowed forward, on the plan for -z (hbx_backward_window):
+        `values` complex64 [B, CH/2, h_v, w_v] and the optional `weight` float32 [B, G, h_v, w_v]
+        sit at val_win (the forward's output window), and the gradient float32 [B, CH/2, h_g, w_g]
+        is taken over grad_win (the forward's input window).  samples None: the real part (a real
+        leaf's gradient); samples [B, CH/2, h_g, w_g] (the leaf): `threshold_backward`'s
+        vb s(x) Re g with its surrogates."""
+        n = values.shape[0] if isinstance(values, torch.Tensor) and values.dim() else 0
+        c = self.cfg
+        wv, (hv, wd_v) = self.window(val_win)
+        wg, (hg, wd_g) = self.window(grad_win)
+        _need(values, "values", torch.complex64, (n, c.channels // 2, hv, wd_v), self.device)
+        values = values.resolve_conj().resolve_neg()   # as simulate_complex: the kernel reads the memory
+        gshape = (n, c.channels // 2, hg, wd_g)
+        if samples is not None:
+            _need(samples, "samples", torch.float32, gshape, self.device)
+            samples = samples.resolve_neg()
+        if weight is not None:
+            _need(weight, "weight", torch.float32, (n, c.groups, hv, wd_v), self.device)
+            weight = weight.resolve_neg()
+        grad = torch.empty(gshape, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.hbx_backward_window(self._h, _ptr(values), _ptr(weight), float(scale),
+                                                C.byref(wv) if wv is not None else None, _ptr(samples),
+                                                int(surrogate), float(p0), float(p1),
+                                                C.byref(wg) if wg is not None else None, n, _ptr(grad),
+                                                _stream(stream)), "hbx_backward_window")
+        return grad
+
+    def loss_window(self, chan_stats: torch.Tensor, out_win=None, kind: int = _lib.LOSS_MSE,
+                    rel_scale: int = _lib.REL_LSQ, stream=None) -> torch.Tensor:
+        """`loss` on the statistics of an output window: n = G h_o w_o (hbx_loss_window)."""
+        n = chan_stats.shape[0] if isinstance(chan_stats, torch.Tensor) and chan_stats.dim() else 0
+        wo, _ = self.window(out_win)
+        _need(chan_stats, "chan_stats", torch.float64, (n, self.cfg.groups, 3), self.device)
+        out = torch.empty((n,), dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.hbx_loss_window(self._h, _ptr(chan_stats), C.byref(wo) if wo is not None else None, n,
+                                            int(kind), int(rel_scale), _ptr(out), _stream(stream)), "hbx_loss_window")
+        return out
+
+    def loss_weight_window(self, intensity: torch.Tensor, target: torch.Tensor, chan_stats: torch.Tensor,
+                           out_win=None, grad_loss: Optional[torch.Tensor] = None, kind: int = _lib.LOSS_MSE,
+                           rel_scale: int = _lib.REL_LSQ, stream=None) -> torch.Tensor:
+        """`loss_weight` over an output window (hbx_loss_weight_window): intensity, target and the
+        returned weight are compact float32 [B, G, h_o, w_o], n = G h_o w_o."""
+        n = intensity.shape[0] if isinstance(intensity, torch.Tensor) and intensity.dim() else 0
+        wo, (ho, wd_o) = self.window(out_win)
+        shape = (n, self.cfg.groups, ho, wd_o)
+        _need(intensity, "intensity", torch.float32, shape, self.device)
+        _need(target, "target", torch.float32, shape, self.device)
+        _need(chan_stats, "chan_stats", torch.float64, (n, self.cfg.groups, 3), self.device)
+        if grad_loss is not None:
+            _need(grad_loss, "grad_loss", torch.float64, (n,), self.device)
+        weight = torch.empty(shape, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.hbx_loss_weight_window(self._h, _ptr(intensity), _ptr(target), _ptr(chan_stats),
+                                                   _ptr(grad_loss), C.byref(wo) if wo is not None else None, n,
+                                                   int(kind), int(rel_scale), _ptr(weight), _stream(stream)),
+                   "hbx_loss_weight_window")
+        return weight
+
     def psnr(self, chan_stats: torch.Tensor, stream=None) -> torch.Tensor:
         n = chan_stats.shape[0]
         _need(chan_stats, "chan_stats", torch.float64, (n, self.cfg.groups, 3), self.device)

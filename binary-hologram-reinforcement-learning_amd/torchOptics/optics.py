@@ -210,8 +210,150 @@ def _ste_args(threshold, ste, ste_width, what: str):
     return float(tau), kind, float(tau), float(k)
 
 
+_GRIDS = (64, 256, 896, 1024)   # the sizes libhbx builds
+
+
+def _window_args(grid, origin, roi, shape, complex_in: bool, field_kind: int, thresholded: bool, what: str):
+    """grid / origin / roi of simulate, intensity and loss -> None without a grid, else (N, the
+    hologram's window, the output window), each window (y0, x0, h, w) in grid coordinates.  Every
+    error is raised here, before any GPU use."""
+    if grid is None:
+        if origin is not None or roi is not None:
+            raise ValueError(f"{what}: origin= and roi= place a hologram in grid=, which is not given")
+        return None
+    if isinstance(grid, bool) or not isinstance(grid, (int, np.integer)) or int(grid) not in _GRIDS:
+        raise ValueError(f"{what}: grid must be one of {_GRIDS}, got {grid!r}")
+    n = int(grid)
+    if complex_in:
+        raise ValueError(f"{what}: grid= takes a real leaf, got a complex field")
+    if field_kind == _lib.FIELD_PHASE and not thresholded:
+        raise ValueError(f"{what}: grid= with field=\"phase\" needs threshold= (phase leaves are not windowed)")
+    h, w = int(shape[-2]), int(shape[-1])
+
+    def inside(win, name):
+        try:
+            y0, x0, hh, ww = (int(v) for v in win)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: {name} must be integers, got {win!r}") from None
+        if y0 < 0 or x0 < 0 or hh < 1 or ww < 1 or y0 + hh > n or x0 + ww > n:
+            raise ValueError(f"{what}: {name} {(y0, x0, hh, ww)} is not a non-empty rectangle of the {n} x {n} grid")
+        return y0, x0, hh, ww
+
+    if origin is None:
+        if h > n or w > n:
+            raise ValueError(f"{what}: a {h} x {w} hologram does not fit the {n} x {n} grid")
+        origin = ((n - h) // 2, (n - w) // 2)
+    elif not isinstance(origin, (tuple, list)) or len(origin) != 2:
+        raise ValueError(f"{what}: origin must be (y0, x0), got {origin!r}")
+    in_win = inside((origin[0], origin[1], h, w), "origin + the hologram")
+    if roi is None:
+        return n, in_win, in_win
+    if not isinstance(roi, (tuple, list)) or len(roi) != 4:
+        raise ValueError(f"{what}: roi must be (y0, x0, h, w), got {roi!r}")
+    return n, in_win, inside(roi, "roi")
+
+
+def _window_plan(win, geom, planes: int, field_kind: int, b: int, adjoint: bool = False):
+    """The forward plan of `planes` real planes per group on the window's grid, or (adjoint) the plan
+    for -z of twice as many -- one complex plane per real plane of the leaf"""
+    wls, dx, dy, z, dev, tf_kind = geom
+    n = win[0]
+    if adjoint:
+        return _plan_for(n, n, 2 * planes, wls, dx, dy, -z, b, dev, tf_kind, field_kind)
+    return _plan_for(n, n, planes, wls, dx, dy, z, b, dev, tf_kind, field_kind)
+
+
+def _window_forward(plan, x, win, ste_args, target=None, want_field=True, want_intensity=True):
+    """hbx_evaluate_threshold_window (ste_args) or hbx_evaluate_real_window of the compact leaf"""
+    _, in_win, out_win = win
+    if ste_args is not None:
+        return plan.evaluate_threshold_window(x, ste_args[0], in_win, target, out_win, want_field, want_intensity)
+    return plan.evaluate_real_window(x, in_win, target, out_win, want_field, want_intensity)
+
+
+def _window_backward(adj, values, x, win, ste_args, weight=None, scale=1.0):
+    """One hbx_backward_window on the plan for -z: the values sit at the forward's output window, the
+    gradient is taken over its input window -- the real part, or the STE gate of the leaf x"""
+    _, in_win, out_win = win
+    if ste_args is None:
+        return adj.backward_window(values, out_win, in_win, weight=weight, scale=scale)
+    _, kind, p0, p1 = ste_args
+    return adj.backward_window(values, out_win, in_win, samples=x, weight=weight, scale=scale, surrogate=kind,
+                               p0=p0, p1=p1)
+
+
+class _WindowSimulate(torch.autograd.Function):
+    """x [B, C, h, w] at the input window of the grid -> the field over the output window, through
+    hbx_evaluate_real_window / _threshold_window.  Backward: one hbx_backward_window of grad_output
+    on the plan for -z (crop_in Re A^H embed_out g, STE-gated for a thresholded leaf)."""
+
+    @staticmethod
+    def forward(ctx, x, geom, win, field_kind, ste_args):
+        ctx.geom, ctx.win, ctx.field_kind, ctx.ste_args = geom, win, field_kind, ste_args
+        ctx.save_for_backward(x)
+        plan = _window_plan(win, geom, x.shape[1], field_kind, x.shape[0])
+        return _window_forward(plan, x, win, ste_args, want_intensity=False)[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        x, = ctx.saved_tensors
+        adj = _window_plan(ctx.win, ctx.geom, x.shape[1], ctx.field_kind, x.shape[0], adjoint=True)
+        g = grad_output.to(torch.complex64).resolve_conj().resolve_neg().contiguous()
+        return _window_backward(adj, g, x, ctx.win, ctx.ste_args), None, None, None, None
+
+
+class _WindowIntensity(torch.autograd.Function):
+    """The plane-mean intensity over the output window; the cropped field is saved, and the backward
+    pass is one hbx_backward_window of it with (2 / P) gI applied in the first pass's load."""
+
+    @staticmethod
+    def forward(ctx, x, geom, win, groups, field_kind, ste_args):
+        ctx.geom, ctx.win, ctx.groups, ctx.field_kind, ctx.ste_args = geom, win, groups, field_kind, ste_args
+        plan = _window_plan(win, geom, x.shape[1] // groups, field_kind, x.shape[0])
+        field, inten, _, _ = _window_forward(plan, x, win, ste_args)
+        ctx.save_for_backward(field, x)
+        return inten
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        field, x = ctx.saved_tensors
+        planes = x.shape[1] // ctx.groups
+        adj = _window_plan(ctx.win, ctx.geom, planes, ctx.field_kind, x.shape[0], adjoint=True)
+        gi = grad_output.to(torch.float32).resolve_neg().contiguous()
+        grad = _window_backward(adj, field, x, ctx.win, ctx.ste_args, weight=gi, scale=2.0 / planes)
+        return grad, None, None, None, None, None
+
+
+class _WindowLoss(torch.autograd.Function):
+    """The relative MSE or PSNR over the output window (n = G h_o w_o); the cropped field, the cropped
+    intensity and the statistics are saved, and the backward pass is hbx_loss_weight_window followed
+    by one hbx_backward_window on the plan for -z."""
+
+    @staticmethod
+    def forward(ctx, x, target, geom, win, groups, kind, rel, field_kind, ste_args):
+        ctx.geom, ctx.win, ctx.groups, ctx.kind, ctx.rel = geom, win, groups, kind, rel
+        ctx.field_kind, ctx.ste_args = field_kind, ste_args
+        plan = _window_plan(win, geom, x.shape[1] // groups, field_kind, x.shape[0])
+        field, inten, stats, _ = _window_forward(plan, x, win, ste_args, target)
+        ctx.save_for_backward(field, inten, stats, target, x)
+        return plan.loss_window(stats, win[2], kind, rel)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        field, inten, stats, target, x = ctx.saved_tensors
+        planes = x.shape[1] // ctx.groups
+        adj = _window_plan(ctx.win, ctx.geom, planes, ctx.field_kind, x.shape[0], adjoint=True)
+        gl = grad_output.to(torch.float64).resolve_neg().contiguous()
+        wgt = adj.loss_weight_window(inten, target, stats, ctx.win[2], gl, ctx.kind, ctx.rel)
+        grad = _window_backward(adj, field, x, ctx.win, ctx.ste_args, weight=wgt, scale=2.0 / planes)
+        return grad, None, None, None, None, None, None, None, None
+
+
 def simulate(x, z: float, strict: bool = False, binary: bool = True, tf="asm", field="amplitude",
-             threshold=None, ste="window", ste_width=0.5, **_) -> torch.Tensor:
+             threshold=None, ste="window", ste_width=0.5, grid=None, origin=None, roi=None, **_) -> torch.Tensor:
     """Free-space propagation of a tensor [B, C, H, W] (or [C, H, W]) by z metres: the
     complex field of every plane, complex64, on the GPU.
 
@@ -238,7 +380,18 @@ def simulate(x, z: float, strict: bool = False, binary: bool = True, tf="asm", f
     hbx_threshold_backward on the plan for -z: dL/dx = vb s(x) Re(A^H g) with vb = 1 or -2 and
     the surrogate derivative s of the step, ste="window": s = 1 on [tau - ste_width, tau +
     ste_width] (math.inf: everywhere), else 0; ste="sigmoid": the derivative of
-    sigmoid((x - tau) / ste_width).  Complex x, or binary=True, with a threshold raises ValueError."""
+    sigmoid((x - tau) / ste_width).  Complex x, or binary=True, with a threshold raises ValueError.
+
+    binary=False with grid=N (64, 256, 896 or 1024; None runs the code above untouched): real x is a
+    hologram [B, C, h, w] of any size h, w <= N, zero-filled into the N x N grid -- outside it there
+    is no light, also for a thresholded field="phase" leaf -- so a guard band costs no F.pad copy and
+    a non-square modulator propagates at all.  origin=(y0, x0) places it (default: centred, ((N - h)
+    // 2, (N - w) // 2)); roi=(y0, x0, h, w) in grid coordinates is the rectangle the field is
+    returned over (default: the hologram's own).  The first pass loads x only inside its rectangle
+    and the last pass stores only the roi (hbx_evaluate_real_window / _threshold_window); the
+    backward pass is one hbx_backward_window on the plan for -z.  A complex x, field="phase"
+    without a threshold, binary=True, or an origin or roi outside the grid raises ValueError before
+    any GPU use."""
     tf_kind = _switch(tf, _TF_NAMES, "tf")
     field_kind = _switch(field, _FIELD_NAMES, "field")
     ste_args = _ste_args(threshold, ste, ste_width, "simulate")
@@ -265,6 +418,9 @@ def simulate(x, z: float, strict: bool = False, binary: bool = True, tf="asm", f
             raise ValueError("tt.simulate: a complex field is used as it is (field=\"amplitude\")")
         if ste_args is not None:
             raise ValueError("tt.simulate: threshold= needs a real leaf, got a complex field")
+    if grid is not None and binary:
+        raise ValueError("simulate: grid= places a real leaf on the continuous path (binary=False)")
+    win = _window_args(grid, origin, roi, t.shape, t.is_complex(), field_kind, ste_args is not None, "simulate")
     if not torch.cuda.is_available():
         raise RuntimeError("tt.simulate needs a ROCm GPU (libhbx.so)")
     if t.is_cuda:
@@ -272,6 +428,20 @@ def simulate(x, z: float, strict: bool = False, binary: bool = True, tf="asm", f
     else:
         dev = torch.cuda.current_device()
         t = t.to(f"cuda:{dev}")
+    if win is not None:
+        # x sits at `origin` of the grid (centred by default), which is dark elsewhere; the field is
+        # returned over `roi` (the hologram's own rectangle by default).  An odd C is padded with a plane
+        # that is sliced off again
+        c = t.shape[1]
+        xs = _pad_real(t, c + (c % 2))
+        geom = (wl, dx, dy, z, dev, tf_kind)
+        if xs.requires_grad and torch.is_grad_enabled():
+            out = _WindowSimulate.apply(xs, geom, win, field_kind, ste_args)
+        else:
+            plan = _window_plan(win, geom, xs.shape[1], field_kind, xs.shape[0])
+            out = _window_forward(plan, xs, win, ste_args, want_intensity=False)[0]
+        out = out[:, :c] if xs.shape[1] != c else out
+        return out[0] if squeeze else out
     if ste_args is not None:
         xs = _phase_samples(t)
         geom = (wl, dx, dy, z, dev, tf_kind)
@@ -565,7 +735,7 @@ class _IntensityThreshold(torch.autograd.Function):
 
 
 def intensity(x, z: float, tf="asm", field="amplitude", save_field: bool = True, threshold=None, ste="window",
-              ste_width=0.5) -> torch.Tensor:
+              ste_width=0.5, grid=None, origin=None, roi=None) -> torch.Tensor:
     """Plane-mean intensity of the propagated field, the quantity every loss of the project goes
     through: float32 [B, G, H, W] (or [G, H, W] for a 3-D x) with
         I[b, g] = mean over the planes p of group g of |IFFT2(FFT2(u[b, p]) H_g(z))|^2,
@@ -599,7 +769,11 @@ def intensity(x, z: float, tf="asm", field="amplitude", save_field: bool = True,
     through hbx_evaluate_threshold; ste and ste_width choose the straight-through backward pass
     (hbx_threshold_backward) as in simulate.  C / G must be even: a padded plane would be
     thresholded too, and its `off` value is 1, not 0, under field="phase".  The field is always
-    saved."""
+    saved.
+
+    grid=N, origin=, roi= as in simulate (real x, with or without threshold=; C / G even): the
+    intensity [B, G, h_o, w_o] over the roi of a hologram zero-filled into the N x N grid.  The
+    cropped field is saved, and the backward pass is one hbx_backward_window."""
     tf_kind = _switch(tf, _TF_NAMES, "tf")
     field_kind = _switch(field, _FIELD_NAMES, "field")
     ste_args = _ste_args(threshold, ste, ste_width, "intensity")
@@ -628,6 +802,9 @@ def intensity(x, z: float, tf="asm", field="amplitude", save_field: bool = True,
             raise ValueError("tt.intensity: threshold= needs a real leaf, got a complex field")
         if (c // groups) % 2:
             raise ValueError(f"intensity: threshold= needs an even number of planes per colour group, got {c // groups}")
+    win = _window_args(grid, origin, roi, t.shape, t.is_complex(), field_kind, ste_args is not None, "intensity")
+    if win is not None and (c // groups) % 2:
+        raise ValueError(f"intensity: grid= needs an even number of planes per colour group, got {c // groups}")
     if not torch.cuda.is_available():
         raise RuntimeError("tt.intensity needs a ROCm GPU (libhbx.so)")
     if t.is_cuda:
@@ -637,7 +814,14 @@ def intensity(x, z: float, tf="asm", field="amplitude", save_field: bool = True,
         t = t.to(f"cuda:{dev}")
     geom = (wls, dx, dy, z, dev, tf_kind)
     b, _, h, w = t.shape
-    if ste_args is not None:
+    if win is not None:
+        xs = _phase_samples(t)
+        if xs.requires_grad and torch.is_grad_enabled():
+            out = _WindowIntensity.apply(xs, geom, win, groups, field_kind, ste_args)
+        else:
+            plan = _window_plan(win, geom, c // groups, field_kind, b)
+            out = _window_forward(plan, xs, win, ste_args, want_field=False)[1]
+    elif ste_args is not None:
         xs = _phase_samples(t)
         if xs.requires_grad and torch.is_grad_enabled():
             out = _IntensityThreshold.apply(xs, geom, groups, field_kind, ste_args)
@@ -760,7 +944,7 @@ class _LossThreshold(torch.autograd.Function):
 
 
 def loss(x, target, z: float, metric="mse", rel_scale="lsq", tf="asm", field="amplitude", threshold=None,
-         ste="window", ste_width=0.5) -> torch.Tensor:
+         ste="window", ste_width=0.5, grid=None, origin=None, roi=None) -> torch.Tensor:
     """The relative loss of a continuous hologram against a target, one value per env, without
     leaving the HIP path and without a host wait: float64 [B] on the device (0-dim for a 3-D x),
         metric="mse"   what tt.relativeLoss(I[b], target[b], F.mse_loss) gives (env.py:131),
@@ -791,7 +975,14 @@ def loss(x, target, z: float, metric="mse", rel_scale="lsq", tf="asm", field="am
     u = 1 - 2 m, thresholded by the first pass of hbx_evaluate_threshold as it loads x.  If x
     requires grad the backward pass is the straight-through estimator: hbx_loss_weight, then one
     hbx_threshold_backward on the plan for -z, dL/dx = vb s(x) Re(A^H((2 / P) w F)) with ste and
-    ste_width as in simulate.  Neither a 0 / 1 copy of x nor the field's gradient is written."""
+    ste_width as in simulate.  Neither a 0 / 1 copy of x nor the field's gradient is written.
+
+    grid=N, origin=, roi= as in simulate (real x, with or without threshold=): the loss of a hologram
+    [B, C, h, w] zero-filled into the N x N grid, taken over the roi only -- target is [B, G, h_o,
+    w_o], and the statistics and the pixel count n = G h_o w_o are the roi's (the reference's crop
+    before it compares, env_1024_24_128.py:144-149).  The cropped field, the cropped intensity and
+    the statistics are saved; the backward pass is hbx_loss_weight_window, then one
+    hbx_backward_window on the plan for -z."""
     kind = _switch(metric, _METRIC_NAMES, "metric")
     rel = _switch(rel_scale, _REL_NAMES, "rel_scale")
     tf_kind = _switch(tf, _TF_NAMES, "tf")
@@ -825,8 +1016,10 @@ def loss(x, target, z: float, metric="mse", rel_scale="lsq", tf="asm", field="am
             raise ValueError(f"loss: threshold= needs an even number of planes per colour group, got {c // groups}")
     if tg.requires_grad:
         raise ValueError("loss: the target is a constant (it requires grad)")
-    if tg.is_complex() or tuple(tg.shape) != (b, groups, h, w):
-        raise ValueError(f"loss: target must be real {(b, groups, h, w)}, got {tuple(tg.shape)} {tg.dtype}")
+    win = _window_args(grid, origin, roi, t.shape, t.is_complex(), field_kind, ste_args is not None, "loss")
+    th, tw = (h, w) if win is None else win[2][2:]     # the target has the roi's shape
+    if tg.is_complex() or tuple(tg.shape) != (b, groups, th, tw):
+        raise ValueError(f"loss: target must be real {(b, groups, th, tw)}, got {tuple(tg.shape)} {tg.dtype}")
     if not torch.cuda.is_available():
         raise RuntimeError("tt.loss needs a ROCm GPU (libhbx.so)")
     if t.is_cuda:
@@ -836,6 +1029,15 @@ def loss(x, target, z: float, metric="mse", rel_scale="lsq", tf="asm", field="am
         t = t.to(f"cuda:{dev}")
     tg = tg.to(device=t.device, dtype=torch.float32).contiguous()
     geom = (wls, dx, dy, z, dev, tf_kind)
+    if win is not None:
+        xs = _phase_samples(t)
+        if xs.requires_grad and torch.is_grad_enabled():
+            out = _WindowLoss.apply(xs, tg, geom, win, groups, kind, rel, field_kind, ste_args)
+        else:
+            plan = _window_plan(win, geom, c // groups, field_kind, b)
+            stats = _window_forward(plan, xs, win, ste_args, tg, want_field=False, want_intensity=False)[2]
+            out = plan.loss_window(stats, win[2], kind, rel)
+        return out[0] if squeeze else out
     if ste_args is not None:
         xs = _phase_samples(t)
         if xs.requires_grad and torch.is_grad_enabled():

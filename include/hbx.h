@@ -422,6 +422,59 @@ int hbx_threshold_backward(hbx_plan_t plan, const float* values, const float* we
                            const float* samples, int32_t surrogate, float p0, float p1,
                            int32_t n_env, float* grad, void* stream);
 
+/* (ABI v15, additive) Windows: holograms of any size zero-filled into the plan's N x N grid, and
+ * outputs, statistics and gradients taken over a rectangle of it.  A window is a rectangle of the
+ * grid, 0 <= y0, 0 <= x0, 1 <= h, 1 <= w, y0 + h <= N, x0 + w <= N, with no alignment requirement; a
+ * null window pointer is the full grid.  Arrays that belong to a window are compact, [..][h][w]
+ * with row pitch w: no N x N copy of any of them is read or written.
+ *   in_win   where the hologram's samples sit.  Outside it the field is 0 (no light), also under
+ *            HBX_FIELD_PHASE, whose unset bit is 1 (as the padding slots at N = 896): the first pass
+ *            loads a pixel only inside the window and takes zeros elsewhere.
+ *   out_win  where the field, the intensity, the statistics and the pixel count n = G h_o w_o of
+ *            psnr and of the losses are taken: the last pass stores, reduces and loads its target
+ *            row only there, and a row block outside it reads nothing.
+ * hbx_evaluate_real_window / hbx_evaluate_threshold_window: values [B][G*P][h_i][w_i] float32;
+ *   target and intensity [B][G][h_o][w_o], field [B][G*P][h_o][w_o][2], chan_stats [B][G][3] over
+ *   out_win, psnr [B] with n = G h_o w_o.  Null-ability and the target / chan_stats pairing are
+ *   hbx_evaluate_threshold's for both calls; with the intensity alone the lean last pass runs.
+ *   Every output equals the unwindowed call's on the zero-embedded samples, sliced to out_win, bit
+ *   for bit (the statistics: the same pixels' terms, summed in the same order without the others).
+ * hbx_backward_window: on the plan for -z.  values [B][G*P/2][h_v][w_v][2] complex64 and the
+ *   nullable weight [B][G][h_v][w_v] are embedded at val_win by hbx_simulate_complex(_weighted)'s
+ *   first pass; grad [B][G*P/2][h_g][w_g] float32 over grad_win is the real part (samples null:
+ *   the gradient of a real leaf) or, with samples [B][G*P/2][h_g][w_g] (the leaf),
+ *   hbx_threshold_backward's vb s(x) Re g with the same surrogates and rules.  The forward's
+ *   out_win is this call's val_win, the forward's in_win its grad_win.
+ * hbx_loss_window / hbx_loss_weight_window: hbx_loss / hbx_loss_weight with n = G h_o w_o and
+ *   compact intensity / target / weight [B][G][h_o][w_o].
+ * A window outside the grid or with h or w < 1: HBX_ERR_INVALID before anything is enqueued.  Every
+ * other rule (null buffers, n_env, chunking by max_jobs, the pass-timer slots, HBX_PRECISION_F32
+ * only, the four built sizes) is the unwindowed calls'.
+ * Not windowed: complex and phase leaves, the bit path and every env, DBS, plane-cache and
+ * incremental entry point, grids larger than 1024; the column pass is unchanged (it does not skip
+ * the zero rows). */
+typedef struct hbx_window {
+  int32_t y0, x0, h, w;
+} hbx_window_t;
+int hbx_evaluate_real_window(hbx_plan_t plan, const float* values, const hbx_window_t* in_win,
+                             const float* target, const hbx_window_t* out_win, int32_t n_env,
+                             float* field, float* intensity, double* chan_stats, double* psnr,
+                             void* stream);
+int hbx_evaluate_threshold_window(hbx_plan_t plan, const float* values, float threshold,
+                                  const hbx_window_t* in_win, const float* target,
+                                  const hbx_window_t* out_win, int32_t n_env, float* field,
+                                  float* intensity, double* chan_stats, double* psnr, void* stream);
+int hbx_backward_window(hbx_plan_t plan, const float* values, const float* weight, float scale,
+                        const hbx_window_t* val_win, const float* samples, int32_t surrogate,
+                        float p0, float p1, const hbx_window_t* grad_win, int32_t n_env,
+                        float* grad, void* stream);
+int hbx_loss_window(hbx_plan_t plan, const double* chan_stats, const hbx_window_t* out_win,
+                    int32_t n_env, int32_t kind, int32_t rel_scale, double* loss, void* stream);
+int hbx_loss_weight_window(hbx_plan_t plan, const float* intensity, const float* target,
+                           const double* chan_stats, const double* grad_loss,
+                           const hbx_window_t* out_win, int32_t n_env, int32_t kind,
+                           int32_t rel_scale, float* weight, void* stream);
+
 /* PSNR from per-channel statistics (tt.relativeLoss(.., tm.get_PSNR),
  * env.py:174): chan_stats[B][G][3] -> psnr[B]. */
 int hbx_psnr(hbx_plan_t plan, const double* chan_stats, int32_t n_env, double* psnr,
