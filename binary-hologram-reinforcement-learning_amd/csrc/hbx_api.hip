@@ -450,6 +450,31 @@ int check_real_plan(hbx_plan_t p, bool complex_field = false) {
   return HBX_OK;
 }
 
+// The outputs of an evaluate call: target and chan_stats come together, there is no psnr without a target,
+// and something is written.  intensity_only (the complex statistics pass): without a target the intensity
+// is the one output, any_output says whether it is there, and both rules share one message
+int check_eval_outputs(const float* target, const double* chan_stats, const double* psnr, bool any_output,
+                       bool intensity_only = false) {
+  if ((target == nullptr) != (chan_stats == nullptr))
+    return fail(HBX_ERR_INVALID, "target and chan_stats are given together or not at all");
+  if (intensity_only) {
+    if (!target && (!any_output || psnr))
+      return fail(HBX_ERR_INVALID, "without a target: intensity is the output, and there is no psnr");
+    return HBX_OK;
+  }
+  if (!target && psnr) return fail(HBX_ERR_INVALID, "without a target there is no psnr");
+  if (!any_output) return fail(HBX_ERR_INVALID, "no output: field, intensity or chan_stats");
+  return HBX_OK;
+}
+
+// the straight-through surrogate of hbx_threshold_backward / hbx_backward_window and its slope
+int check_surrogate(int32_t surrogate, float p1) {
+  if (surrogate != HBX_STE_WINDOW && surrogate != HBX_STE_SIGMOID)
+    return fail(HBX_ERR_INVALID, "surrogate: HBX_STE_WINDOW or HBX_STE_SIGMOID");
+  if (surrogate == HBX_STE_SIGMOID && !(p1 > 0.0f)) return fail(HBX_ERR_INVALID, "HBX_STE_SIGMOID: p1 (the slope k) > 0");
+  return HBX_OK;
+}
+
 // One full propagation of n envs: every plane of every colour group, no flip.
 struct FullRequest {
   // the input, one of: mask bits [n][G*P][N][N/64]; (ABI v15) real samples [n][G*P][N][N] f32;
@@ -490,6 +515,13 @@ struct FullRequest {
   int32_t* plane_slot = nullptr;
   int spares = 1;
 };
+
+// the last pass's straight-through form (check_surrogate has passed): grad = vb s(samples) Re g
+void set_ste(FullRequest& r, const float* samples, float* grad, int32_t surrogate, float p0, float p1) {
+  r.grad_samples = samples; r.grad_phase = grad;
+  r.grad_kind = surrogate == HBX_STE_WINDOW ? hbx::kGradSteWindow : hbx::kGradSteSigmoid;
+  r.grad_p0 = p0; r.grad_p1 = p1;
+}
 
 int propagate_full(hbx_plan_t p, const FullRequest& r, void* stream) {
   hipStream_t st = (hipStream_t)stream;
@@ -672,10 +704,7 @@ int hbx_evaluate_complex(hbx_plan_t p, const float* values, const float* target,
                          float* intensity, double* chan_stats, double* psnr, void* stream) {
   HBX_ENTER(p, n_env, "n_env");
   if (!values) return fail(HBX_ERR_INVALID, "null buffer");
-  if ((target == nullptr) != (chan_stats == nullptr))
-    return fail(HBX_ERR_INVALID, "target and chan_stats are given together or not at all");
-  if (!target && (!intensity || psnr))
-    return fail(HBX_ERR_INVALID, "without a target: intensity is the output, and there is no psnr");
+  if (int rc = check_eval_outputs(target, chan_stats, psnr, intensity != nullptr, true)) return rc;
   if (int rc = check_real_plan(p, true)) return rc;
   FullRequest r;
   r.complex_values = reinterpret_cast<const float2*>(values); r.target = target; r.n = n_env;
@@ -701,10 +730,7 @@ int hbx_evaluate_phase(hbx_plan_t p, const float* phase, const float* target, in
                        float* intensity, double* chan_stats, double* psnr, void* stream) {
   HBX_ENTER(p, n_env, "n_env");
   if (!phase) return fail(HBX_ERR_INVALID, "null buffer");
-  if ((target == nullptr) != (chan_stats == nullptr))
-    return fail(HBX_ERR_INVALID, "target and chan_stats are given together or not at all");
-  if (!target && (!intensity || psnr))
-    return fail(HBX_ERR_INVALID, "without a target: intensity is the output, and there is no psnr");
+  if (int rc = check_eval_outputs(target, chan_stats, psnr, intensity != nullptr, true)) return rc;
   if (int rc = check_real_plan(p, true)) return rc;
   FullRequest r;
   r.phase_values = phase; r.target = target; r.n = n_env;
@@ -732,10 +758,7 @@ int hbx_evaluate_threshold(hbx_plan_t p, const float* values, float threshold, c
                            float* field, float* intensity, double* chan_stats, double* psnr, void* stream) {
   HBX_ENTER(p, n_env, "n_env");
   if (!values) return fail(HBX_ERR_INVALID, "null buffer");
-  if ((target == nullptr) != (chan_stats == nullptr))
-    return fail(HBX_ERR_INVALID, "target and chan_stats are given together or not at all");
-  if (!target && psnr) return fail(HBX_ERR_INVALID, "without a target there is no psnr");
-  if (!field && !intensity && !chan_stats) return fail(HBX_ERR_INVALID, "no output: field, intensity or chan_stats");
+  if (int rc = check_eval_outputs(target, chan_stats, psnr, field || intensity || chan_stats)) return rc;
   if (int rc = check_real_plan(p)) return rc;
   FullRequest r;
   r.real_values = values; r.binarize = true; r.threshold = threshold; r.target = target; r.n = n_env;
@@ -748,16 +771,12 @@ int hbx_threshold_backward(hbx_plan_t p, const float* values, const float* weigh
                            int32_t surrogate, float p0, float p1, int32_t n_env, float* grad, void* stream) {
   HBX_ENTER(p, n_env, "n_env");
   if (!values || !samples || !grad) return fail(HBX_ERR_INVALID, "null buffer");
-  if (surrogate != HBX_STE_WINDOW && surrogate != HBX_STE_SIGMOID)
-    return fail(HBX_ERR_INVALID, "surrogate: HBX_STE_WINDOW or HBX_STE_SIGMOID");
-  if (surrogate == HBX_STE_SIGMOID && !(p1 > 0.0f)) return fail(HBX_ERR_INVALID, "HBX_STE_SIGMOID: p1 (the slope k) > 0");
+  if (int rc = check_surrogate(surrogate, p1)) return rc;
   if (int rc = check_real_plan(p, true)) return rc;
   FullRequest r;
   r.complex_values = reinterpret_cast<const float2*>(values); r.weight = weight; r.n = n_env;
   if (weight) r.scale = scale;
-  r.grad_samples = samples; r.grad_phase = grad;
-  r.grad_kind = surrogate == HBX_STE_WINDOW ? hbx::kGradSteWindow : hbx::kGradSteSigmoid;
-  r.grad_p0 = p0; r.grad_p1 = p1;
+  set_ste(r, samples, grad, surrogate, p0, p1);
   return propagate_full(p, r, stream);
 }
 
@@ -777,10 +796,7 @@ int evaluate_window(hbx_plan_t p, const float* values, bool binarize, float thre
                     double* chan_stats, double* psnr, void* stream) {
   HBX_ENTER(p, n_env, "n_env");
   if (!values) return fail(HBX_ERR_INVALID, "null buffer");
-  if ((target == nullptr) != (chan_stats == nullptr))
-    return fail(HBX_ERR_INVALID, "target and chan_stats are given together or not at all");
-  if (!target && psnr) return fail(HBX_ERR_INVALID, "without a target there is no psnr");
-  if (!field && !intensity && !chan_stats) return fail(HBX_ERR_INVALID, "no output: field, intensity or chan_stats");
+  if (int rc = check_eval_outputs(target, chan_stats, psnr, field || intensity || chan_stats)) return rc;
   FullRequest r;
   if (int rc = resolve_window(p, in_win, "in_win", &r.in_win)) return rc;
   if (int rc = resolve_window(p, out_win, "out_win", &r.out_win)) return rc;
@@ -814,10 +830,7 @@ int hbx_backward_window(hbx_plan_t p, const float* values, const float* weight, 
   HBX_ENTER(p, n_env, "n_env");
   if (!values || !grad) return fail(HBX_ERR_INVALID, "null buffer");
   if (samples) {
-    if (surrogate != HBX_STE_WINDOW && surrogate != HBX_STE_SIGMOID)
-      return fail(HBX_ERR_INVALID, "surrogate: HBX_STE_WINDOW or HBX_STE_SIGMOID");
-    if (surrogate == HBX_STE_SIGMOID && !(p1 > 0.0f))
-      return fail(HBX_ERR_INVALID, "HBX_STE_SIGMOID: p1 (the slope k) > 0");
+    if (int rc = check_surrogate(surrogate, p1)) return rc;
   }
   FullRequest r;
   if (int rc = resolve_window(p, val_win, "val_win", &r.in_win)) return rc;
@@ -826,13 +839,8 @@ int hbx_backward_window(hbx_plan_t p, const float* values, const float* weight, 
   r.windowed = true;
   r.complex_values = reinterpret_cast<const float2*>(values); r.weight = weight; r.n = n_env;
   if (weight) r.scale = scale;
-  if (samples) {
-    r.grad_samples = samples; r.grad_phase = grad;
-    r.grad_kind = surrogate == HBX_STE_WINDOW ? hbx::kGradSteWindow : hbx::kGradSteSigmoid;
-    r.grad_p0 = p0; r.grad_p1 = p1;
-  } else {
-    r.real_part = grad;
-  }
+  if (samples) set_ste(r, samples, grad, surrogate, p0, p1);
+  else r.real_part = grad;
   return propagate_full(p, r, stream);
 }
 
@@ -845,32 +853,17 @@ int check_loss_kind(int32_t kind, int32_t rel_scale) {
 }
 }  // namespace
 
+// hbx_loss and hbx_loss_weight: their window forms over the whole grid (a null window)
 int hbx_loss(hbx_plan_t p, const double* chan_stats, int32_t n_env, int32_t kind, int32_t rel_scale, double* loss,
              void* stream) {
-  int rc = check_plan(p);
-  if (rc) return rc;
-  if ((rc = check_loss_kind(kind, rel_scale))) return rc;
-  if (n_env <= 0) return n_env == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "n_env");
-  if (!chan_stats || !loss) return fail(HBX_ERR_INVALID, "null buffer");
-  HBX_HIP(hipSetDevice(p->device));
-  HBX_HIP(hbx::launch_loss(chan_stats, n_env, p->pd.G, kind, rel_scale, pixel_count(p), p->optics.peak, loss,
-                           (hipStream_t)stream));
-  return HBX_OK;
+  return hbx_loss_window(p, chan_stats, nullptr, n_env, kind, rel_scale, loss, stream);
 }
 
 int hbx_loss_weight(hbx_plan_t p, const float* intensity, const float* target, const double* chan_stats,
                     const double* grad_loss, int32_t n_env, int32_t kind, int32_t rel_scale, float* weight,
                     void* stream) {
-  int rc = check_plan(p);
-  if (rc) return rc;
-  if ((rc = check_loss_kind(kind, rel_scale))) return rc;
-  if (n_env <= 0) return n_env == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "n_env");
-  if (!intensity || !target || !chan_stats || !weight) return fail(HBX_ERR_INVALID, "null buffer");
-  HBX_HIP(hipSetDevice(p->device));
-  HBX_HIP(hbx::launch_loss_weight(intensity, target, chan_stats, grad_loss, n_env, p->pd.G,
-                                  (size_t)p->pd.N * p->pd.N, kind, rel_scale, pixel_count(p), weight,
-                                  (hipStream_t)stream));
-  return HBX_OK;
+  return hbx_loss_weight_window(p, intensity, target, chan_stats, grad_loss, nullptr, n_env, kind, rel_scale, weight,
+                                stream);
 }
 
 int hbx_loss_window(hbx_plan_t p, const double* chan_stats, const hbx_window_t* out_win, int32_t n_env, int32_t kind,

@@ -190,6 +190,13 @@ struct PlanDev {
 //                 |U|^2 go to the env's two spare slots (swapped in on accept)
 constexpr int kPlanesOff = 0, kPlanesFill = 1, kPlanesStep = 2;
 
+// What the real first passes (k_rowfwd_real, k_rowfwd32_real, k_rowfwd896_real) load a row with:
+// real_load_row or threshold_load_row (hbx_rowcol.hpp) ...
+constexpr int kLoadReal = 0, kLoadThreshold = 1;
+// ... and the complex ones (k_rowfwd_cplx, k_rowfwd32_cplx, k_rowfwd896_cplx): complex_load_row,
+// complex_load_row_weighted or phase_load_row
+constexpr int kLoadComplex = 0, kLoadWeighted = 1, kLoadPhase = 2;
+
 // What the complex last passes (k_rowinv_d_cplx, k_rowinv_cplx, k_rowinv896_cplx) write: the plane
 // (field, real part, statistics: kGradNone), or a real leaf's gradient instead of it --
 // phase_grad_row, or ste_grad_row with one of the two surrogate derivatives (hbx_rowcol.hpp).
@@ -395,6 +402,44 @@ hipError_t run_jobs_896(const PlanDev& pd, const PassCall& c, hipStream_t st);
 template <class K, class... A>
 inline void launch_kernel(K k, unsigned blocks, unsigned nt, hipStream_t st, A... a) {
   hipLaunchKernelGGL(k, dim3(blocks), dim3(nt), 0, st, a...);
+}
+
+// The sample passes' kernel pick, once for both dispatchers (launch_passes, run_jobs_896).  F = the size
+// family's kernels (SampleKernels<R>, SampleKernels896): first_real<LK, WIN>(), first_cplx<LK, WIN>() and
+// last_cplx<ST, GK, WIN>() return the instantiation.  The unwindowed forms are named before the windowed
+// ones, and within each in the order the code object has had them: first use fixes a kernel's place in it,
+// and the timings on record were taken with that layout (tools/isa_cmp.py reports a reordering).  What check_pass_call refuses is never named: a windowed
+// phase load, windowed statistics, a windowed phase gradient.
+template <class F>
+inline auto pick_first_pass_real(bool threshold, bool win_in) {
+  auto k = !threshold ? F::template first_real<kLoadReal, false>() : F::template first_real<kLoadThreshold, false>();
+  if (win_in) k = !threshold ? F::template first_real<kLoadReal, true>() : F::template first_real<kLoadThreshold, true>();
+  return k;
+}
+template <class F>
+inline auto pick_first_pass_cplx(int lk, bool win_in) {
+  auto k = lk == kLoadComplex ? F::template first_cplx<kLoadComplex, false>()
+           : lk == kLoadPhase ? F::template first_cplx<kLoadPhase, false>()
+                              : F::template first_cplx<kLoadWeighted, false>();
+  if (win_in)
+    k = lk == kLoadWeighted ? F::template first_cplx<kLoadWeighted, true>() : F::template first_cplx<kLoadComplex, true>();
+  return k;
+}
+// gk = kGradNone: the plane itself, with the statistics or without (hbx_evaluate_complex); kGradPhase
+// (hbx_phase_backward) and the two STE kinds (hbx_threshold_backward): the leaf's gradient instead;
+// windowed: the real part or an STE gradient over out_win
+template <class F>
+inline auto pick_last_pass_cplx(int gk, bool stats, bool windowed) {
+  auto k = gk == kGradNone          ? (stats ? F::template last_cplx<true, kGradNone, false>()
+                                             : F::template last_cplx<false, kGradNone, false>())
+           : gk == kGradSteWindow  ? F::template last_cplx<false, kGradSteWindow, false>()
+           : gk == kGradSteSigmoid ? F::template last_cplx<false, kGradSteSigmoid, false>()
+                                   : F::template last_cplx<false, kGradPhase, false>();
+  if (windowed)
+    k = gk == kGradSteWindow    ? F::template last_cplx<false, kGradSteWindow, true>()
+        : gk == kGradSteSigmoid ? F::template last_cplx<false, kGradSteSigmoid, true>()
+                                : F::template last_cplx<false, kGradNone, true>();
+  return k;
 }
 // 2-D FFT of n_planes [N][N] complex planes in a (result in a; b is scratch of
 // the same size).  Unnormalised both ways.

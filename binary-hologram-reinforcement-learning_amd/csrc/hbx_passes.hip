@@ -460,12 +460,8 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd32(const JobDesc* jobs,
 // block would be a second v (64 VGPRs at N = 1024), which does not fit three workgroups per
 // CU; the co-resident workgroups cover each other's loads instead.  This is the
 // bit kernels' RIT = 1 form with another load, at every launch size (no small / large switch).
-// LK = kLoadThreshold (hbx_evaluate_threshold): threshold_load_row turns each sample into the field of
-// its mask bit, hi where x >= thr and lo elsewhere, as it loads it; the registers, the tail and the
-// geometry are unchanged, and thr / lo / hi are unused without it.
-// WIN (hbx_evaluate_real_window / _threshold_window; off by default, and the kernels without it compile
-// as before): values is compact, [env][CH][win.h][win.w], and sits at win of the grid, which is 0
-// elsewhere -- real_load_row_win loads a pixel only inside it; the A panel of every row is written.
+// LK and WIN: first_pass_load_real (hbx_rowcol.hpp); the registers, the tail and the geometry are the same
+// for every load kind, and the A panel of every row is written whatever the window.
 template <int R, int NT, int LK = kLoadReal, bool WIN = false>
 __global__ __launch_bounds__(NT, 512 / NT) void k_rowfwd_real(const JobDesc* __restrict__ jobs,
                                                         const float* __restrict__ values,
@@ -491,17 +487,7 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowfwd_real(const JobDesc* __r
   const int y0 = wg.rbw * GPB;
   const int y = y0 + grp;
   pk2 v[R];
-  if constexpr (WIN) {
-    const WinRow wr(win, y, t);
-    const size_t ro = wr.in ? WinRow::row_of(win, (size_t)jb.env * CH + jb.group * P + pa, y) : 0;
-    real_load_row_win<R, R, LK>(v, values + ro, (size_t)win.h * win.w, wr, thr, lo, hi);
-  } else {
-    const float* row = values + (((size_t)jb.env * CH + jb.group * P + pa) * N + y) * N;
-    if constexpr (LK == kLoadThreshold)
-      threshold_load_row<R>(v, row, (size_t)N * N, t, thr, lo, hi);
-    else
-      real_load_row<R>(v, row, (size_t)N * N, t);
-  }
+  first_pass_load_real<R, R, LK, WIN>(v, values, jb.env, jb.group, P, CH, pa, y, t, thr, lo, hi, win);
   __syncthreads();  // tw visible
 
   float2* base = ws_a + ((size_t)j * P + pa) * plane_a_elems(R);
@@ -536,15 +522,14 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd32_real(const JobDesc* __restr
   const int y = y0 + grp;
   pk2 v[R];
   if constexpr (WIN) {
+    // first_pass_load_real's window form, written out: through the helper this kernel compiles to two more
+    // scalar instructions, and one of its timed medians lay outside the spread of the blocks before the change
+    // (profiles/sample_passes/window_time_ab.txt)
     const WinRow wr(win, y, t);
     const size_t ro = wr.in ? WinRow::row_of(win, (size_t)jb.env * CH + jb.group * P + pa, y) : 0;
     real_load_row_win<R, R, LK>(v, values + ro, (size_t)win.h * win.w, wr, thr, lo, hi);
   } else {
-    const float* row = values + (((size_t)jb.env * CH + jb.group * P + pa) * N + y) * N;
-    if constexpr (LK == kLoadThreshold)
-      threshold_load_row<R>(v, row, (size_t)N * N, t, thr, lo, hi);
-    else
-      real_load_row<R>(v, row, (size_t)N * N, t);
+    first_pass_load_real<R, R, LK, false>(v, values, jb.env, jb.group, P, CH, pa, y, t, thr, lo, hi, win);
   }
   __syncthreads();  // tw visible
 
@@ -560,14 +545,8 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd32_real(const JobDesc* __restr
 // samples into v as they are, and the shared tail does what it does for two real planes: the row
 // FFT of u = a + i b, split into the half spectra of a = Re u (A plane 2q) and b = Im u (2q + 1).
 // The real kernels' geometry: one row block per workgroup, wg.q = the complex plane.
-// LK = kLoadWeighted (hbx_simulate_complex_weighted): complex_load_row_weighted multiplies the samples by scale *
-// weight[env][group][y][x] as it loads them -- R more VGPRs live across the load (the weights), the
-// tail and the geometry unchanged; weight / scale are unused without it.
-// LK = kLoadPhase (hbx_simulate_phase): phase[env][CH / 2][N][N] f32 instead of values, phase plane q
-// into plane-pair slot q as complex plane q; phase_load_row forms exp(i pi x) as it loads -- R floats
-// live across the load where the complex form holds R pairs.  phase is unused by the other kinds.
-// WIN (hbx_backward_window; kLoadComplex and kLoadWeighted): values [env][CH / 2][win.h][win.w] and weight
-// [env][G][win.h][win.w] are compact and sit at win of the grid, 0 elsewhere (complex_load_row_win).
+// LK and WIN: first_pass_load_cplx (hbx_rowcol.hpp); a phase plane q fills plane-pair slot q as complex
+// plane q does, and the tail and the geometry are the same for every load kind.
 template <int R, int NT, int LK = kLoadComplex, bool WIN = false>
 __global__ __launch_bounds__(NT, 512 / NT) void k_rowfwd_cplx(const JobDesc* __restrict__ jobs,
                                                         const float2* __restrict__ values,
@@ -593,21 +572,7 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowfwd_cplx(const JobDesc* __r
   const int y0 = wg.rbw * GPB;
   const int y = y0 + grp;
   pk2 v[R];
-  if constexpr (WIN) {
-    static_assert(LK != kLoadPhase, "phase leaves are not windowed");
-    const WinRow wr(win, y, t);
-    const size_t ro = wr.in ? WinRow::row_of(win, (size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q, y) : 0;
-    const size_t wo = wr.in ? WinRow::row_of(win, (size_t)jb.env * (CH / P) + jb.group, y) : 0;
-    complex_load_row_win<R, R, LK>(v, values + ro, LK == kLoadWeighted ? weight + wo : nullptr, scale, wr);
-  } else {
-    const size_t row = (((size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q) * N + y) * N;
-    if constexpr (LK == kLoadWeighted)
-      complex_load_row_weighted<R>(v, values + row, weight + (((size_t)jb.env * (CH / P) + jb.group) * N + y) * N, scale, t);
-    else if constexpr (LK == kLoadPhase)
-      phase_load_row<R>(v, phase + row, t);
-    else
-      complex_load_row<R>(v, values + row, t);
-  }
+  first_pass_load_cplx<R, R, LK, WIN>(v, values, weight, scale, phase, jb.env, jb.group, P, CH, wg.q, y, t, win);
   __syncthreads();  // tw visible
 
   float2* base = ws_a + ((size_t)j * P + 2 * wg.q) * plane_a_elems(R);
@@ -642,21 +607,7 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd32_cplx(const JobDesc* __restr
   const int y0 = wg.rbw * GPB;
   const int y = y0 + grp;
   pk2 v[R];
-  if constexpr (WIN) {
-    static_assert(LK != kLoadPhase, "phase leaves are not windowed");
-    const WinRow wr(win, y, t);
-    const size_t ro = wr.in ? WinRow::row_of(win, (size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q, y) : 0;
-    const size_t wo = wr.in ? WinRow::row_of(win, (size_t)jb.env * (CH / P) + jb.group, y) : 0;
-    complex_load_row_win<R, R, LK>(v, values + ro, LK == kLoadWeighted ? weight + wo : nullptr, scale, wr);
-  } else {
-    const size_t row = (((size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q) * N + y) * N;
-    if constexpr (LK == kLoadWeighted)
-      complex_load_row_weighted<R>(v, values + row, weight + (((size_t)jb.env * (CH / P) + jb.group) * N + y) * N, scale, t);
-    else if constexpr (LK == kLoadPhase)
-      phase_load_row<R>(v, phase + row, t);
-    else
-      complex_load_row<R>(v, values + row, t);
-  }
+  first_pass_load_cplx<R, R, LK, WIN>(v, values, weight, scale, phase, jb.env, jb.group, P, CH, wg.q, y, t, win);
   __syncthreads();  // tw visible
 
   float2* base = ws_a + ((size_t)j * P + 2 * wg.q) * plane_a_elems(R);
@@ -1095,29 +1046,17 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv(const JobDesc* __restri
 // the pair is combined on load, v = B[2q] + i B[2q + 1], and ONE inverse FFT per complex plane gives
 // F_q, stored once: 8 N^2 bytes to field and / or 4 N^2 bytes of Re F_q to real_part (both
 // [env][CH / 2][N][N], either nullable).  No |.|^2, partials, plane cache or reconcile.
-// ST (hbx_evaluate_complex; off by default, and the kernels without it compile as before): every
-// plane's |F_q|^2 is also accumulated per pixel, acc += fmaf(re, re, im * im) as k_rowinv_d does, and
-// k_rowinv's tail (rowinv_epilogue) runs with Q = P / 2 as the plane count: the plane-mean intensity
-// row to inten_out [job][N][N], the f64 partials against the target row (tmask = 0: the zero row).
-// field_out and real_out may then both be null.
-// GK = kGradPhase (hbx_phase_backward; kGradNone by default, and the kernels without it compile as
-// before): the plane out of the inverse FFT is the gradient g with respect to the field u = exp(i pi x)
-// of a phase leaf, and the kernel writes grad[env][CH / 2][N][N] f32 = pi (Im g cos pi x - Re g sin pi x)
-// from the samples phase[env][CH / 2][N][N] (phase_grad_row) and nothing else: no complex field, no
-// statistics.
-// GK = kGradSteWindow / kGradSteSigmoid (hbx_threshold_backward): the same geometry for a binary
-// hologram's real leaf x (in `phase`): grad = gvb s(x) Re g with the surrogate derivative s of
-// ste_grad_row and its parameters (ga, gb); gvb / ga / gb are unused by the other kinds.
+// What happens to a plane after its inverse FFT is cplx_plane_out (hbx_rowinv.hpp: ST, GK and WIN, off by
+// default, and the kernels without them compile as before).  ST (hbx_evaluate_complex) also runs k_rowinv's
+// tail (rowinv_epilogue) with Q = P / 2 as the plane count: the plane-mean intensity row to inten_out
+// [job][N][N], the f64 partials against the target row (tmask = 0: the zero row).
 //
 // N = 1024 / 256: k_rowinv_d's direct loads from the tiled B (RowinvLanes).
 // Plane 2q + 1 arrives in two halves of R / 2 values that are folded into v as they land, so the
 // kernel never holds two whole lines (the second register set that cost k_rowinv_d its second
 // block per CU).  N = 256 has the registers for a second line and keeps the next pair in flight
 // under this one's FFT, as k_rowinv_d does with the next plane.
-// WIN (hbx_backward_window; off by default, and the kernels without it compile as before; kGradNone and the
-// two STE kinds, never ST): the one output is a compact array over the window win -- real_out
-// [env][CH / 2][h][w] = Re F_q (kGradNone; field_out is not written), or grad from the leaf's samples
-// in `phase`, both of that shape (grad_row_win).  A row block that shares no row with win reads nothing.
+// WIN: a row block that shares no row with win reads nothing.
 template <int R, bool ST = false, int GK = kGradNone, bool WIN = false>
 __global__ __launch_bounds__(256, 2) void k_rowinv_d_cplx(const JobDesc* __restrict__ jobs,
                                                           const float2* __restrict__ ws_b,
@@ -1130,8 +1069,6 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_d_cplx(const JobDesc* __restr
                                                           const float* __restrict__ phase,
                                                           float* __restrict__ grad, float gvb, float ga,
                                                           float gb, hbx_window_t win) {
-  static_assert(!(ST && GK != kGradNone), "the gradient forms run no statistics");
-  static_assert(!(WIN && (ST || GK == kGradPhase)), "windows: the real part or an STE gradient");
   constexpr int N = R * R, GPB = 256 / R, RB = N / GPB;
   __shared__ float2 tw[N];
   __shared__ float2 scratch[GPB * R * (R + 1)];
@@ -1166,31 +1103,8 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_d_cplx(const JobDesc* __restr
   }
   auto finish_plane = [&](pk2 (&v)[R], int q) {
     fft_group<R, true>(v, t, sc, tw);
-    if constexpr (ST) {
-#pragma unroll
-      for (int k = 0; k < R; ++k) acc[k] += fmaf(v[k].x, v[k].x, v[k].y * v[k].y);
-    }
-    if constexpr (WIN) {
-      const size_t ro = wr.in ? WinRow::row_of(win, ((size_t)jb.env * G + jb.group) * Q + q, y) : 0;
-      grad_row_win<R, R, GK>(v, phase + ro, (GK == kGradNone ? real_out : grad) + ro, wr, gvb, ga, gb);
-      return;
-    }
-    const size_t row = row0 + (size_t)q * N * N;
-    if constexpr (GK == kGradPhase) {   // the samples are loaded behind the FFT: R = 32 never holds a second line
-      phase_grad_row<R, R>(v, phase + row, grad + row);
-      return;
-    } else if constexpr (GK != kGradNone) {
-      ste_grad_row<R, R, GK>(v, phase + row, grad + row, gvb, ga, gb);
-      return;
-    }
-    if (field_out) {
-#pragma unroll
-      for (int k = 0; k < R; ++k) field_out[row + R * k] = from_pk(v[k]);
-    }
-    if (real_out) {
-#pragma unroll
-      for (int k = 0; k < R; ++k) real_out[row + R * k] = v[k].x;
-    }
+    cplx_plane_out<R, R, ST, GK, WIN>(v, acc, jb.env, jb.group, G, Q, q, y, row0, win, wr, field_out, real_out, phase,
+                                      grad, gvb, ga, gb);
   };
   pk2 va[R];
   load_pair(va, 0);
@@ -1233,8 +1147,6 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv_cplx(const JobDesc* __r
                                                         const float* __restrict__ phase,
                                                         float* __restrict__ grad, float gvb, float ga,
                                                         float gb, hbx_window_t win) {
-  static_assert(!(ST && GK != kGradNone), "the gradient forms run no statistics");
-  static_assert(!(WIN && (ST || GK == kGradPhase)), "windows: the real part or an STE gradient");
   constexpr int N = R * R;
   constexpr int GPB = NT / R;          // rows per block
   constexpr int RB = N / GPB;
@@ -1301,30 +1213,25 @@ __global__ __launch_bounds__(NT, 512 / NT) void k_rowinv_cplx(const JobDesc* __r
     for (int jj = 0; jj < R; ++jj) v[jj] = to_pk(tile[tile_pos<R, GPB>(t + R * jj, grp)]);
     lds_barrier();  // tile consumed: reuse it as transpose scratch
     fft_group<R, true>(v, t, PaddedScratch<R>{tile + grp * R * (R + 1)}, tw);
-    if constexpr (ST) {
+    if constexpr (GK == kGradNone && !WIN) {
+      // cplx_plane_out's full-grid field / real-part form, written out: its null tests and stores on the
+      // kernel's own pointers compile to other code here when they come through the helper
+      if constexpr (ST) {
 #pragma unroll
-      for (int k = 0; k < R; ++k) acc[k] += fmaf(v[k].x, v[k].x, v[k].y * v[k].y);
-    }
-    if constexpr (WIN) {
-      const size_t ro = wr.in ? WinRow::row_of(win, ((size_t)jb.env * G + jb.group) * Q + q, y) : 0;
-      grad_row_win<R, R, GK>(v, phase + ro, (GK == kGradNone ? real_out : grad) + ro, wr, gvb, ga, gb);
-      continue;
-    }
-    const size_t row = row0 + (size_t)q * N * N;
-    if constexpr (GK == kGradPhase) {
-      phase_grad_row<R, R>(v, phase + row, grad + row);
-      continue;
-    } else if constexpr (GK != kGradNone) {
-      ste_grad_row<R, R, GK>(v, phase + row, grad + row, gvb, ga, gb);
-      continue;
-    }
-    if (field_out) {
+        for (int k = 0; k < R; ++k) acc[k] += fmaf(v[k].x, v[k].x, v[k].y * v[k].y);
+      }
+      const size_t row = row0 + (size_t)q * N * N;
+      if (field_out) {
 #pragma unroll
-      for (int k = 0; k < R; ++k) field_out[row + R * k] = from_pk(v[k]);
-    }
-    if (real_out) {
+        for (int k = 0; k < R; ++k) field_out[row + R * k] = from_pk(v[k]);
+      }
+      if (real_out) {
 #pragma unroll
-      for (int k = 0; k < R; ++k) real_out[row + R * k] = v[k].x;
+        for (int k = 0; k < R; ++k) real_out[row + R * k] = v[k].x;
+      }
+    } else {
+      cplx_plane_out<R, R, ST, GK, WIN>(v, acc, jb.env, jb.group, G, Q, q, y, row0, win, wr, field_out, real_out,
+                                        phase, grad, gvb, ga, gb);
     }
   }
   if constexpr (ST) {
@@ -1469,6 +1376,33 @@ hipError_t run_fft2d(const PlanDev& pd, float2* a, float2* b, int n_planes, bool
 __global__ void k_reduce_partials(const double* __restrict__ partial, int n_jobs, int RB,
                                   double* __restrict__ job_stats);
 
+// The sample kernels of N = R^2 for the shared pick (hbx_internal.hpp): N = 1024 has first passes of its
+// own, N = 64 a last pass of its own
+template <int R>
+struct SampleKernels {
+  static constexpr int NT = kRowNT<R>;
+  template <int LK, bool WIN>
+  static auto first_real() {
+    if constexpr (R == 32) return k_rowfwd32_real<LK, WIN>;
+    else return k_rowfwd_real<R, NT, LK, WIN>;
+  }
+  template <int LK, bool WIN>
+  static auto first_cplx() {
+    if constexpr (R == 32) {
+      // (the weighted form keeps its place in front of the other two: first use fixes it in the code object)
+      (void)k_rowfwd32_cplx<kLoadWeighted, false>;
+      return k_rowfwd32_cplx<LK, WIN>;
+    } else {
+      return k_rowfwd_cplx<R, NT, LK, WIN>;
+    }
+  }
+  template <bool ST, int GK, bool WIN>
+  static auto last_cplx() {
+    if constexpr (kTiledB<R>) return k_rowinv_d_cplx<R, ST, GK, WIN>;
+    else return k_rowinv_cplx<R, NT, ST, GK, WIN>;
+  }
+};
+
 template <int R, int SK>
 static hipError_t launch_passes(const PlanDev& pd, const PassCall& c, hipStream_t st) {
   constexpr int N = R * R;
@@ -1498,38 +1432,12 @@ static hipError_t launch_passes(const PlanDev& pd, const PassCall& c, hipStream_
   if (tm) tm->begin(0, st);
   if (pass_complex(c)) {   // the load kind: complex samples as they are, times scale * weight, or exp(i pi phase)
     const int lk = c.phase_values ? kLoadPhase : c.complex_weight ? kLoadWeighted : kLoadComplex;
-    auto k = [&] {
-      // (the two kernels that were here first stay first: first use fixes a kernel's place in the code object)
-      if constexpr (R == 32)
-        return lk == kLoadWeighted ? k_rowfwd32_cplx<kLoadWeighted>
-                                   : lk == kLoadComplex ? k_rowfwd32_cplx<kLoadComplex> : k_rowfwd32_cplx<kLoadPhase>;
-      else
-        return lk == kLoadWeighted ? k_rowfwd_cplx<R, NT, kLoadWeighted>
-                                   : lk == kLoadComplex ? k_rowfwd_cplx<R, NT, kLoadComplex>
-                                                        : k_rowfwd_cplx<R, NT, kLoadPhase>;
-    }();
-    // (the windowed forms are named behind the others, here and below: they come last in the code object)
-    if (pass_window_in(c, N)) {
-      if constexpr (R == 32)
-        k = lk == kLoadWeighted ? k_rowfwd32_cplx<kLoadWeighted, true> : k_rowfwd32_cplx<kLoadComplex, true>;
-      else
-        k = lk == kLoadWeighted ? k_rowfwd_cplx<R, NT, kLoadWeighted, true> : k_rowfwd_cplx<R, NT, kLoadComplex, true>;
-    }
-    launch_kernel(k, sample_blocks, NT, st, jobs, c.complex_values, pd.ws_a, pd.tw, P, CH, c.complex_weight,
-                  c.complex_scale, c.phase_values, c.in_win);
+    launch_kernel(pick_first_pass_cplx<SampleKernels<R>>(lk, pass_window_in(c, N)), sample_blocks, NT, st, jobs,
+                  c.complex_values, pd.ws_a, pd.tw, P, CH, c.complex_weight, c.complex_scale, c.phase_values, c.in_win);
   } else if (c.real_values) {
     // the load kind: the samples as they are, or (hbx_evaluate_threshold) the field of the bit [x >= threshold]
-    const bool thr = c.real_binarize != 0;
-    auto k = [&] {
-      if constexpr (R == 32) return !thr ? k_rowfwd32_real<kLoadReal> : k_rowfwd32_real<kLoadThreshold>;
-      else return !thr ? k_rowfwd_real<R, NT, kLoadReal> : k_rowfwd_real<R, NT, kLoadThreshold>;
-    }();
-    if (pass_window_in(c, N)) {
-      if constexpr (R == 32) k = !thr ? k_rowfwd32_real<kLoadReal, true> : k_rowfwd32_real<kLoadThreshold, true>;
-      else k = !thr ? k_rowfwd_real<R, NT, kLoadReal, true> : k_rowfwd_real<R, NT, kLoadThreshold, true>;
-    }
-    launch_kernel(k, sample_blocks, NT, st, jobs, c.real_values, pd.ws_a, pd.tw, P, CH, c.real_threshold, pd.va,
-                  pd.va + pd.vb, c.in_win);
+    launch_kernel(pick_first_pass_real<SampleKernels<R>>(c.real_binarize != 0, pass_window_in(c, N)), sample_blocks, NT,
+                  st, jobs, c.real_values, pd.ws_a, pd.tw, P, CH, c.real_threshold, pd.va, pd.va + pd.vb, c.in_win);
   } else {
     auto k = [&] {
       if constexpr (R == 32) return small ? k_rowfwd32<SK, 1> : k_rowfwd32<SK>;
@@ -1555,33 +1463,9 @@ static hipError_t launch_passes(const PlanDev& pd, const PassCall& c, hipStream_
 
   const unsigned blocks = (unsigned)n_jobs * kRowBlocks;
   if (tm) tm->begin(2, st);
-  if (pass_complex(c)) {   // recombine each plane pair; ST (hbx_evaluate_complex): intensity and partials too;
-                           // kGradPhase (hbx_phase_backward): the phase gradient instead of the field;
-    //                        kGradSte* (hbx_threshold_backward): a binary hologram's gated gradient
-    const bool stats = c.complex_stats != 0;
-    const int gk = c.grad_phase ? c.grad_kind : kGradNone;
-    auto k = [&] {
-      if constexpr (kTiledB<R>)
-        return gk == kGradNone ? (stats ? k_rowinv_d_cplx<R, true> : k_rowinv_d_cplx<R>)
-               : gk == kGradPhase ? k_rowinv_d_cplx<R, false, kGradPhase>
-               : gk == kGradSteWindow ? k_rowinv_d_cplx<R, false, kGradSteWindow>
-                                      : k_rowinv_d_cplx<R, false, kGradSteSigmoid>;
-      else
-        return gk == kGradNone ? (stats ? k_rowinv_cplx<R, NT, true> : k_rowinv_cplx<R, NT>)
-               : gk == kGradPhase ? k_rowinv_cplx<R, NT, false, kGradPhase>
-               : gk == kGradSteWindow ? k_rowinv_cplx<R, NT, false, kGradSteWindow>
-                                      : k_rowinv_cplx<R, NT, false, kGradSteSigmoid>;
-    }();
-    if (c.windowed) {   // the real part or an STE gradient over out_win (check_pass_call)
-      if constexpr (kTiledB<R>)
-        k = gk == kGradNone ? k_rowinv_d_cplx<R, false, kGradNone, true>
-            : gk == kGradSteWindow ? k_rowinv_d_cplx<R, false, kGradSteWindow, true>
-                                   : k_rowinv_d_cplx<R, false, kGradSteSigmoid, true>;
-      else
-        k = gk == kGradNone ? k_rowinv_cplx<R, NT, false, kGradNone, true>
-            : gk == kGradSteWindow ? k_rowinv_cplx<R, NT, false, kGradSteWindow, true>
-                                   : k_rowinv_cplx<R, NT, false, kGradSteSigmoid, true>;
-    }
+  if (pass_complex(c)) {   // recombine each plane pair, or a leaf's gradient instead (pick_last_pass_cplx)
+    const auto k = pick_last_pass_cplx<SampleKernels<R>>(c.grad_phase ? c.grad_kind : kGradNone, c.complex_stats != 0,
+                                                         c.windowed != 0);
     launch_kernel(k, blocks, NT, st, jobs, pd.ws_b, pd.tw, P, pd.G, c.complex_field, c.real_part, tg.rows, tg.mask,
                   pd.partial, c.inten_out, c.grad_samples, c.grad_phase, pd.vb, c.grad_p0, c.grad_p1, c.out_win);
   } else if constexpr (kTiledB<R>) {

@@ -219,11 +219,8 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd896(const JobDesc* __restrict_
 // of the row in planes pa, pb into the (re, im) of v[jj] and zeros above, and rowfwd896_emit --
 // k_rowfwd896's own FFT, split, tile and panel stores -- takes it from there.  One row block per
 // workgroup (no register room for a second row's samples at three workgroups per CU), in
-// blockIdx order; full propagations only.  LK = kLoadThreshold (hbx_evaluate_threshold):
-// threshold_load_row makes each of the 28 loaded samples hi where x >= thr and lo elsewhere; slots
-// >= 28 stay zero, not lo.  thr / lo / hi are unused by kLoadReal.
-// WIN (hbx_evaluate_real_window / _threshold_window; off by default): values is compact,
-// [env][CH][win.h][win.w], and sits at win of the grid, which is 0 elsewhere (real_load_row_win).
+// blockIdx order; full propagations only.  LK and WIN: first_pass_load_real (hbx_rowcol.hpp) on 28 of the
+// lane's 32 slots; slots >= 28 stay zero whatever the load kind (not lo under kLoadThreshold).
 template <int LK = kLoadReal, bool WIN = false>
 __global__ __launch_bounds__(256, 3) void k_rowfwd896_real(const JobDesc* __restrict__ jobs,
                                                            const float* __restrict__ values,
@@ -245,17 +242,7 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd896_real(const JobDesc* __rest
   const int y0 = wg.rbw * kGPB;
   const int y = y0 + grp;
   float2 v[32];
-  if constexpr (WIN) {
-    const WinRow wr(win, y, t);
-    const size_t ro = wr.in ? WinRow::row_of(win, (size_t)jb.env * CH + jb.group * P + pa, y) : 0;
-    real_load_row_win<kR, kL, LK>(v, values + ro, (size_t)win.h * win.w, wr, thr, lo, hi);
-  } else {
-    const float* row = values + (((size_t)jb.env * CH + jb.group * P + pa) * kN + y) * kN;
-    if constexpr (LK == kLoadThreshold)
-      threshold_load_row<kR, kL>(v, row, (size_t)kN * kN, t, thr, lo, hi);
-    else
-      real_load_row<kR, kL>(v, row, (size_t)kN * kN, t);
-  }
+  first_pass_load_real<kR, kL, LK, WIN>(v, values, jb.env, jb.group, P, CH, pa, y, t, thr, lo, hi, win);
   __syncthreads();  // tw visible
 
   float2* base = ws_a + ((size_t)j * P + pa) * kPlaneA;
@@ -265,11 +252,8 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd896_real(const JobDesc* __rest
 // Pass 1 on complex fields (hbx_simulate_complex): values[env][CH / 2][896][896] complex64.
 // complex_load_row puts the complex sample of pixel x = t + 32 jj (jj < 28) into v[jj] as it is and
 // zeros above; rowfwd896_emit then leaves the half spectra of Re u_q and Im u_q in A planes 2q and
-// 2q + 1.  k_rowfwd896_real's geometry, wg.q = the complex plane.  LK = kLoadWeighted (hbx_simulate_complex_weighted):
-// complex_load_row_weighted scales the 28 loaded samples by scale * weight[env][group][y][x]; slots >= 28
-// stay zero.  LK = kLoadPhase (hbx_simulate_phase): phase[env][CH / 2][896][896] f32 instead of values;
-// phase_load_row forms exp(i pi x) of the 28 loaded samples, and slots >= 28 are zero there too.
-// WIN (hbx_backward_window; kLoadComplex and kLoadWeighted): compact values and weight at win, 0 elsewhere.
+// 2q + 1.  k_rowfwd896_real's geometry, wg.q = the complex plane.  LK and WIN: first_pass_load_cplx
+// (hbx_rowcol.hpp) on the 28 loaded samples; slots >= 28 stay zero (not exp(0) under kLoadPhase).
 template <int LK = kLoadComplex, bool WIN = false>
 __global__ __launch_bounds__(256, 3) void k_rowfwd896_cplx(const JobDesc* __restrict__ jobs,
                                                            const float2* __restrict__ values,
@@ -291,21 +275,7 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd896_cplx(const JobDesc* __rest
   const int y0 = wg.rbw * kGPB;
   const int y = y0 + grp;
   float2 v[32];
-  if constexpr (WIN) {
-    static_assert(LK != kLoadPhase, "phase leaves are not windowed");
-    const WinRow wr(win, y, t);
-    const size_t ro = wr.in ? WinRow::row_of(win, (size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q, y) : 0;
-    const size_t wo = wr.in ? WinRow::row_of(win, (size_t)jb.env * (CH / P) + jb.group, y) : 0;
-    complex_load_row_win<kR, kL, LK>(v, values + ro, LK == kLoadWeighted ? weight + wo : nullptr, scale, wr);
-  } else {
-    const size_t row = (((size_t)jb.env * (CH / 2) + jb.group * (P / 2) + wg.q) * kN + y) * kN;
-    if constexpr (LK == kLoadWeighted)
-      complex_load_row_weighted<kR, kL>(v, values + row, weight + (((size_t)jb.env * (CH / P) + jb.group) * kN + y) * kN, scale, t);
-    else if constexpr (LK == kLoadPhase)
-      phase_load_row<kR, kL>(v, phase + row, t);
-    else
-      complex_load_row<kR, kL>(v, values + row, t);
-  }
+  first_pass_load_cplx<kR, kL, LK, WIN>(v, values, weight, scale, phase, jb.env, jb.group, P, CH, wg.q, y, t, win);
   __syncthreads();  // tw visible
 
   float2* base = ws_a + ((size_t)j * P + 2 * wg.q) * kPlaneA;
@@ -565,17 +535,9 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896(const JobDesc* __restrict_
 // halves of 16 registers, so two whole lines are never live), ONE inverse FFT per complex plane, and
 // the plane F_q stored once to field_out and / or its real part to real_out, both
 // [env][CH / 2][896][896].  k_rowinv896's lane bases; no |.|^2, partials or plane cache.
-// ST (hbx_evaluate_complex; off by default, and that kernel compiles as before): |F_q|^2 is also
-// accumulated per pixel as k_rowinv896 does and its tail runs with Q = P / 2 as the plane count --
-// the plane-mean intensity row to inten_out [job][896][896] and the f64 partials against the target
-// row; field_out and real_out may then both be null.
-// GK = kGradPhase (hbx_phase_backward; kGradNone by default): the plane is the gradient with respect to
-// u = exp(i pi x), and grad[env][CH / 2][896][896] f32 = pi (Im g cos pi x - Re g sin pi x) from phase
-// (same shape) is the only output (phase_grad_row on the 28 pixels of a lane).
-// GK = kGradSteWindow / kGradSteSigmoid (hbx_threshold_backward): grad = gvb s(x) Re g for the real
-// leaf x of a binary hologram (in `phase`), s and (ga, gb) as ste_grad_row has them.
-// WIN (hbx_backward_window; kGradNone and the two STE kinds, never ST): the one output, real_out or grad,
-// is compact over the window win, as are the leaf's samples (grad_row_win); a row block outside it reads nothing.
+// ST, GK and WIN: cplx_plane_out (hbx_rowinv.hpp) on the 28 pixels of a lane.  ST (hbx_evaluate_complex)
+// also runs k_rowinv896's tail with Q = P / 2 as the plane count -- the plane-mean intensity row to inten_out
+// [job][896][896] and the f64 partials against the target row; WIN: a row block outside win reads nothing.
 template <bool ST = false, int GK = kGradNone, bool WIN = false>
 __global__ __launch_bounds__(256, 2) void k_rowinv896_cplx(const JobDesc* __restrict__ jobs,
                                                            const float2* __restrict__ ws_b,
@@ -588,8 +550,6 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896_cplx(const JobDesc* __rest
                                                            const float* __restrict__ phase,
                                                            float* __restrict__ grad, float gvb, float ga,
                                                            float gb, hbx_window_t win) {
-  static_assert(!(ST && GK != kGradNone), "the gradient forms run no statistics");
-  static_assert(!(WIN && (ST || GK == kGradPhase)), "windows: the real part or an STE gradient");
   __shared__ float2 tw[kN];
   __shared__ float2 scratch[kSCR];
   for (int i = threadIdx.x; i < kN; i += 256) tw[i] = tw_glob[i];
@@ -626,19 +586,14 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896_cplx(const JobDesc* __rest
 #pragma unroll 1
   for (int q = 0; q < Q; ++q) {
     fft896_sn<true, kInvScalar>(v, t, sc, tw);      // slot layout in, natural out: x = t + 32 k
-    if constexpr (ST) {
+    if constexpr (GK == kGradNone && !WIN) {
+      // cplx_plane_out's full-grid field / real-part form, written out (as in k_rowinv_cplx: through the
+      // helper these stores compile to other code, the spills of the ST form too)
+      if constexpr (ST) {
 #pragma unroll
-      for (int k = 0; k < kL; ++k) acc[k] += fmaf(v[k].x, v[k].x, v[k].y * v[k].y);
-    }
-    const size_t row = row0 + (size_t)q * kN * kN;
-    if constexpr (WIN) {
-      const size_t ro = wr.in ? WinRow::row_of(win, ((size_t)jb.env * G + jb.group) * Q + q, y) : 0;
-      grad_row_win<kR, kL, GK>(v, phase + ro, (GK == kGradNone ? real_out : grad) + ro, wr, gvb, ga, gb);
-    } else if constexpr (GK == kGradPhase) {
-      phase_grad_row<kR, kL>(v, phase + row, grad + row);
-    } else if constexpr (GK != kGradNone) {
-      ste_grad_row<kR, kL, GK>(v, phase + row, grad + row, gvb, ga, gb);
-    } else {
+        for (int k = 0; k < kL; ++k) acc[k] += fmaf(v[k].x, v[k].x, v[k].y * v[k].y);
+      }
+      const size_t row = row0 + (size_t)q * kN * kN;
       if (field_out) {
 #pragma unroll
         for (int k = 0; k < kL; ++k) field_out[row + kR * k] = v[k];
@@ -647,6 +602,9 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896_cplx(const JobDesc* __rest
 #pragma unroll
         for (int k = 0; k < kL; ++k) real_out[row + kR * k] = v[k].x;
       }
+    } else {
+      cplx_plane_out<kR, kL, ST, GK, WIN>(v, acc, jb.env, jb.group, G, Q, q, y, row0, win, wr, field_out, real_out,
+                                          phase, grad, gvb, ga, gb);
     }
     if (q + 1 < Q) load_pair(v, q + 1);   // uniform: no pair is read twice
   }
@@ -659,6 +617,16 @@ __global__ __launch_bounds__(256, 2) void k_rowinv896_cplx(const JobDesc* __rest
 
 __global__ void k_reduce_partials(const double* __restrict__ partial, int n_jobs, int RB,
                                   double* __restrict__ job_stats);
+
+// the sample kernels of N = 896 for the shared pick (hbx_internal.hpp)
+struct SampleKernels896 {
+  template <int LK, bool WIN>
+  static auto first_real() { return k_rowfwd896_real<LK, WIN>; }
+  template <int LK, bool WIN>
+  static auto first_cplx() { return k_rowfwd896_cplx<LK, WIN>; }
+  template <bool ST, int GK, bool WIN>
+  static auto last_cplx() { return k_rowinv896_cplx<ST, GK, WIN>; }
+};
 
 hipError_t run_jobs_896(const PlanDev& pd, const PassCall& c, hipStream_t st) {
   const JobDesc* jobs = c.jobs;
@@ -673,22 +641,15 @@ hipError_t run_jobs_896(const PlanDev& pd, const PassCall& c, hipStream_t st) {
   const unsigned blocks = (unsigned)n_jobs * kRB;   // one workgroup per row block of a job
 
   if (tm) tm->begin(0, st);
-  // (the windowed forms are named behind the others, here and below: they come last in the code object)
   const bool win_in = pass_window_in(c, kN);
-  if (pass_complex(c))   // the load kind: complex samples as they are, times scale * weight, or exp(i pi phase)
-    launch_kernel(!win_in ? (c.complex_weight ? k_rowfwd896_cplx<kLoadWeighted>
-                                 : c.complex_values ? k_rowfwd896_cplx<kLoadComplex> : k_rowfwd896_cplx<kLoadPhase>)
-                              : (c.complex_weight ? k_rowfwd896_cplx<kLoadWeighted, true>
-                                                  : k_rowfwd896_cplx<kLoadComplex, true>),
-                  blocks * (P / 2), 256, st, jobs, c.complex_values, pd.ws_a, pd.tw, P, CH, c.complex_weight,
-                  c.complex_scale, c.phase_values, c.in_win);
-  else if (c.real_values)
+  if (pass_complex(c)) {   // the load kind: complex samples as they are, times scale * weight, or exp(i pi phase)
+    const int lk = c.phase_values ? kLoadPhase : c.complex_weight ? kLoadWeighted : kLoadComplex;
+    launch_kernel(pick_first_pass_cplx<SampleKernels896>(lk, win_in), blocks * (P / 2), 256, st, jobs, c.complex_values,
+                  pd.ws_a, pd.tw, P, CH, c.complex_weight, c.complex_scale, c.phase_values, c.in_win);
+  } else if (c.real_values)
     // the load kind: the samples as they are, or (hbx_evaluate_threshold) the field of the bit [x >= threshold]
-    launch_kernel(!win_in ? (!c.real_binarize ? k_rowfwd896_real<kLoadReal> : k_rowfwd896_real<kLoadThreshold>)
-                              : (!c.real_binarize ? k_rowfwd896_real<kLoadReal, true>
-                                                  : k_rowfwd896_real<kLoadThreshold, true>),
-                  blocks * (P / 2), 256, st, jobs, c.real_values, pd.ws_a, pd.tw, P, CH, c.real_threshold, pd.va,
-                  pd.va + pd.vb, c.in_win);
+    launch_kernel(pick_first_pass_real<SampleKernels896>(c.real_binarize != 0, win_in), blocks * (P / 2), 256, st, jobs,
+                  c.real_values, pd.ws_a, pd.tw, P, CH, c.real_threshold, pd.va, pd.va + pd.vb, c.in_win);
   else
     launch_kernel(k_rowfwd896, blocks / kRit896 * (pair ? 1 : P / 2), 256, st, jobs,
                   reinterpret_cast<const uint32_t*>(c.mask), pd.ws_a, pd.tw, P, CH, pd.va, pd.vb, pair);
@@ -700,18 +661,9 @@ hipError_t run_jobs_896(const PlanDev& pd, const PassCall& c, hipStream_t st) {
   if (tm) tm->end(1, n_jobs, st);
 
   if (tm) tm->begin(2, st);
-  if (pass_complex(c)) {   // recombine each plane pair; ST (hbx_evaluate_complex): intensity and partials too;
-                           // kGradPhase (hbx_phase_backward): the phase gradient instead of the field;
-                           // kGradSte* (hbx_threshold_backward): a binary hologram's gated gradient
-    const int gk = c.grad_phase ? c.grad_kind : kGradNone;
-    auto k = gk == kGradNone ? (c.complex_stats ? k_rowinv896_cplx<true> : k_rowinv896_cplx<false>)
-             : gk == kGradPhase ? k_rowinv896_cplx<false, kGradPhase>
-             : gk == kGradSteWindow ? k_rowinv896_cplx<false, kGradSteWindow>
-                                    : k_rowinv896_cplx<false, kGradSteSigmoid>;
-    if (c.windowed)   // the real part or an STE gradient over out_win (check_pass_call)
-      k = gk == kGradNone ? k_rowinv896_cplx<false, kGradNone, true>
-          : gk == kGradSteWindow ? k_rowinv896_cplx<false, kGradSteWindow, true>
-                                 : k_rowinv896_cplx<false, kGradSteSigmoid, true>;
+  if (pass_complex(c)) {   // recombine each plane pair, or a leaf's gradient instead (pick_last_pass_cplx)
+    const auto k = pick_last_pass_cplx<SampleKernels896>(c.grad_phase ? c.grad_kind : kGradNone, c.complex_stats != 0,
+                                                         c.windowed != 0);
     launch_kernel(k, blocks, 256, st, jobs, pd.ws_b, pd.tw, P, pd.G, c.complex_field, c.real_part, tg.rows, tg.mask,
                   pd.partial, c.inten_out, c.grad_samples, c.grad_phase, pd.vb, c.grad_p0, c.grad_p1, c.out_win);
   } else {

@@ -154,10 +154,6 @@ __device__ __forceinline__ void real_load_row(V (&v)[R], const float* __restrict
   for (int jj = L; jj < R; ++jj) v[jj] = V{0.f, 0.f};
 }
 
-// What the real first passes (k_rowfwd_real, k_rowfwd32_real, k_rowfwd896_real) load a row with:
-// real_load_row or threshold_load_row
-constexpr int kLoadReal = 0, kLoadThreshold = 1;
-
 // Binary holograms from a real leaf (hbx_evaluate_threshold): real_load_row's loads, in its order and
 // all issued before the first use, then each sample x becomes the field of its mask bit [x >= thr]:
 // hi = va + vb where the bit is set, lo = va where it is not -- NaN compares false and gives lo, as
@@ -220,10 +216,6 @@ __device__ __forceinline__ void complex_load_row_weighted(V (&v)[R], const float
 #pragma unroll
   for (int jj = L; jj < R; ++jj) v[jj] = V{0.f, 0.f};
 }
-
-// What the complex first passes (k_rowfwd_cplx, k_rowfwd32_cplx, k_rowfwd896_cplx) load a row with:
-// complex_load_row, complex_load_row_weighted or phase_load_row
-constexpr int kLoadComplex = 0, kLoadWeighted = 1, kLoadPhase = 2;
 
 // Phase holograms (hbx_simulate_phase): u = exp(i pi x) from the float32 sample x.  sincospif reduces
 // the argument exactly (x mod 2 has no rounding in float32, unlike x * float32(pi)), so the error of
@@ -371,6 +363,69 @@ __device__ __forceinline__ void complex_load_row_win(V (&v)[R], const float2* __
   }
 #pragma unroll
   for (int jj = L; jj < R; ++jj) v[jj] = V{0.f, 0.f};
+}
+
+// ---------------------------------------------------------------------------
+// The sample first passes' row load, once for every size (N = R L; k_rowfwd_real / _cplx, their
+// N = 1024 and N = 896 forms): row y of the job's plane into v, up to the barrier that publishes the
+// twiddles.  (env, group) = the job's; they, P, CH and the plane index arrive as scalars and the window
+// by reference, and the addresses are formed here in this order: handed over as a whole JobDesc, as
+// ready size_t indices or with the window by value, the kernels compiled to other code.
+//
+// Real fields: values[env][CH][N][N] f32, planes pa and pa + 1 of the job's group into (re, im).
+//   LK = kLoadReal       the samples as they are (real_load_row)
+//   LK = kLoadThreshold  (hbx_evaluate_threshold) each sample becomes the field of its mask bit, hi where
+//                        x >= thr and lo elsewhere, as it is loaded; thr / lo / hi are unused otherwise
+//   WIN  (hbx_evaluate_real_window / _threshold_window) values is compact, [env][CH][win.h][win.w], and
+//        sits at win of the grid, which is 0 elsewhere: real_load_row_win loads a pixel only inside
+template <int R, int L, int LK, bool WIN, class V>
+__device__ __forceinline__ void first_pass_load_real(V (&v)[R], const float* values, int env, int group,
+                                                     int P, int CH, int pa, int y, int t, float thr, float lo,
+                                                     float hi, const hbx_window_t& win) {
+  constexpr int N = R * L;
+  if constexpr (WIN) {
+    const WinRow wr(win, y, t);
+    const size_t ro = wr.in ? WinRow::row_of(win, (size_t)env * CH + group * P + pa, y) : 0;
+    real_load_row_win<R, L, LK>(v, values + ro, (size_t)win.h * win.w, wr, thr, lo, hi);
+  } else {
+    const float* row = values + (((size_t)env * CH + group * P + pa) * N + y) * N;
+    if constexpr (LK == kLoadThreshold)
+      threshold_load_row<R, L>(v, row, (size_t)N * N, t, thr, lo, hi);
+    else
+      real_load_row<R, L>(v, row, (size_t)N * N, t);
+  }
+}
+
+// Complex fields: values[env][CH / 2][N][N] complex64, complex plane q of the job's group as it is.
+//   LK = kLoadComplex   (hbx_simulate_complex) complex_load_row
+//   LK = kLoadWeighted  (hbx_simulate_complex_weighted) times scale * weight[env][group][y][x] as it is
+//                       loaded -- L more VGPRs live across the load; weight / scale are unused otherwise
+//   LK = kLoadPhase     (hbx_simulate_phase) phase[env][CH / 2][N][N] f32 instead of values, exp(i pi x)
+//                       formed on load -- L floats live where the complex form holds L pairs; phase is
+//                       unused by the other kinds
+//   WIN  (hbx_backward_window; kLoadComplex and kLoadWeighted) values [env][CH / 2][win.h][win.w] and
+//        weight [env][G][win.h][win.w] are compact and sit at win of the grid, 0 elsewhere
+template <int R, int L, int LK, bool WIN, class V>
+__device__ __forceinline__ void first_pass_load_cplx(V (&v)[R], const float2* values,
+                                                     const float* weight, float scale,
+                                                     const float* phase, int env, int group, int P,
+                                                     int CH, int q, int y, int t, const hbx_window_t& win) {
+  constexpr int N = R * L;
+  if constexpr (WIN) {
+    static_assert(LK != kLoadPhase, "phase leaves are not windowed");
+    const WinRow wr(win, y, t);
+    const size_t ro = wr.in ? WinRow::row_of(win, (size_t)env * (CH / 2) + group * (P / 2) + q, y) : 0;
+    const size_t wo = wr.in ? WinRow::row_of(win, (size_t)env * (CH / P) + group, y) : 0;
+    complex_load_row_win<R, L, LK>(v, values + ro, LK == kLoadWeighted ? weight + wo : nullptr, scale, wr);
+  } else {
+    const size_t row = (((size_t)env * (CH / 2) + group * (P / 2) + q) * N + y) * N;
+    if constexpr (LK == kLoadWeighted)
+      complex_load_row_weighted<R, L>(v, values + row, weight + (((size_t)env * (CH / P) + group) * N + y) * N, scale, t);
+    else if constexpr (LK == kLoadPhase)
+      phase_load_row<R, L>(v, phase + row, t);
+    else
+      complex_load_row<R, L>(v, values + row, t);
+  }
 }
 
 // The complex last passes' stores over an output window: g0 / p0 = the compact rows of the output and

@@ -6,8 +6,8 @@
 // <32, 28>).  The block prologue (twiddle staging, the grp / t / rb / j decode) stays
 // written out in the six kernels: as a helper it changed the code of every one of them (the group's
 // scratch offset formed from the shifted instead of the masked thread id, another register assignment).
-// So does the complex kernels' per-plane output step (|F|^2, field_out, real_out): as a helper it changed
-// k_rowinv896_cplx (its spills too) and k_rowinv_cplx.
+// The complex kernels' per-plane output step is cplx_plane_out, except its full-grid field / real-part
+// form in k_rowinv_cplx and k_rowinv896_cplx: as a helper that form changed both (k_rowinv896_cplx's spills too).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -304,6 +304,56 @@ __device__ __forceinline__ void plane_out_win(const V (&v)[NV], float (&acc)[L],
 #pragma unroll
     for (int k = 0; k < L; ++k)
       if (wr.has(R * k)) frow[wr.xo + R * k] = make_float2(v[k].x, v[k].y);
+  }
+}
+
+// One complex plane F_q out of the inverse row FFT of the complex last passes (k_rowinv_d_cplx, k_rowinv_cplx,
+// k_rowinv896_cplx; v: natural layout, x = t + R k; V = pk2, or float2 at 896, stored as it is).  row0 = the
+// lane's pixel x = t of row y of the group's complex plane 0 in an [env][G Q][N][N] array.
+//   ST  (hbx_evaluate_complex) |F_q|^2 is also accumulated per pixel, acc += fmaf(re, re, im * im) as the
+//       bit path's plane_out does; field_out and real_out may then both be null
+//   GK = kGradNone   F_q to field_out and / or Re F_q to real_out, either nullable
+//   GK = kGradPhase  (hbx_phase_backward) the plane is the gradient with respect to u = exp(i pi x): grad
+//                    from the samples in `phase` (phase_grad_row) and nothing else
+//   GK = kGradSteWindow / kGradSteSigmoid  (hbx_threshold_backward) grad = gvb s(x) Re g for a binary
+//                    hologram's real leaf x (in `phase`), s and (ga, gb) as ste_grad_row has them
+//   WIN (hbx_backward_window; kGradNone and the two STE kinds, never ST) the one output, real_out or grad,
+//       is compact over the window, [env][G Q][h][w], as are the leaf's samples (grad_row_win)
+template <int R, int L, bool ST, int GK, bool WIN, class V, int NV>
+__device__ __forceinline__ void cplx_plane_out(V (&v)[NV], float (&acc)[ST ? L : 1], int env, int group, int G,
+                                               int Q, int q, int y, size_t row0, const hbx_window_t& win,
+                                               const WinRow& wr, float2* field_out,
+                                               float* real_out, const float* phase,
+                                               float* grad, float gvb, float ga, float gb) {
+  static_assert(!(ST && GK != kGradNone), "the gradient forms run no statistics");
+  static_assert(!(WIN && (ST || GK == kGradPhase)), "windows: the real part or an STE gradient");
+  constexpr int N = R * L;
+  if constexpr (ST) {
+#pragma unroll
+    for (int k = 0; k < L; ++k) acc[k] += fmaf(v[k].x, v[k].x, v[k].y * v[k].y);
+  }
+  if constexpr (WIN) {
+    const size_t ro = wr.in ? WinRow::row_of(win, ((size_t)env * G + group) * Q + q, y) : 0;
+    grad_row_win<R, L, GK>(v, phase + ro, (GK == kGradNone ? real_out : grad) + ro, wr, gvb, ga, gb);
+  } else {
+    const size_t row = row0 + (size_t)q * N * N;
+    if constexpr (GK == kGradPhase) {   // the samples are loaded behind the FFT: no second line is ever held
+      phase_grad_row<R, L>(v, phase + row, grad + row);
+    } else if constexpr (GK != kGradNone) {
+      ste_grad_row<R, L, GK>(v, phase + row, grad + row, gvb, ga, gb);
+    } else {
+      if (field_out) {
+#pragma unroll
+        for (int k = 0; k < L; ++k) {
+          if constexpr (std::is_same<V, float2>::value) field_out[row + R * k] = v[k];
+          else field_out[row + R * k] = from_pk(v[k]);
+        }
+      }
+      if (real_out) {
+#pragma unroll
+        for (int k = 0; k < L; ++k) real_out[row + R * k] = v[k].x;
+      }
+    }
   }
 }
 
