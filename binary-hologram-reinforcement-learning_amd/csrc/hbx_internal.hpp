@@ -83,6 +83,32 @@ __host__ __device__ constexpr size_t plane_b_elems(int R) {
   return (size_t)(R * R / pan_b(R)) * panel_stride(R, R * R, pan_b(R));
 }
 
+// The launch-size switch of the bit path's first pass and of the column pass (hbx_passes.hip, N = 1024 /
+// 256).  The walking forms -- a workgroup walks rowfwd_iters row blocks of a plane pair, col2_iters lines
+// of a lane group -- trade parallelism for store overlap, which pays only when the launch fills the chip
+// many times over; a launch of fewer than kSmallBlocks workgroups in both passes runs the forms with one
+// row block / one line per workgroup instead.  pass_launch_small is the one place that decides
+// (launch_passes calls it); tests/c/launch_size_table.hip prints where it turns, tests/_launch_size.py
+// restates it for the GPU tests that put one input through both forms (tests/test_gpu_launch_size.py).
+__host__ __device__ constexpr int pass_rowfwd_iters(int R) { return R == 32 ? 4 : (R == 16 ? 2 : 1); }
+__host__ __device__ constexpr int pass_col2_iters(int R) { return R == 32 ? 4 : (R == 16 ? 2 : 1); }
+constexpr unsigned kSmallBlocks = 2048;
+// workgroups of the walking first pass / column pass for n_jobs jobs of P planes (pair: the plane-cached
+// step, one plane pair per job)
+inline unsigned pass_rowfwd_blocks(int R, int P, int n_jobs, bool pair) {
+  const unsigned row_blocks = R * R / panel_rows(R);   // per plane pair
+  return (unsigned)n_jobs * (pair ? 1 : P / 2) * row_blocks / pass_rowfwd_iters(R);
+}
+inline unsigned pass_col2_blocks(int R, int P, int n_jobs, bool pair) {
+  const int gpb = 256 / R;                             // lane groups per workgroup
+  return (unsigned)n_jobs * (pair ? 2 : P) * ((R * R / 2) / (gpb * pass_col2_iters(R)));
+}
+// N = 64 (R = 8) has one form of each kernel, N = 896 its own launcher: never small
+inline bool pass_launch_small(int R, int P, int n_jobs, bool pair) {
+  return (R == 32 || R == 16) && pass_rowfwd_blocks(R, P, n_jobs, pair) < kSmallBlocks &&
+         pass_col2_blocks(R, P, n_jobs, pair) < kSmallBlocks;
+}
+
 // Line kx of a panel-layout plane as addressed by lane t of an R-lane group:
 // element y = t + R jj sits at byte offset voff(t, kx) + joff(jj) from the
 // plane base (joff is a compile-time constant per jj: an SGPR or immediate

@@ -133,7 +133,7 @@ constexpr bool kTiledB = R == 32 || R == 16;
 // row block per workgroup the load -> FFT -> LDS tile -> store chain of the
 // two co-resident workgroups ran nearly serial.
 template <int R>
-constexpr int rowfwd_iters() { return R == 32 ? 4 : (R == 16 ? 2 : 1); }   // N = 256: 2 (r03,
+constexpr int rowfwd_iters() { return pass_rowfwd_iters(R); }   // 4 / 2 / 1 (hbx_internal.hpp).  N = 256: 2 (r03,
 // with nt A stores: 0.0634 -> 0.0585 ms; 4 row blocks 0.0611)
 
 // The job of workgroup's job index j: jobs[j], or (actions non-null: the env step) decoded from
@@ -639,9 +639,9 @@ __global__ __launch_bounds__(256, 3) void k_rowfwd32_cplx(const JobDesc* __restr
 // stage stores.  Rebuilt with the soffset-0 stores (r04) it is exact (the 256 flip
 // map / mono / plane tests, profiles/r04/iter1_tests_r04b.txt) and no faster (0.1445-0.1447 ms vs
 // 0.1432-0.1445 for ITER = 2, profiles/r04/iter1_ab_r04b.txt), so ITER = 2 stays; small launches
-// use ITER = 1 (launch_passes' kSmallBlocks).
+// use ITER = 1 (pass_launch_small, hbx_internal.hpp).
 template <int R>
-__host__ __device__ constexpr int col2_iters() { return R == 32 ? 4 : (R == 16 ? 2 : 1); }
+__host__ __device__ constexpr int col2_iters() { return pass_col2_iters(R); }   // 4 / 2 / 1
 
 // N = 1024 / 256: the output line sets of a k_col2 block (TL lines: group g = slot g of
 // slot tile st, TileB) go out through the FFT scratch.  col2_stage_write: each group
@@ -1420,11 +1420,12 @@ static hipError_t launch_passes(const PlanDev& pd, const PassCall& c, hipStream_
   // (rowfwd_iters row blocks, col2_iters lines) trade parallelism for store overlap, which pays
   // only when the launch fills the chip many times over.  Below kSmallBlocks workgroups the
   // launch runs one row block / one line per workgroup instead -- the same arithmetic, so
-  // bit-identical results (tests/test_gpu_dbs_headline.py plane-cache / full re-propagation).
-  constexpr unsigned kSmallBlocks = 2048;
-  const unsigned rf_blocks = (unsigned)n_jobs * (pair ? 1 : P / 2) * kRowBlocks / rowfwd_iters<R>();
-  const unsigned col_blocks = (unsigned)n_jobs * (pair ? 2 : P) * ((N / 2) / (GPB * col2_iters<R>()));
-  const bool small = kTiledB<R> && rf_blocks < kSmallBlocks && col_blocks < kSmallBlocks;
+  // bit-identical results: tests/test_gpu_launch_size.py puts the same inputs through both forms
+  // and compares every output array.  pass_launch_small (hbx_internal.hpp) decides.
+  static_assert(kRowBlocks == N / panel_rows(R) && GPB == 256 / R, "pass_*_blocks count these workgroups");
+  const unsigned rf_blocks = pass_rowfwd_blocks(R, P, n_jobs, pair != 0);
+  const unsigned col_blocks = pass_col2_blocks(R, P, n_jobs, pair != 0);
+  const bool small = pass_launch_small(R, P, n_jobs, pair != 0);
   // real and complex samples: the bit kernels' geometry (complex: wg.q = the complex plane), one row
   // block per workgroup at every launch size
   const unsigned sample_blocks = (unsigned)n_jobs * (P / 2) * kRowBlocks;

@@ -9,7 +9,9 @@ bits, then the same row FFT, Hermitian split and stores), so
     chan_stats rtol 2e-5, PSNR <= 1e-4 dB.  Samples are drawn as float32 and handed to the
     oracle as their float64 upcast, so no input rounding enters the comparison.
 The real first pass runs one row block per workgroup at every launch size (no small / large
-launch switch as on the bit path), so there is no second regime to cover."""
+launch switch as on the bit path), so the first pass has no second regime to cover; k_col2 behind it
+switches with the job count as on the bit path, and tests/test_gpu_launch_size.py puts real samples
+through both of its forms."""
 import functools
 
 import numpy as np
