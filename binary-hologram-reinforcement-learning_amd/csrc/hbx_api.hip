@@ -467,6 +467,13 @@ int check_eval_outputs(const float* target, const double* chan_stats, const doub
   return HBX_OK;
 }
 
+// the level count of the hbx_*_phase_levels calls and of hbx_quantize_phase
+int check_levels(int32_t levels) {
+  if (levels < 2 || levels > 256)
+    return fail(HBX_ERR_INVALID, "levels: the number of phase levels, 2 <= levels <= 256 (got " + std::to_string(levels) + ")");
+  return HBX_OK;
+}
+
 // the straight-through surrogate of hbx_threshold_backward / hbx_backward_window and its slope
 int check_surrogate(int32_t surrogate, float p1) {
   if (surrogate != HBX_STE_WINDOW && surrogate != HBX_STE_SIGMOID)
@@ -487,6 +494,8 @@ struct FullRequest {
   const float* weight = nullptr;
   float scale = 1.0f;
   const float* phase_values = nullptr; // phase samples [n][G*P/2][N][N] f32, u = exp(i pi x): complex input from here on
+  int phase_levels = 0;                // (hbx_*_phase_levels) L: phase_values, or grad_samples of the phase
+                                       // gradient, are quantized to L levels as they are loaded; 0: continuous
   const float* target = nullptr;       // [n][G][N][N]; null: no statistics
   const int32_t* env_ids = nullptr;    // absolute env ids into every buffer (mask input only); null: 0 .. n - 1
   int n = 0;
@@ -580,6 +589,7 @@ int propagate_full(hbx_plan_t p, const FullRequest& r, void* stream) {
     c.complex_weight = at(r.weight, s_wgt);
     c.complex_scale = r.scale;
     c.phase_values = at(r.phase_values, s_cplx);
+    c.phase_levels = r.phase_levels;
     c.target = at(r.target, s_img);
     c.inten_out = direct ? at(r.intensity, s_img) : (r.intensity ? p->job_inten : nullptr);
     c.field_out = at(r.field, s_field);
@@ -749,6 +759,48 @@ int hbx_phase_backward(hbx_plan_t p, const float* values, const float* weight, f
   r.complex_values = reinterpret_cast<const float2*>(values); r.weight = weight; r.n = n_env;
   if (weight) r.scale = scale;
   r.grad_samples = phase; r.grad_phase = grad_phase;
+  return propagate_full(p, r, stream);
+}
+
+// hbx_simulate_phase with the first pass quantizing the samples to `levels` levels as it loads them
+int hbx_simulate_phase_levels(hbx_plan_t p, const float* phase, int32_t levels, int32_t n_env, float* field,
+                              float* real_part, void* stream) {
+  HBX_ENTER(p, n_env, "n_env");
+  if (int rc = check_levels(levels)) return rc;
+  if (!phase || (!field && !real_part)) return fail(HBX_ERR_INVALID, "null buffer");
+  if (int rc = check_real_plan(p, true)) return rc;
+  FullRequest r;
+  r.phase_values = phase; r.phase_levels = levels; r.n = n_env;
+  r.complex_field = reinterpret_cast<float2*>(field); r.real_part = real_part;
+  return propagate_full(p, r, stream);
+}
+
+// hbx_evaluate_phase with the quantizing first pass
+int hbx_evaluate_phase_levels(hbx_plan_t p, const float* phase, int32_t levels, const float* target, int32_t n_env,
+                              float* field, float* intensity, double* chan_stats, double* psnr, void* stream) {
+  HBX_ENTER(p, n_env, "n_env");
+  if (int rc = check_levels(levels)) return rc;
+  if (!phase) return fail(HBX_ERR_INVALID, "null buffer");
+  if (int rc = check_eval_outputs(target, chan_stats, psnr, intensity != nullptr, true)) return rc;
+  if (int rc = check_real_plan(p, true)) return rc;
+  FullRequest r;
+  r.phase_values = phase; r.phase_levels = levels; r.target = target; r.n = n_env;
+  r.complex_field = reinterpret_cast<float2*>(field); r.complex_stats = true;
+  r.intensity = intensity; r.chan_stats = chan_stats; r.psnr = psnr;
+  return propagate_full(p, r, stream);
+}
+
+// hbx_phase_backward with the last pass quantizing the samples: the straight-through gradient
+int hbx_phase_levels_backward(hbx_plan_t p, const float* values, const float* weight, float scale, const float* phase,
+                              int32_t levels, int32_t n_env, float* grad_phase, void* stream) {
+  HBX_ENTER(p, n_env, "n_env");
+  if (int rc = check_levels(levels)) return rc;
+  if (!values || !phase || !grad_phase) return fail(HBX_ERR_INVALID, "null buffer");
+  if (int rc = check_real_plan(p, true)) return rc;
+  FullRequest r;
+  r.complex_values = reinterpret_cast<const float2*>(values); r.weight = weight; r.n = n_env;
+  if (weight) r.scale = scale;
+  r.grad_samples = phase; r.grad_phase = grad_phase; r.phase_levels = levels;
   return propagate_full(p, r, stream);
 }
 
@@ -1611,6 +1663,17 @@ int hbx_plan_read_timing(hbx_plan_t p, double* ms_total, int64_t* launches, int6
     tm->calls[k] = 0;
     tm->jobs[k] = 0;
   }
+  return HBX_OK;
+}
+
+int hbx_quantize_phase(const float* src, int64_t n_values, int32_t levels, uint8_t* out_levels, float* out_phase,
+                       void* stream) {
+  if (n_values < 0) return fail(HBX_ERR_INVALID, "hbx_quantize_phase: n_values < 0");
+  if (int rc = check_levels(levels)) return rc;
+  if (n_values == 0) return HBX_OK;
+  if (!out_levels && !out_phase) return fail(HBX_ERR_INVALID, "hbx_quantize_phase: no output: out_levels or out_phase");
+  if (!src) return fail(HBX_ERR_INVALID, "hbx_quantize_phase: null buffer");
+  HBX_HIP(hbx::launch_quantize_phase(src, n_values, levels, out_levels, out_phase, (hipStream_t)stream));
   return HBX_OK;
 }
 

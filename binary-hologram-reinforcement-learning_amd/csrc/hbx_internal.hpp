@@ -4,6 +4,7 @@
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "hbx.h"
 
@@ -220,14 +221,43 @@ constexpr int kPlanesOff = 0, kPlanesFill = 1, kPlanesStep = 2;
 // real_load_row or threshold_load_row (hbx_rowcol.hpp) ...
 constexpr int kLoadReal = 0, kLoadThreshold = 1;
 // ... and the complex ones (k_rowfwd_cplx, k_rowfwd32_cplx, k_rowfwd896_cplx): complex_load_row,
-// complex_load_row_weighted or phase_load_row
-constexpr int kLoadComplex = 0, kLoadWeighted = 1, kLoadPhase = 2;
+// complex_load_row_weighted or phase_load_row; kLoadPhaseLevels (hbx_simulate_phase_levels): phase_load_row
+// with the quantizer (quantize_phase_sample, below) between the load and the sincos
+constexpr int kLoadComplex = 0, kLoadWeighted = 1, kLoadPhase = 2, kLoadPhaseLevels = 3;
 
 // What the complex last passes (k_rowinv_d_cplx, k_rowinv_cplx, k_rowinv896_cplx) write: the plane
 // (field, real part, statistics: kGradNone), or a real leaf's gradient instead of it --
 // phase_grad_row, or ste_grad_row with one of the two surrogate derivatives (hbx_rowcol.hpp).
-// PassCall::grad_kind is one of the last three
-constexpr int kGradNone = 0, kGradPhase = 1, kGradSteWindow = 2, kGradSteSigmoid = 3;
+// PassCall::grad_kind is one of the last three.  kGradPhaseLevels (hbx_phase_levels_backward) is never
+// named by a caller: it is kGradPhase with PassCall::phase_levels set (pass_grad_kind), phase_grad_row
+// with the quantizer on the samples it loads
+constexpr int kGradNone = 0, kGradPhase = 1, kGradSteWindow = 2, kGradSteSigmoid = 3, kGradPhaseLevels = 4;
+
+// The phase quantizer (hbx.h, "Quantized phase holograms"): the float32 phase sample x, in units of pi,
+// to the nearest of L levels 2 k / L.  Every operation is float32, round-half-to-even:
+//   r = x - 2 rint(x / 2)   exact, r in [-1, 1] (so a contraction of the subtract into an fma changes nothing)
+//   k = rint(r h)           h = float32(L / 2): one multiply, then the rounding
+//   q = k s                 s = float32(2.0 / L): one multiply
+// Ties go to the even k -- deliberately not hbx_evaluate_threshold's >= rule: rint is one instruction, and
+// a quantizer that is odd in x keeps q(-x) = -q(x).  A non-finite x gives q = NaN (inf - inf).
+// h and s are the host's values (phase_levels_of) wherever a kernel quantizes: the pass kernels, the
+// export kernel (hbx_pack.hip) and the host-side checks share this one definition.
+struct PhaseLevels {
+  float h, s;
+};
+inline PhaseLevels phase_levels_of(int levels) { return {(float)(levels / 2.0), (float)(2.0 / levels)}; }
+__host__ __device__ __forceinline__ float quantize_phase_k(float x, float h) {
+  const float r = x - 2.0f * rintf(x * 0.5f);
+  return rintf(r * h);
+}
+__host__ __device__ __forceinline__ float quantize_phase_sample(float x, float h, float s) {
+  return quantize_phase_k(x, h) * s;
+}
+// the level the device displays, k mod L in [0, L); a NaN k gives 0 by a select, no NaN is ever cast
+__host__ __device__ __forceinline__ int quantize_phase_level(float k, int levels) {
+  const int ki = (int)(k == k ? k : 0.0f);
+  return ki < 0 ? ki + levels : ki;
+}
 
 // One three-pass propagation (run_jobs): everything a launch needs beyond the plan.  A call site
 // names what it sets; check_pass_call states which combinations mean something.
@@ -259,6 +289,12 @@ struct PassCall {
   // u = exp(i pi x) formed by the first pass as it loads them, phase plane q into plane-pair slot q.
   // Everything behind the load is complex_values' path: the same outputs and the same rules
   const float* phase_values = nullptr;
+  // (ABI v15, additive) hbx_*_phase_levels: the number of levels L in [2, 256] the phase samples are
+  // quantized to as they are loaded (quantize_phase_sample), 0 = continuous.  With phase_values: the first
+  // pass propagates exp(i pi q(x)); with the phase-gradient pair below: the last pass evaluates its
+  // gradient at q(grad_samples) -- the straight-through estimator dq/dx := 1.  Neither q nor u is written.
+  // Never with a window (phase leaves are not windowed) or any other load or gradient kind
+  int phase_levels = 0;
   // env step at N = 1024 / 256: the first pass decodes the actions itself (no
   // k_jobs_from_actions launch) and one of its workgroups per job writes the JobDesc the later
   // passes read
@@ -329,6 +365,32 @@ inline bool pass_window_in(const PassCall& c, int N) {
 // The complex path: complex or phase samples in, the pair-recombining last pass out
 inline bool pass_complex(const PassCall& c) { return c.complex_values || c.phase_values; }
 
+// The quantizing forms' constants reach the kernels in arguments their load / gradient kind leaves unread, so
+// no kernel signature changes (and no existing kernel's code): the first pass reads h where the weighted load
+// reads scale and the bits of s in the first word of the window it is never given (phase leaves are not
+// windowed); the last pass reads (h, s) where the STE kinds read (ga, gb).
+inline float pass_first_scale(const PassCall& c) {
+  return c.phase_values && c.phase_levels ? phase_levels_of(c.phase_levels).h : c.complex_scale;
+}
+inline hbx_window_t pass_first_window(const PassCall& c) {
+  if (!(c.phase_values && c.phase_levels)) return c.in_win;
+  const float s = phase_levels_of(c.phase_levels).s;
+  hbx_window_t w = {0, 0, 0, 0};
+  static_assert(sizeof(w.y0) == sizeof(s), "a float's bits in an int32");
+  memcpy(&w.y0, &s, sizeof(s));
+  return w;
+}
+// the last pass's gradient kind and its two parameters
+inline int pass_grad_kind(const PassCall& c) {
+  return !c.grad_phase ? kGradNone : (c.grad_kind == kGradPhase && c.phase_levels ? kGradPhaseLevels : c.grad_kind);
+}
+inline float pass_grad_p0(const PassCall& c) {
+  return pass_grad_kind(c) == kGradPhaseLevels ? phase_levels_of(c.phase_levels).h : c.grad_p0;
+}
+inline float pass_grad_p1(const PassCall& c) {
+  return pass_grad_kind(c) == kGradPhaseLevels ? phase_levels_of(c.phase_levels).s : c.grad_p1;
+}
+
 // Which PassCalls the pass kernels of this plan can run: every field a selected kernel would not
 // read is refused, not ignored.  run_jobs calls it before a timer slot opens or a kernel is enqueued.
 inline hipError_t check_pass_call(const PlanDev& pd, const PassCall& c) {
@@ -359,6 +421,12 @@ inline hipError_t check_pass_call(const PlanDev& pd, const PassCall& c) {
   // the weight rides on the complex load, the threshold on the real one
   ok = ok && (c.complex_values || !c.complex_weight);
   ok = ok && (c.real_values || !c.real_binarize);
+  // the level count: 0 or [2, 256], on the phase load or on the phase gradient and nowhere else, no window
+  if (c.phase_levels != 0) {
+    ok = ok && c.phase_levels >= 2 && c.phase_levels <= 256;
+    ok = ok && (c.phase_values ? !grad_out : (grad_out && c.grad_kind == kGradPhase));
+    ok = ok && !c.windowed;
+  }
   // windows: whole rectangles of the grid; real samples in, or complex samples in and the real part or an
   // STE gradient out; no plane cache, actions, walk or reconcile, and nothing env-major
   if (c.windowed) {
@@ -449,6 +517,8 @@ inline auto pick_first_pass_cplx(int lk, bool win_in) {
                               : F::template first_cplx<kLoadWeighted, false>();
   if (win_in)
     k = lk == kLoadWeighted ? F::template first_cplx<kLoadWeighted, true>() : F::template first_cplx<kLoadComplex, true>();
+  // (the quantizing phase load, named last: it takes its place behind every kernel on record)
+  if (lk == kLoadPhaseLevels) k = F::template first_cplx<kLoadPhaseLevels, false>();
   return k;
 }
 // gk = kGradNone: the plane itself, with the statistics or without (hbx_evaluate_complex); kGradPhase
@@ -465,6 +535,8 @@ inline auto pick_last_pass_cplx(int gk, bool stats, bool windowed) {
     k = gk == kGradSteWindow    ? F::template last_cplx<false, kGradSteWindow, true>()
         : gk == kGradSteSigmoid ? F::template last_cplx<false, kGradSteSigmoid, true>()
                                 : F::template last_cplx<false, kGradNone, true>();
+  // (the quantizing phase gradient, named last as the quantizing load is; never windowed)
+  if (gk == kGradPhaseLevels) k = F::template last_cplx<false, kGradPhaseLevels, false>();
   return k;
 }
 // 2-D FFT of n_planes [N][N] complex planes in a (result in a; b is scratch of
@@ -578,6 +650,9 @@ hipError_t launch_obs_settle(const int32_t* env_ids, int n_ids, float* intensity
 // (ABI v14) hbx_pack.hip: mask values -> bits, and relativeLoss statistics
 hipError_t launch_pack_mask(const void* src, int kind, int64_t n_words, int mode, double thr, uint64_t* bits,
                             int32_t* err, hipStream_t st);
+// (ABI v15, additive) hbx_pack.hip: the phase quantizer's export, level[n] uint8 and / or q[n] f32 (nullable)
+hipError_t launch_quantize_phase(const float* src, int64_t n, int levels, uint8_t* out_levels, float* out_phase,
+                                 hipStream_t st);
 int rel_partial_slots();
 hipError_t launch_rel_stats(const void* x, const void* y, int kind, int64_t n, double count, int rel_scale,
                             double peak, double* part, double* out, hipStream_t st);

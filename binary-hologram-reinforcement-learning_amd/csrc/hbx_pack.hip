@@ -298,6 +298,31 @@ hipError_t launch_loss_weight(const float* inten, const float* target, const dou
   return hipGetLastError();
 }
 
+// hbx_quantize_phase: the phase quantizer (quantize_phase_k, hbx_internal.hpp) on n float32 samples, one
+// streaming pass, element i by thread i of a grid-stride loop (any n, no alignment asked of the pointers):
+// level = k mod L as uint8 to out_levels and / or q = k s to out_phase, either nullable.  h and s are the
+// host's values, the ones the pass kernels quantize with.
+__global__ __launch_bounds__(256) void k_quantize_phase(const float* __restrict__ src, int64_t n, int levels, float h,
+                                                        float s, uint8_t* __restrict__ out_levels,
+                                                        float* __restrict__ out_phase) {
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+    const float k = quantize_phase_k(__builtin_nontemporal_load(src + i), h);
+    if (out_levels) out_levels[i] = (uint8_t)quantize_phase_level(k, levels);
+    if (out_phase) out_phase[i] = k * s;
+  }
+}
+
+hipError_t launch_quantize_phase(const float* src, int64_t n, int levels, uint8_t* out_levels, float* out_phase,
+                                 hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  const int64_t want = (n + 1023) / 1024;   // 4 samples per thread before the grid is capped
+  const unsigned blocks = (unsigned)(want < 256 * 16 ? want : 256 * 16);
+  const PhaseLevels q = phase_levels_of(levels);
+  hipLaunchKernelGGL(k_quantize_phase, dim3(blocks), dim3(256), 0, st, src, n, levels, q.h, q.s, out_levels, out_phase);
+  return hipGetLastError();
+}
+
 hipError_t launch_pack_mask(const void* src, int kind, int64_t n_words, int mode, double thr, uint64_t* bits,
                             int32_t* err, hipStream_t st) {
   if (n_words <= 0) return hipSuccess;

@@ -1432,9 +1432,9 @@ static hipError_t launch_passes(const PlanDev& pd, const PassCall& c, hipStream_
 
   if (tm) tm->begin(0, st);
   if (pass_complex(c)) {   // the load kind: complex samples as they are, times scale * weight, or exp(i pi phase)
-    const int lk = c.phase_values ? kLoadPhase : c.complex_weight ? kLoadWeighted : kLoadComplex;
+    const int lk = c.phase_values ? (c.phase_levels ? kLoadPhaseLevels : kLoadPhase) : c.complex_weight ? kLoadWeighted : kLoadComplex;
     launch_kernel(pick_first_pass_cplx<SampleKernels<R>>(lk, pass_window_in(c, N)), sample_blocks, NT, st, jobs,
-                  c.complex_values, pd.ws_a, pd.tw, P, CH, c.complex_weight, c.complex_scale, c.phase_values, c.in_win);
+                  c.complex_values, pd.ws_a, pd.tw, P, CH, c.complex_weight, pass_first_scale(c), c.phase_values, pass_first_window(c));
   } else if (c.real_values) {
     // the load kind: the samples as they are, or (hbx_evaluate_threshold) the field of the bit [x >= threshold]
     launch_kernel(pick_first_pass_real<SampleKernels<R>>(c.real_binarize != 0, pass_window_in(c, N)), sample_blocks, NT,
@@ -1465,10 +1465,10 @@ static hipError_t launch_passes(const PlanDev& pd, const PassCall& c, hipStream_
   const unsigned blocks = (unsigned)n_jobs * kRowBlocks;
   if (tm) tm->begin(2, st);
   if (pass_complex(c)) {   // recombine each plane pair, or a leaf's gradient instead (pick_last_pass_cplx)
-    const auto k = pick_last_pass_cplx<SampleKernels<R>>(c.grad_phase ? c.grad_kind : kGradNone, c.complex_stats != 0,
+    const auto k = pick_last_pass_cplx<SampleKernels<R>>(pass_grad_kind(c), c.complex_stats != 0,
                                                          c.windowed != 0);
     launch_kernel(k, blocks, NT, st, jobs, pd.ws_b, pd.tw, P, pd.G, c.complex_field, c.real_part, tg.rows, tg.mask,
-                  pd.partial, c.inten_out, c.grad_samples, c.grad_phase, pd.vb, c.grad_p0, c.grad_p1, c.out_win);
+                  pd.partial, c.inten_out, c.grad_samples, c.grad_phase, pd.vb, pass_grad_p0(c), pass_grad_p1(c), c.out_win);
   } else if constexpr (kTiledB<R>) {
     // WALK (r05): a plane-cache walk batch, the last workgroup decides.  LEAN (r06): the plain
     // FFT-mode launch (the headline), its own instantiation without the plane cache / field /

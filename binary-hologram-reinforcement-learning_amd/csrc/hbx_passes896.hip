@@ -643,9 +643,9 @@ hipError_t run_jobs_896(const PlanDev& pd, const PassCall& c, hipStream_t st) {
   if (tm) tm->begin(0, st);
   const bool win_in = pass_window_in(c, kN);
   if (pass_complex(c)) {   // the load kind: complex samples as they are, times scale * weight, or exp(i pi phase)
-    const int lk = c.phase_values ? kLoadPhase : c.complex_weight ? kLoadWeighted : kLoadComplex;
+    const int lk = c.phase_values ? (c.phase_levels ? kLoadPhaseLevels : kLoadPhase) : c.complex_weight ? kLoadWeighted : kLoadComplex;
     launch_kernel(pick_first_pass_cplx<SampleKernels896>(lk, win_in), blocks * (P / 2), 256, st, jobs, c.complex_values,
-                  pd.ws_a, pd.tw, P, CH, c.complex_weight, c.complex_scale, c.phase_values, c.in_win);
+                  pd.ws_a, pd.tw, P, CH, c.complex_weight, pass_first_scale(c), c.phase_values, pass_first_window(c));
   } else if (c.real_values)
     // the load kind: the samples as they are, or (hbx_evaluate_threshold) the field of the bit [x >= threshold]
     launch_kernel(pick_first_pass_real<SampleKernels896>(c.real_binarize != 0, win_in), blocks * (P / 2), 256, st, jobs,
@@ -662,10 +662,10 @@ hipError_t run_jobs_896(const PlanDev& pd, const PassCall& c, hipStream_t st) {
 
   if (tm) tm->begin(2, st);
   if (pass_complex(c)) {   // recombine each plane pair, or a leaf's gradient instead (pick_last_pass_cplx)
-    const auto k = pick_last_pass_cplx<SampleKernels896>(c.grad_phase ? c.grad_kind : kGradNone, c.complex_stats != 0,
+    const auto k = pick_last_pass_cplx<SampleKernels896>(pass_grad_kind(c), c.complex_stats != 0,
                                                          c.windowed != 0);
     launch_kernel(k, blocks, 256, st, jobs, pd.ws_b, pd.tw, P, pd.G, c.complex_field, c.real_part, tg.rows, tg.mask,
-                  pd.partial, c.inten_out, c.grad_samples, c.grad_phase, pd.vb, c.grad_p0, c.grad_p1, c.out_win);
+                  pd.partial, c.inten_out, c.grad_samples, c.grad_phase, pd.vb, pass_grad_p0(c), pass_grad_p1(c), c.out_win);
   } else {
     // (r06) the plain FFT-mode launch gets the lean instantiation (profiles/r06/rowinv896_lean_ab_r06i.txt)
     const bool lean = c.plane_mode == kPlanesOff && !c.field_out;

@@ -228,14 +228,21 @@ __device__ __forceinline__ void phase_sincos(float x, float& c, float& s) { sinc
 // 4-byte non-temporal load per element, a coalesced 4 R-byte run per lane group and jj, all L issued
 // before the first use (as real_load_row) -- and v[jj] = (cos pi x, sin pi x); v[L ..] = 0, not
 // exp(0) (N = 896: the padding is no sample).  The tail then sees complex_load_row's row.
-template <int R, int L = R, class V>
-__device__ __forceinline__ void phase_load_row(V (&v)[R], const float* __restrict__ row, int t) {
+//   LK = kLoadPhaseLevels (hbx_simulate_phase_levels): each sample goes through the quantizer
+//   (quantize_phase_sample, hbx_internal.hpp; qh, qs = its h and s, unused otherwise) between the load and
+//   the sincos -- a few VALU instructions per sample, and the tail sees phase_load_row's row of the
+//   materialised q, which is never written
+template <int R, int L = R, int LK = kLoadPhase, class V>
+__device__ __forceinline__ void phase_load_row(V (&v)[R], const float* __restrict__ row, int t, float qh = 0.0f,
+                                               float qs = 0.0f) {
+  static_assert(LK == kLoadPhase || LK == kLoadPhaseLevels, "a phase load kind");
   float a[L];
 #pragma unroll
   for (int jj = 0; jj < L; ++jj) a[jj] = __builtin_nontemporal_load(row + t + R * jj);
 #pragma unroll
   for (int jj = 0; jj < L; ++jj) {
     float c, s;
+    if constexpr (LK == kLoadPhaseLevels) a[jj] = quantize_phase_sample(a[jj], qh, qs);
     phase_sincos(a[jj], c, s);
     v[jj] = V{c, s};
   }
@@ -250,9 +257,13 @@ __device__ __forceinline__ void phase_load_row(V (&v)[R], const float* __restric
 // same row of the phase samples (read once, non-temporal, behind the FFT: no sample is live across
 // it -- at N = 256, where the registers are there, loading them ahead of the FFT measured no faster,
 // DESIGN.md 4q).  phase_load_row's sincos.
-template <int R, int L, class V, int NV>
+//   GK = kGradPhaseLevels (hbx_phase_levels_backward): the samples go through phase_load_row's quantizer
+//   (qh, qs) first, so the gradient is the same expression at the displayed phase q(x) -- the
+//   straight-through estimator dq/dx := 1
+template <int R, int L, int GK = kGradPhase, class V, int NV>
 __device__ __forceinline__ void phase_grad_row(const V (&v)[NV], const float* __restrict__ p0,
-                                               float* __restrict__ g0) {
+                                               float* __restrict__ g0, float qh = 0.0f, float qs = 0.0f) {
+  static_assert(GK == kGradPhase || GK == kGradPhaseLevels, "a phase gradient kind");
   constexpr float kPiF = 3.14159265358979323846f;
   float a[L];
 #pragma unroll
@@ -260,6 +271,7 @@ __device__ __forceinline__ void phase_grad_row(const V (&v)[NV], const float* __
 #pragma unroll
   for (int k = 0; k < L; ++k) {
     float c, s;
+    if constexpr (GK == kGradPhaseLevels) a[k] = quantize_phase_sample(a[k], qh, qs);
     phase_sincos(a[k], c, s);
     g0[R * k] = kPiF * fmaf(v[k].y, c, -(v[k].x * s));
   }
@@ -403,6 +415,9 @@ __device__ __forceinline__ void first_pass_load_real(V (&v)[R], const float* val
 //   LK = kLoadPhase     (hbx_simulate_phase) phase[env][CH / 2][N][N] f32 instead of values, exp(i pi x)
 //                       formed on load -- L floats live where the complex form holds L pairs; phase is
 //                       unused by the other kinds
+//   LK = kLoadPhaseLevels  (hbx_simulate_phase_levels) kLoadPhase on the quantized samples: the quantizer's
+//                       h arrives in scale and the bits of its s in win.y0, both unread by kLoadPhase
+//                       (pass_first_scale / pass_first_window, hbx_internal.hpp)
 //   WIN  (hbx_backward_window; kLoadComplex and kLoadWeighted) values [env][CH / 2][win.h][win.w] and
 //        weight [env][G][win.h][win.w] are compact and sit at win of the grid, 0 elsewhere
 template <int R, int L, int LK, bool WIN, class V>
@@ -412,7 +427,7 @@ __device__ __forceinline__ void first_pass_load_cplx(V (&v)[R], const float2* va
                                                      int CH, int q, int y, int t, const hbx_window_t& win) {
   constexpr int N = R * L;
   if constexpr (WIN) {
-    static_assert(LK != kLoadPhase, "phase leaves are not windowed");
+    static_assert(LK != kLoadPhase && LK != kLoadPhaseLevels, "phase leaves are not windowed");
     const WinRow wr(win, y, t);
     const size_t ro = wr.in ? WinRow::row_of(win, (size_t)env * (CH / 2) + group * (P / 2) + q, y) : 0;
     const size_t wo = wr.in ? WinRow::row_of(win, (size_t)env * (CH / P) + group, y) : 0;
@@ -423,6 +438,8 @@ __device__ __forceinline__ void first_pass_load_cplx(V (&v)[R], const float2* va
       complex_load_row_weighted<R, L>(v, values + row, weight + (((size_t)env * (CH / P) + group) * N + y) * N, scale, t);
     else if constexpr (LK == kLoadPhase)
       phase_load_row<R, L>(v, phase + row, t);
+    else if constexpr (LK == kLoadPhaseLevels)
+      phase_load_row<R, L, kLoadPhaseLevels>(v, phase + row, t, scale, __int_as_float(win.y0));
     else
       complex_load_row<R, L>(v, values + row, t);
   }

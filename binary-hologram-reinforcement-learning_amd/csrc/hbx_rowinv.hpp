@@ -315,6 +315,8 @@ __device__ __forceinline__ void plane_out_win(const V (&v)[NV], float (&acc)[L],
 //   GK = kGradNone   F_q to field_out and / or Re F_q to real_out, either nullable
 //   GK = kGradPhase  (hbx_phase_backward) the plane is the gradient with respect to u = exp(i pi x): grad
 //                    from the samples in `phase` (phase_grad_row) and nothing else
+//   GK = kGradPhaseLevels  (hbx_phase_levels_backward) kGradPhase at the quantized samples; (ga, gb) = the
+//                    quantizer's (h, s), which kGradPhase leaves unread (pass_grad_p0 / _p1)
 //   GK = kGradSteWindow / kGradSteSigmoid  (hbx_threshold_backward) grad = gvb s(x) Re g for a binary
 //                    hologram's real leaf x (in `phase`), s and (ga, gb) as ste_grad_row has them
 //   WIN (hbx_backward_window; kGradNone and the two STE kinds, never ST) the one output, real_out or grad,
@@ -326,7 +328,7 @@ __device__ __forceinline__ void cplx_plane_out(V (&v)[NV], float (&acc)[ST ? L :
                                                float* real_out, const float* phase,
                                                float* grad, float gvb, float ga, float gb) {
   static_assert(!(ST && GK != kGradNone), "the gradient forms run no statistics");
-  static_assert(!(WIN && (ST || GK == kGradPhase)), "windows: the real part or an STE gradient");
+  static_assert(!(WIN && (ST || GK == kGradPhase || GK == kGradPhaseLevels)), "windows: the real part or an STE gradient");
   constexpr int N = R * L;
   if constexpr (ST) {
 #pragma unroll
@@ -339,6 +341,8 @@ __device__ __forceinline__ void cplx_plane_out(V (&v)[NV], float (&acc)[ST ? L :
     const size_t row = row0 + (size_t)q * N * N;
     if constexpr (GK == kGradPhase) {   // the samples are loaded behind the FFT: no second line is ever held
       phase_grad_row<R, L>(v, phase + row, grad + row);
+    } else if constexpr (GK == kGradPhaseLevels) {
+      phase_grad_row<R, L, kGradPhaseLevels>(v, phase + row, grad + row, ga, gb);
     } else if constexpr (GK != kGradNone) {
       ste_grad_row<R, L, GK>(v, phase + row, grad + row, gvb, ga, gb);
     } else {

@@ -11,12 +11,12 @@ The torchOptics-compatible operator shim lives in the sibling package
 from . import _lib
 from ._lib import (ACCEPT_DBS, ACCEPT_ENV, FIELD_AMPLITUDE, FIELD_PHASE, PRECISION_BF16_STORE,
                    PRECISION_F16_STORE, PRECISION_F32, REL_LSQ, REL_NONE, TF_ASM, TF_FRESNEL, HbxError)
-from .plan import (OpticsConfig, Plan, crop, crop_bits, crop_config, mono_config, pack_bits, pack_mask, rgb_config,
-                   unpack_bits)
+from .plan import (OpticsConfig, Plan, crop, crop_bits, crop_config, mono_config, pack_bits, pack_mask,
+                   quantize_phase, rgb_config, unpack_bits)
 
 __all__ = [
     "OpticsConfig", "Plan", "mono_config", "rgb_config", "pack_bits", "pack_mask", "unpack_bits", "crop", "crop_bits",
-    "crop_config", "HbxError",
+    "crop_config", "quantize_phase", "HbxError",
     "TF_ASM", "TF_FRESNEL", "FIELD_AMPLITUDE", "FIELD_PHASE", "REL_LSQ", "REL_NONE", "ACCEPT_ENV",
     "ACCEPT_DBS", "PRECISION_F32", "PRECISION_BF16_STORE", "PRECISION_F16_STORE", "load_library",
 ]

@@ -48,6 +48,7 @@ EXPORTED_SYMBOLS = (
     "hbx_evaluate_threshold", "hbx_threshold_backward",
     "hbx_evaluate_real_window", "hbx_evaluate_threshold_window", "hbx_backward_window",
     "hbx_loss_window", "hbx_loss_weight_window",
+    "hbx_simulate_phase_levels", "hbx_evaluate_phase_levels", "hbx_phase_levels_backward", "hbx_quantize_phase",
 )
 NUM_PASSES = 5
 PASS_NAMES = ("k_rowfwd", "k_col", "k_rowinv", "k_psf_eval", "k_psf_commit")
@@ -149,6 +150,10 @@ def _declare(lib):
     lib.hbx_simulate_phase.argtypes = [VP, VP, I32, VP, VP, VP]
     lib.hbx_evaluate_phase.argtypes = [VP, VP, VP, I32, VP, VP, VP, VP, VP]
     lib.hbx_phase_backward.argtypes = [VP, VP, VP, C.c_float, VP, I32, VP, VP]
+    lib.hbx_simulate_phase_levels.argtypes = [VP, VP, I32, I32, VP, VP, VP]
+    lib.hbx_evaluate_phase_levels.argtypes = [VP, VP, I32, VP, I32, VP, VP, VP, VP, VP]
+    lib.hbx_phase_levels_backward.argtypes = [VP, VP, VP, C.c_float, VP, I32, I32, VP, VP]
+    lib.hbx_quantize_phase.argtypes = [VP, I64, I32, VP, VP, VP]
     lib.hbx_evaluate_threshold.argtypes = [VP, VP, C.c_float, VP, I32, VP, VP, VP, VP, VP]
     lib.hbx_threshold_backward.argtypes = [VP, VP, VP, C.c_float, VP, I32, C.c_float, C.c_float, I32, VP, VP]
     WP = C.POINTER(Window)

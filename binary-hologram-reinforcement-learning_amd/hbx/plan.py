@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import numbers
 from dataclasses import dataclass, field
 from typing import Optional, Sequence
 
@@ -130,6 +131,40 @@ def pack_mask(values: torch.Tensor, threshold: Optional[float] = None, out: Opti
     if rc != _lib.OK:
         _lib.check(rc, "hbx_pack_mask")
     return out
+
+
+def _levels(levels) -> int:
+    """The level count of the quantized-phase calls as an int: integral (a bool is not a count) -- its range,
+    [2, 256], is the library's check (HBX_ERR_INVALID, "levels" in the message)."""
+    if isinstance(levels, bool) or not isinstance(levels, numbers.Integral):
+        raise TypeError(f"levels must be an integer, got {type(levels).__name__}")
+    return int(levels)
+
+
+def quantize_phase(x: torch.Tensor, levels: int, want_levels: bool = True, want_samples: bool = False, stream=None):
+    """The phase quantizer on a device tensor, one HIP launch (hbx_quantize_phase): `x` float32 phase
+    samples in units of pi, any shape.  Returns the uint8 level k mod L of every sample (what an L-level
+    modulator displays: the phase 2 pi level / L) and / or the float32 quantized sample q = k * float32(2 / L)
+    the `*_phase_levels` calls propagate, each of x's shape: one tensor when one is asked for, else
+    (levels, samples).  Ties go to the even k; a non-finite sample gives level 0 and q = NaN."""
+    if not (want_levels or want_samples):
+        raise ValueError("quantize_phase: want_levels and want_samples are both off")
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
+        raise TypeError("quantize_phase: x must be a float32 torch.Tensor")
+    if not x.is_cuda:
+        raise ValueError("quantize_phase runs on the GPU (hbx_quantize_phase)")
+    levels = _levels(levels)
+    x = x.contiguous().resolve_neg()
+    lv = torch.empty(x.shape, dtype=torch.uint8, device=x.device) if want_levels else None
+    q = torch.empty(x.shape, dtype=torch.float32, device=x.device) if want_samples else None
+    lib = _lib.load()
+    s = stream.cuda_stream if stream is not None else torch._C._cuda_getCurrentRawStream(x.device.index)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.hbx_quantize_phase(_ptr(x), x.numel(), levels, _ptr(lv), _ptr(q), C.c_void_p(s)),
+                   "hbx_quantize_phase")
+    if want_levels and want_samples:
+        return lv, q
+    return lv if want_levels else q
 
 
 def pack_bits(mask: torch.Tensor) -> torch.Tensor:
@@ -494,6 +529,76 @@ class Plan:
         grad = torch.empty(shape, dtype=torch.float32, device=self.device)
         _lib.check(self.lib.hbx_phase_backward(self._h, _ptr(values), _ptr(weight), float(scale), _ptr(phase), n,
                                                _ptr(grad), _stream(stream)), "hbx_phase_backward")
+        return grad
+
+    def simulate_phase_levels(self, phase: torch.Tensor, levels: int, want_field: bool = True, want_real: bool = False,
+                              stream=None):
+        """`simulate_phase` of the hologram an L-level modulator displays (hbx_simulate_phase_levels):
+        the first pass quantizes each sample to the nearest of `levels` phase levels (2 <= levels <= 256,
+        `quantize_phase`'s q) as it loads it; q is never written.  Every output equals
+        `simulate_phase(quantize_phase(phase, levels, False, True))`'s bit for bit."""
+        if not (want_field or want_real):
+            raise ValueError("simulate_phase_levels: want_field and want_real are both off")
+        levels = _levels(levels)
+        n = phase.shape[0] if isinstance(phase, torch.Tensor) and phase.dim() else 0
+        shape = self.phase_shape(n)
+        _need(phase, "phase", torch.float32, shape, self.device)
+        phase = phase.resolve_neg()
+        field = torch.empty(shape + (2,), dtype=torch.float32, device=self.device) if want_field else None
+        real = torch.empty(shape, dtype=torch.float32, device=self.device) if want_real else None
+        _lib.check(self.lib.hbx_simulate_phase_levels(self._h, _ptr(phase), levels, n, _ptr(field), _ptr(real),
+                                                      _stream(stream)), "hbx_simulate_phase_levels")
+        return (torch.view_as_complex(field) if want_field else None), real
+
+    def evaluate_phase_levels(self, phase: torch.Tensor, levels: int, target: Optional[torch.Tensor] = None,
+                              want_field: bool = True, want_intensity: bool = True, stream=None):
+        """`evaluate_phase` with `simulate_phase_levels`'s quantizing first pass
+        (hbx_evaluate_phase_levels): the same returns, each `evaluate_phase`'s on the quantized samples
+        bit for bit."""
+        levels = _levels(levels)
+        n = phase.shape[0] if isinstance(phase, torch.Tensor) and phase.dim() else 0
+        c = self.cfg
+        shape = self.phase_shape(n)
+        _need(phase, "phase", torch.float32, shape, self.device)
+        phase = phase.resolve_neg()
+        if target is None:
+            if not want_intensity:
+                raise ValueError("evaluate_phase_levels: without a target the intensity is the only output")
+        else:
+            _need(target, "target", torch.float32, self.target_shape(n), self.device)
+        field = torch.empty(shape + (2,), dtype=torch.float32, device=self.device) if want_field else None
+        inten = torch.empty(self.target_shape(n), dtype=torch.float32, device=self.device) if want_intensity else None
+        stats = psnr = None
+        if target is not None:
+            stats = torch.empty((n, c.groups, 3), dtype=torch.float64, device=self.device)
+            psnr = torch.empty((n,), dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.hbx_evaluate_phase_levels(self._h, _ptr(phase), levels, _ptr(target), n, _ptr(field),
+                                                      _ptr(inten), _ptr(stats), _ptr(psnr), _stream(stream)),
+                   "hbx_evaluate_phase_levels")
+        return (torch.view_as_complex(field) if want_field else None), inten, stats, psnr
+
+    def phase_levels_backward(self, values: torch.Tensor, phase: torch.Tensor, levels: int,
+                              weight: Optional[torch.Tensor] = None, scale: float = 1.0, stream=None) -> torch.Tensor:
+        """The backward pass of a quantized phase leaf under the straight-through estimator, on the
+        plan for -z (hbx_phase_levels_backward): `phase_backward` with the last pass quantizing the
+        leaf's samples as `simulate_phase_levels` does, pi (Im g cos pi q - Re g sin pi q) -- dq/dx := 1.
+        Equals `phase_backward(values, quantize_phase(phase, levels, False, True), weight, scale)` bit
+        for bit."""
+        levels = _levels(levels)
+        n = values.shape[0] if isinstance(values, torch.Tensor) and values.dim() else 0
+        c = self.cfg
+        shape = self.phase_shape(n)
+        _need(values, "values", torch.complex64, shape, self.device)
+        values = values.resolve_conj().resolve_neg()
+        _need(phase, "phase", torch.float32, shape, self.device)
+        phase = phase.resolve_neg()
+        if weight is not None:
+            _need(weight, "weight", torch.float32, (n, c.groups, c.height, c.width), self.device)
+            weight = weight.resolve_neg()
+        grad = torch.empty(shape, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.hbx_phase_levels_backward(self._h, _ptr(values), _ptr(weight), float(scale), _ptr(phase),
+                                                      levels, n, _ptr(grad), _stream(stream)),
+                   "hbx_phase_levels_backward")
         return grad
 
     def evaluate_threshold(self, values: torch.Tensor, threshold: float, target: Optional[torch.Tensor] = None,

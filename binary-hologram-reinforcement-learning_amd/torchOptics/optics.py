@@ -43,6 +43,13 @@ fallback on either):
   backward pass is the straight-through estimator: the last pass of hbx_threshold_backward
   writes vb s(x) Re g with the surrogate derivative s chosen by ``ste`` / ``ste_width``.  No
   0 / 1 copy of x is written in either direction.
+* ``levels=L`` with ``field="phase"`` on that path (``simulate``, ``intensity`` and ``loss``; real
+  input only, 2 <= L <= 256): x is the leaf of the hologram an L-level phase modulator displays.
+  The first pass of hbx_simulate_phase_levels / hbx_evaluate_phase_levels rounds each sample to the
+  nearest level 2 k / L as it loads it (ties to the even k; hbx.quantize_phase exports the levels),
+  and the backward pass is the straight-through estimator dq/dx := 1: the last pass of
+  hbx_phase_levels_backward writes the continuous gradient at the displayed phase.  Neither the
+  quantized samples nor their field is written; ``levels=None`` is the continuous phase path.
 
 ``intensity`` returns the plane-mean intensity mean_p |A u_p|^2 per colour group -- what every loss
 of the project is built on -- on the continuous path: several wavelengths in one call, no field
@@ -64,6 +71,8 @@ tensors it is one fixed-order f64 reduction (hbx_rel_stats) whose PSNR is read f
 host-mapped memory.
 """
 from __future__ import annotations
+
+import numbers
 
 from typing import Callable, Dict, Optional, Tuple
 
@@ -213,6 +222,30 @@ def _ste_args(threshold, ste, ste_width, what: str):
 _GRIDS = (64, 256, 896, 1024)   # the sizes libhbx builds
 
 
+def _levels_arg(levels, binary: bool, complex_in: bool, field_kind: int, thresholded: bool, grid, what: str):
+    """levels= of simulate, intensity and loss -> None, or the level count L of a quantized phase leaf
+    as an int, 2 <= L <= 256: a real x with field="phase" on the continuous path, neither thresholded
+    (a binary hologram is threshold='s business) nor windowed (phase leaves are not).  Anything else
+    raises ValueError before any GPU use."""
+    if levels is None:
+        return None
+    if isinstance(levels, bool) or not isinstance(levels, numbers.Integral):
+        raise ValueError(f"{what}: levels is an integer number of phase levels, got {levels!r}")
+    if not 2 <= int(levels) <= 256:
+        raise ValueError(f"{what}: 2 <= levels <= 256, got {levels}")
+    if binary:
+        raise ValueError(f"{what}: levels= quantizes a phase leaf on the continuous path (binary=False)")
+    if complex_in:
+        raise ValueError(f"{what}: levels= needs a real phase leaf, got a complex field")
+    if field_kind != _lib.FIELD_PHASE:
+        raise ValueError(f"{what}: levels= quantizes a phase, it needs field=\"phase\"")
+    if thresholded:
+        raise ValueError(f"{what}: levels= and threshold= are two different holograms; give one")
+    if grid is not None:
+        raise ValueError(f"{what}: levels= with grid= (phase leaves are not windowed)")
+    return int(levels)
+
+
 def _window_args(grid, origin, roi, shape, complex_in: bool, field_kind: int, thresholded: bool, what: str):
     """grid / origin / roi of simulate, intensity and loss -> None without a grid, else (N, the
     hologram's window, the output window), each window (y0, x0, h, w) in grid coordinates.  Every
@@ -353,7 +386,8 @@ class _WindowLoss(torch.autograd.Function):
 
 
 def simulate(x, z: float, strict: bool = False, binary: bool = True, tf="asm", field="amplitude",
-             threshold=None, ste="window", ste_width=0.5, grid=None, origin=None, roi=None, **_) -> torch.Tensor:
+             threshold=None, ste="window", ste_width=0.5, grid=None, origin=None, roi=None, levels=None,
+             **_) -> torch.Tensor:
     """Free-space propagation of a tensor [B, C, H, W] (or [C, H, W]) by z metres: the
     complex field of every plane, complex64, on the GPU.
 
@@ -391,7 +425,17 @@ def simulate(x, z: float, strict: bool = False, binary: bool = True, tf="asm", f
     and the last pass stores only the roi (hbx_evaluate_real_window / _threshold_window); the
     backward pass is one hbx_backward_window on the plan for -z.  A complex x, field="phase"
     without a threshold, binary=True, or an origin or roi outside the grid raises ValueError before
-    any GPU use."""
+    any GPU use.
+
+    binary=False with field="phase" and levels=L (2 <= L <= 256; None runs the code above untouched):
+    real x is the leaf of the hologram an L-level phase modulator displays -- each sample goes to the
+    nearest level 2 k / L (hbx.quantize_phase; ties to the even k) in the first pass of
+    hbx_simulate_phase_levels as it loads x, and no quantized copy is written.  The result is
+    simulate's on hbx.quantize_phase(x, L, want_levels=False, want_samples=True) bit for bit.  If x
+    requires grad the backward pass is the straight-through estimator dq/dx := 1, one
+    hbx_phase_levels_backward on the plan for -z: the continuous gradient at the displayed phase.
+    levels with binary=True, a complex x, field="amplitude", threshold=, grid=, a non-integer or a
+    value outside [2, 256] raises ValueError before any GPU use."""
     tf_kind = _switch(tf, _TF_NAMES, "tf")
     field_kind = _switch(field, _FIELD_NAMES, "field")
     ste_args = _ste_args(threshold, ste, ste_width, "simulate")
@@ -420,6 +464,7 @@ def simulate(x, z: float, strict: bool = False, binary: bool = True, tf="asm", f
             raise ValueError("tt.simulate: threshold= needs a real leaf, got a complex field")
     if grid is not None and binary:
         raise ValueError("simulate: grid= places a real leaf on the continuous path (binary=False)")
+    levels = _levels_arg(levels, binary, t.is_complex(), field_kind, ste_args is not None, grid, "simulate")
     win = _window_args(grid, origin, roi, t.shape, t.is_complex(), field_kind, ste_args is not None, "simulate")
     if not torch.cuda.is_available():
         raise RuntimeError("tt.simulate needs a ROCm GPU (libhbx.so)")
@@ -449,6 +494,15 @@ def simulate(x, z: float, strict: bool = False, binary: bool = True, tf="asm", f
             out = _PropagateThreshold.apply(xs, geom, field_kind, ste_args)
         else:
             out = _propagate_threshold(xs, geom, field_kind, ste_args[0])
+        return out[0] if squeeze else out
+    if levels is not None:
+        xs = _phase_samples(t)
+        geom = (wl, dx, dy, z, dev, tf_kind)
+        if xs.requires_grad and torch.is_grad_enabled():
+            out = _PropagatePhaseLevels.apply(xs, geom, levels)
+        else:
+            b, c, h, w = xs.shape
+            out = _plan_for(h, w, 2 * c, wl, dx, dy, z, b, dev, tf_kind).simulate_phase_levels(xs, levels)[0]
         return out[0] if squeeze else out
     if not binary:
         out = _simulate_continuous(t, wl, dx, dy, z, dev, tf_kind, field_kind)
@@ -550,6 +604,31 @@ class _PropagatePhase(torch.autograd.Function):
         b, c, h, w = x.shape
         g = grad_output.to(torch.complex64).resolve_conj().resolve_neg().contiguous()
         return _plan_for(h, w, 2 * c, wl, dx, dy, -z, b, dev, tf_kind).phase_backward(g, x), None
+
+
+class _PropagatePhaseLevels(torch.autograd.Function):
+    """_PropagatePhase for a leaf displayed at L phase levels: x -> A exp(i pi q(x)) through
+    hbx_simulate_phase_levels.  Backward, the straight-through estimator dq/dx := 1: one
+    hbx_phase_levels_backward of grad_output on the plan for -z, whose last pass quantizes the saved
+    samples again and writes pi (Im cos pi q - Re sin pi q).  No double backward."""
+
+    @staticmethod
+    def forward(ctx, x, geom, levels):
+        wl, dx, dy, z, dev, tf_kind = geom
+        b, c, h, w = x.shape
+        ctx.geom, ctx.levels = geom, levels
+        ctx.save_for_backward(x)
+        return _plan_for(h, w, 2 * c, wl, dx, dy, z, b, dev, tf_kind).simulate_phase_levels(x, levels)[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        wl, dx, dy, z, dev, tf_kind = ctx.geom
+        x, = ctx.saved_tensors
+        b, c, h, w = x.shape
+        g = grad_output.to(torch.complex64).resolve_conj().resolve_neg().contiguous()
+        adj = _plan_for(h, w, 2 * c, wl, dx, dy, -z, b, dev, tf_kind)
+        return adj.phase_levels_backward(g, x, ctx.levels), None, None
 
 
 def _propagate_threshold(x: torch.Tensor, geom, field_kind: int, tau: float) -> torch.Tensor:
@@ -708,6 +787,33 @@ class _IntensityPhase(torch.autograd.Function):
         return adj.phase_backward(field, x, weight=gi, scale=2.0 / (c // ctx.groups)), None, None
 
 
+class _IntensityPhaseLevels(torch.autograd.Function):
+    """_IntensityPhase for a leaf displayed at L phase levels: one hbx_evaluate_phase_levels that
+    leaves the field F and I; backward one hbx_phase_levels_backward of F on the plan for -z with
+    (2 / P) gI applied in the first pass's load -- the straight-through estimator.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, x, geom, groups, levels):
+        wls, dx, dy, z, dev, tf_kind = geom
+        b, c, h, w = x.shape
+        ctx.geom, ctx.groups, ctx.levels = geom, groups, levels
+        plan = _plan_for(h, w, 2 * c // groups, wls, dx, dy, z, b, dev, tf_kind)
+        field, inten, _, _ = plan.evaluate_phase_levels(x, levels)
+        ctx.save_for_backward(field, x)
+        return inten
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        wls, dx, dy, z, dev, tf_kind = ctx.geom
+        field, x = ctx.saved_tensors
+        b, c, h, w = x.shape
+        gi = grad_output.to(torch.float32).resolve_neg().contiguous()
+        adj = _plan_for(h, w, 2 * c // ctx.groups, wls, dx, dy, -z, b, dev, tf_kind)
+        grad = adj.phase_levels_backward(field, x, ctx.levels, weight=gi, scale=2.0 / (c // ctx.groups))
+        return grad, None, None, None
+
+
 class _IntensityThreshold(torch.autograd.Function):
     """x -> I = mean_p |A (va + vb [x_p >= tau])|^2 per colour group, x float32 [B, C, H, W]: one
     hbx_evaluate_threshold that leaves the field F and I.  Backward, the straight-through
@@ -735,7 +841,7 @@ class _IntensityThreshold(torch.autograd.Function):
 
 
 def intensity(x, z: float, tf="asm", field="amplitude", save_field: bool = True, threshold=None, ste="window",
-              ste_width=0.5, grid=None, origin=None, roi=None) -> torch.Tensor:
+              ste_width=0.5, grid=None, origin=None, roi=None, levels=None) -> torch.Tensor:
     """Plane-mean intensity of the propagated field, the quantity every loss of the project goes
     through: float32 [B, G, H, W] (or [G, H, W] for a 3-D x) with
         I[b, g] = mean over the planes p of group g of |IFFT2(FFT2(u[b, p]) H_g(z))|^2,
@@ -773,7 +879,11 @@ def intensity(x, z: float, tf="asm", field="amplitude", save_field: bool = True,
 
     grid=N, origin=, roi= as in simulate (real x, with or without threshold=; C / G even): the
     intensity [B, G, h_o, w_o] over the roi of a hologram zero-filled into the N x N grid.  The
-    cropped field is saved, and the backward pass is one hbx_backward_window."""
+    cropped field is saved, and the backward pass is one hbx_backward_window.
+
+    levels=L with field="phase" (real x; as in simulate): the intensity of the hologram displayed at L
+    phase levels, through hbx_evaluate_phase_levels; with a gradient request the backward pass is one
+    hbx_phase_levels_backward, the straight-through estimator.  The field is always saved."""
     tf_kind = _switch(tf, _TF_NAMES, "tf")
     field_kind = _switch(field, _FIELD_NAMES, "field")
     ste_args = _ste_args(threshold, ste, ste_width, "intensity")
@@ -802,6 +912,7 @@ def intensity(x, z: float, tf="asm", field="amplitude", save_field: bool = True,
             raise ValueError("tt.intensity: threshold= needs a real leaf, got a complex field")
         if (c // groups) % 2:
             raise ValueError(f"intensity: threshold= needs an even number of planes per colour group, got {c // groups}")
+    levels = _levels_arg(levels, False, t.is_complex(), field_kind, ste_args is not None, grid, "intensity")
     win = _window_args(grid, origin, roi, t.shape, t.is_complex(), field_kind, ste_args is not None, "intensity")
     if win is not None and (c // groups) % 2:
         raise ValueError(f"intensity: grid= needs an even number of planes per colour group, got {c // groups}")
@@ -828,6 +939,13 @@ def intensity(x, z: float, tf="asm", field="amplitude", save_field: bool = True,
         else:
             plan = _plan_for(h, w, c // groups, wls, dx, dy, z, b, dev, tf_kind, field_kind)
             out = plan.evaluate_threshold(xs, ste_args[0], want_field=False)[1]
+    elif levels is not None:
+        xs = _phase_samples(t)
+        if xs.requires_grad and torch.is_grad_enabled():
+            out = _IntensityPhaseLevels.apply(xs, geom, groups, levels)
+        else:
+            plan = _plan_for(h, w, 2 * c // groups, wls, dx, dy, z, b, dev, tf_kind)
+            out = plan.evaluate_phase_levels(xs, levels, want_field=False)[1]
     elif field_kind == _lib.FIELD_PHASE:
         xs = _phase_samples(t)
         if xs.requires_grad and torch.is_grad_enabled():
@@ -910,6 +1028,36 @@ class _Loss(torch.autograd.Function):
         return (gf if cplx else gr).to(ctx.in_dtype), None, None, None, None, None, None
 
 
+class _LossPhaseLevels(torch.autograd.Function):
+    """_Loss's phase form for a leaf displayed at L phase levels, x float32 [B, C, H, W]: one
+    hbx_evaluate_phase_levels that leaves the field, I and the statistics.  Backward, the
+    straight-through estimator: hbx_loss_weight as _Loss, then one hbx_phase_levels_backward of the
+    field on the plan for -z, whose last pass writes dL/dq as dL/dx.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, x, target, geom, groups, kind, rel, levels):
+        wls, dx, dy, z, dev, tf_kind = geom
+        b, c, h, w = x.shape
+        ctx.geom, ctx.groups, ctx.kind, ctx.rel, ctx.levels = geom, groups, kind, rel, levels
+        plan = _plan_for(h, w, 2 * c // groups, wls, dx, dy, z, b, dev, tf_kind)
+        field, inten, stats, _ = plan.evaluate_phase_levels(x, levels, target)
+        ctx.save_for_backward(field, inten, stats, target, x)
+        return plan.loss(stats, kind, rel)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        wls, dx, dy, z, dev, tf_kind = ctx.geom
+        field, inten, stats, target, x = ctx.saved_tensors
+        b, c, h, w = x.shape
+        groups = ctx.groups
+        adj = _plan_for(h, w, 2 * c // groups, wls, dx, dy, -z, b, dev, tf_kind)
+        gl = grad_output.to(torch.float64).resolve_neg().contiguous()
+        wgt = adj.loss_weight(inten, target, stats, gl, ctx.kind, ctx.rel)   # the plan's G and N only
+        grad = adj.phase_levels_backward(field, x, ctx.levels, weight=wgt, scale=2.0 / (c // groups))
+        return grad, None, None, None, None, None, None
+
+
 class _LossThreshold(torch.autograd.Function):
     """x -> the relative MSE or PSNR per env of I = mean_p |A (va + vb [x_p >= tau])|^2 against a
     constant target, x float32 [B, C, H, W]: one hbx_evaluate_threshold that leaves the field, I
@@ -944,7 +1092,7 @@ class _LossThreshold(torch.autograd.Function):
 
 
 def loss(x, target, z: float, metric="mse", rel_scale="lsq", tf="asm", field="amplitude", threshold=None,
-         ste="window", ste_width=0.5, grid=None, origin=None, roi=None) -> torch.Tensor:
+         ste="window", ste_width=0.5, grid=None, origin=None, roi=None, levels=None) -> torch.Tensor:
     """The relative loss of a continuous hologram against a target, one value per env, without
     leaving the HIP path and without a host wait: float64 [B] on the device (0-dim for a 3-D x),
         metric="mse"   what tt.relativeLoss(I[b], target[b], F.mse_loss) gives (env.py:131),
@@ -982,7 +1130,13 @@ def loss(x, target, z: float, metric="mse", rel_scale="lsq", tf="asm", field="am
     w_o], and the statistics and the pixel count n = G h_o w_o are the roi's (the reference's crop
     before it compares, env_1024_24_128.py:144-149).  The cropped field, the cropped intensity and
     the statistics are saved; the backward pass is hbx_loss_weight_window, then one
-    hbx_backward_window on the plan for -z."""
+    hbx_backward_window on the plan for -z.
+
+    levels=L with field="phase" (real x; as in simulate): the loss of the hologram an L-level phase
+    modulator displays -- hbx.quantize_phase(x, L) is its export -- quantized by the first pass of
+    hbx_evaluate_phase_levels as it loads x.  If x requires grad the backward pass is the
+    straight-through estimator: hbx_loss_weight, then one hbx_phase_levels_backward on the plan for -z.
+    Neither the quantized samples nor exp(i pi q) nor the complex gradient is written."""
     kind = _switch(metric, _METRIC_NAMES, "metric")
     rel = _switch(rel_scale, _REL_NAMES, "rel_scale")
     tf_kind = _switch(tf, _TF_NAMES, "tf")
@@ -1016,6 +1170,7 @@ def loss(x, target, z: float, metric="mse", rel_scale="lsq", tf="asm", field="am
             raise ValueError(f"loss: threshold= needs an even number of planes per colour group, got {c // groups}")
     if tg.requires_grad:
         raise ValueError("loss: the target is a constant (it requires grad)")
+    levels = _levels_arg(levels, False, t.is_complex(), field_kind, ste_args is not None, grid, "loss")
     win = _window_args(grid, origin, roi, t.shape, t.is_complex(), field_kind, ste_args is not None, "loss")
     th, tw = (h, w) if win is None else win[2][2:]     # the target has the roi's shape
     if tg.is_complex() or tuple(tg.shape) != (b, groups, th, tw):
@@ -1045,6 +1200,15 @@ def loss(x, target, z: float, metric="mse", rel_scale="lsq", tf="asm", field="am
         else:
             plan = _plan_for(h, w, c // groups, wls, dx, dy, z, b, dev, tf_kind, field_kind)
             stats = plan.evaluate_threshold(xs, ste_args[0], tg, want_field=False, want_intensity=False)[2]
+            out = plan.loss(stats, kind, rel)
+        return out[0] if squeeze else out
+    if levels is not None:
+        xs = _phase_samples(t)
+        if xs.requires_grad and torch.is_grad_enabled():
+            out = _LossPhaseLevels.apply(xs, tg, geom, groups, kind, rel, levels)
+        else:
+            plan = _plan_for(h, w, 2 * c // groups, wls, dx, dy, z, b, dev, tf_kind)
+            stats = plan.evaluate_phase_levels(xs, levels, tg, want_field=False, want_intensity=False)[2]
             out = plan.loss(stats, kind, rel)
         return out[0] if squeeze else out
     phase = field_kind == _lib.FIELD_PHASE

@@ -379,6 +379,44 @@ int hbx_evaluate_phase(hbx_plan_t plan, const float* phase, const float* target,
 int hbx_phase_backward(hbx_plan_t plan, const float* values, const float* weight, float scale,
                        const float* phase, int32_t n_env, float* grad_phase, void* stream);
 
+/* (ABI v15, additive) Quantized phase holograms: the leaf is the phase x (in units of pi, as above),
+ * the displayed hologram one of `levels` = L phase levels per pixel, 2 <= L <= 256.
+ * The quantizer, one definition used by every entry point below (all float32, round-half-to-even):
+ *   r = x - 2 rint(x / 2)     exact, r in [-1, 1]: unwrapped phases quantize as well as wrapped ones
+ *   k = rint(r h)             h = float32(L / 2), one multiply, then the rounding
+ *   q = k s                   s = float32(2.0 / L), one multiply: the quantized sample, |q - x| mod 2 <= 1 / L
+ *   level = k mod L in [0, L) (k < 0: k + L): what the device displays, the phase 2 pi level / L
+ *   u = exp(i pi q)           hbx_simulate_phase's own sincos applied to q
+ * Ties go to the even k.  This is deliberately not hbx_evaluate_threshold's `>=` rule: the rounding is
+ * one instruction, and the quantizer stays odd in x.  A non-finite x gives q = NaN -- its field and
+ * gradient are whatever the continuous calls give for a NaN sample -- and level 0, formed by a select.
+ *
+ * hbx_simulate_phase_levels, hbx_evaluate_phase_levels, hbx_phase_levels_backward: hbx_simulate_phase,
+ *   hbx_evaluate_phase and hbx_phase_backward in every rule (shapes, null-ability, the target /
+ *   chan_stats pairing, chunking by max_jobs, n_env, HBX_PRECISION_F32 only, the four built sizes, the
+ *   pass-timer slots), except that the first pass of the two forward calls quantizes x as it loads it,
+ *   and the backward's last pass quantizes x the same way and writes the straight-through gradient
+ *     grad_phase = pi (Im g cos pi q - Re g sin pi q),
+ *   dq/dx := 1, the continuous chain rule at the displayed phase.  Neither q nor u nor g is ever
+ *   written.  Bit for bit, every output of the forward calls equals the continuous call's on the
+ *   materialised q (hbx_quantize_phase's out_phase), and grad_phase equals hbx_phase_backward's on q.
+ * hbx_quantize_phase: the export for the display and the materialiser, one streaming kernel, no plan.
+ *   src        n_values float32 samples x (n_values >= 0)
+ *   out_levels n_values uint8 `level`, nullable
+ *   out_phase  n_values float32 q, nullable; at least one of the two non-null
+ * levels outside [2, 256] ("levels" in hbx_last_error()) or a null required pointer: HBX_ERR_INVALID
+ * before anything is enqueued; a reduced-precision plan: HBX_ERR_UNSUPPORTED. */
+int hbx_simulate_phase_levels(hbx_plan_t plan, const float* phase, int32_t levels, int32_t n_env,
+                              float* field, float* real_part, void* stream);
+int hbx_evaluate_phase_levels(hbx_plan_t plan, const float* phase, int32_t levels, const float* target,
+                              int32_t n_env, float* field, float* intensity, double* chan_stats,
+                              double* psnr, void* stream);
+int hbx_phase_levels_backward(hbx_plan_t plan, const float* values, const float* weight, float scale,
+                              const float* phase, int32_t levels, int32_t n_env, float* grad_phase,
+                              void* stream);
+int hbx_quantize_phase(const float* src, int64_t n_values, int32_t levels, uint8_t* out_levels,
+                       float* out_phase, void* stream);
+
 /* (ABI v15, additive) Binary holograms from a real leaf: m = [x >= threshold], u = va + vb m with
  * the plan's field_kind (HBX_FIELD_AMPLITUDE: 0 / 1; HBX_FIELD_PHASE: 1 / -1, vb = -2) -- the field
  * of the mask HBX_PACK_THRESHOLD packs from the same samples (NaN: the bit is off).
