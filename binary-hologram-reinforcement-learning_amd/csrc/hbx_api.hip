@@ -1415,6 +1415,19 @@ int hbx_dbs_walk_planes_fill(hbx_plan_t p, uint64_t* base_mask, const float* tar
                              int64_t n_order, hbx_dbs_walk_t* walk, int64_t* accept_pos, double* accept_psnr,
                              int64_t accept_cap, int32_t K, int32_t batches, int64_t* fill_count,
                              int64_t fill_target, int64_t fill_tol, void* stream) {
+  return hbx_dbs_walk_planes_anneal(p, base_mask, target, base_chan_stats, plane_inten, plane_slot, n_spare_pairs,
+                                    order, n_order, walk, accept_pos, accept_psnr, accept_cap, K, batches,
+                                    fill_count, fill_target, fill_tol, nullptr, 0, stream);
+}
+
+// slack NULL: the fill call, kernel for kernel.  With slack: the same launches with the annealed
+// decision in them (k_walk_planes_anneal, k_rowinv_walk_anneal)
+int hbx_dbs_walk_planes_anneal(hbx_plan_t p, uint64_t* base_mask, const float* target, double* base_chan_stats,
+                               float* plane_inten, int32_t* plane_slot, int32_t n_spare_pairs,
+                               const int64_t* order, int64_t n_order, hbx_dbs_walk_t* walk, int64_t* accept_pos,
+                               double* accept_psnr, int64_t accept_cap, int32_t K, int32_t batches,
+                               int64_t* fill_count, int64_t fill_target, int64_t fill_tol, const double* slack,
+                               int64_t n_slack, void* stream) {
   int rc = check_plan(p);
   if (rc) return rc;
   if (!base_mask || !target || !base_chan_stats || !plane_inten || !plane_slot || !order || !walk)
@@ -1429,6 +1442,9 @@ int hbx_dbs_walk_planes_fill(hbx_plan_t p, uint64_t* base_mask, const float* tar
   if (fill_count && (fill_tol < 0 || fill_target < 0 ||
                      fill_target > (int64_t)p->pd.P * p->pd.N * p->pd.N))
     return fail(HBX_ERR_INVALID, "fill_target in [0, P*H*W] and fill_tol >= 0");
+  // the walk's total lives on the device: the host holds the slack to the order's length, and the
+  // decision reads no slack at or past n_slack whatever the total
+  if (slack && n_slack < n_order) return fail(HBX_ERR_INVALID, "n_slack < n_order: one slack per position of the order");
   HBX_HIP(hipSetDevice(p->device));
   hipStream_t st = (hipStream_t)stream;
   const PlanDev& pd = p->pd;
@@ -1452,6 +1468,7 @@ int hbx_dbs_walk_planes_fill(hbx_plan_t p, uint64_t* base_mask, const float* tar
   wa.count = pixel_count(p); wa.rel_scale = p->optics.rel_scale; wa.peak = p->optics.peak;
   wa.fill_count = fill_count; wa.fill_target = fill_target; wa.fill_tol = fill_tol;
   c.walk_planes = fused ? &wa : nullptr;
+  c.walk_anneal = fused && slack ? 1 : 0;
   // (r06) candidates a batch propagated but did not visit keep their job slot, their pair's B and,
   // when their colour group saw no accept, their partials: the next batch skips those passes for
   // them (fused decision only; the 896 path decides in its own launch and re-propagates)
@@ -1461,10 +1478,13 @@ int hbx_dbs_walk_planes_fill(hbx_plan_t p, uint64_t* base_mask, const float* tar
     wa.phase = p->walk_phase;
     c.walk_phase = p->walk_phase;
   }
-  HBX_HIP(hbx::launch_walk_planes(wa, 0, st));   // this call's first batch of jobs, from the walk state
+  auto decide = [&](int d) {
+    return slack ? hbx::launch_walk_planes_anneal(wa, d, slack, n_slack, st) : hbx::launch_walk_planes(wa, d, st);
+  };
+  HBX_HIP(decide(0));   // this call's first batch of jobs, from the walk state
   for (int b = 0; b < batches; ++b) {
     HBX_HIP(hbx::run_jobs(pd, c, st));
-    if (!fused) HBX_HIP(hbx::launch_walk_planes(wa, 1, st));
+    if (!fused) HBX_HIP(decide(1));
   }
   return HBX_OK;
 }

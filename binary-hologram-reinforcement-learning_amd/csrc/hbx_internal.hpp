@@ -187,6 +187,18 @@ struct WalkPlanesArgs {
   uint8_t* phase = nullptr;
 };
 
+// (extension, hbx_dbs_walk_planes_anneal) the annealed walk's slack: it travels in the plan's 64-byte
+// ticket block, behind the arrival counter, so WalkPlanesArgs -- a by-value argument of every
+// k_rowinv_d -- keeps its size and no existing kernel's descriptor moves.  Written by the call's
+// k_walk_planes_anneal launch, read by the fused decision of the launches behind it.
+struct WalkAnnealBlock {
+  const double* slack;
+  int64_t n_slack;
+};
+__host__ __device__ __forceinline__ WalkAnnealBlock* walk_anneal_block(int32_t* ticket) {
+  return reinterpret_cast<WalkAnnealBlock*>(ticket + 2);   // bytes 8..23 of the block
+}
+
 // What a plan owns: geometry, tables, workspaces.  Never copied to describe a launch -- what one
 // propagation needs beyond the plan is a PassCall (below).
 struct PlanDev {
@@ -349,6 +361,7 @@ struct PassCall {
                                                 // 2 none (WalkPlanesArgs::phase; nullptr = all)
   const WalkPlanesArgs* walk_planes = nullptr;  // (r05) plane-cache walk batch: the last k_rowinv_d
                                                 // workgroup decides (hbx_walk_planes.hpp)
+  int walk_anneal = 0;                          // 1: the annealed decision (k_rowinv_walk_anneal; walk_planes set)
 };
 
 // a window (hbx_window_t) that is a non-empty rectangle of the N x N grid
@@ -404,6 +417,7 @@ inline hipError_t check_pass_call(const PlanDev& pd, const PassCall& c) {
             (c.phase_values != nullptr) == 1;
   ok = ok && (!planes || (c.plane_pool && c.plane_slot && (tiled || pd.R == 0)));
   ok = ok && (!c.walk_planes || (c.plane_mode == kPlanesStep && tiled));
+  ok = ok && (!c.walk_anneal || c.walk_planes);
   ok = ok && (!c.rc_pending == !c.rc_cache) && (!c.rc_pending || tiled);
   ok = ok && (c.actions || !c.act_err);
   if (pd.R == 0) ok = ok && !c.walk_phase && !c.actions && !c.skip_reduce;
@@ -641,6 +655,8 @@ hipError_t launch_recon_reconcile(const int32_t* pending, float* recon, float* i
                                   size_t hw, hipStream_t st);
 // plane cache (ABI v9): slot[env][i] = i for the listed envs (env_ids nullable: 0 .. n_ids - 1)
 hipError_t launch_walk_planes(const WalkPlanesArgs& a, int decide, hipStream_t st);
+hipError_t launch_walk_planes_anneal(const WalkPlanesArgs& a, int decide, const double* slack, int64_t n_slack,
+                                     hipStream_t st);
 hipError_t launch_plane_slot_init(const int32_t* env_ids, int n_ids, int32_t* slot, int CHS, hipStream_t st);
 hipError_t launch_obs_sync(const int32_t* env_ids, int n_ids, const uint64_t* mask, int8_t* state_bytes,
                            float* intensity, float* recon, int32_t* pending, int resolve, int CH, int G, size_t hw,

@@ -654,4 +654,25 @@ hipError_t launch_psnr(const double* chan_stats, int n, int G, double* psnr, dou
   return hipGetLastError();
 }
 
+// The annealed walk's stand-alone decision (hbx_dbs_walk_planes_anneal, EXTENSION; walk_planes_decide
+// with ANNEAL): each call's first batch of jobs, and every decision at N = 896.  It also leaves the
+// slack pointer and length in the plan's ticket block for the fused decisions of the launches behind
+// it (WalkAnnealBlock).  Behind every other kernel of this file: none of them moves.
+__global__ void k_walk_planes_anneal(WalkPlanesArgs a, int decide, const double* slack, int64_t n_slack) {
+  __shared__ __attribute__((aligned(16))) char lds[walk_planes_anneal_lds_bytes(128)];
+  if (threadIdx.x == 0) {
+    WalkAnnealBlock* blk = walk_anneal_block(a.ticket);
+    blk->slack = slack;
+    blk->n_slack = n_slack;
+  }
+  walk_planes_decide<false, true>(a, decide, lds, slack, n_slack);
+}
+
+hipError_t launch_walk_planes_anneal(const WalkPlanesArgs& a, int decide, const double* slack, int64_t n_slack,
+                                     hipStream_t st) {
+  if (a.RB > 128 || a.K > 256 || !slack || !a.ticket) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_walk_planes_anneal, dim3(1), dim3(256), 0, st, a, decide, slack, n_slack);
+  return hipGetLastError();
+}
+
 }  // namespace hbx

@@ -1403,6 +1403,70 @@ struct SampleKernels {
   }
 };
 
+// The annealed walk's last pass (hbx_dbs_walk_planes_anneal, EXTENSION): a walk batch of k_rowinv_d<R, true>
+// -- always a plane-cache step -- whose last-arriving workgroup takes the annealed decision
+// (walk_planes_arrive<true>).  A kernel of its own with k_rowinv_d's argument list, so that every k_rowinv_d
+// instantiation keeps its name, code and place; it carries the walk batch's path alone (no full
+// propagation, field, reconcile or window code).  field_out, rc_pending, rc_cache and win are not read.
+template <int R>
+__global__ __launch_bounds__(256, 2) void k_rowinv_walk_anneal(const JobDesc* __restrict__ jobs,
+                                                               const float2* __restrict__ ws_b,
+                                                               const float* __restrict__ target,
+                                                               const float2* __restrict__ tw_glob, int P, int G,
+                                                               double* __restrict__ partial,
+                                                               float* __restrict__ inten_out,
+                                                               float2* __restrict__ field_out, size_t tmask,
+                                                               int inten_by_env, int plane_mode,
+                                                               float* __restrict__ plane_pool,
+                                                               const int32_t* __restrict__ plane_slot,
+                                                               int plane_spares, int spare_base,
+                                                               const int32_t* __restrict__ rc_pending,
+                                                               float* __restrict__ rc_cache, WalkPlanesArgs wk,
+                                                               hbx_window_t win) {
+  constexpr int N = R * R, GPB = 256 / R, RB = N / GPB;
+  static_assert(walk_planes_anneal_lds_bytes(RB) <= GPB * R * (R + 1) * 8, "the decision's LDS fits the scratch");
+  __shared__ float2 tw[N];
+  __shared__ float2 scratch[GPB * R * (R + 1)];
+  __shared__ double red[GPB][3];
+  for (int i = threadIdx.x; i < N; i += 256) tw[i] = tw_glob[i];
+
+  const int grp = threadIdx.x / R;
+  const int t = threadIdx.x % R;
+  const int bid = xcd_pair<RB>(blockIdx.x);
+  const int rb = bid % RB;
+  const int j = bid / RB;
+  const JobDesc jb = jobs[j];
+  if (wk.phase && wk.phase[j] == 2) {   // a kept walk slot: its partials and fresh pair stand
+    walk_planes_arrive<true>(wk, reinterpret_cast<char*>(scratch));
+    return;
+  }
+  if (jb.env < 0) {
+    rowinv_zero_partial<true>(partial, j, RB, rb);
+    walk_planes_arrive<true>(wk, reinterpret_cast<char*>(scratch));
+    return;
+  }
+  const int y = rb * GPB + grp;
+  constexpr int PLB = N * N;                 // float2 per B plane
+  const __amdgpu_buffer_rsrc_t rs = plane_rsrc(ws_b + (size_t)j * P * PLB, (unsigned)((size_t)P * PLB * 8));
+  const RowinvLanes<R> ln(y, t);
+  auto load_plane = [&](pk2 (&v)[R], int p) { rowinv_load_plane(v, ln, rs, p); };
+  float acc[R];
+#pragma unroll
+  for (int k = 0; k < R; ++k) acc[k] = 0.0f;
+  const PaddedScratch<R> sc{scratch + grp * R * (R + 1)};
+  const PlaneCache<R> pc(jb, j, y, G, P, plane_spares, spare_base, plane_pool, plane_slot);
+  auto finish_plane = [&](pk2 (&v)[R], int p) {
+    fft_group<R, true>(v, t, sc, tw);
+    plane_out<R, R>(v, acc, pc, jb, G, P, p, t, nullptr, kPlanesStep);
+  };
+  pk2 va[R];
+  rowinv_planes_step(va, acc, pc, jb, P, t, load_plane, finish_plane);   // only the flipped plane's pair is in B
+  rowinv_epilogue<R, R, GPB, true>(acc, P, G, jb, j, y, rb, grp, t, target, tmask, inten_out, inten_by_env, partial,
+                                   red, nullptr, nullptr);
+  __syncthreads();   // every group is done with its scratch region: the decision's LDS
+  walk_planes_arrive<true>(wk, reinterpret_cast<char*>(scratch));
+}
+
 template <int R, int SK>
 static hipError_t launch_passes(const PlanDev& pd, const PassCall& c, hipStream_t st) {
   constexpr int N = R * R;
@@ -1480,6 +1544,7 @@ static hipError_t launch_passes(const PlanDev& pd, const PassCall& c, hipStream_
     auto k = k_rowinv_d<R, true>;
     if (!c.walk_planes) k = lean ? k_rowinv_d<R, false, true> : k_rowinv_d<R>;
     if (c.windowed) k = lean ? k_rowinv_d<R, false, true, true> : k_rowinv_d<R, false, false, true>;
+    if (c.walk_anneal) k = k_rowinv_walk_anneal<R>;   // (behind every k_rowinv_d: their layout stays)
     launch_kernel(k, blocks, 256, st, jobs, pd.ws_b, tg.rows, pd.tw, P, pd.G, pd.partial, c.inten_out, c.field_out,
                   tg.mask, c.inten_by_env, c.plane_mode, c.plane_pool, c.plane_slot, c.plane_spares, c.spare_base,
                   c.rc_pending, c.rc_cache, c.walk_planes ? *c.walk_planes : WalkPlanesArgs{}, c.out_win);

@@ -21,6 +21,8 @@ __host__ __device__ constexpr size_t walk_planes_lds_bytes(int RB) {
   return (size_t)kWalkPlanesCJ * 3 * RB * 8 + 256 * 3 * 8 + 256 * sizeof(JobDesc) + 256 * 8 + 256 * 4 * 4 +
          512 * 8 + 3 * HBX_MAX_GROUPS * 8 + 128 + HBX_MAX_GROUPS * 8 + 16;
 }
+// ... and for the annealed decision (ANNEAL below): the batch's slack behind all of it
+__host__ __device__ constexpr size_t walk_planes_anneal_lds_bytes(int RB) { return walk_planes_lds_bytes(RB) + 256 * 8; }
 
 // (ABI v13, extension -- no reference counterpart) the on-pixel ratio constraint: a
 // flip moving group g's on-pixel count C by d = +-1 is admissible iff |C + d - T| <= tol or it
@@ -59,8 +61,16 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t walk_planes_rsrc(const void* b
 // they still need (0 all, 1 only k_rowinv_d, 2 nothing; see WalkPlanesArgs).  SC1: the partials come from other workgroups of the SAME launch
 // (the fused decision), written through with sc1 stores -- read them with sc1 loads, which miss
 // this XCD's L2.
-template <bool SC1>
-__device__ __forceinline__ void walk_planes_decide(const WalkPlanesArgs& a, int decide, char* lds) {
+// ANNEAL (hbx_dbs_walk_planes_anneal, EXTENSION -- no reference counterpart): the candidate at
+// position q of the order is accepted iff ps > (prev - slack[q]) in float64, one subtraction rounded
+// once and then the compare (hbx/dbs.py first_accepting carries the same expression).  A NaN slack
+// rejects, +inf accepts every candidate that has a PSNR, a candidate without one (inadmissible under
+// the fill rule) is rejected whatever its slack.  slack is never read at or past n_slack or the
+// walk's total: such a position counts as NaN.  Everything else is the greedy decision's; without
+// ANNEAL the function compiles to the code it was.
+template <bool SC1, bool ANNEAL = false>
+__device__ __forceinline__ void walk_planes_decide(const WalkPlanesArgs& a, int decide, char* lds,
+                                                   const double* slack = nullptr, int64_t n_slack = 0) {
   const int RB = a.RB, K = a.K, G = a.G, P = a.P, H = a.H, W = a.W;
   constexpr int CJ = kWalkPlanesCJ;
   char* q = lds;
@@ -77,6 +87,8 @@ __device__ __forceinline__ void walk_planes_decide(const WalkPlanesArgs& a, int 
   double* s_dbl = reinterpret_cast<double*>(carve(4 * 8));              // prev, last, init, stop_diff
   int64_t* s_fill = reinterpret_cast<int64_t*>(carve(HBX_MAX_GROUPS * 8));   // on-pixel counts (fill on)
   uint64_t* s_tpair = reinterpret_cast<uint64_t*>(carve(8));            // (group, pair)s this batch accepted into
+  double* s_slack = nullptr;                                            // [i] slack of the batch's candidate i
+  if constexpr (ANNEAL) s_slack = reinterpret_cast<double*>(carve(256 * 8));
   hbx_dbs_walk_t* w = a.w;
   const int k = threadIdx.x;
   const int64_t hw = (int64_t)H * W;
@@ -90,6 +102,10 @@ __device__ __forceinline__ void walk_planes_decide(const WalkPlanesArgs& a, int 
   JobDesc jb_k;
   jb_k.env = -1;
   if (decide && k < K) jb_k = a.jobs[k];
+  double sl_k = NAN;                        // (ANNEAL) depends on pos alone: out with the other up-front loads
+  if constexpr (ANNEAL) {
+    if (decide && k < K && pos0 + k < total0 && pos0 + k < n_slack) sl_k = slack[pos0 + k];
+  }
   if (decide && k < 3 * G) s_base[k] = a.base_stats[k];
   if (a.fill_count && k < G) s_fill[k] = a.fill_count[k];
   const __amdgpu_buffer_rsrc_t rp = walk_planes_rsrc(a.partial, (unsigned)((size_t)K * RB * 3 * 8));
@@ -119,6 +135,9 @@ __device__ __forceinline__ void walk_planes_decide(const WalkPlanesArgs& a, int 
     s_tpair[0] = 0;
   }
   for (int i = k; i < 2 * K; i += blockDim.x) s_order[i] = (pos0 + i < total0) ? a.order[pos0 + i] : -1;
+  if constexpr (ANNEAL) {
+    if (decide && k < K) s_slack[k] = sl_k;
+  }
   if (decide && k < K) {
     s_job[k] = jb_k;
     if (jb_k.env >= 0) {
@@ -196,7 +215,10 @@ __device__ __forceinline__ void walk_planes_decide(const WalkPlanesArgs& a, int 
         ps = psnr_from(sxy, sxx, syy, a.count, a.rel_scale, a.peak);
       }
       last = ps;
-      if (ps > prev) {                     // commit candidate c
+      bool take;
+      if constexpr (ANNEAL) take = ps > (prev - s_slack[i]);   // one subtraction, rounded once, then the compare
+      else take = ps > prev;
+      if (take) {                          // commit candidate c
         const int ch = jb.group * P + jb.flip_plane;
         const int pix = jb.flip_pix;
         a.mask[(size_t)ch * H * (W / 64) + (size_t)(pix / W) * (W / 64) + (pix % W) / 64] =
@@ -292,8 +314,18 @@ __device__ __forceinline__ void walk_planes_decide(const WalkPlanesArgs& a, int 
 // agent-scope ticket per block; the block holding the last ticket resets the counter for the next
 // launch and decides (the psf walk's recipe, hbx_walk.hip k_walk_step: relaxed ticket + sc1 loads,
 // pinned to gfx950's cache policy, every walk test checks the accept sequence against the oracle).
+// ANNEAL: the slack pointer and length come from the plan's ticket block (WalkAnnealBlock, written by
+// the call's k_walk_planes_anneal launch ahead of its batches) -- the same ticket, the same sc1 loads.
+template <bool ANNEAL = false>
 __device__ __forceinline__ void walk_planes_arrive(const WalkPlanesArgs& a, char* lds) {
   __shared__ int s_last_block;
+  const double* slack = nullptr;
+  int64_t n_slack = 0;
+  if constexpr (ANNEAL) {
+    const WalkAnnealBlock* blk = walk_anneal_block(a.ticket);
+    slack = blk->slack;
+    n_slack = blk->n_slack;
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -302,7 +334,11 @@ __device__ __forceinline__ void walk_planes_arrive(const WalkPlanesArgs& a, char
     if (s_last_block) __hip_atomic_store(a.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   __syncthreads();
-  if (s_last_block) walk_planes_decide<true>(a, 1, lds);
+  if constexpr (ANNEAL) {
+    if (s_last_block) walk_planes_decide<true, true>(a, 1, lds, slack, n_slack);
+  } else {
+    if (s_last_block) walk_planes_decide<true>(a, 1, lds);
+  }
 }
 
 }  // namespace hbx

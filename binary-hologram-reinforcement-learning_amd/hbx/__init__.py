@@ -4,6 +4,8 @@ Public surface:
   OpticsConfig, mono_config, rgb_config, Plan     propagation operator (hbx_plan_t)
   HologramVecEnv, BinaryHologramEnv               env.py / env_1024_24.py drop-ins
   dbs.greedy, dbs.probe                           DBS*.py / range.py drivers
+  dbs.greedy(slack=), dbs.metropolis_slack,       EXTENSION: annealed / threshold / minimum-gain
+  dbs.threshold_slack, dbs.replay                 acceptance in the FFT-mode walk, best-state replay
   dist                                            one-process-per-GPU sharding helpers
 The torchOptics-compatible operator shim lives in the sibling package
 ``torchOptics`` (optics.Tensor / simulate / relativeLoss, metrics.get_PSNR).

@@ -40,7 +40,7 @@ EXPORTED_SYMBOLS = (
     "hbx_eval_flips_psf", "hbx_commit_flip_psf", "hbx_dbs_walk_psf",
     "hbx_plan_set_precision", "hbx_plan_precision", "hbx_env_obs_sync",
     "hbx_planes_fill", "hbx_eval_flips_planes", "hbx_commit_flip_planes", "hbx_dbs_walk_planes",
-    "hbx_dbs_walk_planes_fill", "hbx_host_alloc", "hbx_host_free", "hbx_pack_mask", "hbx_rel_stats",
+    "hbx_dbs_walk_planes_fill", "hbx_dbs_walk_planes_anneal", "hbx_host_alloc", "hbx_host_free", "hbx_pack_mask", "hbx_rel_stats",
     "hbx_simulate_real", "hbx_propagate_real", "hbx_simulate_complex",
     "hbx_simulate_complex_weighted", "hbx_intensity_real",
     "hbx_evaluate_real", "hbx_evaluate_complex", "hbx_loss", "hbx_loss_weight",
@@ -177,6 +177,8 @@ def _declare(lib):
     lib.hbx_dbs_walk_planes.argtypes = [VP, VP, VP, VP, VP, VP, I32, VP, I64, VP, VP, VP, I64, I32, I32, VP]
     lib.hbx_dbs_walk_planes_fill.argtypes = [VP, VP, VP, VP, VP, VP, I32, VP, I64, VP, VP, VP, I64, I32, I32, VP,
                                              I64, I64, VP]
+    lib.hbx_dbs_walk_planes_anneal.argtypes = [VP, VP, VP, VP, VP, VP, I32, VP, I64, VP, VP, VP, I64, I32, I32, VP,
+                                               I64, I64, VP, I64, VP]
     lib.hbx_host_alloc.argtypes = [C.c_size_t, C.POINTER(VP), C.POINTER(VP)]
     lib.hbx_host_free.argtypes = [VP]
     lib.hbx_pack_mask.argtypes = [VP, I32, I64, I32, C.c_double, VP, VP, VP]

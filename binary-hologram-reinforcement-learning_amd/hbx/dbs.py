@@ -48,6 +48,15 @@ class GreedyResult:
     last_psnr: Optional[float] = None    # psnr of the last visited candidate (accepted or not)
     seconds: float = 0.0
     fill_counts: Optional[List[int]] = None   # on-pixel count per colour group at the end (fill_ratio runs)
+    # the best state of the run, from the accept log (with slack= the final state need not be it):
+    # its PSNR, and the number of accepts after which it held (0: the initial state; the first
+    # time the maximum was reached).  A greedy run's are its final values.  dbs.replay rebuilds it
+    best_psnr: Optional[float] = None
+    best_accepts: int = 0
+
+    def __post_init__(self):
+        if self.best_psnr is None:
+            self.best_psnr, self.best_accepts = best_of_log(self.initial_psnr, self.accepted_psnr)
 
 
 class KController:
@@ -90,6 +99,97 @@ def first_improving(psnr: np.ndarray, prev: float) -> Optional[int]:
     """Index of the first candidate with psnr > prev (strict, DBS_1024_24.py:355)."""
     idx = np.nonzero(psnr > prev)[0]
     return int(idx[0]) if idx.size else None
+
+
+def first_accepting(psnr: np.ndarray, prev: float, slack: np.ndarray) -> Optional[int]:
+    """Index of the first candidate with psnr[i] > (prev - slack[i]), in float64: one subtraction
+    rounded once, then the compare -- the annealed walk's predicate (hbx.h
+    hbx_dbs_walk_planes_anneal, EXTENSION).  A NaN slack or PSNR rejects, +inf accepts every
+    candidate that has a PSNR, a negative slack -g demands a gain of more than g; zero slack is
+    first_improving."""
+    bar = np.float64(prev) - np.asarray(slack, np.float64)
+    idx = np.nonzero(np.asarray(psnr, np.float64) > bar)[0]
+    return int(idx[0]) if idx.size else None
+
+
+def _schedule(total, start, end, what):
+    if int(total) != total or int(total) < 1:
+        raise ValueError(f"{what}: total must be an integer >= 1, got {total!r}")
+    start, end = float(start), float(end)
+    if not (math.isfinite(start) and math.isfinite(end) and start > 0.0 and end > 0.0):
+        raise ValueError(f"{what}: temperatures must be finite and positive, got {start!r}, {end!r}")
+    total = int(total)
+    if total == 1:
+        return np.full(1, start, np.float64)
+    i = np.arange(total, dtype=np.float64)
+    return start * (end / start) ** (i / (total - 1))
+
+
+def metropolis_slack(total: int, t_start: float, t_end: float, seed: int) -> np.ndarray:
+    """Slack of a Metropolis walk (simulated annealing) over `total` candidates, float64 [total]:
+
+        u   = np.random.default_rng(seed).random(total)
+        T_i = t_start * (t_end / t_start) ** (i / (total - 1))        (T_0 = t_start when total = 1)
+        slack_i = -T_i * np.log1p(-u_i)
+
+    so candidate i is accepted iff psnr > prev - slack_i, i.e. with probability exp(-(prev - psnr) /
+    T_i) when it lowers the PSNR and always when it raises it.  Temperatures are in dB of PSNR,
+    finite and positive; total >= 1.  Numpy only and deterministic: the caller owns T, u and the seed."""
+    t = _schedule(total, t_start, t_end, "metropolis_slack")
+    u = np.random.default_rng(seed).random(int(total))
+    return -t * np.log1p(-u)
+
+
+def threshold_slack(total: int, tau_start: float, tau_end: float) -> np.ndarray:
+    """Slack of threshold accepting over `total` candidates, float64 [total]: the geometric schedule
+    tau_i = tau_start * (tau_end / tau_start) ** (i / (total - 1)) itself, no randomness (a candidate
+    is accepted iff it lowers the PSNR by less than tau_i).  Thresholds in dB of PSNR, finite and
+    positive; total >= 1."""
+    return _schedule(total, tau_start, tau_end, "threshold_slack")
+
+
+def best_of_log(initial_psnr: float, accepted_psnr) -> tuple:
+    """(best PSNR, accepts after which it held) of an accept log: the first maximum of
+    [initial_psnr, *accepted_psnr]; 0 accepts means the initial state."""
+    a = np.asarray(accepted_psnr, np.float64)
+    if a.size == 0 or not np.any(a > initial_psnr):
+        return float(initial_psnr), 0
+    i = int(np.argmax(a))                 # the first maximum (an accepted PSNR is never NaN)
+    return float(a[i]), i + 1
+
+
+def replay(mask0, order, accepted_positions):
+    """The packed mask [CH][H][W/64] int64 after the accepts at `accepted_positions` of `order`,
+    from the walk's starting mask `mask0` (tensor or array; returned as the same kind, a copy): each
+    accept toggles its pixel's bit, so a pixel that `order` visits in several sweeps and that was
+    accepted an even number of times is back where it started.  With
+    res.accepted_positions[:res.best_accepts] it rebuilds a run's best state."""
+    is_t = isinstance(mask0, torch.Tensor)
+    m = (mask0.detach().cpu().numpy() if is_t else np.asarray(mask0)).astype(np.int64, copy=True)
+    if m.ndim != 3:
+        raise ValueError("replay: mask0 is a packed mask [CH][H][W/64]")
+    ch_n, h, w = m.shape[0], m.shape[1], m.shape[2] * 64
+    a = np.asarray(order, np.int64)[np.asarray(accepted_positions, np.int64)]
+    if a.size and (a.min() < 0 or a.max() >= ch_n * h * w):
+        raise ValueError("replay: an accepted action lies outside the mask")
+    ch, rem = np.divmod(a, h * w)
+    r, col = np.divmod(rem, w)
+    words = m.view(np.uint64)
+    np.bitwise_xor.at(words, (ch, r, col // 64), np.uint64(1) << (col % 64).astype(np.uint64))
+    return torch.from_numpy(m).to(mask0.device) if is_t else m
+
+
+def _check_slack(slack, total: int, what: str) -> np.ndarray:
+    """slack as float64 [>= total] (host), or ValueError -- before any GPU use."""
+    try:
+        s = np.ascontiguousarray(np.asarray(slack, dtype=np.float64))
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"{what}: slack must be array-like float64 ({e})") from None
+    if s.ndim != 1:
+        raise ValueError(f"{what}: slack is one value per position of the order, got shape {s.shape}")
+    if s.shape[0] < total:
+        raise ValueError(f"{what}: slack has {s.shape[0]} values for {total} candidates to visit")
+    return s
 
 
 def greedy_dataset(n_images: int, load, order_for, plan_factory, per_gpu: int = 4,
@@ -438,10 +538,13 @@ def walk_k_planes(q: float, groups: int = 3, k_min: int = 1, k_max: int = 64, ta
 class _PlanesWalk(_Walk):
     """Host side of the device-decided FFT-mode walk (hbx_dbs_walk_planes): the same two
     chunks in flight as _Walk, no refreshes (the FFT mode is exact), K from walk_k_planes.
-    fill = (fill_ratio, fill_tol): the on-pixel ratio constraint (hbx_dbs_walk_planes_fill)."""
+    fill = (fill_ratio, fill_tol): the on-pixel ratio constraint (hbx_dbs_walk_planes_fill).
+    slack: float64 [>= total] on the host, the per-candidate acceptance slack
+    (hbx_dbs_walk_planes_anneal); the order then holds exactly the candidates to visit."""
 
-    def __init__(self, *args, fill=None, **kw):
+    def __init__(self, *args, fill=None, slack=None, **kw):
         self.fill = fill
+        self.slack = slack
         super().__init__(*args, **kw)
 
     def _setup(self, plan, mask, target, total, stop_diff, k_min, k_max, refresh_every, dev, s):
@@ -450,6 +553,10 @@ class _PlanesWalk(_Walk):
             c = plan.cfg
             counts = torch.as_tensor(fill_counts(mask, c.groups, c.planes)).to(dev)
             self.fill_arg = (counts, fill_target(self.fill[0], c.planes, c.height, c.width), int(self.fill[1]))
+        self.slack_t = None
+        if self.slack is not None:           # one slack per position of the order handed to the walk
+            self.order_t = self.order_t[:total]
+            self.slack_t = torch.from_numpy(np.ascontiguousarray(self.slack[:total])).to(dev)
         self.k_hi = max(1, min(k_max, plan.max_jobs, 256))
         self.pool = plan.plane_pool(self.k_hi)
         stats, psnr0 = plan.planes_fill(mask, target, *self.pool, stream=s)
@@ -481,7 +588,8 @@ class _PlanesWalk(_Walk):
 
     def _chunk_n(self, stream, batches):
         self.plan.dbs_walk_planes(self.mask, self.target, self.base_stats, *self.pool, self.order_t, self.wbuf,
-                                  self.log_pos, self.log_psnr, self.k, batches, stream=stream, fill=self.fill_arg)
+                                  self.log_pos, self.log_psnr, self.k, batches, stream=stream, fill=self.fill_arg,
+                                  slack=self.slack_t)
 
     def result(self) -> GreedyResult:
         r = super().result()
@@ -555,7 +663,7 @@ def greedy_many(plans: Sequence[Plan], masks: Sequence[torch.Tensor], targets: S
                 stop_diff: Optional[float] = None, k_max: Optional[int] = None,
                 max_candidates: Optional[int] = None, refresh_every: int = 4096,
                 concurrency: int = 4, mode: str = "psf", fill_ratio: Optional[float] = None,
-                fill_tol: int = 1) -> List[GreedyResult]:
+                fill_tol: int = 1, slacks=None) -> List[GreedyResult]:
     """DBS_1024_24.py's loop over several images (`:208-211`), up to `concurrency`
     images' greedy walks side by side: walk i on plans[i] (one plan per image:
     its own workspace, tables and walk buffers) and its own HIP stream, the host
@@ -565,13 +673,24 @@ def greedy_many(plans: Sequence[Plan], masks: Sequence[torch.Tensor], targets: S
     greedy(mode="psf") on that image alone); "fft": the FFT-mode walks on the plane cache
     (hbx_dbs_walk_planes; each result exactly greedy(mode="fft") on that image alone).
     fill_ratio / fill_tol (mode="fft" only): the on-pixel ratio constraint of greedy() (an
-    extension, hbx_dbs_walk_planes_fill).  Masks are modified in place."""
+    extension, hbx_dbs_walk_planes_fill).  slacks (mode="fft" only, EXTENSION): one acceptance slack
+    array or None per image, as greedy(slack=).  Masks are modified in place."""
     if mode not in ("psf", "fft"):
         raise ValueError(f"greedy_many: mode must be 'psf' or 'fft', got {mode!r}")
     if fill_ratio is not None and mode != "fft":
         raise ValueError("fill_ratio: the on-pixel constraint is built for mode='fft' only")
     if not (len(plans) == len(masks) == len(targets) == len(orders)):
         raise ValueError("one plan, mask, target and order per image")
+    if slacks is None:
+        slacks = [None] * len(plans)
+    else:
+        if mode != "fft":
+            raise ValueError("slacks: the acceptance slack is built for mode='fft' only")
+        if len(slacks) != len(plans):
+            raise ValueError("one slack array (or None) per image")
+        slacks = [None if sl is None else
+                  _check_slack(sl, len(o) if max_candidates is None else min(len(o), max_candidates), "greedy_many")
+                  for sl, o in zip(slacks, orders)]
     step = max(1, int(concurrency))
     for g0 in range(0, len(plans), step):
         # each walk writes its plan's walk partials and job workspace from its own stream
@@ -580,18 +699,20 @@ def greedy_many(plans: Sequence[Plan], masks: Sequence[torch.Tensor], targets: S
     results: List[GreedyResult] = []
     for g0 in range(0, len(plans), step):
         walks = []
-        for plan, mask, target, order in zip(plans[g0:g0 + step], masks[g0:g0 + step], targets[g0:g0 + step],
-                                             orders[g0:g0 + step]):
+        for plan, mask, target, order, slack in zip(plans[g0:g0 + step], masks[g0:g0 + step],
+                                                    targets[g0:g0 + step], orders[g0:g0 + step],
+                                                    slacks[g0:g0 + step]):
             order_t = torch.as_tensor(np.asarray(order, np.int64)).to(plan.device)
             total = int(order_t.shape[0]) if max_candidates is None else min(int(order_t.shape[0]), max_candidates)
             if total == 0:                     # nothing to visit (the device walks take a non-empty order)
                 walks.append(greedy(plan, mask, target, [], mode="fft" if mode == "fft" else "psf",
-                                    fill_ratio=fill_ratio, fill_tol=fill_tol))
+                                    fill_ratio=fill_ratio, fill_tol=fill_tol, slack=slack))
             elif mode == "fft":
                 km = min(k_max or plan.max_jobs, plan.max_jobs)
                 walks.append(_PlanesWalk(plan, mask, target, order_t, total, stop_diff, 1, km,
                                          _walk_stream(plan.device, len(walks)), 0,
-                                         fill=None if fill_ratio is None else (fill_ratio, fill_tol)))
+                                         fill=None if fill_ratio is None else (fill_ratio, fill_tol),
+                                         slack=slack))
             else:
                 walks.append(_Walk(plan, mask, target, order_t, total, stop_diff, 1, k_max or _lib.WALK_MAX_K,
                                    _walk_stream(plan.device, len(walks)), refresh_every))
@@ -608,7 +729,7 @@ def greedy(plan: Plan, mask: torch.Tensor, target: torch.Tensor, order, stop_dif
            k_min: Optional[int] = None, k_max: Optional[int] = None, max_candidates: Optional[int] = None,
            stream=None, mode: str = "fft", refresh_every: int = 4096, progress=None,
            graphs: bool = False, planes: Optional[bool] = None, device_walk: Optional[bool] = None,
-           fill_ratio: Optional[float] = None, fill_tol: int = 1) -> GreedyResult:
+           fill_ratio: Optional[float] = None, fill_tol: int = 1, slack=None) -> GreedyResult:
     """mask [CH][H][W/64] int64 (modified in place), target [G][H][W] f32.
 
     mode="fft": every candidate is the FFT-mode propagation of its colour group
@@ -636,9 +757,23 @@ def greedy(plan: Plan, mask: torch.Tensor, target: torch.Tensor, order, stop_dif
     on-pixel count away from round(fill_ratio * P * H * W) by more than fill_tol pixels is visited
     and rejected without a propagation (fill_admissible); the result's fill_counts are the final
     per-group counts.  Device walk: hbx_dbs_walk_planes_fill; host-decided batches: the same rule
-    on the host, so both give the same accept sequence."""
+    on the host, so both give the same accept sequence.
+    slack (EXTENSION, mode="fft" only; the reference has the strict rule alone): array-like float64,
+    one value per candidate to visit.  The candidate at position q is accepted iff psnr_q >
+    (prev_psnr - slack[q]) in float64 (first_accepting; hbx.h hbx_dbs_walk_planes_anneal): zeros are
+    the greedy rule, metropolis_slack simulated annealing, threshold_slack threshold accepting, -g a
+    minimum gain; NaN rejects, +inf accepts whatever has a PSNR.  It runs on the device walk, the
+    host-decided batches and planes=False with the same accept sequence, and combines with
+    fill_ratio, stop_diff (checked at an accept, as ever), k_min, k_max and max_candidates.  The final
+    state need not be the best one: the result's best_psnr / best_accepts name it and replay()
+    rebuilds it.  slack=None runs exactly the greedy code."""
     if mode not in ("fft", "psf", "psf_host"):
         raise ValueError(f"mode must be 'fft', 'psf' or 'psf_host', got {mode!r}")
+    if slack is not None:
+        if mode != "fft":
+            raise ValueError("slack: the acceptance slack is built for mode='fft' only")
+        n_visit = len(order) if max_candidates is None else min(len(order), max(0, int(max_candidates)))
+        slack = _check_slack(slack, n_visit, "greedy")
     if fill_ratio is not None:
         if mode != "fft":
             raise ValueError("fill_ratio: the on-pixel constraint is built for mode='fft' only")
@@ -674,7 +809,8 @@ def greedy(plan: Plan, mask: torch.Tensor, target: torch.Tensor, order, stop_dif
             raise ValueError("graphs=True: the FFT-mode device walk has no graph variant (device_walk=False "
                              "for host-decided batches, or mode='psf')")
         w = _PlanesWalk(plan, mask, target, order_t, total, stop_diff, k_min or 1, k_max, stream, 0,
-                        progress=progress, fill=None if fill_ratio is None else (fill_ratio, fill_tol))
+                        progress=progress, fill=None if fill_ratio is None else (fill_ratio, fill_tol),
+                        slack=slack)
         while not w.finished:
             w.advance()
         return w.result()
@@ -735,7 +871,7 @@ def greedy(plan: Plan, mask: torch.Tensor, target: torch.Tensor, order, stop_dif
                 r, col = divmod(rem, c.width)
                 if not fill_admissible(int(counts[ch // c.planes]), f_t, f_tol, int(bits[ch, r, col])):
                     ps[j] = np.nan
-        i = first_improving(ps, prev)
+        i = first_improving(ps, prev) if slack is None else first_accepting(ps, prev, slack[pos:pos + k])
         ctl.update(i)
         if i is None:
             last = None if math.isnan(ps[k - 1]) else float(ps[k - 1])

@@ -732,6 +732,31 @@ int hbx_dbs_walk_planes_fill(hbx_plan_t plan, uint64_t* base_mask, const float* 
                              int64_t accept_cap, int32_t K, int32_t batches, int64_t* fill_count,
                              int64_t fill_target, int64_t fill_tol, void* stream);
 
+/* (ABI v15, additive) EXTENSION, no reference counterpart (the reference has the strict rule alone,
+ * DBS_1024_24.py:355): the device walk under a per-candidate acceptance slack -- simulated
+ * annealing, threshold accepting and a minimum-gain rule in one predicate.  slack[n_slack] float64
+ * (device), one value per position of `order`; the candidate at position q is accepted iff
+ *     psnr_q > (prev_psnr - slack[q])      in float64: one subtraction, rounded once, then the compare
+ * (hbx.dbs.first_accepting, the host-decided batches of hbx.dbs.greedy with slack=, is the same
+ * expression, so both give the same accept sequence bit for bit).  slack 0: the greedy rule.  A NaN
+ * slack rejects its candidate; +inf accepts every candidate that has a PSNR; a negative slack -g
+ * demands an improvement of more than g.  Under fill_count an inadmissible candidate has no PSNR and
+ * is rejected whatever its slack; both rules apply.  stop_diff stays where the walk has it: checked
+ * when a candidate is accepted, psnr - init_psnr >= stop_diff; a candidate its slack rejects does not
+ * stop the walk.  prev_psnr is the CURRENT state's PSNR, no longer the best seen: the best state is
+ * recovered from the accept log (hbx.dbs.replay), no kernel tracks it.
+ * n_slack < n_order: HBX_ERR_INVALID (the message names the slack), checked before anything is enqueued;
+ * the device reads no slack at or past n_slack (or the walk's total).  slack NULL: this is
+ * hbx_dbs_walk_planes_fill, kernel for kernel.  Every other rule is that call's: K bounds, one walk per
+ * plan, batches after `done` are no-ops, the precision modes.  hbx_dbs_walk_t is unchanged. */
+int hbx_dbs_walk_planes_anneal(hbx_plan_t plan, uint64_t* base_mask, const float* target,
+                               double* base_chan_stats, float* plane_inten, int32_t* plane_slot,
+                               int32_t n_spare_pairs, const int64_t* order, int64_t n_order,
+                               hbx_dbs_walk_t* walk, int64_t* accept_pos, double* accept_psnr,
+                               int64_t accept_cap, int32_t K, int32_t batches, int64_t* fill_count,
+                               int64_t fill_target, int64_t fill_tol, const double* slack,
+                               int64_t n_slack, void* stream);
+
 /* Incremental-field ("PSF") mode (reported separately from
  * the FFT-mode headline).  tt.simulate is linear, so flipping pixel (c, r, col)
  * changes only plane c's field, by delta * h_g shifted to (r, col), where
