@@ -108,6 +108,26 @@ std::complex<double> transfer(const hbx_optics_t& o, double wl, double fx, doubl
   return {std::cos(ph), std::sin(ph)};
 }
 
+// The transfer-function table [G][N/2 + 1][N] of the optics o (its z), float64 rounded once to complex64:
+// the one copy of the loop, for the plan's own table (hbx_plan_create) and a focal stack's (hbx_plan_set_depths)
+void fill_htab(const hbx_optics_t& o, float2* ht) {
+  const int N = o.height, G = o.groups;
+  const size_t hrow = (size_t)(N / 2 + 1) * N;
+  // ifft2 normalisation, and 1/2: the row passes write 2 A (their Hermitian split drops its
+  // 0.5 factors, r06), the column passes multiply by H / 2 -- powers of two, so every product
+  // and so B are the bits of A x H (hbx_passes.hip, pass 1).  Only the column passes read ht.
+  const double scale = 0.5 / ((double)N * (double)N);
+  for (int g = 0; g < G; ++g)
+    for (int kx = 0; kx <= N / 2; ++kx) {
+      const double fx = fftfreq(kx, N, o.dx);
+      for (int ky = 0; ky < N; ++ky) {
+        const double fy = fftfreq(ky, N, o.dy);
+        const std::complex<double> h = transfer(o, o.wavelength[g], fx, fy) * scale;
+        ht[g * hrow + (size_t)kx * N + ky] = make_float2((float)h.real(), (float)h.imag());
+      }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -195,19 +215,7 @@ int hbx_plan_create(hbx_plan_t* out, const hbx_optics_t* o, int32_t max_jobs, in
   }
   const size_t hrow = (size_t)(N / 2 + 1) * N;
   std::vector<float2> ht((size_t)G * hrow);
-  // ifft2 normalisation, and 1/2: the row passes write 2 A (their Hermitian split drops its
-  // 0.5 factors, r06), the column passes multiply by H / 2 -- powers of two, so every product
-  // and so B are the bits of A x H (hbx_passes.hip, pass 1).  Only the column passes read ht.
-  const double scale = 0.5 / ((double)N * (double)N);
-  for (int g = 0; g < G; ++g)
-    for (int kx = 0; kx <= N / 2; ++kx) {
-      const double fx = fftfreq(kx, N, o->dx);
-      for (int ky = 0; ky < N; ++ky) {
-        const double fy = fftfreq(ky, N, o->dy);
-        const std::complex<double> h = transfer(*o, o->wavelength[g], fx, fy) * scale;
-        ht[g * hrow + (size_t)kx * N + ky] = make_float2((float)h.real(), (float)h.imag());
-      }
-    }
+  fill_htab(*o, ht.data());
   // partial slots per job: row blocks of the last pass (8 rows each on the generic path)
   const int RB = R ? N / (256 / R) : N / 8;
   // the generic path ping-pongs full planes between A and B
@@ -262,6 +270,7 @@ int hbx_plan_destroy(hbx_plan_t p) {
   (void)hipSetDevice(p->device);
   if (p->pd.tw) (void)hipFree(p->pd.tw);
   if (p->pd.htab) (void)hipFree(p->pd.htab);
+  if (p->pd.htab_stack) (void)hipFree(p->pd.htab_stack);
   if (p->pd.ws_a) (void)hipFree(p->pd.ws_a);
   if (p->pd.ws_b) (void)hipFree(p->pd.ws_b);
   if (p->pd.partial) (void)hipFree(p->pd.partial);
@@ -312,6 +321,45 @@ int hbx_plan_pipeline(hbx_plan_t p) {
   int rc = check_plan(p);
   if (rc) return rc;
   return HBX_PIPE_THREE_PASS;   // the only pipeline built since ABI v8
+}
+
+// (extension) a focal stack's tables: fill_htab once per depth, uploaded as plan creation uploads its own
+int hbx_plan_set_depths(hbx_plan_t p, const double* z, int32_t n_depths) {
+  int rc = check_plan(p);
+  if (rc) return rc;
+  if (n_depths < 0 || n_depths > HBX_MAX_DEPTHS)
+    return fail(HBX_ERR_INVALID, "n_depths: the number of depths, 0 <= n_depths <= " + std::to_string(HBX_MAX_DEPTHS));
+  if (n_depths > 0 && !z) return fail(HBX_ERR_INVALID, "null depths");
+  for (int d = 0; d < n_depths; ++d)
+    if (!std::isfinite(z[d])) return fail(HBX_ERR_INVALID, "depths: every z must be finite");
+  HBX_HIP(hipSetDevice(p->device));
+  PlanDev& pd = p->pd;
+  float2* tab = nullptr;
+  if (n_depths > 0) {
+    const size_t per = (size_t)pd.G * (size_t)(pd.N / 2 + 1) * pd.N;
+    std::vector<float2> ht((size_t)n_depths * per);
+    for (int d = 0; d < n_depths; ++d) {
+      hbx_optics_t o = p->optics;
+      o.z = z[d];
+      fill_htab(o, ht.data() + (size_t)d * per);
+    }
+    if (hipMalloc(&tab, ht.size() * sizeof(float2)) != hipSuccess) return fail(HBX_ERR_NOMEM, "depth tables");
+    if (hipMemcpy(tab, ht.data(), ht.size() * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(tab);
+      return fail(HBX_ERR_HIP, "depth table upload");
+    }
+  }
+  HBX_HIP(hipDeviceSynchronize());   // no launch still reads the earlier set
+  if (pd.htab_stack) (void)hipFree(pd.htab_stack);
+  pd.htab_stack = tab;
+  pd.n_depths = n_depths;
+  return HBX_OK;
+}
+
+int hbx_plan_depths(hbx_plan_t p) {
+  int rc = check_plan(p);
+  if (rc) return rc;
+  return p->pd.n_depths;
 }
 
 }  // extern "C"
@@ -896,6 +944,155 @@ int hbx_backward_window(hbx_plan_t p, const float* values, const float* weight, 
   return propagate_full(p, r, stream);
 }
 
+// ---------------------------------------------------------------------------
+// Focal stacks (include/hbx.h, "Focal stacks")
+// ---------------------------------------------------------------------------
+namespace {
+int check_stack_plan(hbx_plan_t p, bool complex_field) {
+  if (int rc = check_real_plan(p, complex_field)) return rc;
+  if (p->pd.n_depths < 1) return fail(HBX_ERR_INVALID, "no depths set on the plan (hbx_plan_set_depths)");
+  return HBX_OK;
+}
+bool leaf_kind_known(int32_t kind) { return kind >= HBX_LEAF_REAL && kind <= HBX_LEAF_PHASE_LEVELS; }
+}  // namespace
+
+int hbx_evaluate_stack(hbx_plan_t p, const void* values, const hbx_leaf_t* leaf, const float* target, int32_t n_env,
+                       float* field, float* intensity, double* chan_stats, void* stream) {
+  HBX_ENTER(p, n_env, "n_env");
+  if (!leaf || !leaf_kind_known(leaf->kind)) return fail(HBX_ERR_INVALID, "leaf: a known HBX_LEAF_* kind");
+  if (!values) return fail(HBX_ERR_INVALID, "null buffer");
+  const bool real_in = leaf->kind == HBX_LEAF_REAL || leaf->kind == HBX_LEAF_THRESHOLD;
+  if (leaf->kind == HBX_LEAF_PHASE_LEVELS) {
+    if (int rc = check_levels(leaf->levels)) return rc;
+  }
+  if (int rc = real_in ? check_eval_outputs(target, chan_stats, nullptr, field || intensity || chan_stats)
+                       : check_eval_outputs(target, chan_stats, nullptr, intensity != nullptr, true))
+    return rc;
+  if (int rc = check_stack_plan(p, !real_in)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const PlanDev& pd = p->pd;
+  const int G = pd.G, CH = pd.G * pd.P, D = pd.n_depths;
+  const int chunk = p->max_jobs / G;
+  HBX_HIP(hipSetDevice(p->device));
+  // real input: the intensity goes through job_inten and a scatter, as propagate_full sends it
+  const bool scatter = real_in && intensity;
+  if (scatter) {
+    if (int rc = ensure_job_inten(p)) return rc;
+  }
+  const size_t hw = (size_t)pd.N * pd.N;
+  const size_t s_in = (real_in ? (size_t)CH : (size_t)(CH / 2)) * hw * (leaf->kind == HBX_LEAF_COMPLEX ? 2 : 1);   // floats
+  const size_t s_fld = (real_in ? (size_t)CH : (size_t)(CH / 2)) * hw;   // float2
+  const size_t s_img = (size_t)G * hw, s_stat = (size_t)G * 3;
+  const float* vals = static_cast<const float*>(values);
+  for (int i0 = 0; i0 < n_env; i0 += chunk) {
+    const int n = std::min(chunk, n_env - i0);
+    for (int d = 0; d < D; ++d) {
+      // depth d's block of every depth-major array, at the chunk's first env
+      const size_t e = (size_t)d * n_env + i0;
+      auto at = [e](auto* q, size_t stride) { return q ? q + e * stride : nullptr; };
+      PassCall c;
+      c.jobs = p->full_jobs;
+      c.n_jobs = n * G;
+      const float* v = vals + (size_t)i0 * s_in;
+      switch (leaf->kind) {
+        case HBX_LEAF_THRESHOLD: c.real_binarize = 1; c.real_threshold = leaf->threshold;   // fallthrough
+        case HBX_LEAF_REAL: c.real_values = v; break;
+        case HBX_LEAF_COMPLEX: c.complex_values = reinterpret_cast<const float2*>(v); break;
+        case HBX_LEAF_PHASE_LEVELS: c.phase_levels = leaf->levels;   // fallthrough
+        default: c.phase_values = v; break;
+      }
+      c.target = at(target, s_img);
+      if (real_in) {
+        c.inten_out = intensity ? p->job_inten : nullptr;
+        c.field_out = at(reinterpret_cast<float2*>(field), s_fld);
+      } else {
+        c.inten_out = at(intensity, s_img);
+        c.complex_field = at(reinterpret_cast<float2*>(field), s_fld);
+        c.complex_stats = 1;
+      }
+      c.stack_depth = d;
+      c.stack_skip_first = d > 0;   // the row spectra of this chunk are in ws_a
+      HBX_HIP(hbx::run_jobs(pd, c, st));
+      if (chan_stats)
+        HBX_HIP(hbx::launch_full_finalize(c.jobs, pd.job_stats, n, G, at(chan_stats, s_stat), nullptr, pixel_count(p),
+                                          p->optics.rel_scale, p->optics.peak, EnvDev{}, 0, st));
+      if (scatter)
+        HBX_HIP(hbx::launch_scatter_intensity(c.jobs, n * G, p->job_inten, at(intensity, s_img), G, hw, nullptr, st));
+    }
+  }
+  return HBX_OK;
+}
+
+int hbx_backward_stack(hbx_plan_t p, const float* values, const float* weight, float scale, const hbx_leaf_t* leaf,
+                       const float* samples, int32_t n_env, float* grad_field, float* grad, void* stream) {
+  HBX_ENTER(p, n_env, "n_env");
+  if (!leaf || !leaf_kind_known(leaf->kind)) return fail(HBX_ERR_INVALID, "leaf: a known HBX_LEAF_* kind");
+  if (!values) return fail(HBX_ERR_INVALID, "null buffer");
+  if ((grad_field != nullptr) == (grad != nullptr))
+    return fail(HBX_ERR_INVALID, "exactly one of grad_field and grad is given");
+  if ((leaf->kind == HBX_LEAF_COMPLEX) != (grad_field != nullptr))
+    return fail(HBX_ERR_INVALID, "grad_field is a complex leaf's output, grad every other leaf's");
+  const bool needs_samples = leaf->kind == HBX_LEAF_PHASE || leaf->kind == HBX_LEAF_PHASE_LEVELS ||
+                             leaf->kind == HBX_LEAF_THRESHOLD;
+  if (needs_samples != (samples != nullptr))
+    return fail(HBX_ERR_INVALID, "samples: the leaf's x for a phase, L-level or thresholded leaf, null otherwise");
+  if (leaf->kind == HBX_LEAF_PHASE_LEVELS) {
+    if (int rc = check_levels(leaf->levels)) return rc;
+  }
+  if (leaf->kind == HBX_LEAF_THRESHOLD) {
+    if (int rc = check_surrogate(leaf->surrogate, leaf->p1)) return rc;
+  }
+  if (int rc = check_stack_plan(p, true)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const PlanDev& pd = p->pd;
+  const int G = pd.G, CH = pd.G * pd.P, D = pd.n_depths;
+  if (p->max_jobs < G * D)
+    return fail(HBX_ERR_INVALID, "max_jobs must be >= groups * depths (" + std::to_string(G * D) + ") for a stack's backward");
+  const int chunk = p->max_jobs / D / G;     // envs per chunk
+  const int nj = chunk * G;                  // job slots per depth
+  HBX_HIP(hipSetDevice(p->device));
+  const size_t hw = (size_t)pd.N * pd.N;
+  const size_t s_cplx = (size_t)(CH / 2) * hw;   // complex planes (float2), sample planes (float)
+  const size_t s_img = (size_t)G * hw;
+  const float2* vals = reinterpret_cast<const float2*>(values);
+  for (int i0 = 0; i0 < n_env; i0 += chunk) {
+    const int n = std::min(chunk, n_env - i0);
+    for (int d = 0; d < D; ++d) {   // depth d: first and column pass into its slot range
+      const size_t e = (size_t)d * n_env + i0;
+      PassCall c;
+      c.jobs = p->full_jobs;
+      c.n_jobs = n * G;
+      c.complex_values = vals + e * s_cplx;
+      if (weight) {
+        c.complex_weight = weight + e * s_img;
+        c.complex_scale = scale;
+      }
+      c.stack_depth = d;
+      c.stack_skip_last = 1;
+      c.stack_slot0 = d * nj;
+      HBX_HIP(hbx::run_jobs(pd, c, st));
+    }
+    PassCall o;   // the one output, of the chunk's envs
+    o.jobs = p->full_jobs;
+    o.n_jobs = n * G;
+    float* g = grad ? grad + (size_t)i0 * s_cplx : nullptr;
+    const float* x = samples ? samples + (size_t)i0 * s_cplx : nullptr;
+    switch (leaf->kind) {
+      case HBX_LEAF_COMPLEX: o.complex_field = reinterpret_cast<float2*>(grad_field) + (size_t)i0 * s_cplx; break;
+      case HBX_LEAF_REAL: o.real_part = g; break;
+      case HBX_LEAF_PHASE_LEVELS: o.phase_levels = leaf->levels;   // fallthrough
+      case HBX_LEAF_PHASE: o.grad_samples = x; o.grad_phase = g; break;
+      default:
+        o.grad_samples = x; o.grad_phase = g;
+        o.grad_kind = leaf->surrogate == HBX_STE_WINDOW ? hbx::kGradSteWindow : hbx::kGradSteSigmoid;
+        o.grad_p0 = leaf->p0; o.grad_p1 = leaf->p1;
+        break;
+    }
+    HBX_HIP(hbx::run_stack_last(pd, o, D, nj, st));
+  }
+  return HBX_OK;
+}
+
 namespace {
 int check_loss_kind(int32_t kind, int32_t rel_scale) {
   if (kind != HBX_LOSS_MSE && kind != HBX_LOSS_PSNR) return fail(HBX_ERR_INVALID, "kind: HBX_LOSS_MSE or HBX_LOSS_PSNR");
@@ -946,6 +1143,38 @@ int hbx_loss_weight_window(hbx_plan_t p, const float* intensity, const float* ta
   HBX_HIP(hipSetDevice(p->device));
   HBX_HIP(hbx::launch_loss_weight(intensity, target, chan_stats, grad_loss, n_env, p->pd.G, (size_t)w.h * w.w, kind,
                                   rel_scale, (double)p->pd.G * w.h * w.w, weight, (hipStream_t)stream));
+  return HBX_OK;
+}
+
+int hbx_loss_stack(hbx_plan_t p, const double* chan_stats, int32_t n_env, int32_t kind, int32_t rel_scale,
+                   double* loss, void* stream) {
+  int rc = check_plan(p);
+  if (rc) return rc;
+  if ((rc = check_loss_kind(kind, rel_scale))) return rc;
+  if (n_env <= 0) return n_env == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "n_env");
+  if (!chan_stats || !loss) return fail(HBX_ERR_INVALID, "null buffer");
+  const int D = p->pd.n_depths;
+  if (D < 1) return fail(HBX_ERR_INVALID, "no depths set on the plan (hbx_plan_set_depths)");
+  HBX_HIP(hipSetDevice(p->device));
+  HBX_HIP(hbx::launch_loss_stack(chan_stats, n_env, p->pd.G, D, kind, rel_scale, (double)D * pixel_count(p),
+                                 p->optics.peak, loss, (hipStream_t)stream));
+  return HBX_OK;
+}
+
+int hbx_loss_weight_stack(hbx_plan_t p, const float* intensity, const float* target, const double* chan_stats,
+                          const double* grad_loss, int32_t n_env, int32_t kind, int32_t rel_scale, float* weight,
+                          void* stream) {
+  int rc = check_plan(p);
+  if (rc) return rc;
+  if ((rc = check_loss_kind(kind, rel_scale))) return rc;
+  if (n_env <= 0) return n_env == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "n_env");
+  if (!intensity || !target || !chan_stats || !weight) return fail(HBX_ERR_INVALID, "null buffer");
+  const int D = p->pd.n_depths;
+  if (D < 1) return fail(HBX_ERR_INVALID, "no depths set on the plan (hbx_plan_set_depths)");
+  HBX_HIP(hipSetDevice(p->device));
+  HBX_HIP(hbx::launch_loss_weight_stack(intensity, target, chan_stats, grad_loss, n_env, p->pd.G, D,
+                                        (size_t)p->pd.N * p->pd.N, kind, rel_scale, (double)D * pixel_count(p), weight,
+                                        (hipStream_t)stream));
   return HBX_OK;
 }
 

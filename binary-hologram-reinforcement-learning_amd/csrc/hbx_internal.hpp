@@ -218,6 +218,11 @@ struct PlanDev {
   float* zero_row;     // [N] zeros: the target row of a propagation without a target
   int store_kind;      // HBX_PRECISION_*: rounding of the pass intermediates (0 = f32, the product)
   PassTimer* timer;    // nullable
+  // (extension, hbx_plan_set_depths) the focal stack's tables: depth d's table is the htab of a plan
+  // created with optics.z = z[d], bit for bit.  Null / 0 until depths are set; only a PassCall with
+  // stack_depth >= 0 reads them
+  float2* htab_stack;  // [n_depths][G][N/2 + 1][N]
+  int n_depths;
 };
 
 // plane-cached FFT mode (ABI v9; N = 1024 / 896 / 256), PassCall::plane_mode:
@@ -362,7 +367,27 @@ struct PassCall {
   const WalkPlanesArgs* walk_planes = nullptr;  // (r05) plane-cache walk batch: the last k_rowinv_d
                                                 // workgroup decides (hbx_walk_planes.hpp)
   int walk_anneal = 0;                          // 1: the annealed decision (k_rowinv_walk_anneal; walk_planes set)
+  // (extension, hbx_evaluate_stack / hbx_backward_stack) a focal stack runs the three passes in pieces.
+  // stack_depth >= 0: the column pass multiplies by depth stack_depth's table (PlanDev::htab_stack), -1 by
+  // the plan's own.  stack_skip_first: the first pass does not run -- ws_a holds the chunk's row spectra,
+  // left by the call for depth 0 (they do not depend on z).  stack_skip_last: the call ends behind the
+  // column pass -- the depth-summing last pass (StackLast, run_stack_last) reads the D slot ranges of ws_b.
+  // stack_slot0: the job slot of ws_a / ws_b the call's job 0 runs in (the backward puts depth d's jobs at
+  // d * nj).  Sample inputs only; no window, plane cache, actions, walk or reconcile (check_pass_call)
+  int stack_depth = -1;
+  int stack_skip_first = 0;
+  int stack_skip_last = 0;
+  int stack_slot0 = 0;
 };
+// whether any focal-stack field is set
+inline bool pass_stack(const PassCall& c) {
+  return c.stack_depth >= 0 || c.stack_skip_first || c.stack_skip_last || c.stack_slot0 != 0;
+}
+// the transfer-function table the column pass of this call reads
+inline const float2* pass_htab(const PlanDev& pd, const PassCall& c) {
+  if (c.stack_depth < 0) return pd.htab;
+  return pd.htab_stack + (size_t)c.stack_depth * pd.G * (size_t)(pd.N / 2 + 1) * pd.N;
+}
 
 // a window (hbx_window_t) that is a non-empty rectangle of the N x N grid
 inline bool window_in_grid(const hbx_window_t& w, int N) {
@@ -424,7 +449,7 @@ inline hipError_t check_pass_call(const PlanDev& pd, const PassCall& c) {
   // real, complex and phase samples: the f32 product path alone
   if (!c.mask) ok = ok && f32 && !planes && !c.actions && !walk;
   // complex or phase in, complex out: the pair-recombining last pass writes these and nothing else ...
-  ok = ok && (pass_complex(c) ? (complex_out || grad_out) && !c.field_out && !c.inten_by_env && !c.rc_pending &&
+  ok = ok && (pass_complex(c) ? (complex_out || grad_out || c.stack_skip_last) && !c.field_out && !c.inten_by_env && !c.rc_pending &&
                                     !c.skip_reduce
                               : !complex_out && !grad_out);
   // ... or the phase gradient alone, from its samples
@@ -448,6 +473,19 @@ inline hipError_t check_pass_call(const PlanDev& pd, const PassCall& c) {
     ok = ok && (c.real_values || (c.complex_values && !c.complex_field && !c.complex_stats &&
                                   (c.real_part || (grad_out && c.grad_kind != kGradPhase))));
     ok = ok && !planes && !c.actions && !walk && !c.rc_pending && !c.inten_by_env && !c.skip_reduce;
+  }
+  // a focal stack's pieces: a depth the plan has a table for (every piece names one); sample inputs on the
+  // f32 path; no window, plane cache, actions, walk or reconcile, nothing env-major, the reduction as it is.
+  // A call that stops behind the column pass has complex samples in and no output of its own; one that
+  // skips the first pass is a forward piece (the slot offset is the backward's)
+  if (pass_stack(c)) {
+    ok = ok && c.stack_depth >= 0 && c.stack_depth < pd.n_depths && pd.htab_stack;
+    ok = ok && !c.mask && f32;
+    ok = ok && !c.windowed && !planes && !c.actions && !walk && !c.rc_pending && !c.inten_by_env && !c.skip_reduce;
+    ok = ok && c.stack_slot0 >= 0;
+    ok = ok && !(c.stack_skip_first && (c.stack_skip_last || c.stack_slot0 != 0));
+    ok = ok && (!c.stack_slot0 || c.stack_skip_last);
+    if (c.stack_skip_last) ok = ok && c.complex_values && !complex_out && !grad_out && !c.target && !c.inten_out;
   }
   return ok ? hipSuccess : hipErrorInvalidValue;
 }
@@ -505,6 +543,26 @@ struct EnvParams {
 hipError_t run_jobs(const PlanDev& pd, const PassCall& c, hipStream_t st);
 // its N = 896 form (hbx_passes896.hip; run_jobs has checked the call)
 hipError_t run_jobs_896(const PlanDev& pd, const PassCall& c, hipStream_t st);
+// (extension, hbx_backward_stack) the depth-summing last pass: c names the jobs (n_jobs per depth) and the
+// one output of a complex last pass -- complex_field, real_part, or grad_samples / grad_phase with their kind --
+// and nothing else; depth d's column-pass output sits in job slots [d * slot_stride, d * slot_stride + n_jobs)
+// of ws_b (the PassCalls with stack_skip_last and stack_slot0 = d * slot_stride put it there)
+inline hipError_t check_stack_last(const PlanDev& pd, const PassCall& c, int n_depths, int slot_stride) {
+  const bool grad_out = c.grad_samples || c.grad_phase;
+  bool ok = pd.store_kind == HBX_PRECISION_F32 && n_depths >= 1 && n_depths <= HBX_MAX_DEPTHS;
+  ok = ok && c.n_jobs >= 1 && slot_stride >= c.n_jobs;
+  ok = ok && !c.mask && !c.real_values && !c.complex_values && !c.phase_values && !c.complex_weight;
+  ok = ok && (c.complex_field != nullptr) + (c.real_part != nullptr) + (grad_out ? 1 : 0) == 1;
+  ok = ok && (!grad_out || (c.grad_samples && c.grad_phase));
+  ok = ok && (c.grad_kind == kGradPhase ||
+              (grad_out && (c.grad_kind == kGradSteWindow || (c.grad_kind == kGradSteSigmoid && c.grad_p1 > 0.0f))));
+  ok = ok && (c.phase_levels == 0 || (c.phase_levels >= 2 && c.phase_levels <= 256 && grad_out && c.grad_kind == kGradPhase));
+  ok = ok && !c.target && !c.inten_out && !c.field_out && !c.complex_stats && !c.windowed && !c.actions &&
+       c.plane_mode == kPlanesOff && !c.walk_phase && !c.walk_planes && !c.rc_pending && !c.skip_reduce && !pass_stack(c);
+  return ok ? hipSuccess : hipErrorInvalidValue;
+}
+hipError_t run_stack_last(const PlanDev& pd, const PassCall& c, int n_depths, int slot_stride, hipStream_t st);
+hipError_t run_stack_last_896(const PlanDev& pd, const PassCall& c, int n_depths, int slot_stride, hipStream_t st);
 // One kernel launch of `blocks` workgroups of `nt` threads: the caller picks the instantiation (a
 // function pointer: every variant of a kernel family has one signature) and writes the arguments once
 template <class K, class... A>
@@ -679,5 +737,12 @@ hipError_t launch_loss(const double* chan_stats, int n, int G, int kind, int rel
 hipError_t launch_loss_weight(const float* inten, const float* target, const double* chan_stats,
                               const double* grad_loss, int n, int G, size_t hw, int kind, int rel_scale, double count,
                               float* weight, hipStream_t st);
+// (extension) hbx_pack.hip: the same over a focal stack -- chan_stats[D][n][G][3] -> loss[n], and
+// weight[D][n][G][hw] from inten / target [D][n][G][hw]; an env's sums run over its D G channels, d outer
+hipError_t launch_loss_stack(const double* chan_stats, int n, int G, int D, int kind, int rel_scale, double count,
+                             double peak, double* loss, hipStream_t st);
+hipError_t launch_loss_weight_stack(const float* inten, const float* target, const double* chan_stats,
+                                    const double* grad_loss, int n, int G, int D, size_t hw, int kind, int rel_scale,
+                                    double count, float* weight, hipStream_t st);
 
 }  // namespace hbx

@@ -270,7 +270,103 @@ __global__ __launch_bounds__(256) void k_loss_weight1(const float* __restrict__ 
   }
 }
 
+// (extension, focal stacks) an env's sums over its D G channels of chan_stats[D][n][G][3]: d outer, g inner,
+// from 0.0 as env_sums -- at D = 1 the same additions in the same order
+__device__ __forceinline__ void env_sums_stack(const double* __restrict__ chan_stats, int b, int n, int G, int D,
+                                               double& sxy, double& sxx, double& syy) {
+  sxy = 0.0; sxx = 0.0; syy = 0.0;
+  for (int d = 0; d < D; ++d)
+    for (int g = 0; g < G; ++g) {
+      const double* s = chan_stats + (((size_t)d * n + b) * G + g) * 3;
+      sxy += s[0]; sxx += s[1]; syy += s[2];
+    }
+}
+
+// hbx_loss_stack: chan_stats[D][n][G][3] -> loss[n]; k_loss's expressions on the stack's sums, count = D G hw
+__global__ void k_loss_stack(const double* __restrict__ chan_stats, int n, int G, int D, int kind, int rel_scale,
+                             double count, double peak, double* __restrict__ loss) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= n) return;
+  double sxy, sxx, syy;
+  env_sums_stack(chan_stats, b, n, G, D, sxy, sxx, syy);
+  loss[b] = kind == HBX_LOSS_PSNR ? psnr_from(sxy, sxx, syy, count, rel_scale, peak)
+                                  : rel_mse_from(sxy, sxx, syy, count, rel_scale);
+}
+
+// hbx_loss_weight_stack: weight[d][b] = a_b I[d][b] + c_b T[d][b], one (a, c) per env for the whole stack,
+// loss_weight_coeffs' expressions on the stack's sums.  bx workgroups per (depth, env) image set of n4 16-byte
+// pieces; blockIdx.x = (d n + b) bx + piece block, so the images are indexed as k_loss_weight indexes an env's
+__global__ __launch_bounds__(256) void k_loss_weight_stack(const float4* __restrict__ inten,
+                                                           const float4* __restrict__ target,
+                                                           const double* __restrict__ chan_stats,
+                                                           const double* __restrict__ grad_loss, int n, int G, int D,
+                                                           int64_t n4, unsigned bx, int kind, int rel_scale,
+                                                           double count, float4* __restrict__ weight) {
+  const int db = blockIdx.x / bx;   // d * n + b
+  const int b = db % n;
+  double sxy, sxx, syy;
+  env_sums_stack(chan_stats, b, n, G, D, sxy, sxx, syy);
+  double a, c;   // dMSE/dI = a I + c T
+  if (rel_scale == HBX_REL_LSQ) {
+    const double s = sxx > 0.0 ? sxy / sxx : 0.0;   // no scale to differentiate: a = c = 0
+    a = 2.0 * s * s / count;
+    c = sxx > 0.0 ? -2.0 * s / count : 0.0;
+  } else {
+    a = 2.0 / count;
+    c = -2.0 / count;
+  }
+  if (kind == HBX_LOSS_PSNR) {
+    const double mse = rel_mse_from(sxy, sxx, syy, count, rel_scale);
+    const double f = mse > 0.0 ? -(10.0 / 2.302585092994045684) / mse : 0.0;
+    a *= f;
+    c *= f;
+  }
+  const double up = grad_loss ? grad_loss[b] : 1.0;
+  const float af = (float)(a * up), cf = (float)(c * up);
+  const int64_t base = (int64_t)db * n4;
+  const int64_t i0 = (int64_t)(blockIdx.x % bx) * (256 * kLossPer) + threadIdx.x;
+  float4 I[kLossPer], T[kLossPer];
+#pragma unroll
+  for (int k = 0; k < kLossPer; ++k) {
+    const int64_t i = i0 + 256 * k;
+    if (i < n4) {
+      I[k] = inten[base + i];
+      T[k] = target[base + i];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < kLossPer; ++k) {
+    const int64_t i = i0 + 256 * k;
+    if (i < n4)
+      weight[base + i] = make_float4(fmaf(af, I[k].x, cf * T[k].x), fmaf(af, I[k].y, cf * T[k].y),
+                                     fmaf(af, I[k].z, cf * T[k].z), fmaf(af, I[k].w, cf * T[k].w));
+  }
+}
+
 }  // namespace
+
+hipError_t launch_loss_stack(const double* chan_stats, int n, int G, int D, int kind, int rel_scale, double count,
+                             double peak, double* loss, hipStream_t st) {
+  hipLaunchKernelGGL(k_loss_stack, dim3((n + 63) / 64), dim3(64), 0, st, chan_stats, n, G, D, kind, rel_scale, count,
+                     peak, loss);
+  return hipGetLastError();
+}
+
+// (full-grid images only: G hw is a multiple of 4 at every built size, and the caller's arrays are whole
+// tensors; a misaligned pointer is refused, not taken one float at a time)
+hipError_t launch_loss_weight_stack(const float* inten, const float* target, const double* chan_stats,
+                                    const double* grad_loss, int n, int G, int D, size_t hw, int kind, int rel_scale,
+                                    double count, float* weight, hipStream_t st) {
+  const int64_t n1 = (int64_t)G * (int64_t)hw;
+  const auto misaligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) != 0; };
+  if (n1 % 4 != 0 || misaligned(inten) || misaligned(target) || misaligned(weight)) return hipErrorInvalidValue;
+  const int64_t n4 = n1 / 4;
+  const unsigned bx = (unsigned)((n4 + 256 * kLossPer - 1) / (256 * kLossPer));
+  hipLaunchKernelGGL(k_loss_weight_stack, dim3(bx * (unsigned)n * (unsigned)D), dim3(256), 0, st,
+                     reinterpret_cast<const float4*>(inten), reinterpret_cast<const float4*>(target), chan_stats,
+                     grad_loss, n, G, D, n4, bx, kind, rel_scale, count, reinterpret_cast<float4*>(weight));
+  return hipGetLastError();
+}
 
 hipError_t launch_loss(const double* chan_stats, int n, int G, int kind, int rel_scale, double count, double peak,
                        double* loss, hipStream_t st) {

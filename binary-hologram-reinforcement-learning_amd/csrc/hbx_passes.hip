@@ -1494,26 +1494,32 @@ static hipError_t launch_passes(const PlanDev& pd, const PassCall& c, hipStream_
   // block per workgroup at every launch size
   const unsigned sample_blocks = (unsigned)n_jobs * (P / 2) * kRowBlocks;
 
-  if (tm) tm->begin(0, st);
-  if (pass_complex(c)) {   // the load kind: complex samples as they are, times scale * weight, or exp(i pi phase)
-    const int lk = c.phase_values ? (c.phase_levels ? kLoadPhaseLevels : kLoadPhase) : c.complex_weight ? kLoadWeighted : kLoadComplex;
-    launch_kernel(pick_first_pass_cplx<SampleKernels<R>>(lk, pass_window_in(c, N)), sample_blocks, NT, st, jobs,
-                  c.complex_values, pd.ws_a, pd.tw, P, CH, c.complex_weight, pass_first_scale(c), c.phase_values, pass_first_window(c));
-  } else if (c.real_values) {
-    // the load kind: the samples as they are, or (hbx_evaluate_threshold) the field of the bit [x >= threshold]
-    launch_kernel(pick_first_pass_real<SampleKernels<R>>(c.real_binarize != 0, pass_window_in(c, N)), sample_blocks, NT,
-                  st, jobs, c.real_values, pd.ws_a, pd.tw, P, CH, c.real_threshold, pd.va, pd.va + pd.vb, c.in_win);
-  } else {
-    auto k = [&] {
-      if constexpr (R == 32) return small ? k_rowfwd32<SK, 1> : k_rowfwd32<SK>;
-      else if constexpr (kTiledB<R>) return small ? k_rowfwd<R, NT, SK, 1> : k_rowfwd<R, NT, SK>;
-      else return k_rowfwd<R, NT, SK>;
-    }();
-    launch_kernel(k, small ? rf_blocks * rowfwd_iters<R>() : rf_blocks, NT, st, jobs,
-                  reinterpret_cast<const uint32_t*>(c.mask), pd.ws_a, pd.tw, P, CH, pd.va, pd.vb, pair, c.actions,
-                  c.act_err, c.walk_phase);
+  // (focal stacks) the job slot the call runs in, and its pieces: a forward piece behind depth 0 finds the
+  // row spectra in ws_a, a backward piece ends behind the column pass.  Every other call: slot 0, all three
+  float2* const ws_a = pd.ws_a + (size_t)c.stack_slot0 * P * plane_a_elems(R);
+  float2* const ws_b = pd.ws_b + (size_t)c.stack_slot0 * P * plane_b_elems(R);
+  if (!c.stack_skip_first) {
+    if (tm) tm->begin(0, st);
+    if (pass_complex(c)) {   // the load kind: complex samples as they are, times scale * weight, or exp(i pi phase)
+      const int lk = c.phase_values ? (c.phase_levels ? kLoadPhaseLevels : kLoadPhase) : c.complex_weight ? kLoadWeighted : kLoadComplex;
+      launch_kernel(pick_first_pass_cplx<SampleKernels<R>>(lk, pass_window_in(c, N)), sample_blocks, NT, st, jobs,
+                    c.complex_values, ws_a, pd.tw, P, CH, c.complex_weight, pass_first_scale(c), c.phase_values, pass_first_window(c));
+    } else if (c.real_values) {
+      // the load kind: the samples as they are, or (hbx_evaluate_threshold) the field of the bit [x >= threshold]
+      launch_kernel(pick_first_pass_real<SampleKernels<R>>(c.real_binarize != 0, pass_window_in(c, N)), sample_blocks, NT,
+                    st, jobs, c.real_values, ws_a, pd.tw, P, CH, c.real_threshold, pd.va, pd.va + pd.vb, c.in_win);
+    } else {
+      auto k = [&] {
+        if constexpr (R == 32) return small ? k_rowfwd32<SK, 1> : k_rowfwd32<SK>;
+        else if constexpr (kTiledB<R>) return small ? k_rowfwd<R, NT, SK, 1> : k_rowfwd<R, NT, SK>;
+        else return k_rowfwd<R, NT, SK>;
+      }();
+      launch_kernel(k, small ? rf_blocks * rowfwd_iters<R>() : rf_blocks, NT, st, jobs,
+                    reinterpret_cast<const uint32_t*>(c.mask), ws_a, pd.tw, P, CH, pd.va, pd.vb, pair, c.actions,
+                    c.act_err, c.walk_phase);
+    }
+    if (tm) tm->end(0, n_jobs, st);
   }
-  if (tm) tm->end(0, n_jobs, st);
 
   if (tm) tm->begin(1, st);
   {
@@ -1521,17 +1527,18 @@ static hipError_t launch_passes(const PlanDev& pd, const PassCall& c, hipStream_
       if constexpr (kTiledB<R>) return small ? k_col2<R, SK, 1> : k_col2<R, SK>;
       else return k_col2<R, SK>;
     }();
-    launch_kernel(k, small ? col_blocks * col2_iters<R>() : col_blocks, 256, st, jobs, pd.ws_a, pd.ws_b, pd.htab,
+    launch_kernel(k, small ? col_blocks * col2_iters<R>() : col_blocks, 256, st, jobs, ws_a, ws_b, pass_htab(pd, c),
                   pd.tw, P, pair, c.walk_phase);
   }
   if (tm) tm->end(1, n_jobs, st);
+  if (c.stack_skip_last) return hipGetLastError();
 
   const unsigned blocks = (unsigned)n_jobs * kRowBlocks;
   if (tm) tm->begin(2, st);
   if (pass_complex(c)) {   // recombine each plane pair, or a leaf's gradient instead (pick_last_pass_cplx)
     const auto k = pick_last_pass_cplx<SampleKernels<R>>(pass_grad_kind(c), c.complex_stats != 0,
                                                          c.windowed != 0);
-    launch_kernel(k, blocks, NT, st, jobs, pd.ws_b, pd.tw, P, pd.G, c.complex_field, c.real_part, tg.rows, tg.mask,
+    launch_kernel(k, blocks, NT, st, jobs, ws_b, pd.tw, P, pd.G, c.complex_field, c.real_part, tg.rows, tg.mask,
                   pd.partial, c.inten_out, c.grad_samples, c.grad_phase, pd.vb, pass_grad_p0(c), pass_grad_p1(c), c.out_win);
   } else if constexpr (kTiledB<R>) {
     // WALK (r05): a plane-cache walk batch, the last workgroup decides.  LEAN (r06): the plain
@@ -1545,11 +1552,11 @@ static hipError_t launch_passes(const PlanDev& pd, const PassCall& c, hipStream_
     if (!c.walk_planes) k = lean ? k_rowinv_d<R, false, true> : k_rowinv_d<R>;
     if (c.windowed) k = lean ? k_rowinv_d<R, false, true, true> : k_rowinv_d<R, false, false, true>;
     if (c.walk_anneal) k = k_rowinv_walk_anneal<R>;   // (behind every k_rowinv_d: their layout stays)
-    launch_kernel(k, blocks, 256, st, jobs, pd.ws_b, tg.rows, pd.tw, P, pd.G, pd.partial, c.inten_out, c.field_out,
+    launch_kernel(k, blocks, 256, st, jobs, ws_b, tg.rows, pd.tw, P, pd.G, pd.partial, c.inten_out, c.field_out,
                   tg.mask, c.inten_by_env, c.plane_mode, c.plane_pool, c.plane_slot, c.plane_spares, c.spare_base,
                   c.rc_pending, c.rc_cache, c.walk_planes ? *c.walk_planes : WalkPlanesArgs{}, c.out_win);
   } else {
-    launch_kernel(!c.windowed ? k_rowinv<R, NT> : k_rowinv<R, NT, true>, blocks, NT, st, jobs, pd.ws_b, tg.rows, pd.tw,
+    launch_kernel(!c.windowed ? k_rowinv<R, NT> : k_rowinv<R, NT, true>, blocks, NT, st, jobs, ws_b, tg.rows, pd.tw,
                   P, pd.G, pd.partial, c.inten_out, c.field_out, tg.mask, c.inten_by_env, c.out_win);
   }
   if (tm) tm->end(2, n_jobs, st);
@@ -1575,6 +1582,201 @@ hipError_t run_jobs(const PlanDev& pd, const PassCall& c, hipStream_t st) {
     HBX_PASSES_CASE(8, HBX_PRECISION_BF16_STORE)
     HBX_PASSES_CASE(8, HBX_PRECISION_F16_STORE)
 #undef HBX_PASSES_CASE
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Focal stacks (hbx_backward_stack, EXTENSION): the depth-summing complex last pass
+// ---------------------------------------------------------------------------
+// The backward of a stack is linear: the leaf's gradient is the sum over the D depths of the adjoint
+// propagations.  Depth d's first and column pass leave job j's B planes in slot d * slot_stride + j of ws_b;
+// these kernels add the D slots' rows as they load them (rowinv_load_pair_stack; N = 64: as the shares of the
+// tile arrive), run ONE inverse row FFT per complex plane and write the gradient once -- where D single-depth
+// last passes run D FFTs and D stores, and D - 1 read-add-write passes follow.  Each is its single-depth
+// sibling's geometry (k_rowinv_d_cplx, k_rowinv_cplx) without the statistics and window forms, with the
+// argument list of its own (D and the float2 stride between depth slots), named and instantiated behind every
+// other kernel of this file, so that none of them moves.  ws_b is the first depth's job 0.
+template <int R, int GK = kGradNone>
+__global__ __launch_bounds__(256, 2) void k_rowinv_d_cplx_stack(const JobDesc* __restrict__ jobs,
+                                                                const float2* __restrict__ ws_b,
+                                                                const float2* __restrict__ tw_glob, int P, int G,
+                                                                int D, size_t dstride,
+                                                                float2* __restrict__ field_out,
+                                                                float* __restrict__ real_out,
+                                                                const float* __restrict__ phase,
+                                                                float* __restrict__ grad, float gvb, float ga,
+                                                                float gb) {
+  constexpr int N = R * R, GPB = 256 / R, RB = N / GPB;
+  __shared__ float2 tw[N];
+  __shared__ float2 scratch[GPB * R * (R + 1)];
+  for (int i = threadIdx.x; i < N; i += 256) tw[i] = tw_glob[i];
+
+  const int grp = threadIdx.x / R;
+  const int t = threadIdx.x % R;
+  const int bid = xcd_pair<RB>(blockIdx.x);
+  const int rb = bid % RB;
+  const int j = bid / RB;
+  const JobDesc jb = jobs[j];
+  if (jb.env < 0) return;   // uniform per block
+  const int y = rb * GPB + grp;
+  const hbx_window_t win = {0, 0, 0, 0};
+  const WinRow wr(win, y, t);   // (unread: no window form)
+  const int Q = P / 2;                        // complex planes per group
+  constexpr int PLB = N * N;                 // float2 per B plane
+  const float2* job_b = ws_b + (size_t)j * P * PLB;
+  const unsigned job_bytes = (unsigned)((size_t)P * PLB * 8);
+  const RowinvLanes<R> ln(y, t);
+  auto load_pair = [&](pk2 (&v)[R], int q) { rowinv_load_pair_stack(v, ln, job_b, dstride, job_bytes, D, q); };
+  const PaddedScratch<R> sc{scratch + grp * R * (R + 1)};
+  const size_t row0 = (((size_t)jb.env * G + jb.group) * Q * N + y) * N + t;   // complex plane 0, pixel x = t
+  float acc[1];
+  auto finish_plane = [&](pk2 (&v)[R], int q) {
+    fft_group<R, true>(v, t, sc, tw);
+    cplx_plane_out<R, R, false, GK, false>(v, acc, jb.env, jb.group, G, Q, q, y, row0, win, wr, field_out, real_out,
+                                           phase, grad, gvb, ga, gb);
+  };
+  pk2 va[R];
+  load_pair(va, 0);
+  __syncthreads();  // tw visible
+  // (N = 256: its sibling keeps the next pair in flight in a second register set.  Here depth 0's pair in flight
+  // under the FFT measured the same as this one set at D = 2, 3 and 4 -- the pass is bound by the D planes it
+  // reads, profiles/focal_stack/stack256_prefetch_ab.txt -- so both sizes run the one loop)
+#pragma unroll 1
+  for (int q = 0; q < Q; ++q) {
+    finish_plane(va, q);
+    if (q + 1 < Q) load_pair(va, q + 1);   // uniform: no pair is read twice
+  }
+}
+
+// N = 64: k_rowinv_cplx's LDS tile transpose.  A thread's share of the pair's two plane tiles is combined as
+// it arrives, depth by depth in the same order -- (((a_0 + i b_0) + a_1) + i b_1) + ... -- and written to the tile
+template <int R, int NT, int GK = kGradNone>
+__global__ __launch_bounds__(NT, 512 / NT) void k_rowinv_cplx_stack(const JobDesc* __restrict__ jobs,
+                                                                    const float2* __restrict__ ws_b,
+                                                                    const float2* __restrict__ tw_glob, int P, int G,
+                                                                    int D, size_t dstride,
+                                                                    float2* __restrict__ field_out,
+                                                                    float* __restrict__ real_out,
+                                                                    const float* __restrict__ phase,
+                                                                    float* __restrict__ grad, float gvb, float ga,
+                                                                    float gb) {
+  constexpr int N = R * R;
+  constexpr int GPB = NT / R;          // rows per block
+  constexpr int RB = N / GPB;
+  constexpr int CH16 = N * GPB / 2;     // 16-B chunks per plane tile
+  constexpr int PER = CH16 / NT;
+  static_assert(CH16 % NT == 0, "chunking");
+  constexpr int SCR = GPB * R * (R + 1);   // padded transpose scratch reuses the tile
+  __shared__ float2 tw[N];
+  __shared__ __attribute__((aligned(16))) float2 tile[SCR > N * GPB ? SCR : N * GPB];
+
+  for (int i = threadIdx.x; i < N; i += NT) tw[i] = tw_glob[i];
+
+  const int grp = threadIdx.x / R;
+  const int t = threadIdx.x % R;
+  const int bid = xcd_pair<RB>(blockIdx.x);
+  const int rb = bid % RB;
+  const int j = bid / RB;
+  const JobDesc jb = jobs[j];
+  if (jb.env < 0) return;   // uniform per block
+  const int y0 = rb * GPB;
+  const int y = y0 + grp;
+  const hbx_window_t win = {0, 0, 0, 0};
+  const WinRow wr(win, y, t);   // (unread: no window form)
+  const int Q = P / 2;
+  constexpr size_t PLB = plane_b_elems(R);
+  const float2* jbase = ws_b + (size_t)j * P * PLB;
+
+  float4 pv[PER];   // this thread's share of the summed, recombined pair, one pair ahead
+  auto load_pair = [&](int q) {
+    const float2* a = jbase + (size_t)(2 * q) * PLB;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {   // depth 0, as k_rowinv_cplx combines it: B[2q] + i B[2q + 1]
+      const TileChunk ch = tile_chunk<NT, GPB>(i);
+      const float4 pa = ld_stream4(a + LayoutB<R>::at(ch.line, y0 + ch.r2));
+      const float4 pb = ld_stream4(a + PLB + LayoutB<R>::at(ch.line, y0 + ch.r2));
+      pv[i] = make_float4(pa.x - pb.y, pa.y + pb.x, pa.z - pb.w, pa.w + pb.z);
+    }
+#pragma unroll 1
+    for (int d = 1; d < D; ++d) {
+      const float2* ad = a + (size_t)d * dstride;
+#pragma unroll
+      for (int i = 0; i < PER; ++i) {
+        const TileChunk ch = tile_chunk<NT, GPB>(i);
+        const float4 pa = ld_stream4(ad + LayoutB<R>::at(ch.line, y0 + ch.r2));
+        const float4 pb = ld_stream4(ad + PLB + LayoutB<R>::at(ch.line, y0 + ch.r2));
+        pv[i].x += pa.x; pv[i].y += pa.y; pv[i].z += pa.z; pv[i].w += pa.w;
+        pv[i].x -= pb.y; pv[i].y += pb.x; pv[i].z -= pb.w; pv[i].w += pb.z;
+      }
+    }
+  };
+  load_pair(0);
+  const size_t row0 = (((size_t)jb.env * G + jb.group) * Q * N + y) * N + t;
+  float acc[1];
+
+#pragma unroll 1
+  for (int q = 0; q < Q; ++q) {
+    lds_barrier();  // previous plane's scratch use is over (also publishes tw)
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const TileChunk ch = tile_chunk<NT, GPB>(i);
+      tile[tile_pos<R, GPB>(ch.line, ch.r2)] = make_float2(pv[i].x, pv[i].y);
+      tile[tile_pos<R, GPB>(ch.line, ch.r2 + 1)] = make_float2(pv[i].z, pv[i].w);
+    }
+    if (q + 1 < Q) load_pair(q + 1);   // next pair's tiles in flight under this plane's FFT
+    lds_barrier();
+    pk2 v[R];
+#pragma unroll
+    for (int jj = 0; jj < R; ++jj) v[jj] = to_pk(tile[tile_pos<R, GPB>(t + R * jj, grp)]);
+    lds_barrier();  // tile consumed: reuse it as transpose scratch
+    fft_group<R, true>(v, t, PaddedScratch<R>{tile + grp * R * (R + 1)}, tw);
+    cplx_plane_out<R, R, false, GK, false>(v, acc, jb.env, jb.group, G, Q, q, y, row0, win, wr, field_out, real_out,
+                                           phase, grad, gvb, ga, gb);
+  }
+}
+
+// the stack kernels of N = R^2; gk: the output kind (pass_grad_kind), D = n_depths
+template <int R>
+static hipError_t launch_stack_last(const PlanDev& pd, const PassCall& c, int n_depths, int slot_stride,
+                                    hipStream_t st) {
+  constexpr int N = R * R;
+  constexpr int NT = kRowNT<R>;
+  constexpr int kRowBlocks = N / (NT / R);
+  auto pick = [](int gk) {
+    if constexpr (kTiledB<R>) {
+      auto k = k_rowinv_d_cplx_stack<R, kGradNone>;
+      if (gk == kGradPhase) k = k_rowinv_d_cplx_stack<R, kGradPhase>;
+      if (gk == kGradSteWindow) k = k_rowinv_d_cplx_stack<R, kGradSteWindow>;
+      if (gk == kGradSteSigmoid) k = k_rowinv_d_cplx_stack<R, kGradSteSigmoid>;
+      if (gk == kGradPhaseLevels) k = k_rowinv_d_cplx_stack<R, kGradPhaseLevels>;
+      return k;
+    } else {
+      auto k = k_rowinv_cplx_stack<R, NT, kGradNone>;
+      if (gk == kGradPhase) k = k_rowinv_cplx_stack<R, NT, kGradPhase>;
+      if (gk == kGradSteWindow) k = k_rowinv_cplx_stack<R, NT, kGradSteWindow>;
+      if (gk == kGradSteSigmoid) k = k_rowinv_cplx_stack<R, NT, kGradSteSigmoid>;
+      if (gk == kGradPhaseLevels) k = k_rowinv_cplx_stack<R, NT, kGradPhaseLevels>;
+      return k;
+    }
+  };
+  PassTimer* tm = pd.timer;
+  if (tm) tm->begin(2, st);
+  launch_kernel(pick(pass_grad_kind(c)), (unsigned)c.n_jobs * kRowBlocks, NT, st, c.jobs, pd.ws_b, pd.tw, pd.P, pd.G,
+                n_depths, (size_t)slot_stride * pd.P * plane_b_elems(R), c.complex_field, c.real_part, c.grad_samples,
+                c.grad_phase, pd.vb, pass_grad_p0(c), pass_grad_p1(c));
+  if (tm) tm->end(2, c.n_jobs, st);
+  return hipGetLastError();
+}
+
+hipError_t run_stack_last(const PlanDev& pd, const PassCall& c, int n_depths, int slot_stride, hipStream_t st) {
+  const hipError_t e = check_stack_last(pd, c, n_depths, slot_stride);
+  if (e != hipSuccess) return e;
+  switch (pd.R) {
+    case 0: return run_stack_last_896(pd, c, n_depths, slot_stride, st);
+    case 32: return launch_stack_last<32>(pd, c, n_depths, slot_stride, st);
+    case 16: return launch_stack_last<16>(pd, c, n_depths, slot_stride, st);
+    case 8: return launch_stack_last<8>(pd, c, n_depths, slot_stride, st);
     default: return hipErrorInvalidValue;
   }
 }

@@ -640,43 +640,112 @@ hipError_t run_jobs_896(const PlanDev& pd, const PassCall& c, hipStream_t st) {
   const PassTarget tg = pass_target(pd, c);
   const unsigned blocks = (unsigned)n_jobs * kRB;   // one workgroup per row block of a job
 
-  if (tm) tm->begin(0, st);
-  const bool win_in = pass_window_in(c, kN);
-  if (pass_complex(c)) {   // the load kind: complex samples as they are, times scale * weight, or exp(i pi phase)
-    const int lk = c.phase_values ? (c.phase_levels ? kLoadPhaseLevels : kLoadPhase) : c.complex_weight ? kLoadWeighted : kLoadComplex;
-    launch_kernel(pick_first_pass_cplx<SampleKernels896>(lk, win_in), blocks * (P / 2), 256, st, jobs, c.complex_values,
-                  pd.ws_a, pd.tw, P, CH, c.complex_weight, pass_first_scale(c), c.phase_values, pass_first_window(c));
-  } else if (c.real_values)
-    // the load kind: the samples as they are, or (hbx_evaluate_threshold) the field of the bit [x >= threshold]
-    launch_kernel(pick_first_pass_real<SampleKernels896>(c.real_binarize != 0, win_in), blocks * (P / 2), 256, st, jobs,
-                  c.real_values, pd.ws_a, pd.tw, P, CH, c.real_threshold, pd.va, pd.va + pd.vb, c.in_win);
-  else
-    launch_kernel(k_rowfwd896, blocks / kRit896 * (pair ? 1 : P / 2), 256, st, jobs,
-                  reinterpret_cast<const uint32_t*>(c.mask), pd.ws_a, pd.tw, P, CH, pd.va, pd.vb, pair);
-  if (tm) tm->end(0, n_jobs, st);
+  // (focal stacks) the call's job slot and pieces, as launch_passes has them
+  float2* const ws_a = pd.ws_a + (size_t)c.stack_slot0 * P * kPlaneA;
+  float2* const ws_b = pd.ws_b + (size_t)c.stack_slot0 * P * kPlaneB;
+  if (!c.stack_skip_first) {
+    if (tm) tm->begin(0, st);
+    const bool win_in = pass_window_in(c, kN);
+    if (pass_complex(c)) {   // the load kind: complex samples as they are, times scale * weight, or exp(i pi phase)
+      const int lk = c.phase_values ? (c.phase_levels ? kLoadPhaseLevels : kLoadPhase) : c.complex_weight ? kLoadWeighted : kLoadComplex;
+      launch_kernel(pick_first_pass_cplx<SampleKernels896>(lk, win_in), blocks * (P / 2), 256, st, jobs, c.complex_values,
+                    ws_a, pd.tw, P, CH, c.complex_weight, pass_first_scale(c), c.phase_values, pass_first_window(c));
+    } else if (c.real_values)
+      // the load kind: the samples as they are, or (hbx_evaluate_threshold) the field of the bit [x >= threshold]
+      launch_kernel(pick_first_pass_real<SampleKernels896>(c.real_binarize != 0, win_in), blocks * (P / 2), 256, st, jobs,
+                    c.real_values, ws_a, pd.tw, P, CH, c.real_threshold, pd.va, pd.va + pd.vb, c.in_win);
+    else
+      launch_kernel(k_rowfwd896, blocks / kRit896 * (pair ? 1 : P / 2), 256, st, jobs,
+                    reinterpret_cast<const uint32_t*>(c.mask), ws_a, pd.tw, P, CH, pd.va, pd.vb, pair);
+    if (tm) tm->end(0, n_jobs, st);
+  }
 
   if (tm) tm->begin(1, st);
-  launch_kernel(k_col896, (unsigned)n_jobs * (pair ? 2 : P) * kColLB, 256, st, jobs, pd.ws_a, pd.ws_b, pd.htab,
+  launch_kernel(k_col896, (unsigned)n_jobs * (pair ? 2 : P) * kColLB, 256, st, jobs, ws_a, ws_b, pass_htab(pd, c),
                 pd.tw, P, pair);
   if (tm) tm->end(1, n_jobs, st);
+  if (c.stack_skip_last) return hipGetLastError();
 
   if (tm) tm->begin(2, st);
   if (pass_complex(c)) {   // recombine each plane pair, or a leaf's gradient instead (pick_last_pass_cplx)
     const auto k = pick_last_pass_cplx<SampleKernels896>(pass_grad_kind(c), c.complex_stats != 0,
                                                          c.windowed != 0);
-    launch_kernel(k, blocks, 256, st, jobs, pd.ws_b, pd.tw, P, pd.G, c.complex_field, c.real_part, tg.rows, tg.mask,
+    launch_kernel(k, blocks, 256, st, jobs, ws_b, pd.tw, P, pd.G, c.complex_field, c.real_part, tg.rows, tg.mask,
                   pd.partial, c.inten_out, c.grad_samples, c.grad_phase, pd.vb, pass_grad_p0(c), pass_grad_p1(c), c.out_win);
   } else {
     // (r06) the plain FFT-mode launch gets the lean instantiation (profiles/r06/rowinv896_lean_ab_r06i.txt)
     const bool lean = c.plane_mode == kPlanesOff && !c.field_out;
     launch_kernel(!c.windowed ? (lean ? k_rowinv896<true> : k_rowinv896<false>)
                               : (lean ? k_rowinv896<true, true> : k_rowinv896<false, true>),
-                  blocks, 256, st, jobs, pd.ws_b, tg.rows, pd.tw, P, pd.G, pd.partial, c.inten_out, c.field_out, tg.mask,
+                  blocks, 256, st, jobs, ws_b, tg.rows, pd.tw, P, pd.G, pd.partial, c.inten_out, c.field_out, tg.mask,
                   c.inten_by_env, c.plane_mode, c.plane_pool, c.plane_slot, c.plane_spares, c.spare_base, c.out_win);
   }
   if (tm) tm->end(2, n_jobs, st);
   if (pass_reduces(c))   // (skip_reduce is refused at 896: check_pass_call)
     hipLaunchKernelGGL(k_reduce_partials, dim3(n_jobs), dim3(64), 0, st, pd.partial, n_jobs, kRB, pd.job_stats);
+  return hipGetLastError();
+}
+
+// Focal stacks (hbx_backward_stack, EXTENSION): k_rowinv896_cplx with the pair summed over the D depth slots of
+// ws_b as it is loaded (rowinv_load_pair_stack, hbx_rowinv.hpp; hbx_passes.hip has the account), one inverse FFT
+// per complex plane, the gradient written once.  No statistics or window form; an argument list of its own,
+// behind every other kernel of this file.
+template <int GK = kGradNone>
+__global__ __launch_bounds__(256, 2) void k_rowinv896_cplx_stack(const JobDesc* __restrict__ jobs,
+                                                                 const float2* __restrict__ ws_b,
+                                                                 const float2* __restrict__ tw_glob, int P, int G,
+                                                                 int D, size_t dstride,
+                                                                 float2* __restrict__ field_out,
+                                                                 float* __restrict__ real_out,
+                                                                 const float* __restrict__ phase,
+                                                                 float* __restrict__ grad, float gvb, float ga,
+                                                                 float gb) {
+  __shared__ float2 tw[kN];
+  __shared__ float2 scratch[kSCR];
+  for (int i = threadIdx.x; i < kN; i += 256) tw[i] = tw_glob[i];
+
+  const int grp = threadIdx.x / kR;
+  const int t = threadIdx.x % kR;
+  const int bid = xcd_pair<kRB>(blockIdx.x);
+  const int rb = bid % kRB;
+  const int j = bid / kRB;
+  const JobDesc jb = jobs[j];
+  if (jb.env < 0) return;   // uniform per block
+  const int y = rb * kGPB + grp;
+  const hbx_window_t win = {0, 0, 0, 0};
+  const WinRow wr(win, y, t);   // (unread: no window form)
+  const int Q = P / 2;                            // complex planes per group
+  const float2* job_b = ws_b + (size_t)j * P * kPlaneB;
+  const unsigned job_bytes = (unsigned)((size_t)P * kPlaneB * 8);
+  const Rowinv896Lanes ln(y, t);
+  const PaddedScratch<kR> sc{scratch + grp * kR * (kR + 1)};
+  const size_t row0 = (((size_t)jb.env * G + jb.group) * Q * kN + y) * kN + t;   // complex plane 0, pixel x = t
+  float acc[1];
+  float2 v[32];
+  rowinv_load_pair_stack(v, ln, job_b, dstride, job_bytes, D, 0);
+  __syncthreads();  // tw visible
+#pragma unroll 1
+  for (int q = 0; q < Q; ++q) {
+    fft896_sn<true, kInvScalar>(v, t, sc, tw);      // slot layout in, natural out: x = t + 32 k
+    cplx_plane_out<kR, kL, false, GK, false>(v, acc, jb.env, jb.group, G, Q, q, y, row0, win, wr, field_out, real_out,
+                                             phase, grad, gvb, ga, gb);
+    if (q + 1 < Q) rowinv_load_pair_stack(v, ln, job_b, dstride, job_bytes, D, q + 1);   // uniform
+  }
+}
+
+hipError_t run_stack_last_896(const PlanDev& pd, const PassCall& c, int n_depths, int slot_stride, hipStream_t st) {
+  const int gk = pass_grad_kind(c);
+  auto k = k_rowinv896_cplx_stack<kGradNone>;
+  if (gk == kGradPhase) k = k_rowinv896_cplx_stack<kGradPhase>;
+  if (gk == kGradSteWindow) k = k_rowinv896_cplx_stack<kGradSteWindow>;
+  if (gk == kGradSteSigmoid) k = k_rowinv896_cplx_stack<kGradSteSigmoid>;
+  if (gk == kGradPhaseLevels) k = k_rowinv896_cplx_stack<kGradPhaseLevels>;
+  PassTimer* tm = pd.timer;
+  if (tm) tm->begin(2, st);
+  launch_kernel(k, (unsigned)c.n_jobs * kRB, 256, st, c.jobs, pd.ws_b, pd.tw, pd.P, pd.G, n_depths,
+                (size_t)slot_stride * pd.P * kPlaneB, c.complex_field, c.real_part, c.grad_samples, c.grad_phase, pd.vb,
+                pass_grad_p0(c), pass_grad_p1(c));
+  if (tm) tm->end(2, c.n_jobs, st);
   return hipGetLastError();
 }
 

@@ -1,7 +1,9 @@
 // hbx_rowinv.hpp -- the pieces the last-pass kernels share across size classes (hbx_passes.hip:
 // k_rowinv_d, k_rowinv and their _cplx forms; hbx_passes896.hip: k_rowinv896, k_rowinv896_cplx):
 // invalid-job exit, the direct loads from the tiled B and the pair-combining load, the chunk decode
-// of the N = 64 tile, the plane cache and its step schedule, the bit path's per-plane outputs and the tail.
+// of the N = 64 tile, the plane cache and its step schedule, the bit path's per-plane outputs and the tail;
+// and, for the depth-summing last passes of a focal stack (k_rowinv_d_cplx_stack, k_rowinv_cplx_stack,
+// k_rowinv896_cplx_stack), the pair load that adds the depth slots: rowinv_load_pair_stack.
 // <int R, int L = R> as real_load_row: R lanes per group, L values per lane, N = R L (N = 896 is
 // <32, 28>).  The block prologue (twiddle staging, the grp / t / rb / j decode) stays
 // written out in the six kernels: as a helper it changed the code of every one of them (the group's
@@ -100,6 +102,46 @@ __device__ __forceinline__ void rowinv_load_pair(V (&v)[Lanes::kRegs], const Lan
     for (int k = 0; k < H; ++k) {
       v[h * H + k].x -= w[k].y;
       v[h * H + k].y += w[k].x;
+    }
+  }
+}
+
+// Focal stacks (hbx_backward_stack): the job's pair q summed over D depths whose B slots lie dstride float2
+// apart, v = (((B_0[2q] + i B_0[2q + 1]) + B_1[2q]) + i B_1[2q + 1]) + ... in float32, d ascending.  Depth 0
+// is rowinv_load_pair itself -- the running line starts from its value, never from 0.0f, so D = 1 gives the
+// single-depth bits (the sign of a zero included) -- and every further plane arrives in halves of kRegs / 2
+// values that are added as they land: v and half a line are live, as in rowinv_load_pair.  A job's planes are
+// addressed through a descriptor of its own per depth (the stride between depths can pass 4 GiB).
+template <class Lanes, class V>
+__device__ __forceinline__ void rowinv_load_pair_stack(V (&v)[Lanes::kRegs], const Lanes& ln, const float2* job_b,
+                                                       size_t dstride, unsigned job_bytes, int D, int q) {
+  rowinv_load_pair(v, ln, plane_rsrc(job_b, job_bytes), q);
+  constexpr int H = Lanes::kRegs / 2;
+  const int po = 2 * q * Lanes::kPlaneBytes;
+#pragma unroll 1
+  for (int d = 1; d < D; ++d) {
+    const __amdgpu_buffer_rsrc_t rs = plane_rsrc(job_b + (size_t)d * dstride, job_bytes);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      float2 w[H];
+#pragma unroll
+      for (int k = 0; k < H; ++k) w[k] = ln.load(rs, po, h * H + k);
+#pragma unroll
+      for (int k = 0; k < H; ++k) {
+        v[h * H + k].x += w[k].x;
+        v[h * H + k].y += w[k].y;
+      }
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      float2 w[H];
+#pragma unroll
+      for (int k = 0; k < H; ++k) w[k] = ln.load(rs, po + Lanes::kPlaneBytes, h * H + k);
+#pragma unroll
+      for (int k = 0; k < H; ++k) {
+        v[h * H + k].x -= w[k].y;
+        v[h * H + k].y += w[k].x;
+      }
     }
   }
 }

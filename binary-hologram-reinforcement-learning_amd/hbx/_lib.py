@@ -31,6 +31,8 @@ PACK_BINARY, PACK_THRESHOLD = 0, 1
 REL_WORKSPACE_DOUBLES = 3072
 LOSS_MSE, LOSS_PSNR = 0, 1                      # hbx_loss / hbx_loss_weight kinds
 STE_WINDOW, STE_SIGMOID = 0, 1                  # hbx_threshold_backward surrogates
+MAX_DEPTHS = 8                                  # hbx_plan_set_depths: depths of a focal stack
+LEAF_REAL, LEAF_THRESHOLD, LEAF_COMPLEX, LEAF_PHASE, LEAF_PHASE_LEVELS = 0, 1, 2, 3, 4   # hbx_leaf_t.kind
 
 EXPORTED_SYMBOLS = (
     "hbx_abi_version", "hbx_last_error", "hbx_plan_create", "hbx_plan_destroy",
@@ -49,6 +51,8 @@ EXPORTED_SYMBOLS = (
     "hbx_evaluate_real_window", "hbx_evaluate_threshold_window", "hbx_backward_window",
     "hbx_loss_window", "hbx_loss_weight_window",
     "hbx_simulate_phase_levels", "hbx_evaluate_phase_levels", "hbx_phase_levels_backward", "hbx_quantize_phase",
+    "hbx_plan_set_depths", "hbx_plan_depths", "hbx_evaluate_stack", "hbx_backward_stack",
+    "hbx_loss_stack", "hbx_loss_weight_stack",
 )
 NUM_PASSES = 5
 PASS_NAMES = ("k_rowfwd", "k_col", "k_rowinv", "k_psf_eval", "k_psf_commit")
@@ -77,6 +81,12 @@ class Optics(C.Structure):
 class Window(C.Structure):
     """hbx_window_t (include/hbx.h): a rectangle (y0, x0, h, w) of the plan's N x N grid."""
     _fields_ = [("y0", C.c_int32), ("x0", C.c_int32), ("h", C.c_int32), ("w", C.c_int32)]
+
+
+class Leaf(C.Structure):
+    """hbx_leaf_t (include/hbx.h): the leaf kind of a focal-stack call and its parameters."""
+    _fields_ = [("kind", C.c_int32), ("levels", C.c_int32), ("threshold", C.c_float), ("surrogate", C.c_int32),
+                ("p0", C.c_float), ("p1", C.c_float)]
 
 
 class DbsWalk(C.Structure):
@@ -163,6 +173,13 @@ def _declare(lib):
     lib.hbx_loss_window.argtypes = [VP, VP, WP, I32, I32, I32, VP, VP]
     lib.hbx_loss_weight_window.argtypes = [VP, VP, VP, VP, VP, WP, I32, I32, I32, VP, VP]
     lib.hbx_loss.argtypes = [VP, VP, I32, I32, I32, VP, VP]
+    LP = C.POINTER(Leaf)
+    lib.hbx_plan_set_depths.argtypes = [VP, C.POINTER(C.c_double), I32]
+    lib.hbx_plan_depths.argtypes = [VP]
+    lib.hbx_evaluate_stack.argtypes = [VP, VP, LP, VP, I32, VP, VP, VP, VP]
+    lib.hbx_backward_stack.argtypes = [VP, VP, VP, C.c_float, LP, VP, I32, VP, VP, VP]
+    lib.hbx_loss_stack.argtypes = [VP, VP, I32, I32, I32, VP, VP]
+    lib.hbx_loss_weight_stack.argtypes = [VP, VP, VP, VP, VP, I32, I32, I32, VP, VP]
     lib.hbx_loss_weight.argtypes = [VP, VP, VP, VP, VP, I32, I32, I32, VP, VP]
     lib.hbx_flip_map.argtypes = [VP, VP, VP, VP, VP, VP]
     lib.hbx_eval_flips_psf.argtypes = [VP, VP, VP, VP, VP, VP, VP, I32, VP, VP, VP]

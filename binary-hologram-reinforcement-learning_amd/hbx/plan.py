@@ -685,6 +685,133 @@ class Plan:
                                             _stream(stream)), "hbx_loss_weight")
         return weight
 
+    # --- focal stacks (hbx_*_stack): one hologram at D depths, depth-major arrays [D, B, ...] ---
+    def set_depths(self, zs):
+        """The depths of this plan's focal stack (hbx_plan_set_depths): a sequence of 1 to 8 finite
+        distances, or an empty one to free the tables.  Depth d's transfer-function table is that of
+        a plan created with z = zs[d], bit for bit; the plan's own z and every other call are
+        untouched.  Synchronises; not for use with work of this plan in flight."""
+        zs = tuple(float(v) for v in zs)
+        if len(zs) > _lib.MAX_DEPTHS:
+            raise ValueError(f"set_depths: at most {_lib.MAX_DEPTHS} depths, got {len(zs)}")
+        if not all(math.isfinite(v) for v in zs):
+            raise ValueError(f"set_depths: every depth must be finite, got {zs!r}")
+        arr = (C.c_double * max(len(zs), 1))(*zs)
+        with torch.cuda.device(self.device_index):
+            _lib.check(self.lib.hbx_plan_set_depths(self._h, arr, len(zs)), "hbx_plan_set_depths")
+        self.generation += 1
+
+    @property
+    def depths(self) -> int:
+        """hbx_plan_depths: the number of depths set (0: none)."""
+        rc = int(self.lib.hbx_plan_depths(self._h))
+        if rc < 0:
+            _lib.check(rc, "hbx_plan_depths")
+        return rc
+
+    def _leaf(self, kind: int, levels=None, threshold: float = 0.0, surrogate: int = _lib.STE_WINDOW,
+              p0: float = -math.inf, p1: float = math.inf) -> _lib.Leaf:
+        if kind not in (_lib.LEAF_REAL, _lib.LEAF_THRESHOLD, _lib.LEAF_COMPLEX, _lib.LEAF_PHASE, _lib.LEAF_PHASE_LEVELS):
+            raise ValueError(f"leaf kind must be one of hbx._lib.LEAF_*, got {kind!r}")
+        lv = _levels(levels) if kind == _lib.LEAF_PHASE_LEVELS else 0
+        return _lib.Leaf(int(kind), lv, float(threshold), int(surrogate), float(p0), float(p1))
+
+    def evaluate_stack(self, values: torch.Tensor, kind: int, target: Optional[torch.Tensor] = None,
+                       want_field: bool = True, want_intensity: bool = True, levels=None, threshold: float = 0.0,
+                       stream=None):
+        """The single-depth evaluate call of leaf kind `kind` (hbx._lib.LEAF_*) at every depth of the
+        stack, with the first pass run once (hbx_evaluate_stack).  `values` as that call takes them
+        ([B, CH, H, W] float32 for LEAF_REAL / LEAF_THRESHOLD, [B, CH/2, H, W] complex64 for
+        LEAF_COMPLEX, float32 for the phase kinds); `target` float32 [D, B, G, H, W] or None.
+        Returns (field complex64 [D, B, C, H, W] | None, intensity float32 [D, B, G, H, W] | None,
+        chan_stats float64 [D, B, G, 3] | None); depth d of each equals the single-depth call's on a
+        plan for zs[d] bit for bit."""
+        leaf = self._leaf(kind, levels, threshold)
+        n = values.shape[0] if isinstance(values, torch.Tensor) and values.dim() else 0
+        c = self.cfg
+        d = self.depths
+        real_in = kind in (_lib.LEAF_REAL, _lib.LEAF_THRESHOLD)
+        planes = c.channels if real_in else c.channels // 2
+        shape = (n, planes, c.height, c.width)
+        _need(values, "values", torch.complex64 if kind == _lib.LEAF_COMPLEX else torch.float32, shape, self.device)
+        values = values.resolve_conj().resolve_neg() if kind == _lib.LEAF_COMPLEX else values.resolve_neg()
+        tshape = (d,) + tuple(self.target_shape(n))
+        if target is not None:
+            _need(target, "target", torch.float32, tshape, self.device)
+        elif not want_intensity and not (real_in and want_field):
+            raise ValueError("evaluate_stack: no target, and nothing else asked for that the call can write alone")
+        field = torch.empty((d,) + shape + (2,), dtype=torch.float32, device=self.device) if want_field else None
+        inten = torch.empty(tshape, dtype=torch.float32, device=self.device) if want_intensity else None
+        stats = torch.empty((d, n, c.groups, 3), dtype=torch.float64, device=self.device) if target is not None else None
+        _lib.check(self.lib.hbx_evaluate_stack(self._h, _ptr(values), C.byref(leaf), _ptr(target), n, _ptr(field),
+                                               _ptr(inten), _ptr(stats), _stream(stream)), "hbx_evaluate_stack")
+        return (torch.view_as_complex(field) if want_field else None), inten, stats
+
+    def backward_stack(self, values: torch.Tensor, kind: int, samples: Optional[torch.Tensor] = None,
+                       weight: Optional[torch.Tensor] = None, scale: float = 1.0, levels=None,
+                       surrogate: int = _lib.STE_WINDOW, p0: float = -math.inf, p1: float = math.inf,
+                       stream=None) -> torch.Tensor:
+        """The backward pass of a leaf under a loss over the stack, on the plan whose depths are the
+        negated ones (hbx_backward_stack): `values` complex64 [D, B, CH/2, H, W] (per depth the
+        gradient with respect to the field or, with `weight` float32 [D, B, G, H, W], the saved
+        field), one depth-summing last pass, and the one output without a depth: complex64
+        [B, CH/2, H, W] for LEAF_COMPLEX, else float32 [B, CH/2, H, W] -- the real part (LEAF_REAL),
+        `phase_backward`'s, `phase_levels_backward`'s or `threshold_backward`'s gradient of the
+        summed field, from `samples` float32 [B, CH/2, H, W] (the leaf's x) as those calls use it."""
+        leaf = self._leaf(kind, levels, 0.0, surrogate, p0, p1)
+        n = values.shape[1] if isinstance(values, torch.Tensor) and values.dim() > 1 else 0
+        c = self.cfg
+        d = self.depths
+        shape = self.phase_shape(n)
+        _need(values, "values", torch.complex64, (d,) + tuple(shape), self.device)
+        values = values.resolve_conj().resolve_neg()
+        needs = kind in (_lib.LEAF_PHASE, _lib.LEAF_PHASE_LEVELS, _lib.LEAF_THRESHOLD)
+        if needs != (samples is not None):
+            raise ValueError("backward_stack: samples are the leaf of a phase, L-level or thresholded leaf, else None")
+        if samples is not None:
+            _need(samples, "samples", torch.float32, shape, self.device)
+            samples = samples.resolve_neg()
+        if weight is not None:
+            _need(weight, "weight", torch.float32, (d,) + tuple(self.target_shape(n)), self.device)
+            weight = weight.resolve_neg()
+        cplx = kind == _lib.LEAF_COMPLEX
+        out = torch.empty(tuple(shape) + ((2,) if cplx else ()), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.hbx_backward_stack(self._h, _ptr(values), _ptr(weight), float(scale), C.byref(leaf),
+                                               _ptr(samples), n, _ptr(out) if cplx else None,
+                                               None if cplx else _ptr(out), _stream(stream)), "hbx_backward_stack")
+        return torch.view_as_complex(out) if cplx else out
+
+    def loss_stack(self, chan_stats: torch.Tensor, kind: int = _lib.LOSS_MSE, rel_scale: int = _lib.REL_LSQ,
+                   stream=None) -> torch.Tensor:
+        """chan_stats [D, B, G, 3] -> `loss` per env over the whole stack, float64 [B] (hbx_loss_stack):
+        the sums run over an env's D G channels, n = D G H W, one least-squares scale per env."""
+        n = chan_stats.shape[1] if isinstance(chan_stats, torch.Tensor) and chan_stats.dim() > 1 else 0
+        _need(chan_stats, "chan_stats", torch.float64, (self.depths, n, self.cfg.groups, 3), self.device)
+        out = torch.empty((n,), dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.hbx_loss_stack(self._h, _ptr(chan_stats), n, int(kind), int(rel_scale), _ptr(out),
+                                           _stream(stream)), "hbx_loss_stack")
+        return out
+
+    def loss_weight_stack(self, intensity: torch.Tensor, target: torch.Tensor, chan_stats: torch.Tensor,
+                          grad_loss: Optional[torch.Tensor] = None, kind: int = _lib.LOSS_MSE,
+                          rel_scale: int = _lib.REL_LSQ, stream=None) -> torch.Tensor:
+        """`loss_stack`'s gradient with respect to the intensity, float32 [D, B, G, H, W]
+        (hbx_loss_weight_stack): grad_loss[b] * d loss_b / d intensity[:, b] = a_b I + c_b T, one
+        (a_b, c_b) per env for all depths; grad_loss float64 [B] or None (ones)."""
+        n = intensity.shape[1] if isinstance(intensity, torch.Tensor) and intensity.dim() > 1 else 0
+        d = self.depths
+        tshape = (d,) + tuple(self.target_shape(n))
+        _need(intensity, "intensity", torch.float32, tshape, self.device)
+        _need(target, "target", torch.float32, tshape, self.device)
+        _need(chan_stats, "chan_stats", torch.float64, (d, n, self.cfg.groups, 3), self.device)
+        if grad_loss is not None:
+            _need(grad_loss, "grad_loss", torch.float64, (n,), self.device)
+        weight = torch.empty(tshape, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.hbx_loss_weight_stack(self._h, _ptr(intensity), _ptr(target), _ptr(chan_stats),
+                                                  _ptr(grad_loss), n, int(kind), int(rel_scale), _ptr(weight),
+                                                  _stream(stream)), "hbx_loss_weight_stack")
+        return weight
+
     # --- windows (hbx_*_window): holograms of any size zero-filled into the grid, outputs over a rectangle ---
     def window(self, win):
         """(y0, x0, h, w) | None -> (the _lib.Window to pass, or None for the full grid, and its

@@ -84,7 +84,8 @@ from hbx import _lib
 
 from . import metrics as _metrics
 
-__all__ = ["Tensor", "simulate", "intensity", "loss", "relativeLoss", "imread", "check_binary"]
+__all__ = ["Tensor", "simulate", "intensity", "loss", "relativeLoss", "imread", "check_binary",
+           "simulate_stack", "intensity_stack", "loss_stack"]
 
 
 class Tensor(torch.Tensor):
@@ -134,17 +135,25 @@ def _switch(value, names: Dict[str, int], what: str) -> int:
 
 
 def _plan_for(h: int, w: int, planes: int, wl, dx: float, dy: float, z: float, n: int, dev: int,
-              tf: int = _lib.TF_ASM, field: int = _lib.FIELD_AMPLITUDE):
+              tf: int = _lib.TF_ASM, field: int = _lib.FIELD_AMPLITUDE, depths: Tuple[float, ...] = (),
+              depth_slots: bool = False):
     """The cached plan of `planes` real planes per group; wl: one wavelength, or a tuple of G (one
-    colour group each, tt.intensity); n: envs per launch (the plan holds n * G jobs)."""
+    colour group each, tt.intensity); n: envs per launch (the plan holds n * G jobs).  depths: the
+    focal stack's distances (the *_stack calls; part of the cache key), or () for no stack.
+    depth_slots: the plan runs a stack's backward pass, whose chunk of n envs takes n * G * D job
+    slots (the forward reuses its workspace from depth to depth and takes n * G)."""
     wls = tuple(float(v) for v in wl) if isinstance(wl, (tuple, list)) else (float(wl),)
     groups = len(wls)
-    key = (h, w, groups, planes, wls, float(dx), float(dy), float(z), dev, tf, field)
+    depths = tuple(float(v) for v in depths)
+    key = (h, w, groups, planes, wls, float(dx), float(dy), float(z), dev, tf, field, depths)
+    jobs = max(n, 1) * groups * (max(len(depths), 1) if depth_slots else 1)
     p = _PLANS.get(key)
-    if p is None or p.max_jobs < n * groups:
+    if p is None or p.max_jobs < jobs:
         cfg = hbx.OpticsConfig(h, w, groups, planes, wls, float(dx), float(dy), float(z),
                                tf, field, _lib.REL_LSQ, 1.0)
-        p = hbx.Plan(cfg, max_jobs=max(n, 1) * groups, device=dev)
+        p = hbx.Plan(cfg, max_jobs=jobs, device=dev)
+        if depths:
+            p.set_depths(depths)
         _PLANS[key] = p
     return p
 
@@ -1219,6 +1228,264 @@ def loss(x, target, z: float, metric="mse", rel_scale="lsq", tf="asm", field="am
     else:
         plan, _, _, stats = _evaluate(t, tg, geom, groups, False, phase)
         out = plan.loss(stats, kind, rel)
+    return out[0] if squeeze else out
+
+
+# ---------------------------------------------------------------------------------------------
+# Focal stacks: one hologram propagated to D depths (hbx_*_stack), outputs depth-major [D, B, ...]
+# ---------------------------------------------------------------------------------------------
+def _depths_arg(zs, what: str) -> Tuple[float, ...]:
+    """zs of the *_stack calls -> a tuple of 1 to 8 finite floats; anything else raises ValueError."""
+    try:
+        out = tuple(float(v) for v in zs)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: zs is a sequence of depths (numbers), got {zs!r}") from None
+    if not 1 <= len(out) <= _lib.MAX_DEPTHS:
+        raise ValueError(f"{what}: 1 to {_lib.MAX_DEPTHS} depths, got {len(out)}")
+    if not all(np.isfinite(v) for v in out):
+        raise ValueError(f"{what}: every depth must be finite, got {out!r}")
+    return out
+
+
+class _StackSpec:
+    """What a *_stack call fixed before any GPU use: geometry, depths, the leaf kind and its parameters."""
+
+    def __init__(self, wls, dx, dy, tf_kind, zs, leaf, field_kind, ste_args, levels):
+        self.wls, self.dx, self.dy, self.tf_kind, self.zs, self.leaf = wls, dx, dy, tf_kind, zs, leaf
+        self.field_kind, self.ste_args, self.levels = field_kind, ste_args, levels
+        self.groups = len(wls)
+        self.dev = None                  # the device index, set once the input is on it (_stack_device)
+
+    def forward_plan(self, x):
+        b, c, h, w = x.shape
+        real_in = self.leaf in (_lib.LEAF_REAL, _lib.LEAF_THRESHOLD)
+        planes = (c if real_in else 2 * c) // self.groups
+        fk = self.field_kind if self.leaf == _lib.LEAF_THRESHOLD else _lib.FIELD_AMPLITUDE
+        return _plan_for(h, w, planes, self.wls, self.dx, self.dy, self.zs[0], b, self.dev, self.tf_kind, fk, self.zs)
+
+    def adjoint_plan(self, x):
+        """The plan for the negated depths, 2 C / G real planes per group (C complex ones), with the
+        leaf's field kind (its vb) for a thresholded leaf; B G D job slots, one chunk of the backward."""
+        b, c, h, w = x.shape
+        fk = self.field_kind if self.leaf == _lib.LEAF_THRESHOLD else _lib.FIELD_AMPLITUDE
+        nz = tuple(-v for v in self.zs)
+        return _plan_for(h, w, 2 * c // self.groups, self.wls, self.dx, self.dy, nz[0], b, self.dev, self.tf_kind, fk, nz,
+                         depth_slots=True)
+
+    def evaluate(self, x, target=None, want_field=True, want_intensity=True):
+        tau = self.ste_args[0] if self.ste_args is not None else 0.0
+        plan = self.forward_plan(x)
+        return (plan,) + plan.evaluate_stack(x, self.leaf, target, want_field=want_field, want_intensity=want_intensity,
+                                             levels=self.levels, threshold=tau)
+
+    def backward(self, x, values, weight=None, scale=1.0):
+        """One hbx_backward_stack: the leaf's gradient summed over the depths."""
+        kw = {}
+        if self.leaf == _lib.LEAF_THRESHOLD:
+            _, kw["surrogate"], kw["p0"], kw["p1"] = self.ste_args
+        needs = self.leaf in (_lib.LEAF_PHASE, _lib.LEAF_PHASE_LEVELS, _lib.LEAF_THRESHOLD)
+        return self.adjoint_plan(x).backward_stack(values, self.leaf, samples=x if needs else None, weight=weight,
+                                                   scale=scale, levels=self.levels, **kw)
+
+
+class _SimulateStack(torch.autograd.Function):
+    """x -> the fields A(z_d) u(x) of every depth, complex64 [D, B, C, H, W] (hbx_evaluate_stack).
+    Backward: one hbx_backward_stack of grad_output on the plan for the negated depths, whose last
+    pass sums the D adjoint propagations and writes the leaf's gradient once.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, x, spec):
+        ctx.spec = spec
+        ctx.save_for_backward(x)
+        return spec.evaluate(x)[1]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        x, = ctx.saved_tensors
+        g = grad_output.to(torch.complex64).resolve_conj().resolve_neg().contiguous()
+        return ctx.spec.backward(x, g), None
+
+
+class _IntensityStack(torch.autograd.Function):
+    """x -> the plane-mean intensities of every depth, float32 [D, B, G, H, W], the per-depth fields
+    saved.  Backward: hbx_backward_stack of the saved fields with (2 / P) grad_output applied in the
+    first passes' loads.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, x, spec):
+        ctx.spec = spec
+        _, field, inten, _ = spec.evaluate(x)
+        ctx.save_for_backward(x, field)
+        return inten
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        x, field = ctx.saved_tensors
+        gi = grad_output.to(torch.float32).resolve_neg().contiguous()
+        return ctx.spec.backward(x, field, weight=gi, scale=2.0 / (x.shape[1] // ctx.spec.groups)), None
+
+
+class _LossStack(torch.autograd.Function):
+    """x -> the relative MSE or PSNR per env over the whole stack (hbx_evaluate_stack, hbx_loss_stack),
+    the per-depth fields, intensities and statistics saved.  Backward: hbx_loss_weight_stack (a I + c T
+    with one (a, c) per env for all depths), then one hbx_backward_stack.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, x, target, spec, kind, rel):
+        ctx.spec, ctx.kind, ctx.rel = spec, kind, rel
+        plan, field, inten, stats = spec.evaluate(x, target)
+        ctx.save_for_backward(x, field, inten, stats, target)
+        return plan.loss_stack(stats, kind, rel)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        x, field, inten, stats, target = ctx.saved_tensors
+        spec = ctx.spec
+        gl = grad_output.to(torch.float64).resolve_neg().contiguous()
+        wgt = spec.adjoint_plan(x).loss_weight_stack(inten, target, stats, gl, ctx.kind, ctx.rel)
+        grad = spec.backward(x, field, weight=wgt, scale=2.0 / (x.shape[1] // spec.groups))
+        return grad, None, None, None, None
+
+
+def _stack_args(x, zs, tf, field, threshold, ste, ste_width, levels, grid, origin, roi, what: str):
+    """The checks every *_stack call makes before any GPU use -> (t [B, C, H, W], the _StackSpec without
+    its device, whether x was 3-D)."""
+    if grid is not None or origin is not None or roi is not None:
+        raise ValueError(f"{what}: grid=, origin= and roi= are not accepted (focal stacks are not windowed)")
+    zs = _depths_arg(zs, what)
+    tf_kind = _switch(tf, _TF_NAMES, "tf")
+    field_kind = _switch(field, _FIELD_NAMES, "field")
+    ste_args = _ste_args(threshold, ste, ste_width, what)
+    meta = _meta_of(x)
+    wl = meta["wl"]
+    wls = tuple(float(v) for v in wl) if isinstance(wl, (tuple, list)) else (float(wl),)
+    groups = len(wls)
+    if not 1 <= groups <= _lib.MAX_GROUPS:
+        raise ValueError(f"{what}: 1 to {_lib.MAX_GROUPS} wavelengths, got {groups}")
+    dx, dy = meta.get("dx", (hbx.plan.PIXEL_PITCH,) * 2)
+    t = x.as_subclass(torch.Tensor) if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+    squeeze = t.dim() == 3
+    if squeeze:
+        t = t.unsqueeze(0)
+    if t.dim() != 4:
+        raise ValueError(f"{what} expects [B, C, H, W] or [C, H, W], got {tuple(t.shape)}")
+    c = t.shape[1]
+    if c == 0 or c % groups:
+        raise ValueError(f"{what}: {c} planes do not split into {groups} colour groups")
+    if t.is_complex() and field_kind != _lib.FIELD_AMPLITUDE:
+        raise ValueError(f"{what}: a complex field is used as it is (field=\"amplitude\")")
+    if ste_args is not None and t.is_complex():
+        raise ValueError(f"{what}: threshold= needs a real leaf, got a complex field")
+    levels = _levels_arg(levels, False, t.is_complex(), field_kind, ste_args is not None, None, what)
+    if t.is_complex():
+        leaf = _lib.LEAF_COMPLEX
+    elif ste_args is not None:
+        leaf = _lib.LEAF_THRESHOLD
+    elif levels is not None:
+        leaf = _lib.LEAF_PHASE_LEVELS
+    elif field_kind == _lib.FIELD_PHASE:
+        leaf = _lib.LEAF_PHASE
+    else:
+        leaf = _lib.LEAF_REAL
+    if leaf in (_lib.LEAF_REAL, _lib.LEAF_THRESHOLD) and (c // groups) % 2:
+        raise ValueError(f"{what}: a real or thresholded leaf needs an even number of planes per colour group, "
+                         f"got {c // groups}")
+    if t.shape[2] != t.shape[3] or t.shape[2] not in _GRIDS:
+        raise ValueError(f"{what}: the hologram is one of the built grids {_GRIDS} squared, got {tuple(t.shape[2:])}")
+    return t, _StackSpec(wls, dx, dy, tf_kind, zs, leaf, field_kind, ste_args, levels), squeeze
+
+
+def _stack_device(t, spec):
+    """The device tensor the kernels read (by torch ops: autograd carries the casts back); names the
+    device in the spec."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("tt.*_stack needs a ROCm GPU (libhbx.so)")
+    if t.is_cuda:
+        dev = t.device.index
+    else:
+        dev = torch.cuda.current_device()
+        t = t.to(f"cuda:{dev}")
+    spec.dev = dev
+    if spec.leaf == _lib.LEAF_COMPLEX:
+        return t.to(torch.complex64).resolve_conj().resolve_neg().contiguous()
+    return _phase_samples(t)
+
+
+def simulate_stack(x, zs, tf="asm", field="amplitude", threshold=None, ste="window", ste_width=0.5, levels=None,
+                   grid=None, origin=None, roi=None) -> torch.Tensor:
+    """The propagated field of one hologram at every depth of `zs` (1 to 8 distances, repeats and
+    negative values allowed): complex64 [D, B, C, H, W] ([D, C, H, W] for a 3-D x), depth d what
+    ``tt.simulate(x, zs[d], binary=False, ...)`` returns, from ONE first pass, D column passes and D
+    last passes (hbx_evaluate_stack).  x, tf, field, threshold / ste / ste_width and levels are the
+    continuous path's as in simulate, intensity and loss: a real field, a complex field, a phase
+    (field="phase"), an L-level phase (levels=) or the real leaf of a binary hologram (threshold=);
+    a real or thresholded leaf needs an even number of planes per colour group.  If x requires grad
+    the backward pass is one hbx_backward_stack on the plan for the negated depths, whose last pass
+    adds the D adjoint propagations as it loads them and writes the leaf's gradient once.  grid=,
+    origin= and roi= raise ValueError (focal stacks are not windowed).  No double backward."""
+    t, spec, squeeze = _stack_args(x, zs, tf, field, threshold, ste, ste_width, levels, grid, origin, roi,
+                                   "simulate_stack")
+    xs = _stack_device(t, spec)
+    if xs.requires_grad and torch.is_grad_enabled():
+        out = _SimulateStack.apply(xs, spec)
+    else:
+        out = spec.evaluate(xs)[1]
+    return out[:, 0] if squeeze else out
+
+
+def intensity_stack(x, zs, tf="asm", field="amplitude", threshold=None, ste="window", ste_width=0.5, levels=None,
+                    grid=None, origin=None, roi=None) -> torch.Tensor:
+    """``tt.intensity`` at every depth of `zs`: float32 [D, B, G, H, W] ([D, G, H, W] for a 3-D x), the
+    arguments as simulate_stack's.  With a gradient request the per-depth fields are saved and the
+    backward pass is one hbx_backward_stack with (2 / P) grad_output applied in the first passes'
+    loads; without one no field is written."""
+    t, spec, squeeze = _stack_args(x, zs, tf, field, threshold, ste, ste_width, levels, grid, origin, roi,
+                                   "intensity_stack")
+    xs = _stack_device(t, spec)
+    if xs.requires_grad and torch.is_grad_enabled():
+        out = _IntensityStack.apply(xs, spec)
+    else:
+        out = spec.evaluate(xs, want_field=False)[2]
+    return out[:, 0] if squeeze else out
+
+
+def loss_stack(x, target, zs, metric="mse", rel_scale="lsq", tf="asm", field="amplitude", threshold=None,
+               ste="window", ste_width=0.5, levels=None, grid=None, origin=None, roi=None) -> torch.Tensor:
+    """``tt.loss`` over a focal stack: one value per env, float64 [B] on the device (0-dim for a 3-D
+    x), of the intensities at every depth of `zs` against ``target`` float32 [D, B, G, H, W]
+    ([D, G, H, W] for a 3-D x), a constant.  The sums of I T, I^2 and T^2 run over an env's D G
+    channels and n = D G H W: with rel_scale="lsq" ONE least-squares scale per env for the whole
+    stack (one source power), with "none" the mean of the D per-depth losses.  metric, rel_scale
+    and the leaf arguments as in loss and simulate_stack.  If x requires grad the forward saves the
+    per-depth fields, intensities and statistics, and the backward pass is hbx_loss_weight_stack
+    followed by ONE hbx_backward_stack on the plan for the negated depths -- where D calls of
+    tt.loss run D first passes forward, and D last passes and D - 1 additions of gradient-sized
+    temporaries backward.  grid=, origin= and roi= raise ValueError.  No double backward."""
+    kind = _switch(metric, _METRIC_NAMES, "metric")
+    rel = _switch(rel_scale, _REL_NAMES, "rel_scale")
+    t, spec, squeeze = _stack_args(x, zs, tf, field, threshold, ste, ste_width, levels, grid, origin, roi,
+                                   "loss_stack")
+    tg = target.as_subclass(torch.Tensor) if isinstance(target, torch.Tensor) else torch.as_tensor(np.asarray(target))
+    if tg.dim() != (4 if squeeze else 5):
+        raise ValueError(f"loss_stack: target must be [D, B, G, H, W] ([D, G, H, W] for a 3-D x), got {tuple(tg.shape)}")
+    if squeeze:
+        tg = tg.unsqueeze(1)
+    b, _, h, w = t.shape
+    want = (len(spec.zs), b, spec.groups, h, w)
+    if tg.is_complex() or tuple(tg.shape) != want:
+        raise ValueError(f"loss_stack: target must be real {want}, got {tuple(tg.shape)} {tg.dtype}")
+    if tg.requires_grad:
+        raise ValueError("loss_stack: the target is a constant (it requires grad)")
+    xs = _stack_device(t, spec)
+    tg = tg.to(device=xs.device, dtype=torch.float32).contiguous()
+    if xs.requires_grad and torch.is_grad_enabled():
+        out = _LossStack.apply(xs, tg, spec, kind, rel)
+    else:
+        plan, _, _, stats = spec.evaluate(xs, tg, want_field=False, want_intensity=False)
+        out = plan.loss_stack(stats, kind, rel)
     return out[0] if squeeze else out
 
 

@@ -513,6 +513,102 @@ int hbx_loss_weight_window(hbx_plan_t plan, const float* intensity, const float*
                            const hbx_window_t* out_win, int32_t n_env, int32_t kind,
                            int32_t rel_scale, float* weight, void* stream);
 
+/* (ABI v15, additive) Focal stacks: one hologram propagated to D depths, 1 <= D <= HBX_MAX_DEPTHS, with
+ * the gradient of a loss over all of them.  A plan keeps its own z and table; the stack's depths are a
+ * second set of tables on the same plan, and arrays that carry a depth are depth-major -- each depth a
+ * contiguous block in the single-depth layout.
+ *
+ * hbx_plan_set_depths: builds the D transfer-function tables [D][G][N/2+1][N] with hbx_plan_create's own
+ *   loop (one copy of it): depth d's table is, bit for bit, the table of a plan created with
+ *   optics.z = z[d].  It replaces an earlier set; n_depths = 0 frees the tables (z may then be null).
+ *   It synchronises the device, as plan creation does, and is not for use with work in flight.  The
+ *   plan's own z, its table and every other call are untouched.  A non-finite z[d], a null z, or
+ *   n_depths outside [0, HBX_MAX_DEPTHS]: HBX_ERR_INVALID, and the earlier set stays.
+ * hbx_plan_depths: D (0: none set).
+ *
+ * hbx_evaluate_stack: the forward of every sample leaf kind, named by leaf->kind:
+ *   HBX_LEAF_REAL          values [B][G*P][H][W] float32, hbx_evaluate_real's                (Pc = P)
+ *   HBX_LEAF_THRESHOLD     the same, hbx_evaluate_threshold's with leaf->threshold           (Pc = P)
+ *   HBX_LEAF_COMPLEX       values [B][G*P/2][H][W][2] complex64, hbx_evaluate_complex's      (Pc = P/2)
+ *   HBX_LEAF_PHASE         values [B][G*P/2][H][W] float32, hbx_evaluate_phase's             (Pc = P/2)
+ *   HBX_LEAF_PHASE_LEVELS  the same, hbx_evaluate_phase_levels' with leaf->levels            (Pc = P/2)
+ *   (the leaf's other members are not read by the forward.)
+ *   target, intensity [D][B][G][H][W] float32; field [D][B][G*Pc][H][W][2]; chan_stats [D][B][G][3].
+ *   Depth d's block of every output equals, bit for bit, what the single-depth call of that kind writes
+ *   on a plan created with z = z[d]; nothing outside a depth's block is written.  Null-ability and the
+ *   target / chan_stats pairing are hbx_evaluate_threshold's for the two real kinds and
+ *   hbx_evaluate_complex's for the other three (there is no psnr output).
+ *   Per chunk of max_jobs / G envs the first pass runs ONCE -- the row spectrum it leaves does not depend
+ *   on z -- then for d = 0 .. D - 1 the column pass with table d and the single-depth call's own last pass
+ *   and reduction into depth d's block: 1 + 2 D pass launches where D calls run 3 D.  The pass-timer
+ *   slots get one HBX_PASS_ROWFWD record per chunk and one HBX_PASS_COL and HBX_PASS_ROWINV record per depth.
+ *   No depths set on the plan: HBX_ERR_INVALID ("depths" in hbx_last_error()); an unknown kind, a null
+ *   leaf or values, levels outside [2, 256] for HBX_LEAF_PHASE_LEVELS: HBX_ERR_INVALID.
+ *
+ * hbx_backward_stack: the whole backward pass of a leaf under a loss over the stack, on the plan whose
+ *   depths are the negated ones (set_depths(-z[d])), one call for all depths.
+ *   values  [D][B][G*P/2][H][W][2] complex64: per depth the gradient with respect to the propagated field
+ *           or, with weight, the saved field itself; weight [D][B][G][H][W] float32 (nullable) and scale
+ *           are hbx_phase_backward's, per depth
+ *   leaf    what the one output is, and where: exactly one of grad_field and grad is non-null
+ *     HBX_LEAF_COMPLEX       grad_field [B][G*P/2][H][W][2] = sum_d g_d, g_d the plane
+ *                            hbx_simulate_complex(_weighted) writes as field on the plan for -z[d]
+ *     HBX_LEAF_REAL          grad [B][G*P/2][H][W] float32 = Re sum_d g_d
+ *     HBX_LEAF_PHASE         grad = hbx_phase_backward's formula at sum_d g_d, samples the leaf's x
+ *     HBX_LEAF_PHASE_LEVELS  grad = hbx_phase_levels_backward's, with leaf->levels
+ *     HBX_LEAF_THRESHOLD     grad = hbx_threshold_backward's vb s(x) Re sum_d g_d, with leaf->surrogate,
+ *                            leaf->p0 and leaf->p1 as that call takes them
+ *   samples [B][G*P/2][H][W] float32, the leaf's x, used exactly as the single-depth backward calls use
+ *           it: required for the last three kinds, null for the first two.  The outputs carry no depth.
+ *   A chunk holds nj = max_jobs / D jobs (a whole number of envs): depth d's first pass (the unchanged
+ *   complex or weighted load) and column pass (table d) run in job slots [d nj, (d + 1) nj) of the plan's
+ *   workspace, and ONE depth-summing last pass adds the D slots' rows as it loads them, runs one inverse
+ *   row FFT per complex plane and writes the gradient once -- where D single-depth calls run D inverse
+ *   FFTs and D stores, and D - 1 read-add-write passes over gradient-sized temporaries follow.  The sum
+ *   sits on the recombined side of the pair recombination: the running line starts from depth 0's
+ *   recombined value B_0[2q] + i B_0[2q+1] (never from 0.0f) and takes B_d[2q], then i B_d[2q+1], d
+ *   ascending, each one float32 addition per component.  D = 1 therefore gives the single-depth backward
+ *   call's bits, the sign of a zero included; D > 1 agrees with D single-depth calls added in float32 up
+ *   to the order of the additions.  max_jobs < G * D: HBX_ERR_INVALID ("max_jobs" in hbx_last_error())
+ *   before anything is enqueued.  Timer slots: D HBX_PASS_ROWFWD and HBX_PASS_COL records and one
+ *   HBX_PASS_ROWINV record per chunk.
+ *
+ * hbx_loss_stack / hbx_loss_weight_stack: hbx_loss / hbx_loss_weight with an env's sums taken over all
+ *   D G channels in fixed order (d outer, g inner) and n = D G H W: chan_stats [D][B][G][3] -> loss [B],
+ *   and weight [D][B][G][H][W] from intensity and target of that shape.  One least-squares scale per env
+ *   for the whole stack (one source power).  D is the plan's.  At D = 1 both give hbx_loss's and
+ *   hbx_loss_weight's bits; the degenerate-env rule (an all-zero weight, never a NaN) carries over.
+ *
+ * Every call with an n_env: 0 is OK and < 0 HBX_ERR_INVALID; the four built sizes.  hbx_evaluate_stack and
+ * hbx_backward_stack run on HBX_PRECISION_F32 plans only (else HBX_ERR_UNSUPPORTED); hbx_plan_set_depths and
+ * the two loss calls do not look at the plan's precision (as hbx_loss does not).  Out of scope: windows; the bit path and every env, DBS,
+ * plane-cache and incremental entry point; reduced-precision plans; per-depth wavelengths or pitches;
+ * more than HBX_MAX_DEPTHS depths; summing in the column pass. */
+#define HBX_MAX_DEPTHS 8
+#define HBX_LEAF_REAL 0          /* hbx_evaluate_real's input            */
+#define HBX_LEAF_THRESHOLD 1     /* hbx_evaluate_threshold's (threshold)  */
+#define HBX_LEAF_COMPLEX 2       /* hbx_evaluate_complex's                */
+#define HBX_LEAF_PHASE 3         /* hbx_evaluate_phase's                  */
+#define HBX_LEAF_PHASE_LEVELS 4  /* hbx_evaluate_phase_levels' (levels)   */
+typedef struct hbx_leaf {
+  int32_t kind, levels;
+  float threshold;
+  int32_t surrogate;
+  float p0, p1;
+} hbx_leaf_t;
+int hbx_plan_set_depths(hbx_plan_t plan, const double* z, int32_t n_depths);
+int hbx_plan_depths(hbx_plan_t plan);
+int hbx_evaluate_stack(hbx_plan_t plan, const void* values, const hbx_leaf_t* leaf, const float* target,
+                       int32_t n_env, float* field, float* intensity, double* chan_stats, void* stream);
+int hbx_backward_stack(hbx_plan_t plan, const float* values, const float* weight, float scale,
+                       const hbx_leaf_t* leaf, const float* samples, int32_t n_env, float* grad_field,
+                       float* grad, void* stream);
+int hbx_loss_stack(hbx_plan_t plan, const double* chan_stats, int32_t n_env, int32_t kind,
+                   int32_t rel_scale, double* loss, void* stream);
+int hbx_loss_weight_stack(hbx_plan_t plan, const float* intensity, const float* target,
+                          const double* chan_stats, const double* grad_loss, int32_t n_env, int32_t kind,
+                          int32_t rel_scale, float* weight, void* stream);
+
 /* PSNR from per-channel statistics (tt.relativeLoss(.., tm.get_PSNR),
  * env.py:174): chan_stats[B][G][3] -> psnr[B]. */
 int hbx_psnr(hbx_plan_t plan, const double* chan_stats, int32_t n_env, double* psnr,
