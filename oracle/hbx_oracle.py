@@ -147,6 +147,89 @@ def propagate(field_planes: np.ndarray, h: np.ndarray) -> np.ndarray:
     return np.fft.ifft2(np.fft.fft2(field_planes, axes=(-2, -1)) * h, axes=(-2, -1))
 
 
+# hbx_plan_set_precision's store kinds (include/hbx.h HBX_PRECISION_*); None is the unrounded model
+PRECISION_BF16_STORE, PRECISION_F16_STORE = 1, 2
+
+
+def round_bf16(x) -> np.ndarray:
+    """float32 values rounded to bfloat16 (8 significant bits, float32's exponent range), nearest, ties
+    to the even significand, returned as float32.  Stated by its meaning: the value is scaled so that one
+    bfloat16 step is 1 and rounded to the nearest integer, ties to even (numpy.rint), in float64, where
+    every float32 and every such multiple is exact.  Below the smallest normal the step stays that of the
+    lowest binade (gradual underflow); a result past the largest finite bfloat16 is the infinity; the
+    sign of a zero and NaN pass through."""
+    x = np.asarray(x, np.float32)
+    v = x.astype(np.float64)
+    _, e = np.frexp(v)                                   # |v| = m 2^e, m in [0.5, 1): the binade is e - 1
+    e = np.maximum(e.astype(np.int64) - 1, -126)         # float32's (and bfloat16's) lowest normal binade
+    step = np.ldexp(1.0, e - 7)                          # 7 fraction bits
+    with np.errstate(invalid="ignore"):
+        r = np.rint(v / step) * step
+    largest = (2.0 - 2.0 ** -7) * 2.0 ** 127
+    r = np.where(np.abs(r) > largest, np.copysign(np.inf, v), r)
+    r = np.where(np.isfinite(v), r, v)
+    return r.astype(np.float32)
+
+
+def round_f16(x) -> np.ndarray:
+    """float32 values rounded to IEEE binary16 (numpy.float16: nearest even, subnormals, overflow to
+    the infinity), returned as float32."""
+    with np.errstate(over="ignore"):
+        return np.asarray(x, np.float32).astype(np.float16).astype(np.float32)
+
+
+def store_round(x, store_kind) -> np.ndarray:
+    """Re and im of a complex128 array each rounded as a pass intermediate's store rounds them: to
+    float32 (what the kernel holds) and then to the store type.  store_kind None: x itself."""
+    if store_kind is None:
+        return x
+    if store_kind == PRECISION_BF16_STORE:
+        r = round_bf16
+    elif store_kind == PRECISION_F16_STORE:
+        r = round_f16
+    else:
+        raise ValueError(f"unknown store_kind {store_kind}")
+    x = np.asarray(x, np.complex128)
+    out = np.empty(x.shape, np.complex128)      # by parts: 1j * inf would put a NaN into the real part
+    out.real = r(x.real.astype(np.float32))
+    out.imag = r(x.imag.astype(np.float32))
+    return out
+
+
+def propagate_rounded(field_planes: np.ndarray, h: np.ndarray, store_kind=None, round_a: bool = True,
+                      round_b: bool = True) -> np.ndarray:
+    """`propagate` of real planes [P, N, N] with the two pass intermediates rounded as a plan with
+    hbx_plan_set_precision(store_kind) stores them (PRECISION_BF16_STORE / PRECISION_F16_STORE), in float64:
+
+        A   = FFT_x(u)                               the row spectrum (first pass)
+        A_r = round(A)                               re and im each
+        B   = IFFT_y(FFT_y(A_r) H) / N               the column pass's output
+        B_r = round(B)
+        U   = N IFFT_x(B_r)                          the last pass (its own 1 / N undone: B carries it)
+
+    The scales are the stored values' own, which matters where the store type's grid is not
+    scale-invariant (fp16 subnormals and overflow):
+      * A: the row passes store 2 A (csrc/hbx_passes.hip, rowfwd_emit / rowfwd32_emit: the Hermitian split
+        drops its 0.5 factors); store_round_a rounds 0.5 v to fp16 and doubles it, i.e. the fp16 value of A
+        itself, and for bf16 -- float32's exponent range -- the factor 2 commutes with the rounding.
+      * B: htab holds H / (2 N^2) (csrc/hbx_internal.hpp PlanDev::htab; csrc/hbx_api.hip fill_htab: scale =
+        0.5 / N^2) and the kernels' FFTs are unnormalised, so k_col2 stores
+        sum_ky [sum_y 2 A] H / (2 N^2) e^{+i..} = IFFT_y(FFT_y(A) H) / N with numpy's normalised IFFT;
+        store_round rounds that value as it is (col2_stage_write and the two direct stores of k_col2).
+    The half spectrum's Hermitian packing is not modelled: the rounding is elementwise and odd, so the
+    mirror line kx -> N - kx of a real plane's A is the conjugate of the rounded line.  store_kind None
+    is `propagate`.  round_a / round_b (tests of the statistic's power): leave one store unrounded."""
+    u = np.asarray(field_planes, np.float64)
+    n = u.shape[-1]
+    a = np.fft.fft(u, axis=-1)
+    if round_a:
+        a = store_round(a, store_kind)
+    b = np.fft.ifft(np.fft.fft(a, axis=-2) * h, axis=-2) / n
+    if round_b:
+        b = store_round(b, store_kind)
+    return n * np.fft.ifft(b, axis=-1)
+
+
 def group_intensity(mask_group: np.ndarray, h: np.ndarray,
                     field_kind: int = FIELD_AMPLITUDE) -> np.ndarray:
     """env.py:172-173 / DBS_1024_24.py:328-329: mean over the P planes of |U_p|^2.
