@@ -92,6 +92,16 @@ def _need(t: torch.Tensor, name: str, dtype: torch.dtype, shape, device: torch.d
         raise ValueError(f"{name} must be contiguous")
 
 
+def _batch(t, axis: int = 0) -> int:
+    """The envs of an argument, its length along `axis`; 0 for what has no such axis (the _need
+    that follows names the fault)."""
+    return t.shape[axis] if isinstance(t, torch.Tensor) and t.dim() > axis else 0
+
+
+def _complex(field: Optional[torch.Tensor]):
+    return None if field is None else torch.view_as_complex(field)
+
+
 _PACK_KIND = {torch.bool: _lib.SRC_U8, torch.int8: _lib.SRC_U8, torch.uint8: _lib.SRC_U8,
               torch.float32: _lib.SRC_F32, torch.float64: _lib.SRC_F64}
 _PACK_ALIGN = {_lib.SRC_U8: 4, _lib.SRC_F32: 16, _lib.SRC_F64: 32}
@@ -331,6 +341,27 @@ class Plan:
                    "hbx_simulate")
         return torch.view_as_complex(field), inten
 
+    # -- the leaf calls: samples (real, complex, phase, thresholded) instead of bits ------------
+    def _in(self, t, name: str, dtype: torch.dtype, shape, optional: bool = False):
+        """_need, then the tensor whose memory the kernel may read: a lazily conjugated or negated
+        view (t.conj()) shares the unresolved memory, so it is materialised (a copy only when such a
+        bit is set).  optional: None passes through."""
+        if optional and t is None:
+            return None
+        _need(t, name, dtype, shape, self.device)
+        return t.resolve_conj().resolve_neg() if dtype.is_complex else t.resolve_neg()
+
+    def _outputs(self, field_shape, image_shape, want_field: bool, want_intensity: bool, with_stats: bool):
+        """The buffers of an evaluate call -> (field as float32 pairs | None, a float32 image per
+        group | None, chan_stats | None, psnr | None); the last two come with a target."""
+        dev = self.device
+        field = torch.empty(field_shape + (2,), dtype=torch.float32, device=dev) if want_field else None
+        inten = torch.empty(image_shape, dtype=torch.float32, device=dev) if want_intensity else None
+        if not with_stats:
+            return field, inten, None, None
+        return (field, inten, torch.empty(image_shape[:2] + (3,), dtype=torch.float64, device=dev),
+                torch.empty(image_shape[:1], dtype=torch.float64, device=dev))
+
     def values_shape(self, n: int):
         c = self.cfg
         return (n, c.channels, c.height, c.width)
@@ -339,13 +370,9 @@ class Plan:
         """`simulate` on a real-valued field (hbx_simulate_real, ABI v15): `values` float32
         [B, CH, H, W] are the field samples themselves (u = value; the plan's field_kind is not
         applied).  Returns (field complex64 [B, CH, H, W], intensity [B, G, H, W] | None)."""
-        n = values.shape[0] if isinstance(values, torch.Tensor) and values.dim() else 0
-        c = self.cfg
-        _need(values, "values", torch.float32, self.values_shape(n), self.device)
-        values = values.resolve_neg()              # a lazily negated view shares the un-negated memory
-        field = torch.empty((n, c.channels, c.height, c.width, 2), dtype=torch.float32, device=self.device)
-        inten = torch.empty((n, c.groups, c.height, c.width), dtype=torch.float32,
-                            device=self.device) if want_intensity else None
+        n = _batch(values)
+        values = self._in(values, "values", torch.float32, self.values_shape(n))
+        field, inten, _, _ = self._outputs(self.values_shape(n), self.target_shape(n), True, want_intensity, False)
         _lib.check(self.lib.hbx_simulate_real(self._h, _ptr(values), n, _ptr(field), _ptr(inten),
                                               _stream(stream)), "hbx_simulate_real")
         return torch.view_as_complex(field), inten
@@ -365,18 +392,11 @@ class Plan:
         None is hbx_simulate_complex itself (scale is then not applied)."""
         if not (want_field or want_real):
             raise ValueError("simulate_complex: want_field and want_real are both off")
-        n = values.shape[0] if isinstance(values, torch.Tensor) and values.dim() else 0
-        c = self.cfg
-        shape = (n, c.channels // 2, c.height, c.width)
-        _need(values, "values", torch.complex64, shape, self.device)
-        # a lazily conjugated / negated view (values.conj()) shares the unconjugated memory the
-        # kernel would read: materialise it (a copy only when such a bit is set)
-        values = values.resolve_conj().resolve_neg()
-        if weight is not None:
-            _need(weight, "weight", torch.float32, (n, c.groups, c.height, c.width), self.device)
-            weight = weight.resolve_neg()
-        field = torch.empty(shape + (2,), dtype=torch.float32, device=self.device) if want_field else None
-        real = torch.empty(shape, dtype=torch.float32, device=self.device) if want_real else None
+        n = _batch(values)
+        shape = self.phase_shape(n)
+        values = self._in(values, "values", torch.complex64, shape)
+        weight = self._in(weight, "weight", torch.float32, self.target_shape(n), optional=True)
+        field, real, _, _ = self._outputs(shape, shape, want_field, want_real, False)
         if weight is None:
             _lib.check(self.lib.hbx_simulate_complex(self._h, _ptr(values), n, _ptr(field), _ptr(real),
                                                      _stream(stream)), "hbx_simulate_complex")
@@ -384,16 +404,14 @@ class Plan:
             _lib.check(self.lib.hbx_simulate_complex_weighted(self._h, _ptr(values), _ptr(weight), float(scale), n,
                                                               _ptr(field), _ptr(real), _stream(stream)),
                        "hbx_simulate_complex_weighted")
-        return (torch.view_as_complex(field) if want_field else None), real
+        return _complex(field), real
 
     def intensity_real(self, values: torch.Tensor, stream=None) -> torch.Tensor:
         """Plane-mean intensity float32 [B, G, H, W] of a real-valued field (hbx_intensity_real):
         `simulate_real(.., want_intensity=True)`'s intensity, bit for bit, with no field written."""
-        n = values.shape[0] if isinstance(values, torch.Tensor) and values.dim() else 0
-        c = self.cfg
-        _need(values, "values", torch.float32, self.values_shape(n), self.device)
-        values = values.resolve_neg()              # a lazily negated view shares the un-negated memory
-        inten = torch.empty((n, c.groups, c.height, c.width), dtype=torch.float32, device=self.device)
+        n = _batch(values)
+        values = self._in(values, "values", torch.float32, self.values_shape(n))
+        inten = torch.empty(self.target_shape(n), dtype=torch.float32, device=self.device)
         _lib.check(self.lib.hbx_intensity_real(self._h, _ptr(values), n, _ptr(inten), _stream(stream)),
                    "hbx_intensity_real")
         return inten
@@ -402,15 +420,10 @@ class Plan:
                        stream=None):
         """`propagate` on a real-valued field (hbx_propagate_real, ABI v15): returns
         (intensity|None, chan_stats, psnr)."""
-        n = values.shape[0] if isinstance(values, torch.Tensor) and values.dim() else 0
-        c = self.cfg
-        _need(values, "values", torch.float32, self.values_shape(n), self.device)
-        values = values.resolve_neg()              # a lazily negated view shares the un-negated memory
+        n = _batch(values)
+        values = self._in(values, "values", torch.float32, self.values_shape(n))
         _need(target, "target", torch.float32, self.target_shape(n), self.device)
-        inten = torch.empty((n, c.groups, c.height, c.width), dtype=torch.float32,
-                            device=self.device) if want_intensity else None
-        stats = torch.empty((n, c.groups, 3), dtype=torch.float64, device=self.device)
-        psnr = torch.empty((n,), dtype=torch.float64, device=self.device)
+        _, inten, stats, psnr = self._outputs(None, self.target_shape(n), False, want_intensity, True)
         _lib.check(self.lib.hbx_propagate_real(self._h, _ptr(values), _ptr(target), n, _ptr(inten),
                                                _ptr(stats), _ptr(psnr), _stream(stream)), "hbx_propagate_real")
         return inten, stats, psnr
@@ -420,19 +433,14 @@ class Plan:
         """`propagate_real` that may also write `simulate_real`'s field, in one launch set
         (hbx_evaluate_real): returns (field complex64 [B, CH, H, W] | None, intensity | None,
         chan_stats, psnr), each bit for bit what those two calls give."""
-        n = values.shape[0] if isinstance(values, torch.Tensor) and values.dim() else 0
-        c = self.cfg
-        _need(values, "values", torch.float32, self.values_shape(n), self.device)
-        values = values.resolve_neg()              # a lazily negated view shares the un-negated memory
+        n = _batch(values)
+        values = self._in(values, "values", torch.float32, self.values_shape(n))
         _need(target, "target", torch.float32, self.target_shape(n), self.device)
-        field = torch.empty((n, c.channels, c.height, c.width, 2), dtype=torch.float32,
-                            device=self.device) if want_field else None
-        inten = torch.empty(self.target_shape(n), dtype=torch.float32, device=self.device) if want_intensity else None
-        stats = torch.empty((n, c.groups, 3), dtype=torch.float64, device=self.device)
-        psnr = torch.empty((n,), dtype=torch.float64, device=self.device)
+        field, inten, stats, psnr = self._outputs(self.values_shape(n), self.target_shape(n), want_field,
+                                                  want_intensity, True)
         _lib.check(self.lib.hbx_evaluate_real(self._h, _ptr(values), _ptr(target), n, _ptr(field), _ptr(inten),
                                               _ptr(stats), _ptr(psnr), _stream(stream)), "hbx_evaluate_real")
-        return (torch.view_as_complex(field) if want_field else None), inten, stats, psnr
+        return _complex(field), inten, stats, psnr
 
     def evaluate_complex(self, values: torch.Tensor, target: Optional[torch.Tensor] = None, want_field: bool = True,
                          want_intensity: bool = True, stream=None):
@@ -442,25 +450,19 @@ class Plan:
         [B, G, H, W] | None, chan_stats | None, psnr | None).  intensity[b, g] is the mean of
         |field|^2 over the group's CH/2G complex planes; the field is `simulate_complex`'s bit for
         bit.  target None: the intensity alone (no statistics, no psnr)."""
-        n = values.shape[0] if isinstance(values, torch.Tensor) and values.dim() else 0
-        c = self.cfg
-        shape = (n, c.channels // 2, c.height, c.width)
-        _need(values, "values", torch.complex64, shape, self.device)
-        values = values.resolve_conj().resolve_neg()   # as simulate_complex: the kernel reads the memory
+        n = _batch(values)
+        shape = self.phase_shape(n)
+        values = self._in(values, "values", torch.complex64, shape)
         if target is None:
             if not want_intensity:
                 raise ValueError("evaluate_complex: without a target the intensity is the only output")
         else:
             _need(target, "target", torch.float32, self.target_shape(n), self.device)
-        field = torch.empty(shape + (2,), dtype=torch.float32, device=self.device) if want_field else None
-        inten = torch.empty(self.target_shape(n), dtype=torch.float32, device=self.device) if want_intensity else None
-        stats = psnr = None
-        if target is not None:
-            stats = torch.empty((n, c.groups, 3), dtype=torch.float64, device=self.device)
-            psnr = torch.empty((n,), dtype=torch.float64, device=self.device)
+        field, inten, stats, psnr = self._outputs(shape, self.target_shape(n), want_field, want_intensity,
+                                                  target is not None)
         _lib.check(self.lib.hbx_evaluate_complex(self._h, _ptr(values), _ptr(target), n, _ptr(field), _ptr(inten),
                                                  _ptr(stats), _ptr(psnr), _stream(stream)), "hbx_evaluate_complex")
-        return (torch.view_as_complex(field) if want_field else None), inten, stats, psnr
+        return _complex(field), inten, stats, psnr
 
     def phase_shape(self, n: int):
         c = self.cfg
@@ -472,15 +474,13 @@ class Plan:
         reduced exactly.  Returns (field complex64 [B, CH/2, H, W] | None, real_part | None)."""
         if not (want_field or want_real):
             raise ValueError("simulate_phase: want_field and want_real are both off")
-        n = phase.shape[0] if isinstance(phase, torch.Tensor) and phase.dim() else 0
+        n = _batch(phase)
         shape = self.phase_shape(n)
-        _need(phase, "phase", torch.float32, shape, self.device)
-        phase = phase.resolve_neg()                # a lazily negated view shares the un-negated memory
-        field = torch.empty(shape + (2,), dtype=torch.float32, device=self.device) if want_field else None
-        real = torch.empty(shape, dtype=torch.float32, device=self.device) if want_real else None
+        phase = self._in(phase, "phase", torch.float32, shape)
+        field, real, _, _ = self._outputs(shape, shape, want_field, want_real, False)
         _lib.check(self.lib.hbx_simulate_phase(self._h, _ptr(phase), n, _ptr(field), _ptr(real), _stream(stream)),
                    "hbx_simulate_phase")
-        return (torch.view_as_complex(field) if want_field else None), real
+        return _complex(field), real
 
     def evaluate_phase(self, phase: torch.Tensor, target: Optional[torch.Tensor] = None, want_field: bool = True,
                        want_intensity: bool = True, stream=None):
@@ -488,25 +488,19 @@ class Plan:
         [B, CH/2, H, W] as `simulate_phase`; returns (field | None, intensity | None, chan_stats |
         None, psnr | None) as `evaluate_complex`, the field `simulate_phase`'s bit for bit.  target
         None: the intensity alone."""
-        n = phase.shape[0] if isinstance(phase, torch.Tensor) and phase.dim() else 0
-        c = self.cfg
+        n = _batch(phase)
         shape = self.phase_shape(n)
-        _need(phase, "phase", torch.float32, shape, self.device)
-        phase = phase.resolve_neg()
+        phase = self._in(phase, "phase", torch.float32, shape)
         if target is None:
             if not want_intensity:
                 raise ValueError("evaluate_phase: without a target the intensity is the only output")
         else:
             _need(target, "target", torch.float32, self.target_shape(n), self.device)
-        field = torch.empty(shape + (2,), dtype=torch.float32, device=self.device) if want_field else None
-        inten = torch.empty(self.target_shape(n), dtype=torch.float32, device=self.device) if want_intensity else None
-        stats = psnr = None
-        if target is not None:
-            stats = torch.empty((n, c.groups, 3), dtype=torch.float64, device=self.device)
-            psnr = torch.empty((n,), dtype=torch.float64, device=self.device)
+        field, inten, stats, psnr = self._outputs(shape, self.target_shape(n), want_field, want_intensity,
+                                                  target is not None)
         _lib.check(self.lib.hbx_evaluate_phase(self._h, _ptr(phase), _ptr(target), n, _ptr(field), _ptr(inten),
                                                _ptr(stats), _ptr(psnr), _stream(stream)), "hbx_evaluate_phase")
-        return (torch.view_as_complex(field) if want_field else None), inten, stats, psnr
+        return _complex(field), inten, stats, psnr
 
     def phase_backward(self, values: torch.Tensor, phase: torch.Tensor, weight: Optional[torch.Tensor] = None,
                        scale: float = 1.0, stream=None) -> torch.Tensor:
@@ -516,16 +510,11 @@ class Plan:
         float32 [B, CH/2, H, W] = pi (Im g cos pi x - Re g sin pi x), g the field `simulate_complex`
         would return -- which is not written.  With the saved field as values, the loss's or the
         intensity's incoming gradient as weight and scale = 2 / planes this is dL/dx."""
-        n = values.shape[0] if isinstance(values, torch.Tensor) and values.dim() else 0
-        c = self.cfg
+        n = _batch(values)
         shape = self.phase_shape(n)
-        _need(values, "values", torch.complex64, shape, self.device)
-        values = values.resolve_conj().resolve_neg()   # as simulate_complex: the kernel reads the memory
-        _need(phase, "phase", torch.float32, shape, self.device)
-        phase = phase.resolve_neg()
-        if weight is not None:
-            _need(weight, "weight", torch.float32, (n, c.groups, c.height, c.width), self.device)
-            weight = weight.resolve_neg()
+        values = self._in(values, "values", torch.complex64, shape)
+        phase = self._in(phase, "phase", torch.float32, shape)
+        weight = self._in(weight, "weight", torch.float32, self.target_shape(n), optional=True)
         grad = torch.empty(shape, dtype=torch.float32, device=self.device)
         _lib.check(self.lib.hbx_phase_backward(self._h, _ptr(values), _ptr(weight), float(scale), _ptr(phase), n,
                                                _ptr(grad), _stream(stream)), "hbx_phase_backward")
@@ -540,15 +529,13 @@ class Plan:
         if not (want_field or want_real):
             raise ValueError("simulate_phase_levels: want_field and want_real are both off")
         levels = _levels(levels)
-        n = phase.shape[0] if isinstance(phase, torch.Tensor) and phase.dim() else 0
+        n = _batch(phase)
         shape = self.phase_shape(n)
-        _need(phase, "phase", torch.float32, shape, self.device)
-        phase = phase.resolve_neg()
-        field = torch.empty(shape + (2,), dtype=torch.float32, device=self.device) if want_field else None
-        real = torch.empty(shape, dtype=torch.float32, device=self.device) if want_real else None
+        phase = self._in(phase, "phase", torch.float32, shape)
+        field, real, _, _ = self._outputs(shape, shape, want_field, want_real, False)
         _lib.check(self.lib.hbx_simulate_phase_levels(self._h, _ptr(phase), levels, n, _ptr(field), _ptr(real),
                                                       _stream(stream)), "hbx_simulate_phase_levels")
-        return (torch.view_as_complex(field) if want_field else None), real
+        return _complex(field), real
 
     def evaluate_phase_levels(self, phase: torch.Tensor, levels: int, target: Optional[torch.Tensor] = None,
                               want_field: bool = True, want_intensity: bool = True, stream=None):
@@ -556,26 +543,20 @@ class Plan:
         (hbx_evaluate_phase_levels): the same returns, each `evaluate_phase`'s on the quantized samples
         bit for bit."""
         levels = _levels(levels)
-        n = phase.shape[0] if isinstance(phase, torch.Tensor) and phase.dim() else 0
-        c = self.cfg
+        n = _batch(phase)
         shape = self.phase_shape(n)
-        _need(phase, "phase", torch.float32, shape, self.device)
-        phase = phase.resolve_neg()
+        phase = self._in(phase, "phase", torch.float32, shape)
         if target is None:
             if not want_intensity:
                 raise ValueError("evaluate_phase_levels: without a target the intensity is the only output")
         else:
             _need(target, "target", torch.float32, self.target_shape(n), self.device)
-        field = torch.empty(shape + (2,), dtype=torch.float32, device=self.device) if want_field else None
-        inten = torch.empty(self.target_shape(n), dtype=torch.float32, device=self.device) if want_intensity else None
-        stats = psnr = None
-        if target is not None:
-            stats = torch.empty((n, c.groups, 3), dtype=torch.float64, device=self.device)
-            psnr = torch.empty((n,), dtype=torch.float64, device=self.device)
+        field, inten, stats, psnr = self._outputs(shape, self.target_shape(n), want_field, want_intensity,
+                                                  target is not None)
         _lib.check(self.lib.hbx_evaluate_phase_levels(self._h, _ptr(phase), levels, _ptr(target), n, _ptr(field),
                                                       _ptr(inten), _ptr(stats), _ptr(psnr), _stream(stream)),
                    "hbx_evaluate_phase_levels")
-        return (torch.view_as_complex(field) if want_field else None), inten, stats, psnr
+        return _complex(field), inten, stats, psnr
 
     def phase_levels_backward(self, values: torch.Tensor, phase: torch.Tensor, levels: int,
                               weight: Optional[torch.Tensor] = None, scale: float = 1.0, stream=None) -> torch.Tensor:
@@ -585,16 +566,11 @@ class Plan:
         Equals `phase_backward(values, quantize_phase(phase, levels, False, True), weight, scale)` bit
         for bit."""
         levels = _levels(levels)
-        n = values.shape[0] if isinstance(values, torch.Tensor) and values.dim() else 0
-        c = self.cfg
+        n = _batch(values)
         shape = self.phase_shape(n)
-        _need(values, "values", torch.complex64, shape, self.device)
-        values = values.resolve_conj().resolve_neg()
-        _need(phase, "phase", torch.float32, shape, self.device)
-        phase = phase.resolve_neg()
-        if weight is not None:
-            _need(weight, "weight", torch.float32, (n, c.groups, c.height, c.width), self.device)
-            weight = weight.resolve_neg()
+        values = self._in(values, "values", torch.complex64, shape)
+        phase = self._in(phase, "phase", torch.float32, shape)
+        weight = self._in(weight, "weight", torch.float32, self.target_shape(n), optional=True)
         grad = torch.empty(shape, dtype=torch.float32, device=self.device)
         _lib.check(self.lib.hbx_phase_levels_backward(self._h, _ptr(values), _ptr(weight), float(scale), _ptr(phase),
                                                       levels, n, _ptr(grad), _stream(stream)),
@@ -609,25 +585,18 @@ class Plan:
         complex64 [B, CH, H, W] | None, intensity | None, chan_stats | None, psnr | None), each
         `evaluate_real`'s on the materialised samples bit for bit; chan_stats and psnr come with a
         target.  At least one of want_field, want_intensity and target is needed."""
-        n = values.shape[0] if isinstance(values, torch.Tensor) and values.dim() else 0
-        c = self.cfg
-        _need(values, "values", torch.float32, self.values_shape(n), self.device)
-        values = values.resolve_neg()              # a lazily negated view shares the un-negated memory
+        n = _batch(values)
+        values = self._in(values, "values", torch.float32, self.values_shape(n))
         if target is not None:
             _need(target, "target", torch.float32, self.target_shape(n), self.device)
         elif not (want_field or want_intensity):
             raise ValueError("evaluate_threshold: no target, and want_field and want_intensity are both off")
-        field = torch.empty((n, c.channels, c.height, c.width, 2), dtype=torch.float32,
-                            device=self.device) if want_field else None
-        inten = torch.empty(self.target_shape(n), dtype=torch.float32, device=self.device) if want_intensity else None
-        stats = psnr = None
-        if target is not None:
-            stats = torch.empty((n, c.groups, 3), dtype=torch.float64, device=self.device)
-            psnr = torch.empty((n,), dtype=torch.float64, device=self.device)
+        field, inten, stats, psnr = self._outputs(self.values_shape(n), self.target_shape(n), want_field, want_intensity,
+                                                  target is not None)
         _lib.check(self.lib.hbx_evaluate_threshold(self._h, _ptr(values), float(threshold), _ptr(target), n,
                                                    _ptr(field), _ptr(inten), _ptr(stats), _ptr(psnr),
                                                    _stream(stream)), "hbx_evaluate_threshold")
-        return (torch.view_as_complex(field) if want_field else None), inten, stats, psnr
+        return _complex(field), inten, stats, psnr
 
     def threshold_backward(self, values: torch.Tensor, samples: torch.Tensor, weight: Optional[torch.Tensor] = None,
                            scale: float = 1.0, surrogate: int = _lib.STE_WINDOW, p0: float = -math.inf,
@@ -639,16 +608,11 @@ class Plan:
         vb s(x) Re g, vb this plan's (1 or -2) and g the field `simulate_complex` would return --
         which is not written.  STE_WINDOW: s = [p0 <= x <= p1] (the default is the plain estimator);
         STE_SIGMOID: s = k sg (1 - sg), sg = sigmoid(k (x - p0)), k = p1 > 0."""
-        n = values.shape[0] if isinstance(values, torch.Tensor) and values.dim() else 0
-        c = self.cfg
+        n = _batch(values)
         shape = self.phase_shape(n)
-        _need(values, "values", torch.complex64, shape, self.device)
-        values = values.resolve_conj().resolve_neg()   # as simulate_complex: the kernel reads the memory
-        _need(samples, "samples", torch.float32, shape, self.device)
-        samples = samples.resolve_neg()
-        if weight is not None:
-            _need(weight, "weight", torch.float32, (n, c.groups, c.height, c.width), self.device)
-            weight = weight.resolve_neg()
+        values = self._in(values, "values", torch.complex64, shape)
+        samples = self._in(samples, "samples", torch.float32, shape)
+        weight = self._in(weight, "weight", torch.float32, self.target_shape(n), optional=True)
         grad = torch.empty(shape, dtype=torch.float32, device=self.device)
         _lib.check(self.lib.hbx_threshold_backward(self._h, _ptr(values), _ptr(weight), float(scale), _ptr(samples),
                                                    int(surrogate), float(p0), float(p1), n, _ptr(grad),
@@ -659,7 +623,7 @@ class Plan:
              stream=None) -> torch.Tensor:
         """chan_stats [B, G, 3] -> the relative MSE or PSNR per env, float64 [B] on the device
         (hbx_loss): tt.relativeLoss(.., F.mse_loss / tm.get_PSNR) without the host wait."""
-        n = chan_stats.shape[0] if isinstance(chan_stats, torch.Tensor) and chan_stats.dim() else 0
+        n = _batch(chan_stats)
         _need(chan_stats, "chan_stats", torch.float64, (n, self.cfg.groups, 3), self.device)
         out = torch.empty((n,), dtype=torch.float64, device=self.device)
         _lib.check(self.lib.hbx_loss(self._h, _ptr(chan_stats), n, int(kind), int(rel_scale), _ptr(out),
@@ -673,7 +637,7 @@ class Plan:
         (hbx_loss_weight): grad_loss[b] * d loss_b / d intensity[b] = a_b I + c_b T; grad_loss
         float64 [B] or None (ones).  `simulate_complex(field, weight=.., scale=2 / planes)` on the
         plan for -z turns it into the gradient with respect to the hologram."""
-        n = intensity.shape[0] if isinstance(intensity, torch.Tensor) and intensity.dim() else 0
+        n = _batch(intensity)
         _need(intensity, "intensity", torch.float32, self.target_shape(n), self.device)
         _need(target, "target", torch.float32, self.target_shape(n), self.device)
         _need(chan_stats, "chan_stats", torch.float64, (n, self.cfg.groups, 3), self.device)
@@ -727,14 +691,13 @@ class Plan:
         chan_stats float64 [D, B, G, 3] | None); depth d of each equals the single-depth call's on a
         plan for zs[d] bit for bit."""
         leaf = self._leaf(kind, levels, threshold)
-        n = values.shape[0] if isinstance(values, torch.Tensor) and values.dim() else 0
+        n = _batch(values)
         c = self.cfg
         d = self.depths
         real_in = kind in (_lib.LEAF_REAL, _lib.LEAF_THRESHOLD)
         planes = c.channels if real_in else c.channels // 2
         shape = (n, planes, c.height, c.width)
-        _need(values, "values", torch.complex64 if kind == _lib.LEAF_COMPLEX else torch.float32, shape, self.device)
-        values = values.resolve_conj().resolve_neg() if kind == _lib.LEAF_COMPLEX else values.resolve_neg()
+        values = self._in(values, "values", torch.complex64 if kind == _lib.LEAF_COMPLEX else torch.float32, shape)
         tshape = (d,) + tuple(self.target_shape(n))
         if target is not None:
             _need(target, "target", torch.float32, tshape, self.device)
@@ -745,7 +708,7 @@ class Plan:
         stats = torch.empty((d, n, c.groups, 3), dtype=torch.float64, device=self.device) if target is not None else None
         _lib.check(self.lib.hbx_evaluate_stack(self._h, _ptr(values), C.byref(leaf), _ptr(target), n, _ptr(field),
                                                _ptr(inten), _ptr(stats), _stream(stream)), "hbx_evaluate_stack")
-        return (torch.view_as_complex(field) if want_field else None), inten, stats
+        return _complex(field), inten, stats
 
     def backward_stack(self, values: torch.Tensor, kind: int, samples: Optional[torch.Tensor] = None,
                        weight: Optional[torch.Tensor] = None, scale: float = 1.0, levels=None,
@@ -759,21 +722,15 @@ class Plan:
         `phase_backward`'s, `phase_levels_backward`'s or `threshold_backward`'s gradient of the
         summed field, from `samples` float32 [B, CH/2, H, W] (the leaf's x) as those calls use it."""
         leaf = self._leaf(kind, levels, 0.0, surrogate, p0, p1)
-        n = values.shape[1] if isinstance(values, torch.Tensor) and values.dim() > 1 else 0
-        c = self.cfg
+        n = _batch(values, 1)
         d = self.depths
         shape = self.phase_shape(n)
-        _need(values, "values", torch.complex64, (d,) + tuple(shape), self.device)
-        values = values.resolve_conj().resolve_neg()
+        values = self._in(values, "values", torch.complex64, (d,) + tuple(shape))
         needs = kind in (_lib.LEAF_PHASE, _lib.LEAF_PHASE_LEVELS, _lib.LEAF_THRESHOLD)
         if needs != (samples is not None):
             raise ValueError("backward_stack: samples are the leaf of a phase, L-level or thresholded leaf, else None")
-        if samples is not None:
-            _need(samples, "samples", torch.float32, shape, self.device)
-            samples = samples.resolve_neg()
-        if weight is not None:
-            _need(weight, "weight", torch.float32, (d,) + tuple(self.target_shape(n)), self.device)
-            weight = weight.resolve_neg()
+        samples = self._in(samples, "samples", torch.float32, shape, optional=True)
+        weight = self._in(weight, "weight", torch.float32, (d,) + tuple(self.target_shape(n)), optional=True)
         cplx = kind == _lib.LEAF_COMPLEX
         out = torch.empty(tuple(shape) + ((2,) if cplx else ()), dtype=torch.float32, device=self.device)
         _lib.check(self.lib.hbx_backward_stack(self._h, _ptr(values), _ptr(weight), float(scale), C.byref(leaf),
@@ -785,7 +742,7 @@ class Plan:
                    stream=None) -> torch.Tensor:
         """chan_stats [D, B, G, 3] -> `loss` per env over the whole stack, float64 [B] (hbx_loss_stack):
         the sums run over an env's D G channels, n = D G H W, one least-squares scale per env."""
-        n = chan_stats.shape[1] if isinstance(chan_stats, torch.Tensor) and chan_stats.dim() > 1 else 0
+        n = _batch(chan_stats, 1)
         _need(chan_stats, "chan_stats", torch.float64, (self.depths, n, self.cfg.groups, 3), self.device)
         out = torch.empty((n,), dtype=torch.float64, device=self.device)
         _lib.check(self.lib.hbx_loss_stack(self._h, _ptr(chan_stats), n, int(kind), int(rel_scale), _ptr(out),
@@ -798,7 +755,7 @@ class Plan:
         """`loss_stack`'s gradient with respect to the intensity, float32 [D, B, G, H, W]
         (hbx_loss_weight_stack): grad_loss[b] * d loss_b / d intensity[:, b] = a_b I + c_b T, one
         (a_b, c_b) per env for all depths; grad_loss float64 [B] or None (ones)."""
-        n = intensity.shape[1] if isinstance(intensity, torch.Tensor) and intensity.dim() > 1 else 0
+        n = _batch(intensity, 1)
         d = self.depths
         tshape = (d,) + tuple(self.target_shape(n))
         _need(intensity, "intensity", torch.float32, tshape, self.device)
@@ -825,23 +782,17 @@ class Plan:
         return _lib.Window(y0, x0, h, w), (h, w)
 
     def _evaluate_window(self, name, values, threshold, in_win, target, out_win, want_field, want_intensity, stream):
-        n = values.shape[0] if isinstance(values, torch.Tensor) and values.dim() else 0
+        n = _batch(values)
         c = self.cfg
         wi, (hi, wd_i) = self.window(in_win)
         wo, (ho, wd_o) = self.window(out_win)
-        _need(values, "values", torch.float32, (n, c.channels, hi, wd_i), self.device)
-        values = values.resolve_neg()              # a lazily negated view shares the un-negated memory
+        values = self._in(values, "values", torch.float32, (n, c.channels, hi, wd_i))
         if target is not None:
             _need(target, "target", torch.float32, (n, c.groups, ho, wd_o), self.device)
         elif not (want_field or want_intensity):
             raise ValueError(f"{name}: no target, and want_field and want_intensity are both off")
-        field = torch.empty((n, c.channels, ho, wd_o, 2), dtype=torch.float32,
-                            device=self.device) if want_field else None
-        inten = torch.empty((n, c.groups, ho, wd_o), dtype=torch.float32, device=self.device) if want_intensity else None
-        stats = psnr = None
-        if target is not None:
-            stats = torch.empty((n, c.groups, 3), dtype=torch.float64, device=self.device)
-            psnr = torch.empty((n,), dtype=torch.float64, device=self.device)
+        field, inten, stats, psnr = self._outputs((n, c.channels, ho, wd_o), (n, c.groups, ho, wd_o), want_field,
+                                                  want_intensity, target is not None)
         pi, po = (C.byref(wi) if wi is not None else None), (C.byref(wo) if wo is not None else None)
         if threshold is None:
             rc = self.lib.hbx_evaluate_real_window(self._h, _ptr(values), pi, _ptr(target), po, n, _ptr(field),
@@ -851,7 +802,7 @@ class Plan:
                                                         n, _ptr(field), _ptr(inten), _ptr(stats), _ptr(psnr),
                                                         _stream(stream))
         _lib.check(rc, "hbx_" + name)
-        return (torch.view_as_complex(field) if want_field else None), inten, stats, psnr
+        return _complex(field), inten, stats, psnr
 
     def evaluate_real_window(self, values: torch.Tensor, in_win=None, target: Optional[torch.Tensor] = None,
                              out_win=None, want_field: bool = True, want_intensity: bool = True, stream=None):
@@ -883,19 +834,14 @@ class Plan:
         is taken over grad_win (the forward's input window).  samples None: the real part (a real
         leaf's gradient); samples [B, CH/2, h_g, w_g] (the leaf): `threshold_backward`'s
         vb s(x) Re g with its surrogates."""
-        n = values.shape[0] if isinstance(values, torch.Tensor) and values.dim() else 0
+        n = _batch(values)
         c = self.cfg
         wv, (hv, wd_v) = self.window(val_win)
         wg, (hg, wd_g) = self.window(grad_win)
-        _need(values, "values", torch.complex64, (n, c.channels // 2, hv, wd_v), self.device)
-        values = values.resolve_conj().resolve_neg()   # as simulate_complex: the kernel reads the memory
+        values = self._in(values, "values", torch.complex64, (n, c.channels // 2, hv, wd_v))
         gshape = (n, c.channels // 2, hg, wd_g)
-        if samples is not None:
-            _need(samples, "samples", torch.float32, gshape, self.device)
-            samples = samples.resolve_neg()
-        if weight is not None:
-            _need(weight, "weight", torch.float32, (n, c.groups, hv, wd_v), self.device)
-            weight = weight.resolve_neg()
+        samples = self._in(samples, "samples", torch.float32, gshape, optional=True)
+        weight = self._in(weight, "weight", torch.float32, (n, c.groups, hv, wd_v), optional=True)
         grad = torch.empty(gshape, dtype=torch.float32, device=self.device)
         _lib.check(self.lib.hbx_backward_window(self._h, _ptr(values), _ptr(weight), float(scale),
                                                 C.byref(wv) if wv is not None else None, _ptr(samples),
@@ -907,7 +853,7 @@ class Plan:
     def loss_window(self, chan_stats: torch.Tensor, out_win=None, kind: int = _lib.LOSS_MSE,
                     rel_scale: int = _lib.REL_LSQ, stream=None) -> torch.Tensor:
         """`loss` on the statistics of an output window: n = G h_o w_o (hbx_loss_window)."""
-        n = chan_stats.shape[0] if isinstance(chan_stats, torch.Tensor) and chan_stats.dim() else 0
+        n = _batch(chan_stats)
         wo, _ = self.window(out_win)
         _need(chan_stats, "chan_stats", torch.float64, (n, self.cfg.groups, 3), self.device)
         out = torch.empty((n,), dtype=torch.float64, device=self.device)
@@ -920,7 +866,7 @@ class Plan:
                            rel_scale: int = _lib.REL_LSQ, stream=None) -> torch.Tensor:
         """`loss_weight` over an output window (hbx_loss_weight_window): intensity, target and the
         returned weight are compact float32 [B, G, h_o, w_o], n = G h_o w_o."""
-        n = intensity.shape[0] if isinstance(intensity, torch.Tensor) and intensity.dim() else 0
+        n = _batch(intensity)
         wo, (ho, wd_o) = self.window(out_win)
         shape = (n, self.cfg.groups, ho, wd_o)
         _need(intensity, "intensity", torch.float32, shape, self.device)

@@ -295,103 +295,433 @@ def _window_args(grid, origin, roi, shape, complex_in: bool, field_kind: int, th
     return n, in_win, inside(roi, "roi")
 
 
-def _window_plan(win, geom, planes: int, field_kind: int, b: int, adjoint: bool = False):
-    """The forward plan of `planes` real planes per group on the window's grid, or (adjoint) the plan
-    for -z of twice as many -- one complex plane per real plane of the leaf"""
+def _depths_arg(zs, what: str) -> Tuple[float, ...]:
+    """zs of the *_stack calls -> a tuple of 1 to 8 finite floats; anything else raises ValueError."""
+    try:
+        out = tuple(float(v) for v in zs)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: zs is a sequence of depths (numbers), got {zs!r}") from None
+    if not 1 <= len(out) <= _lib.MAX_DEPTHS:
+        raise ValueError(f"{what}: 1 to {_lib.MAX_DEPTHS} depths, got {len(out)}")
+    if not all(np.isfinite(v) for v in out):
+        raise ValueError(f"{what}: every depth must be finite, got {out!r}")
+    return out
+
+
+def _phase_samples(t: torch.Tensor) -> torch.Tensor:
+    """The float32 contiguous samples of a real leaf, by torch ops: autograd carries a float64
+    leaf's cast back."""
+    return t.to(torch.float32).resolve_neg().contiguous()
+
+
+def _pad_real(t: torch.Tensor, cp: int) -> torch.Tensor:
+    """float32 contiguous [B, cp, H, W] of a real device tensor [B, C, H, W], cp = C or C + 1 (a
+    zero plane: the kernels take plane pairs)."""
+    b, c, h, w = t.shape
+    if cp == c:
+        return t.to(torch.float32).resolve_neg().contiguous()
+    vals = torch.zeros((b, cp, h, w), dtype=torch.float32, device=t.device)
+    vals[:, :c] = t
+    return vals
+
+
+def _plane_mean(field: torch.Tensor, groups: int) -> torch.Tensor:
+    """mean over each group's planes of |field|^2: complex [B, C, H, W] -> float32 [B, G, H, W]"""
+    b, c, h, w = field.shape
+    return torch.view_as_real(field).square().sum(-1).view(b, groups, c // groups, h, w).mean(2)
+
+
+# the Plan methods of the two phase kinds at a single depth: field alone, evaluate, backward
+_PHASE_CALLS = {_lib.LEAF_PHASE: ("simulate_phase", "evaluate_phase", "phase_backward"),
+                _lib.LEAF_PHASE_LEVELS: ("simulate_phase_levels", "evaluate_phase_levels", "phase_levels_backward")}
+
+
+class _Leaf:
+    """What a call fixed before any GPU use: the geometry (wls, dx, dy, tf_kind; dev once the input
+    is on its device), the leaf kind (_lib.LEAF_*) with field_kind, ste_args and levels, the planes c
+    of the tensor the kernels read, and the extent -- exactly one of a single depth z, a window
+    (N, in_win, out_win) at depth z (_window_args) or a focal stack zs.  Which Plan method a leaf kind
+    and an extent take is decided here and nowhere else.
+
+    A plan carries 2 C / G real planes per group for the complex and phase kinds and for every
+    adjoint, C / G (padded to even) for a real or thresholded forward; a thresholded leaf's plans and
+    a window's have the field kind given (the leaf's vb), every other plan FIELD_AMPLITUDE."""
+
+    def __init__(self, wls, dx, dy, tf_kind, leaf, field_kind=_lib.FIELD_AMPLITUDE, ste_args=None, levels=None,
+                 c=0, z=None, win=None, zs=None, recompute=False, dev=None):
+        self.wls, self.dx, self.dy, self.tf_kind, self.leaf, self.dev = wls, dx, dy, tf_kind, leaf, dev
+        self.field_kind, self.ste_args, self.levels, self.c = field_kind, ste_args, levels, c
+        self.z, self.win, self.zs = z, win, zs
+        self.groups = len(wls)
+        self.real_in = leaf in (_lib.LEAF_REAL, _lib.LEAF_THRESHOLD)
+        self.plan_field = field_kind if leaf == _lib.LEAF_THRESHOLD or win is not None else _lib.FIELD_AMPLITUDE
+        self.tau = ste_args[0] if ste_args is not None else 0.0
+        self.ste = {} if ste_args is None else dict(surrogate=ste_args[1], p0=ste_args[2], p1=ste_args[3])
+        # the backward's last pass reads the leaf's samples / the Functions save the leaf (a window and
+        # a stack take the gradient's shape from it)
+        self.reads_leaf = leaf in (_lib.LEAF_PHASE, _lib.LEAF_PHASE_LEVELS, _lib.LEAF_THRESHOLD)
+        self.keeps_leaf = self.reads_leaf or win is not None or zs is not None
+        # tt.intensity(save_field=False) of a real leaf at one depth: keep x, form the field again
+        self.recompute = recompute and leaf == _lib.LEAF_REAL and not (win or zs)
+
+    def _plan(self, b, planes, h, w, adjoint):
+        if self.win is not None:
+            h = w = self.win[0]
+        if self.zs is None:
+            return _plan_for(h, w, planes // self.groups, self.wls, self.dx, self.dy, -self.z if adjoint else self.z, b,
+                             self.dev, self.tf_kind, self.plan_field)
+        depths = tuple(-v for v in self.zs) if adjoint else self.zs
+        return _plan_for(h, w, planes // self.groups, self.wls, self.dx, self.dy, depths[0], b, self.dev, self.tf_kind,
+                         self.plan_field, depths, depth_slots=adjoint)
+
+    def forward_plan(self, x):
+        b, c, h, w = x.shape
+        return self._plan(b, c + (c % 2) if self.real_in else 2 * c, h, w, False)
+
+    def adjoint_plan(self, t):
+        """The plan for -z (the negated depths) of one complex plane per plane of t [.., B, C, H, W]: the
+        leaf, or the values of a backward pass that does not keep it.  A stack's takes B G D job slots."""
+        b, c, h, w = t.shape[-4:]
+        return self._plan(b, 2 * c, h, w, True)
+
+    def kept(self, x):
+        return (x,) if self.keeps_leaf else ()
+
+    def evaluate(self, x, target=None, want_field=True, want_intensity=True):
+        """One forward launch set -> (plan, field | None, intensity | None, chan_stats | None).  A real
+        or thresholded leaf of an odd C is padded with a zero plane here: the field keeps it, and the
+        intensity is the mean over the C planes given."""
+        plan, leaf = self.forward_plan(x), self.leaf
+        if self.zs is not None:
+            return (plan,) + plan.evaluate_stack(x, leaf, target, want_field=want_field, want_intensity=want_intensity,
+                                                 levels=self.levels, threshold=self.tau)
+        c = x.shape[1]
+        cp = c + (c % 2) if self.real_in else c
+        if cp != c:
+            x = _pad_real(x, cp)
+        if self.win is not None:
+            _, in_win, out_win = self.win
+            if leaf == _lib.LEAF_THRESHOLD:
+                out = plan.evaluate_threshold_window(x, self.tau, in_win, target, out_win, want_field, want_intensity)
+            else:
+                out = plan.evaluate_real_window(x, in_win, target, out_win, want_field, want_intensity)
+        elif leaf == _lib.LEAF_THRESHOLD:
+            out = plan.evaluate_threshold(x, self.tau, target, want_field, want_intensity)
+        elif leaf == _lib.LEAF_REAL:
+            if target is not None:
+                out = plan.evaluate_real(x, target, want_field, want_intensity)
+            elif want_field:
+                out = plan.simulate_real(x, want_intensity)
+            else:
+                out = None, plan.intensity_real(x)             # no field is written
+        elif leaf == _lib.LEAF_COMPLEX:
+            if target is not None:
+                out = plan.evaluate_complex(x, target, want_field, want_intensity)
+            else:                                               # |.|^2 and the mean are torch ops
+                field, _ = plan.simulate_complex(x)
+                out = (field if want_field else None), (_plane_mean(field, self.groups) if want_intensity else None)
+        else:
+            simulate, evaluate, _ = _PHASE_CALLS[leaf]
+            lv = (self.levels,) if leaf == _lib.LEAF_PHASE_LEVELS else ()
+            if target is None and not want_intensity:
+                out = getattr(plan, simulate)(x, *lv)[:1]
+            else:
+                out = getattr(plan, evaluate)(x, *lv, target, want_field, want_intensity)
+        field, inten, stats = (tuple(out) + (None, None))[:3]
+        if cp != c and inten is not None:
+            inten = inten * (cp / c)                            # the kernel's mean counts the zero plane
+        return plan, field, inten, stats
+
+    def field(self, x):
+        """The propagated field of every plane of x (a stack's call also writes the intensity)"""
+        field = self.evaluate(x, want_intensity=self.zs is not None)[1]
+        return field if field.shape[-3] == x.shape[1] else field[:, :x.shape[1]]
+
+    def backward(self, x, values, weight=None, scale=1.0, adj=None):
+        """One launch set on the adjoint plan (adj, where the caller has fetched it already): the
+        leaf's gradient from `values` (the gradient with respect to the field, or with `weight` the
+        saved field).  x: the leaf where the Functions keep it, else None.  A real leaf receives the
+        real part, a complex one the field, the phase kinds and a thresholded leaf what the last pass
+        of their backward call writes."""
+        if adj is None:
+            adj = self.adjoint_plan(values if x is None else x)
+        samples = x if self.reads_leaf else None
+        if self.zs is not None:
+            return adj.backward_stack(values, self.leaf, samples=samples, weight=weight, scale=scale,
+                                      levels=self.levels, **self.ste)
+        if self.win is not None:                                # values at the forward's output window
+            return adj.backward_window(values, self.win[2], self.win[1], samples=samples, weight=weight, scale=scale,
+                                       **self.ste)
+        if self.leaf == _lib.LEAF_THRESHOLD:
+            return adj.threshold_backward(values, x, weight=weight, scale=scale, **self.ste)
+        if self.leaf in _PHASE_CALLS:
+            lv = (self.levels,) if self.leaf == _lib.LEAF_PHASE_LEVELS else ()
+            return getattr(adj, _PHASE_CALLS[self.leaf][2])(values, x, *lv, weight=weight, scale=scale)
+        cplx = self.leaf == _lib.LEAF_COMPLEX
+        gf, gr = adj.simulate_complex(values, want_field=cplx, want_real=not cplx, weight=weight, scale=scale)
+        grad = gf if cplx else gr
+        return grad if grad.shape[1] == self.c else grad[:, :self.c]    # a padded field's zero plane
+
+    def loss(self, plan, stats, kind, rel):
+        if self.zs is not None:
+            return plan.loss_stack(stats, kind, rel)
+        if self.win is not None:
+            return plan.loss_window(stats, self.win[2], kind, rel)
+        return plan.loss(stats, kind, rel)
+
+    def loss_weight(self, adj, inten, target, stats, gl, kind, rel):
+        """dL/dI = a I + c T per env on the adjoint plan (its G and N only)"""
+        if self.zs is not None:
+            return adj.loss_weight_stack(inten, target, stats, gl, kind, rel)
+        if self.win is not None:
+            return adj.loss_weight_window(inten, target, stats, self.win[2], gl, kind, rel)
+        return adj.loss_weight(inten, target, stats, gl, kind, rel)
+
+
+def _evaluate(t: torch.Tensor, target: torch.Tensor, geom, groups: int, want_field: bool, phase: bool = False):
+    """One launch set on a device tensor [B, C, H, W] at one depth (real, complex, or phase samples)
+    -> (plan, field | None, intensity | None, chan_stats)"""
     wls, dx, dy, z, dev, tf_kind = geom
-    n = win[0]
-    if adjoint:
-        return _plan_for(n, n, 2 * planes, wls, dx, dy, -z, b, dev, tf_kind, field_kind)
-    return _plan_for(n, n, planes, wls, dx, dy, z, b, dev, tf_kind, field_kind)
+    leaf = _lib.LEAF_PHASE if phase else _lib.LEAF_COMPLEX if t.is_complex() else _lib.LEAF_REAL
+    t = t.to(torch.complex64).resolve_conj().resolve_neg().contiguous() if t.is_complex() else _phase_samples(t)
+    return _Leaf(wls, dx, dy, tf_kind, leaf, c=t.shape[1], z=z, dev=dev).evaluate(t, target, want_field, want_field)
 
 
-def _window_forward(plan, x, win, ste_args, target=None, want_field=True, want_intensity=True):
-    """hbx_evaluate_threshold_window (ste_args) or hbx_evaluate_real_window of the compact leaf"""
-    _, in_win, out_win = win
-    if ste_args is not None:
-        return plan.evaluate_threshold_window(x, ste_args[0], in_win, target, out_win, want_field, want_intensity)
-    return plan.evaluate_real_window(x, in_win, target, out_win, want_field, want_intensity)
+def _materialised(grad_output: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """grad_output as the kernels read it: torch conjugates and negates lazily (the grad_output of a
+    loss that ends in F.conj()), and the kernels read the memory behind data_ptr()"""
+    g = grad_output.to(dtype)
+    return (g.resolve_conj() if dtype.is_complex else g).resolve_neg().contiguous()
 
 
-def _window_backward(adj, values, x, win, ste_args, weight=None, scale=1.0):
-    """One hbx_backward_window on the plan for -z: the values sit at the forward's output window, the
-    gradient is taken over its input window -- the real part, or the STE gate of the leaf x"""
-    _, in_win, out_win = win
-    if ste_args is None:
-        return adj.backward_window(values, out_win, in_win, weight=weight, scale=scale)
-    _, kind, p0, p1 = ste_args
-    return adj.backward_window(values, out_win, in_win, samples=x, weight=weight, scale=scale, surrogate=kind,
-                               p0=p0, p1=p1)
-
-
-class _WindowSimulate(torch.autograd.Function):
-    """x [B, C, h, w] at the input window of the grid -> the field over the output window, through
-    hbx_evaluate_real_window / _threshold_window.  Backward: one hbx_backward_window of grad_output
-    on the plan for -z (crop_in Re A^H embed_out g, STE-gated for a thresholded leaf)."""
+class _Simulate(torch.autograd.Function):
+    """x -> the field A u(x) of every plane (every depth of a stack), for every leaf kind.  Backward:
+    one launch set of grad_output on the adjoint plan (A^H g = IFFT2(FFT2(g) conj H(z)), and
+    conj H(z) = H(-z) for both transfer functions), whose last pass writes the leaf's gradient
+    (_Leaf.backward).  No double backward."""
 
     @staticmethod
-    def forward(ctx, x, geom, win, field_kind, ste_args):
-        ctx.geom, ctx.win, ctx.field_kind, ctx.ste_args = geom, win, field_kind, ste_args
-        ctx.save_for_backward(x)
-        plan = _window_plan(win, geom, x.shape[1], field_kind, x.shape[0])
-        return _window_forward(plan, x, win, ste_args, want_intensity=False)[0]
+    def forward(ctx, x, spec):
+        ctx.spec = spec
+        ctx.save_for_backward(*spec.kept(x))
+        return spec.field(x)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_output):
-        x, = ctx.saved_tensors
-        adj = _window_plan(ctx.win, ctx.geom, x.shape[1], ctx.field_kind, x.shape[0], adjoint=True)
-        g = grad_output.to(torch.complex64).resolve_conj().resolve_neg().contiguous()
-        return _window_backward(adj, g, x, ctx.win, ctx.ste_args), None, None, None, None
+        x, = ctx.saved_tensors or (None,)
+        return ctx.spec.backward(x, _materialised(grad_output, torch.complex64)), None
 
 
-class _WindowIntensity(torch.autograd.Function):
-    """The plane-mean intensity over the output window; the cropped field is saved, and the backward
-    pass is one hbx_backward_window of it with (2 / P) gI applied in the first pass's load."""
+class _Intensity(torch.autograd.Function):
+    """x -> I = mean_p |A u_p|^2 per colour group, with the field F = A u saved (and the leaf where
+    its backward reads it).  dL/du = A^H((2 / P) gI F): one launch set of F on the adjoint plan, whose
+    first pass applies (2 / P) gI as it loads F -- the complex tensor (2 / P) gI F is never
+    written.  spec.recompute: only x is saved, and the backward forms F again first.  No double
+    backward."""
 
     @staticmethod
-    def forward(ctx, x, geom, win, groups, field_kind, ste_args):
-        ctx.geom, ctx.win, ctx.groups, ctx.field_kind, ctx.ste_args = geom, win, groups, field_kind, ste_args
-        plan = _window_plan(win, geom, x.shape[1] // groups, field_kind, x.shape[0])
-        field, inten, _, _ = _window_forward(plan, x, win, ste_args)
-        ctx.save_for_backward(field, x)
+    def forward(ctx, x, spec):
+        ctx.spec = spec
+        if spec.recompute:
+            ctx.save_for_backward(x)
+            return spec.evaluate(x, want_field=False)[2]
+        _, field, inten, _ = spec.evaluate(x)
+        ctx.save_for_backward(field, *spec.kept(x))
         return inten
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_output):
-        field, x = ctx.saved_tensors
-        planes = x.shape[1] // ctx.groups
-        adj = _window_plan(ctx.win, ctx.geom, planes, ctx.field_kind, x.shape[0], adjoint=True)
-        gi = grad_output.to(torch.float32).resolve_neg().contiguous()
-        grad = _window_backward(adj, field, x, ctx.win, ctx.ste_args, weight=gi, scale=2.0 / planes)
-        return grad, None, None, None, None, None
+        spec, saved = ctx.spec, ctx.saved_tensors
+        if spec.recompute:
+            field, x = spec.evaluate(saved[0], want_intensity=False)[1], None
+        else:
+            field, x = saved[0], (saved[1] if len(saved) > 1 else None)
+        gi = _materialised(grad_output, torch.float32)
+        return spec.backward(x, field, weight=gi, scale=2.0 / (spec.c // spec.groups)), None
 
 
-class _WindowLoss(torch.autograd.Function):
-    """The relative MSE or PSNR over the output window (n = G h_o w_o); the cropped field, the cropped
-    intensity and the statistics are saved, and the backward pass is hbx_loss_weight_window followed
-    by one hbx_backward_window on the plan for -z."""
+class _Loss(torch.autograd.Function):
+    """x -> the relative MSE or PSNR per env of I = mean_p |A u_p|^2 against a constant target (over
+    the roi of a window, over all depths of a stack).  The forward pass is one launch set that leaves
+    the field F, I and the statistics; with w = gL dL/dI = a I + c T (_Leaf.loss_weight: a, c per
+    env from the statistics and the incoming gradient gL), dL/du = A^H((2 / P) w F): one launch set
+    of F on the adjoint plan, as _Intensity's backward pass.  No double backward."""
 
     @staticmethod
-    def forward(ctx, x, target, geom, win, groups, kind, rel, field_kind, ste_args):
-        ctx.geom, ctx.win, ctx.groups, ctx.kind, ctx.rel = geom, win, groups, kind, rel
-        ctx.field_kind, ctx.ste_args = field_kind, ste_args
-        plan = _window_plan(win, geom, x.shape[1] // groups, field_kind, x.shape[0])
-        field, inten, stats, _ = _window_forward(plan, x, win, ste_args, target)
-        ctx.save_for_backward(field, inten, stats, target, x)
-        return plan.loss_window(stats, win[2], kind, rel)
+    def forward(ctx, x, target, spec, kind, rel):
+        ctx.spec, ctx.kind, ctx.rel = spec, kind, rel
+        plan, field, inten, stats = spec.evaluate(x, target)
+        ctx.save_for_backward(field, inten, stats, target, *spec.kept(x))
+        return spec.loss(plan, stats, kind, rel)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_output):
-        field, inten, stats, target, x = ctx.saved_tensors
-        planes = x.shape[1] // ctx.groups
-        adj = _window_plan(ctx.win, ctx.geom, planes, ctx.field_kind, x.shape[0], adjoint=True)
-        gl = grad_output.to(torch.float64).resolve_neg().contiguous()
-        wgt = adj.loss_weight_window(inten, target, stats, ctx.win[2], gl, ctx.kind, ctx.rel)
-        grad = _window_backward(adj, field, x, ctx.win, ctx.ste_args, weight=wgt, scale=2.0 / planes)
-        return grad, None, None, None, None, None, None, None, None
+        spec = ctx.spec
+        field, inten, stats, target, x = ctx.saved_tensors + (() if spec.keeps_leaf else (None,))
+        gl = _materialised(grad_output, torch.float64)
+        adj = spec.adjoint_plan(field if x is None else x)
+        wgt = spec.loss_weight(adj, inten, target, stats, gl, ctx.kind, ctx.rel)
+        grad = spec.backward(x, field, weight=wgt, scale=2.0 / (spec.c // spec.groups), adj=adj)
+        return grad, None, None, None, None
+
+
+def _as_tensor(x) -> torch.Tensor:
+    return x.as_subclass(torch.Tensor) if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+
+
+def _leaf_args(x, what: str, tf, field, threshold, ste, ste_width, grid, origin, roi, levels, z=None, zs=None,
+               binary: bool = False, save_field: bool = True):
+    """The checks of every public call, all before any GPU use -> (t [B, C, H, W] as given, the _Leaf
+    without its device, whether x was 3-D).  what: the public function's name; its own rules are
+    `simulate`: one wavelength, any C (an odd one is padded); `intensity`: an odd C / G only for one
+    group of a real or complex field or a phase; `loss`: an even C / G for a real field; the *_stack
+    calls (zs given): no window, an even C / G for a real or thresholded leaf, a built grid."""
+    stacked = zs is not None
+    if stacked:
+        if grid is not None or origin is not None or roi is not None:
+            raise ValueError(f"{what}: grid=, origin= and roi= are not accepted (focal stacks are not windowed)")
+        zs = _depths_arg(zs, what)
+    tf_kind = _switch(tf, _TF_NAMES, "tf")
+    field_kind = _switch(field, _FIELD_NAMES, "field")
+    ste_args = _ste_args(threshold, ste, ste_width, what)
+    if ste_args is not None and binary:
+        raise ValueError("simulate: threshold= binarizes a real leaf on the continuous path (binary=False)")
+    meta = _meta_of(x)
+    wl = meta["wl"]
+    if what == "simulate":
+        if isinstance(wl, (tuple, list)) and len(wl) != 1:
+            raise ValueError("simulate: one wavelength per call (the reference splits RGB groups, "
+                             "env_1024_24.py:149-155)")
+    wls = tuple(float(v) for v in wl) if isinstance(wl, (tuple, list)) else (float(wl),)
+    groups = len(wls)
+    if not 1 <= groups <= _lib.MAX_GROUPS:
+        raise ValueError(f"{what}: 1 to {_lib.MAX_GROUPS} wavelengths, got {groups}")
+    dx, dy = meta.get("dx", (hbx.plan.PIXEL_PITCH,) * 2)
+    t = _as_tensor(x)
+    squeeze = t.dim() == 3
+    if squeeze:
+        t = t.unsqueeze(0)
+    if t.dim() != 4:
+        forms = "[B, C, H, W]" if what == "simulate" else "[B, C, H, W] or [C, H, W]"
+        raise ValueError(f"{what} expects {forms}, got {tuple(t.shape)}")
+    c, cplx, thresholded = t.shape[1], t.is_complex(), ste_args is not None
+    if what != "simulate" and (c == 0 or c % groups):
+        raise ValueError(f"{what}: {c} planes do not split into {groups} colour groups")
+    per, odd = c // groups, (c // groups) % 2
+    if what == "intensity" and groups > 1 and odd:
+        raise ValueError(f"intensity: {groups} colour groups need an even number of planes each, got {per}")
+    tt_what = what if stacked else "tt." + what
+    if cplx and binary:
+        raise ValueError("tt.simulate (hbx) propagates binary {0,1} masks only, as the reference does")
+    if cplx and field_kind != _lib.FIELD_AMPLITUDE:
+        raise ValueError(f"{tt_what}: a complex field is used as it is (field=\"amplitude\")")
+    if what == "loss" and not cplx and field_kind == _lib.FIELD_AMPLITUDE and odd:
+        raise ValueError(f"loss: a real field needs an even number of planes per colour group, got {per}")
+    if thresholded:
+        if cplx:
+            raise ValueError(f"{tt_what}: threshold= needs a real leaf, got a complex field")
+        if what in ("intensity", "loss") and odd:
+            raise ValueError(f"{what}: threshold= needs an even number of planes per colour group, got {per}")
+    if grid is not None and binary:
+        raise ValueError("simulate: grid= places a real leaf on the continuous path (binary=False)")
+    levels = _levels_arg(levels, binary, cplx, field_kind, thresholded, grid, what)
+    win = _window_args(grid, origin, roi, t.shape, cplx, field_kind, thresholded, what)
+    if win is not None and what == "intensity" and odd:
+        raise ValueError(f"intensity: grid= needs an even number of planes per colour group, got {per}")
+    if cplx:
+        leaf = _lib.LEAF_COMPLEX
+    elif thresholded:
+        leaf = _lib.LEAF_THRESHOLD
+    elif levels is not None:
+        leaf = _lib.LEAF_PHASE_LEVELS
+    elif field_kind == _lib.FIELD_PHASE:
+        leaf = _lib.LEAF_PHASE
+    else:
+        leaf = _lib.LEAF_REAL
+    if stacked:
+        if leaf in (_lib.LEAF_REAL, _lib.LEAF_THRESHOLD) and odd:
+            raise ValueError(f"{what}: a real or thresholded leaf needs an even number of planes per colour group, "
+                             f"got {per}")
+        if t.shape[2] != t.shape[3] or t.shape[2] not in _GRIDS:
+            raise ValueError(f"{what}: the hologram is one of the built grids {_GRIDS} squared, got {tuple(t.shape[2:])}")
+    # a windowed simulate pads an odd C by torch ops (the Function sees, and returns, the pair)
+    c_seen = c + (c % 2) if win is not None else c
+    spec = _Leaf(wls, dx, dy, tf_kind, leaf, field_kind, ste_args, levels, c=c_seen, z=z, win=win, zs=zs,
+                 recompute=not save_field)
+    return t, spec, squeeze
+
+
+def _target_arg(target, want: Tuple[int, ...], squeeze: bool, what: str) -> torch.Tensor:
+    """target of loss and loss_stack -> the tensor of shape `want` (given without the env axis for a
+    3-D x), a real constant; anything else raises ValueError."""
+    tg = _as_tensor(target)
+    axis = len(want) - 4                                        # the env axis: after a stack's depth axis
+    if axis and tg.dim() != (4 if squeeze else 5):
+        raise ValueError(f"{what}: target must be [D, B, G, H, W] ([D, G, H, W] for a 3-D x), got {tuple(tg.shape)}")
+    if squeeze:
+        tg = tg.unsqueeze(axis)
+    if tg.is_complex() or tuple(tg.shape) != want:
+        raise ValueError(f"{what}: target must be real {want}, got {tuple(tg.shape)} {tg.dtype}")
+    if tg.requires_grad:
+        raise ValueError(f"{what}: the target is a constant (it requires grad)")
+    return tg
+
+
+def _device_leaf(t: torch.Tensor, spec: _Leaf, what: str, cast: bool = True) -> torch.Tensor:
+    """The device tensor the kernels read, cast by torch ops (autograd carries the casts of a float64
+    or complex128 leaf back); names the device in the spec."""
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"tt.{'*_stack' if spec.zs is not None else what} needs a ROCm GPU (libhbx.so)")
+    if t.is_cuda:
+        spec.dev = t.device.index
+    else:
+        spec.dev = torch.cuda.current_device()
+        t = t.to(f"cuda:{spec.dev}")
+    if not cast:
+        return t
+    if spec.leaf == _lib.LEAF_COMPLEX:
+        return t.to(torch.complex64).resolve_conj().resolve_neg().contiguous()
+    return _pad_real(t, spec.c) if spec.c != t.shape[1] else _phase_samples(t)
+
+
+def _wants_grad(xs: torch.Tensor) -> bool:
+    return xs.requires_grad and torch.is_grad_enabled()
+
+
+def _simulate(t, spec, squeeze, what):
+    """simulate's continuous path and simulate_stack on the checked input: through _Simulate with a
+    gradient request, else the plain call with no graph"""
+    xs = _device_leaf(t, spec, what)
+    out = _Simulate.apply(xs, spec) if _wants_grad(xs) else spec.field(xs)
+    if out.shape[-3] != t.shape[1]:
+        out = out[:, :t.shape[1]]                               # the plane a windowed odd C was padded with
+    return out.select(0 if spec.zs is None else 1, 0) if squeeze else out
+
+
+def _intensity(t, spec, squeeze, what):
+    """intensity and intensity_stack on the checked input; without a gradient request no field is kept"""
+    xs = _device_leaf(t, spec, what)
+    out = _Intensity.apply(xs, spec) if _wants_grad(xs) else spec.evaluate(xs, want_field=False)[2]
+    return out.select(0 if spec.zs is None else 1, 0) if squeeze else out
+
+
+def _loss(t, target, spec, squeeze, what, kind, rel):
+    """loss and loss_stack on the checked input: the target has the shape of the intensity (a window's
+    roi, a stack's depths first); without a gradient request neither field nor intensity is written"""
+    b, _, h, w = t.shape
+    depths = () if spec.zs is None else (len(spec.zs),)
+    tg = _target_arg(target, depths + (b, spec.groups) + ((h, w) if spec.win is None else spec.win[2][2:]), squeeze, what)
+    xs = _device_leaf(t, spec, what)
+    tg = tg.to(device=xs.device, dtype=torch.float32).contiguous()
+    if _wants_grad(xs):
+        out = _Loss.apply(xs, tg, spec, kind, rel)
+    else:
+        plan, _, _, stats = spec.evaluate(xs, tg, want_field=False, want_intensity=False)
+        out = spec.loss(plan, stats, kind, rel)
+    return out[0] if squeeze else out
 
 
 def simulate(x, z: float, strict: bool = False, binary: bool = True, tf="asm", field="amplitude",
@@ -445,82 +775,16 @@ def simulate(x, z: float, strict: bool = False, binary: bool = True, tf="asm", f
     hbx_phase_levels_backward on the plan for -z: the continuous gradient at the displayed phase.
     levels with binary=True, a complex x, field="amplitude", threshold=, grid=, a non-integer or a
     value outside [2, 256] raises ValueError before any GPU use."""
-    tf_kind = _switch(tf, _TF_NAMES, "tf")
-    field_kind = _switch(field, _FIELD_NAMES, "field")
-    ste_args = _ste_args(threshold, ste, ste_width, "simulate")
-    if ste_args is not None and binary:
-        raise ValueError("simulate: threshold= binarizes a real leaf on the continuous path (binary=False)")
-    meta = _meta_of(x)
-    wl = meta["wl"]
-    if isinstance(wl, (tuple, list)):
-        if len(wl) != 1:
-            raise ValueError("simulate: one wavelength per call (the reference splits RGB groups, "
-                             "env_1024_24.py:149-155)")
-        wl = wl[0]
-    dx, dy = meta.get("dx", (hbx.plan.PIXEL_PITCH,) * 2)
-    t = x.as_subclass(torch.Tensor) if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
-    squeeze = t.dim() == 3
-    if squeeze:
-        t = t.unsqueeze(0)
-    if t.dim() != 4:
-        raise ValueError(f"simulate expects [B, C, H, W], got {tuple(t.shape)}")
-    if t.is_complex():
-        if binary:
-            raise ValueError("tt.simulate (hbx) propagates binary {0,1} masks only, as the reference does")
-        if field_kind != _lib.FIELD_AMPLITUDE:
-            raise ValueError("tt.simulate: a complex field is used as it is (field=\"amplitude\")")
-        if ste_args is not None:
-            raise ValueError("tt.simulate: threshold= needs a real leaf, got a complex field")
-    if grid is not None and binary:
-        raise ValueError("simulate: grid= places a real leaf on the continuous path (binary=False)")
-    levels = _levels_arg(levels, binary, t.is_complex(), field_kind, ste_args is not None, grid, "simulate")
-    win = _window_args(grid, origin, roi, t.shape, t.is_complex(), field_kind, ste_args is not None, "simulate")
-    if not torch.cuda.is_available():
-        raise RuntimeError("tt.simulate needs a ROCm GPU (libhbx.so)")
-    if t.is_cuda:
-        dev = t.device.index
-    else:
-        dev = torch.cuda.current_device()
-        t = t.to(f"cuda:{dev}")
-    if win is not None:
-        # x sits at `origin` of the grid (centred by default), which is dark elsewhere; the field is
-        # returned over `roi` (the hologram's own rectangle by default).  An odd C is padded with a plane
-        # that is sliced off again
-        c = t.shape[1]
-        xs = _pad_real(t, c + (c % 2))
-        geom = (wl, dx, dy, z, dev, tf_kind)
-        if xs.requires_grad and torch.is_grad_enabled():
-            out = _WindowSimulate.apply(xs, geom, win, field_kind, ste_args)
-        else:
-            plan = _window_plan(win, geom, xs.shape[1], field_kind, xs.shape[0])
-            out = _window_forward(plan, xs, win, ste_args, want_intensity=False)[0]
-        out = out[:, :c] if xs.shape[1] != c else out
-        return out[0] if squeeze else out
-    if ste_args is not None:
-        xs = _phase_samples(t)
-        geom = (wl, dx, dy, z, dev, tf_kind)
-        if xs.requires_grad and torch.is_grad_enabled():
-            out = _PropagateThreshold.apply(xs, geom, field_kind, ste_args)
-        else:
-            out = _propagate_threshold(xs, geom, field_kind, ste_args[0])
-        return out[0] if squeeze else out
-    if levels is not None:
-        xs = _phase_samples(t)
-        geom = (wl, dx, dy, z, dev, tf_kind)
-        if xs.requires_grad and torch.is_grad_enabled():
-            out = _PropagatePhaseLevels.apply(xs, geom, levels)
-        else:
-            b, c, h, w = xs.shape
-            out = _plan_for(h, w, 2 * c, wl, dx, dy, z, b, dev, tf_kind).simulate_phase_levels(xs, levels)[0]
-        return out[0] if squeeze else out
+    t, spec, squeeze = _leaf_args(x, "simulate", tf, field, threshold, ste, ste_width, grid, origin, roi, levels, z=z,
+                                  binary=binary)
     if not binary:
-        out = _simulate_continuous(t, wl, dx, dy, z, dev, tf_kind, field_kind)
-        return out[0] if squeeze else out
-    sc = _scratch(dev)
+        return _simulate(t, spec, squeeze, "simulate")
+    t = _device_leaf(t, spec, "simulate", cast=False)
+    sc = _scratch(spec.dev)
     _raise_pending(sc)                              # an earlier call's input, already checked
     b, c, h, w = t.shape
     cp = c + (c % 2)                                # the kernels pack plane pairs
-    plan = _plan_for(h, w, cp, wl, dx, dy, z, b, dev, tf_kind, field_kind)
+    plan = _plan_for(h, w, cp, spec.wls, spec.dx, spec.dy, z, b, spec.dev, spec.tf_kind, spec.field_kind)
     if cp == c:
         bits = hbx.pack_mask(t, error_ptr=sc.err_dev)
     else:
@@ -528,325 +792,11 @@ def simulate(x, z: float, strict: bool = False, binary: bool = True, tf="asm", f
         bits[:, :c] = hbx.pack_mask(t, error_ptr=sc.err_dev)
     field, _ = plan.simulate(bits)
     if strict:
-        torch.cuda.current_stream(dev).synchronize()
+        torch.cuda.current_stream(spec.dev).synchronize()
         _raise_pending(sc)
     if cp != c:
         field = field[:, :c]
     return field[0] if squeeze else field
-
-
-def _propagate_complex(u: torch.Tensor, wl, dx, dy, z, dev: int, tf_kind: int, want_field: bool = True):
-    """IFFT2(FFT2(u) H(z)) of a complex device tensor [B, C, H, W] through hbx_simulate_complex, on
-    the plan with 2 C real planes (= C complex planes): the complex field, or with
-    want_field=False its real part only (float32)."""
-    b, c, h, w = u.shape
-    # the samples are the field: the plan's bit mapping (field_kind) plays no part
-    plan = _plan_for(h, w, 2 * c, wl, dx, dy, z, b, dev, tf_kind, _lib.FIELD_AMPLITUDE)
-    # resolve_conj / resolve_neg: torch conjugates and negates lazily (x.conj(), and the grad_output
-    # of a loss that ends in F.conj()), and the kernels read the memory behind data_ptr()
-    u = u.to(torch.complex64).resolve_conj().resolve_neg().contiguous()
-    field, real = plan.simulate_complex(u, want_field=want_field, want_real=not want_field)
-    return field if want_field else real
-
-
-def _propagate_real(t: torch.Tensor, wl, dx, dy, z, dev: int, tf_kind: int) -> torch.Tensor:
-    """The same of a real device tensor [B, C, H, W] through hbx_simulate_real."""
-    b, c, h, w = t.shape
-    cp = c + (c % 2)                                # the kernels take plane pairs: pad with a zero plane
-    if cp == c:
-        vals = t.to(torch.float32).resolve_neg().contiguous()   # a lazy negation (x.conj().imag) made real
-    else:
-        vals = torch.zeros((b, cp, h, w), dtype=torch.float32, device=t.device)
-        vals[:, :c] = t
-    plan = _plan_for(h, w, cp, wl, dx, dy, z, b, dev, tf_kind, _lib.FIELD_AMPLITUDE)
-    out, _ = plan.simulate_real(vals)
-    return out[:, :c] if cp != c else out
-
-
-class _Propagate(torch.autograd.Function):
-    """u -> A u = IFFT2(FFT2(u) H(z)) with its adjoint as the backward pass.  A^H g =
-    IFFT2(FFT2(g) conj H(z)), and conj H(z) = H(-z) for both transfer functions, so the gradient
-    is hbx_simulate_complex of grad_output on the plan for -z: the whole field for a complex
-    input, its real part (the only output written) for a real one.  No double backward."""
-
-    @staticmethod
-    def forward(ctx, t, geom):
-        ctx.geom = geom
-        ctx.in_dtype = t.dtype
-        wl, dx, dy, z, dev, tf_kind = geom
-        if t.is_complex():
-            return _propagate_complex(t, wl, dx, dy, z, dev, tf_kind)
-        return _propagate_real(t, wl, dx, dy, z, dev, tf_kind)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_output):
-        wl, dx, dy, z, dev, tf_kind = ctx.geom
-        grad = _propagate_complex(grad_output, wl, dx, dy, -z, dev, tf_kind, want_field=ctx.in_dtype.is_complex)
-        return grad.to(ctx.in_dtype), None
-
-
-def _phase_samples(t: torch.Tensor) -> torch.Tensor:
-    """The float32 contiguous samples of a real phase leaf, by torch ops: autograd carries a
-    float64 leaf's cast back."""
-    return t.to(torch.float32).resolve_neg().contiguous()
-
-
-class _PropagatePhase(torch.autograd.Function):
-    """x -> A exp(i pi x) through hbx_simulate_phase, x float32 [B, C, H, W].  Backward: one
-    hbx_phase_backward of grad_output on the plan for -z, whose last pass turns A^H g into
-    dL/dx = pi (Im cos pi x - Re sin pi x) from the saved samples.  No double backward."""
-
-    @staticmethod
-    def forward(ctx, x, geom):
-        wl, dx, dy, z, dev, tf_kind = geom
-        b, c, h, w = x.shape
-        ctx.geom = geom
-        ctx.save_for_backward(x)
-        return _plan_for(h, w, 2 * c, wl, dx, dy, z, b, dev, tf_kind).simulate_phase(x)[0]
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_output):
-        wl, dx, dy, z, dev, tf_kind = ctx.geom
-        x, = ctx.saved_tensors
-        b, c, h, w = x.shape
-        g = grad_output.to(torch.complex64).resolve_conj().resolve_neg().contiguous()
-        return _plan_for(h, w, 2 * c, wl, dx, dy, -z, b, dev, tf_kind).phase_backward(g, x), None
-
-
-class _PropagatePhaseLevels(torch.autograd.Function):
-    """_PropagatePhase for a leaf displayed at L phase levels: x -> A exp(i pi q(x)) through
-    hbx_simulate_phase_levels.  Backward, the straight-through estimator dq/dx := 1: one
-    hbx_phase_levels_backward of grad_output on the plan for -z, whose last pass quantizes the saved
-    samples again and writes pi (Im cos pi q - Re sin pi q).  No double backward."""
-
-    @staticmethod
-    def forward(ctx, x, geom, levels):
-        wl, dx, dy, z, dev, tf_kind = geom
-        b, c, h, w = x.shape
-        ctx.geom, ctx.levels = geom, levels
-        ctx.save_for_backward(x)
-        return _plan_for(h, w, 2 * c, wl, dx, dy, z, b, dev, tf_kind).simulate_phase_levels(x, levels)[0]
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_output):
-        wl, dx, dy, z, dev, tf_kind = ctx.geom
-        x, = ctx.saved_tensors
-        b, c, h, w = x.shape
-        g = grad_output.to(torch.complex64).resolve_conj().resolve_neg().contiguous()
-        adj = _plan_for(h, w, 2 * c, wl, dx, dy, -z, b, dev, tf_kind)
-        return adj.phase_levels_backward(g, x, ctx.levels), None, None
-
-
-def _propagate_threshold(x: torch.Tensor, geom, field_kind: int, tau: float) -> torch.Tensor:
-    """The field of the binary hologram [x >= tau] of float32 samples [B, C, H, W], every plane,
-    through hbx_evaluate_threshold; an odd C is padded with a plane that is sliced off again."""
-    wl, dx, dy, z, dev, tf_kind = geom
-    b, c, h, w = x.shape
-    cp = c + (c % 2)
-    plan = _plan_for(h, w, cp, wl, dx, dy, z, b, dev, tf_kind, field_kind)
-    out = plan.evaluate_threshold(_pad_real(x, cp), tau, want_intensity=False)[0]
-    return out[:, :c] if cp != c else out
-
-
-def _threshold_backward(values: torch.Tensor, x: torch.Tensor, geom, groups: int, field_kind: int, ste_args,
-                        weight: Optional[torch.Tensor] = None, scale: float = 1.0) -> torch.Tensor:
-    """One hbx_threshold_backward on the plan for -z with the leaf's field kind (its vb): values
-    complex64 and x float32, both [B, C, H, W] -- real plane q of the leaf is complex plane q of
-    that plan, so nothing is padded."""
-    wls, dx, dy, z, dev, tf_kind = geom
-    b, c, h, w = x.shape
-    _, kind, p0, p1 = ste_args
-    adj = _plan_for(h, w, 2 * c // groups, wls, dx, dy, -z, b, dev, tf_kind, field_kind)
-    return adj.threshold_backward(values, x, weight=weight, scale=scale, surrogate=kind, p0=p0, p1=p1)
-
-
-class _PropagateThreshold(torch.autograd.Function):
-    """x -> A (va + vb [x >= tau]) through hbx_evaluate_threshold, x float32 [B, C, H, W].
-    Backward, the straight-through estimator: one hbx_threshold_backward of grad_output on the plan
-    for -z, whose last pass writes vb s(x) Re(A^H g) from the saved samples.  No double backward."""
-
-    @staticmethod
-    def forward(ctx, x, geom, field_kind, ste_args):
-        ctx.geom, ctx.field_kind, ctx.ste_args = geom, field_kind, ste_args
-        ctx.save_for_backward(x)
-        return _propagate_threshold(x, geom, field_kind, ste_args[0])
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_output):
-        x, = ctx.saved_tensors
-        g = grad_output.to(torch.complex64).resolve_conj().resolve_neg().contiguous()
-        return _threshold_backward(g, x, ctx.geom, 1, ctx.field_kind, ctx.ste_args), None, None, None
-
-
-def _simulate_continuous(t: torch.Tensor, wl, dx, dy, z, dev: int, tf_kind: int, field_kind: int) -> torch.Tensor:
-    """simulate's binary=False path on a device tensor [B, C, H, W]: real planes through
-    hbx_simulate_real, complex fields through hbx_simulate_complex, phase samples through
-    hbx_simulate_phase; through _Propagate / _PropagatePhase when a gradient is wanted."""
-    geom = (wl, dx, dy, z, dev, tf_kind)
-    if field_kind == _lib.FIELD_PHASE and not t.is_complex():
-        x = _phase_samples(t)
-        if x.requires_grad and torch.is_grad_enabled():
-            return _PropagatePhase.apply(x, geom)
-        b, c, h, w = x.shape
-        return _plan_for(h, w, 2 * c, wl, dx, dy, z, b, dev, tf_kind).simulate_phase(x)[0]
-    if t.requires_grad and torch.is_grad_enabled():
-        return _Propagate.apply(t, geom)
-    if t.is_complex():
-        return _propagate_complex(t, *geom)
-    return _propagate_real(t, *geom)
-
-
-def _pad_real(t: torch.Tensor, cp: int) -> torch.Tensor:
-    """float32 contiguous [B, cp, H, W] of a real device tensor [B, C, H, W], cp = C or C + 1 (a
-    zero plane: the kernels take plane pairs)."""
-    b, c, h, w = t.shape
-    if cp == c:
-        return t.to(torch.float32).resolve_neg().contiguous()
-    vals = torch.zeros((b, cp, h, w), dtype=torch.float32, device=t.device)
-    vals[:, :c] = t
-    return vals
-
-
-def _plane_mean(field: torch.Tensor, groups: int) -> torch.Tensor:
-    """mean over each group's planes of |field|^2: complex [B, C, H, W] -> float32 [B, G, H, W]"""
-    b, c, h, w = field.shape
-    return torch.view_as_real(field).square().sum(-1).view(b, groups, c // groups, h, w).mean(2)
-
-
-class _Intensity(torch.autograd.Function):
-    """u -> I = mean_p |A u_p|^2 per colour group, A u = IFFT2(FFT2(u) H_g(z)).  With F = A u saved,
-    dL/du = A^H((2 / P) gI F): one hbx_simulate_complex_weighted of F on the plan for -z (twice the
-    real planes per group), whose first pass applies (2 / P) gI as it loads F -- the complex
-    tensor (2 / P) gI F is never written.  A real u receives the real part (the only output
-    written), a complex u the field.  No double backward."""
-
-    @staticmethod
-    def forward(ctx, t, geom, groups, save_field):
-        wls, dx, dy, z, dev, tf_kind = geom
-        b, c, h, w = t.shape
-        ctx.geom, ctx.groups, ctx.in_dtype, ctx.planes = geom, groups, t.dtype, c
-        if t.is_complex():
-            plan = _plan_for(h, w, 2 * c // groups, wls, dx, dy, z, b, dev, tf_kind)
-            field, _ = plan.simulate_complex(t.to(torch.complex64).resolve_conj().resolve_neg().contiguous())
-            ctx.save_for_backward(field)
-            return _plane_mean(field, groups)
-        cp = c + (c % 2)
-        vals = _pad_real(t, cp)
-        plan = _plan_for(h, w, cp // groups, wls, dx, dy, z, b, dev, tf_kind)
-        if save_field:
-            field, inten = plan.simulate_real(vals, want_intensity=True)
-            ctx.save_for_backward(field)
-        else:
-            inten = plan.intensity_real(vals)
-            ctx.save_for_backward(t)
-        ctx.recompute = not save_field
-        return inten * (cp / c) if cp != c else inten      # the kernel's mean counts the zero plane
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_output):
-        wls, dx, dy, z, dev, tf_kind = ctx.geom
-        groups, c = ctx.groups, ctx.planes
-        saved, = ctx.saved_tensors
-        b, _, h, w = saved.shape
-        cplx = ctx.in_dtype.is_complex
-        if not cplx and ctx.recompute:                     # save_field=False: the field again, from the input
-            cp = c + (c % 2)
-            field, _ = _plan_for(h, w, cp // groups, wls, dx, dy, z, b, dev, tf_kind).simulate_real(_pad_real(saved, cp))
-        else:
-            field = saved
-        cf = field.shape[1]                                # complex planes of the adjoint: C, or C + 1 padded
-        gi = grad_output.to(torch.float32).resolve_neg().contiguous()
-        adj = _plan_for(h, w, 2 * cf // groups, wls, dx, dy, -z, b, dev, tf_kind)
-        gf, gr = adj.simulate_complex(field, want_field=cplx, want_real=not cplx, weight=gi,
-                                      scale=2.0 / (c // groups))
-        grad = gf if cplx else gr
-        if cf != c:
-            grad = grad[:, :c]
-        return grad.to(ctx.in_dtype), None, None, None
-
-
-class _IntensityPhase(torch.autograd.Function):
-    """x -> I = mean_p |A exp(i pi x_p)|^2 per colour group, x float32 [B, C, H, W]: one
-    hbx_evaluate_phase that leaves the field F and I.  Backward: one hbx_phase_backward of F on
-    the plan for -z with (2 / P) gI applied in the first pass's load and dL/dx out of the last
-    pass.  No double backward."""
-
-    @staticmethod
-    def forward(ctx, x, geom, groups):
-        wls, dx, dy, z, dev, tf_kind = geom
-        b, c, h, w = x.shape
-        ctx.geom, ctx.groups = geom, groups
-        field, inten, _, _ = _plan_for(h, w, 2 * c // groups, wls, dx, dy, z, b, dev, tf_kind).evaluate_phase(x)
-        ctx.save_for_backward(field, x)
-        return inten
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_output):
-        wls, dx, dy, z, dev, tf_kind = ctx.geom
-        field, x = ctx.saved_tensors
-        b, c, h, w = x.shape
-        gi = grad_output.to(torch.float32).resolve_neg().contiguous()
-        adj = _plan_for(h, w, 2 * c // ctx.groups, wls, dx, dy, -z, b, dev, tf_kind)
-        return adj.phase_backward(field, x, weight=gi, scale=2.0 / (c // ctx.groups)), None, None
-
-
-class _IntensityPhaseLevels(torch.autograd.Function):
-    """_IntensityPhase for a leaf displayed at L phase levels: one hbx_evaluate_phase_levels that
-    leaves the field F and I; backward one hbx_phase_levels_backward of F on the plan for -z with
-    (2 / P) gI applied in the first pass's load -- the straight-through estimator.  No double backward."""
-
-    @staticmethod
-    def forward(ctx, x, geom, groups, levels):
-        wls, dx, dy, z, dev, tf_kind = geom
-        b, c, h, w = x.shape
-        ctx.geom, ctx.groups, ctx.levels = geom, groups, levels
-        plan = _plan_for(h, w, 2 * c // groups, wls, dx, dy, z, b, dev, tf_kind)
-        field, inten, _, _ = plan.evaluate_phase_levels(x, levels)
-        ctx.save_for_backward(field, x)
-        return inten
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_output):
-        wls, dx, dy, z, dev, tf_kind = ctx.geom
-        field, x = ctx.saved_tensors
-        b, c, h, w = x.shape
-        gi = grad_output.to(torch.float32).resolve_neg().contiguous()
-        adj = _plan_for(h, w, 2 * c // ctx.groups, wls, dx, dy, -z, b, dev, tf_kind)
-        grad = adj.phase_levels_backward(field, x, ctx.levels, weight=gi, scale=2.0 / (c // ctx.groups))
-        return grad, None, None, None
-
-
-class _IntensityThreshold(torch.autograd.Function):
-    """x -> I = mean_p |A (va + vb [x_p >= tau])|^2 per colour group, x float32 [B, C, H, W]: one
-    hbx_evaluate_threshold that leaves the field F and I.  Backward, the straight-through
-    estimator: one hbx_threshold_backward of F on the plan for -z with (2 / P) gI applied in the
-    first pass's load and vb s(x) Re(.) out of the last pass.  No double backward."""
-
-    @staticmethod
-    def forward(ctx, x, geom, groups, field_kind, ste_args):
-        wls, dx, dy, z, dev, tf_kind = geom
-        b, c, h, w = x.shape
-        ctx.geom, ctx.groups, ctx.field_kind, ctx.ste_args = geom, groups, field_kind, ste_args
-        plan = _plan_for(h, w, c // groups, wls, dx, dy, z, b, dev, tf_kind, field_kind)
-        field, inten, _, _ = plan.evaluate_threshold(x, ste_args[0])
-        ctx.save_for_backward(field, x)
-        return inten
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_output):
-        field, x = ctx.saved_tensors
-        gi = grad_output.to(torch.float32).resolve_neg().contiguous()
-        grad = _threshold_backward(field, x, ctx.geom, ctx.groups, ctx.field_kind, ctx.ste_args, weight=gi,
-                                   scale=2.0 / (x.shape[1] // ctx.groups))
-        return grad, None, None, None, None
 
 
 def intensity(x, z: float, tf="asm", field="amplitude", save_field: bool = True, threshold=None, ste="window",
@@ -893,211 +843,12 @@ def intensity(x, z: float, tf="asm", field="amplitude", save_field: bool = True,
     levels=L with field="phase" (real x; as in simulate): the intensity of the hologram displayed at L
     phase levels, through hbx_evaluate_phase_levels; with a gradient request the backward pass is one
     hbx_phase_levels_backward, the straight-through estimator.  The field is always saved."""
-    tf_kind = _switch(tf, _TF_NAMES, "tf")
-    field_kind = _switch(field, _FIELD_NAMES, "field")
-    ste_args = _ste_args(threshold, ste, ste_width, "intensity")
-    meta = _meta_of(x)
-    wl = meta["wl"]
-    wls = tuple(float(v) for v in wl) if isinstance(wl, (tuple, list)) else (float(wl),)
-    groups = len(wls)
-    if not 1 <= groups <= _lib.MAX_GROUPS:
-        raise ValueError(f"intensity: 1 to {_lib.MAX_GROUPS} wavelengths, got {groups}")
-    dx, dy = meta.get("dx", (hbx.plan.PIXEL_PITCH,) * 2)
-    t = x.as_subclass(torch.Tensor) if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
-    squeeze = t.dim() == 3
-    if squeeze:
-        t = t.unsqueeze(0)
-    if t.dim() != 4:
-        raise ValueError(f"intensity expects [B, C, H, W] or [C, H, W], got {tuple(t.shape)}")
-    c = t.shape[1]
-    if c == 0 or c % groups:
-        raise ValueError(f"intensity: {c} planes do not split into {groups} colour groups")
-    if groups > 1 and (c // groups) % 2:
-        raise ValueError(f"intensity: {groups} colour groups need an even number of planes each, got {c // groups}")
-    if t.is_complex() and field_kind != _lib.FIELD_AMPLITUDE:
-        raise ValueError("tt.intensity: a complex field is used as it is (field=\"amplitude\")")
-    if ste_args is not None:
-        if t.is_complex():
-            raise ValueError("tt.intensity: threshold= needs a real leaf, got a complex field")
-        if (c // groups) % 2:
-            raise ValueError(f"intensity: threshold= needs an even number of planes per colour group, got {c // groups}")
-    levels = _levels_arg(levels, False, t.is_complex(), field_kind, ste_args is not None, grid, "intensity")
-    win = _window_args(grid, origin, roi, t.shape, t.is_complex(), field_kind, ste_args is not None, "intensity")
-    if win is not None and (c // groups) % 2:
-        raise ValueError(f"intensity: grid= needs an even number of planes per colour group, got {c // groups}")
-    if not torch.cuda.is_available():
-        raise RuntimeError("tt.intensity needs a ROCm GPU (libhbx.so)")
-    if t.is_cuda:
-        dev = t.device.index
-    else:
-        dev = torch.cuda.current_device()
-        t = t.to(f"cuda:{dev}")
-    geom = (wls, dx, dy, z, dev, tf_kind)
-    b, _, h, w = t.shape
-    if win is not None:
-        xs = _phase_samples(t)
-        if xs.requires_grad and torch.is_grad_enabled():
-            out = _WindowIntensity.apply(xs, geom, win, groups, field_kind, ste_args)
-        else:
-            plan = _window_plan(win, geom, c // groups, field_kind, b)
-            out = _window_forward(plan, xs, win, ste_args, want_field=False)[1]
-    elif ste_args is not None:
-        xs = _phase_samples(t)
-        if xs.requires_grad and torch.is_grad_enabled():
-            out = _IntensityThreshold.apply(xs, geom, groups, field_kind, ste_args)
-        else:
-            plan = _plan_for(h, w, c // groups, wls, dx, dy, z, b, dev, tf_kind, field_kind)
-            out = plan.evaluate_threshold(xs, ste_args[0], want_field=False)[1]
-    elif levels is not None:
-        xs = _phase_samples(t)
-        if xs.requires_grad and torch.is_grad_enabled():
-            out = _IntensityPhaseLevels.apply(xs, geom, groups, levels)
-        else:
-            plan = _plan_for(h, w, 2 * c // groups, wls, dx, dy, z, b, dev, tf_kind)
-            out = plan.evaluate_phase_levels(xs, levels, want_field=False)[1]
-    elif field_kind == _lib.FIELD_PHASE:
-        xs = _phase_samples(t)
-        if xs.requires_grad and torch.is_grad_enabled():
-            out = _IntensityPhase.apply(xs, geom, groups)
-        else:
-            plan = _plan_for(h, w, 2 * c // groups, wls, dx, dy, z, b, dev, tf_kind)
-            out = plan.evaluate_phase(xs, want_field=False)[1]
-    elif t.requires_grad and torch.is_grad_enabled():
-        out = _Intensity.apply(t, geom, groups, bool(save_field))
-    elif t.is_complex():
-        plan = _plan_for(h, w, 2 * c // groups, wls, dx, dy, z, b, dev, tf_kind)
-        fld, _ = plan.simulate_complex(t.to(torch.complex64).resolve_conj().resolve_neg().contiguous())
-        out = _plane_mean(fld, groups)
-    else:
-        cp = c + (c % 2)
-        plan = _plan_for(h, w, cp // groups, wls, dx, dy, z, b, dev, tf_kind)
-        out = plan.intensity_real(_pad_real(t, cp))
-        if cp != c:
-            out = out * (cp / c)
-    return out[0] if squeeze else out
+    t, spec, squeeze = _leaf_args(x, "intensity", tf, field, threshold, ste, ste_width, grid, origin, roi, levels, z=z,
+                                  save_field=bool(save_field))
+    return _intensity(t, spec, squeeze, "intensity")
 
 
 _METRIC_NAMES = {"mse": _lib.LOSS_MSE, "psnr": _lib.LOSS_PSNR}
-
-
-def _evaluate(t: torch.Tensor, target: torch.Tensor, geom, groups: int, want_field: bool, phase: bool = False):
-    """One launch set on a device tensor [B, C, H, W] (real: hbx_evaluate_real, complex:
-    hbx_evaluate_complex, phase samples: hbx_evaluate_phase) -> (plan, field | None, intensity |
-    None, chan_stats); the intensity is written only beside the field (the backward pass reads both)."""
-    wls, dx, dy, z, dev, tf_kind = geom
-    b, c, h, w = t.shape
-    if phase:
-        plan = _plan_for(h, w, 2 * c // groups, wls, dx, dy, z, b, dev, tf_kind)
-        field, inten, stats, _ = plan.evaluate_phase(t, target, want_field=want_field, want_intensity=want_field)
-    elif t.is_complex():
-        plan = _plan_for(h, w, 2 * c // groups, wls, dx, dy, z, b, dev, tf_kind)
-        field, inten, stats, _ = plan.evaluate_complex(
-            t.to(torch.complex64).resolve_conj().resolve_neg().contiguous(), target, want_field=want_field,
-            want_intensity=want_field)
-    else:
-        plan = _plan_for(h, w, c // groups, wls, dx, dy, z, b, dev, tf_kind)
-        field, inten, stats, _ = plan.evaluate_real(_pad_real(t, c), target, want_field=want_field,
-                                                    want_intensity=want_field)
-    return plan, field, inten, stats
-
-
-class _Loss(torch.autograd.Function):
-    """u -> the relative MSE or PSNR per env of I = mean_p |A u_p|^2 against a constant target.  The
-    forward pass is one launch set that leaves the field F = A u, I and the statistics; with
-    w = gL dL/dI = a I + c T (hbx_loss_weight: a, c per env from the statistics and the incoming
-    gradient gL), dL/du = A^H((2 / P) w F): one hbx_simulate_complex_weighted of F on the plan for -z,
-    as tt.intensity's backward pass.  A real u receives the real part, a complex u the field.
-    phase: t holds float32 phase samples x, u = exp(i pi x) (hbx_evaluate_phase), and the backward's
-    launch set is hbx_phase_backward, whose last pass writes dL/dx.  No double backward."""
-
-    @staticmethod
-    def forward(ctx, t, target, geom, groups, kind, rel, phase=False):
-        ctx.geom, ctx.groups, ctx.kind, ctx.rel, ctx.phase = geom, groups, kind, rel, phase
-        ctx.in_dtype, ctx.planes = t.dtype, t.shape[1]
-        plan, field, inten, stats = _evaluate(t, target, geom, groups, True, phase)
-        ctx.save_for_backward(field, inten, stats, target, *((t,) if phase else ()))
-        return plan.loss(stats, kind, rel)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_output):
-        wls, dx, dy, z, dev, tf_kind = ctx.geom
-        groups, c = ctx.groups, ctx.planes
-        field, inten, stats, target = ctx.saved_tensors[:4]
-        b, cf, h, w = field.shape
-        cplx = ctx.in_dtype.is_complex
-        adj = _plan_for(h, w, 2 * cf // groups, wls, dx, dy, -z, b, dev, tf_kind)
-        gl = grad_output.to(torch.float64).resolve_neg().contiguous()
-        wgt = adj.loss_weight(inten, target, stats, gl, ctx.kind, ctx.rel)   # the plan's G and N only
-        if ctx.phase:
-            grad = adj.phase_backward(field, ctx.saved_tensors[4], weight=wgt, scale=2.0 / (c // groups))
-            return grad, None, None, None, None, None, None
-        gf, gr = adj.simulate_complex(field, want_field=cplx, want_real=not cplx, weight=wgt,
-                                      scale=2.0 / (c // groups))
-        return (gf if cplx else gr).to(ctx.in_dtype), None, None, None, None, None, None
-
-
-class _LossPhaseLevels(torch.autograd.Function):
-    """_Loss's phase form for a leaf displayed at L phase levels, x float32 [B, C, H, W]: one
-    hbx_evaluate_phase_levels that leaves the field, I and the statistics.  Backward, the
-    straight-through estimator: hbx_loss_weight as _Loss, then one hbx_phase_levels_backward of the
-    field on the plan for -z, whose last pass writes dL/dq as dL/dx.  No double backward."""
-
-    @staticmethod
-    def forward(ctx, x, target, geom, groups, kind, rel, levels):
-        wls, dx, dy, z, dev, tf_kind = geom
-        b, c, h, w = x.shape
-        ctx.geom, ctx.groups, ctx.kind, ctx.rel, ctx.levels = geom, groups, kind, rel, levels
-        plan = _plan_for(h, w, 2 * c // groups, wls, dx, dy, z, b, dev, tf_kind)
-        field, inten, stats, _ = plan.evaluate_phase_levels(x, levels, target)
-        ctx.save_for_backward(field, inten, stats, target, x)
-        return plan.loss(stats, kind, rel)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_output):
-        wls, dx, dy, z, dev, tf_kind = ctx.geom
-        field, inten, stats, target, x = ctx.saved_tensors
-        b, c, h, w = x.shape
-        groups = ctx.groups
-        adj = _plan_for(h, w, 2 * c // groups, wls, dx, dy, -z, b, dev, tf_kind)
-        gl = grad_output.to(torch.float64).resolve_neg().contiguous()
-        wgt = adj.loss_weight(inten, target, stats, gl, ctx.kind, ctx.rel)   # the plan's G and N only
-        grad = adj.phase_levels_backward(field, x, ctx.levels, weight=wgt, scale=2.0 / (c // groups))
-        return grad, None, None, None, None, None, None
-
-
-class _LossThreshold(torch.autograd.Function):
-    """x -> the relative MSE or PSNR per env of I = mean_p |A (va + vb [x_p >= tau])|^2 against a
-    constant target, x float32 [B, C, H, W]: one hbx_evaluate_threshold that leaves the field, I
-    and the statistics.  Backward, the straight-through estimator: hbx_loss_weight as _Loss, then
-    one hbx_threshold_backward of the field on the plan for -z, whose last pass writes
-    vb s(x) Re(A^H((2 / P) w F)).  No double backward."""
-
-    @staticmethod
-    def forward(ctx, x, target, geom, groups, kind, rel, field_kind, ste_args):
-        wls, dx, dy, z, dev, tf_kind = geom
-        b, c, h, w = x.shape
-        ctx.geom, ctx.groups, ctx.kind, ctx.rel = geom, groups, kind, rel
-        ctx.field_kind, ctx.ste_args = field_kind, ste_args
-        plan = _plan_for(h, w, c // groups, wls, dx, dy, z, b, dev, tf_kind, field_kind)
-        field, inten, stats, _ = plan.evaluate_threshold(x, ste_args[0], target)
-        ctx.save_for_backward(field, inten, stats, target, x)
-        return plan.loss(stats, kind, rel)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_output):
-        wls, dx, dy, z, dev, tf_kind = ctx.geom
-        field, inten, stats, target, x = ctx.saved_tensors
-        b, c, h, w = x.shape
-        groups = ctx.groups
-        adj = _plan_for(h, w, 2 * c // groups, wls, dx, dy, -z, b, dev, tf_kind, ctx.field_kind)
-        gl = grad_output.to(torch.float64).resolve_neg().contiguous()
-        wgt = adj.loss_weight(inten, target, stats, gl, ctx.kind, ctx.rel)   # the plan's G and N only
-        grad = _threshold_backward(field, x, ctx.geom, groups, ctx.field_kind, ctx.ste_args, weight=wgt,
-                                   scale=2.0 / (c // groups))
-        return grad, None, None, None, None, None, None, None
 
 
 def loss(x, target, z: float, metric="mse", rel_scale="lsq", tf="asm", field="amplitude", threshold=None,
@@ -1148,272 +899,13 @@ def loss(x, target, z: float, metric="mse", rel_scale="lsq", tf="asm", field="am
     Neither the quantized samples nor exp(i pi q) nor the complex gradient is written."""
     kind = _switch(metric, _METRIC_NAMES, "metric")
     rel = _switch(rel_scale, _REL_NAMES, "rel_scale")
-    tf_kind = _switch(tf, _TF_NAMES, "tf")
-    field_kind = _switch(field, _FIELD_NAMES, "field")
-    ste_args = _ste_args(threshold, ste, ste_width, "loss")
-    meta = _meta_of(x)
-    wl = meta["wl"]
-    wls = tuple(float(v) for v in wl) if isinstance(wl, (tuple, list)) else (float(wl),)
-    groups = len(wls)
-    if not 1 <= groups <= _lib.MAX_GROUPS:
-        raise ValueError(f"loss: 1 to {_lib.MAX_GROUPS} wavelengths, got {groups}")
-    dx, dy = meta.get("dx", (hbx.plan.PIXEL_PITCH,) * 2)
-    t = x.as_subclass(torch.Tensor) if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
-    tg = target.as_subclass(torch.Tensor) if isinstance(target, torch.Tensor) else torch.as_tensor(np.asarray(target))
-    squeeze = t.dim() == 3
-    if squeeze:
-        t, tg = t.unsqueeze(0), tg.unsqueeze(0)
-    if t.dim() != 4:
-        raise ValueError(f"loss expects [B, C, H, W] or [C, H, W], got {tuple(x.shape)}")
-    b, c, h, w = t.shape
-    if c == 0 or c % groups:
-        raise ValueError(f"loss: {c} planes do not split into {groups} colour groups")
-    if t.is_complex() and field_kind != _lib.FIELD_AMPLITUDE:
-        raise ValueError("tt.loss: a complex field is used as it is (field=\"amplitude\")")
-    if not t.is_complex() and field_kind == _lib.FIELD_AMPLITUDE and (c // groups) % 2:
-        raise ValueError(f"loss: a real field needs an even number of planes per colour group, got {c // groups}")
-    if ste_args is not None:
-        if t.is_complex():
-            raise ValueError("tt.loss: threshold= needs a real leaf, got a complex field")
-        if (c // groups) % 2:
-            raise ValueError(f"loss: threshold= needs an even number of planes per colour group, got {c // groups}")
-    if tg.requires_grad:
-        raise ValueError("loss: the target is a constant (it requires grad)")
-    levels = _levels_arg(levels, False, t.is_complex(), field_kind, ste_args is not None, grid, "loss")
-    win = _window_args(grid, origin, roi, t.shape, t.is_complex(), field_kind, ste_args is not None, "loss")
-    th, tw = (h, w) if win is None else win[2][2:]     # the target has the roi's shape
-    if tg.is_complex() or tuple(tg.shape) != (b, groups, th, tw):
-        raise ValueError(f"loss: target must be real {(b, groups, th, tw)}, got {tuple(tg.shape)} {tg.dtype}")
-    if not torch.cuda.is_available():
-        raise RuntimeError("tt.loss needs a ROCm GPU (libhbx.so)")
-    if t.is_cuda:
-        dev = t.device.index
-    else:
-        dev = torch.cuda.current_device()
-        t = t.to(f"cuda:{dev}")
-    tg = tg.to(device=t.device, dtype=torch.float32).contiguous()
-    geom = (wls, dx, dy, z, dev, tf_kind)
-    if win is not None:
-        xs = _phase_samples(t)
-        if xs.requires_grad and torch.is_grad_enabled():
-            out = _WindowLoss.apply(xs, tg, geom, win, groups, kind, rel, field_kind, ste_args)
-        else:
-            plan = _window_plan(win, geom, c // groups, field_kind, b)
-            stats = _window_forward(plan, xs, win, ste_args, tg, want_field=False, want_intensity=False)[2]
-            out = plan.loss_window(stats, win[2], kind, rel)
-        return out[0] if squeeze else out
-    if ste_args is not None:
-        xs = _phase_samples(t)
-        if xs.requires_grad and torch.is_grad_enabled():
-            out = _LossThreshold.apply(xs, tg, geom, groups, kind, rel, field_kind, ste_args)
-        else:
-            plan = _plan_for(h, w, c // groups, wls, dx, dy, z, b, dev, tf_kind, field_kind)
-            stats = plan.evaluate_threshold(xs, ste_args[0], tg, want_field=False, want_intensity=False)[2]
-            out = plan.loss(stats, kind, rel)
-        return out[0] if squeeze else out
-    if levels is not None:
-        xs = _phase_samples(t)
-        if xs.requires_grad and torch.is_grad_enabled():
-            out = _LossPhaseLevels.apply(xs, tg, geom, groups, kind, rel, levels)
-        else:
-            plan = _plan_for(h, w, 2 * c // groups, wls, dx, dy, z, b, dev, tf_kind)
-            stats = plan.evaluate_phase_levels(xs, levels, tg, want_field=False, want_intensity=False)[2]
-            out = plan.loss(stats, kind, rel)
-        return out[0] if squeeze else out
-    phase = field_kind == _lib.FIELD_PHASE
-    if phase:
-        t = _phase_samples(t)
-    if t.requires_grad and torch.is_grad_enabled():
-        out = _Loss.apply(t, tg, geom, groups, kind, rel, phase)
-    else:
-        plan, _, _, stats = _evaluate(t, tg, geom, groups, False, phase)
-        out = plan.loss(stats, kind, rel)
-    return out[0] if squeeze else out
+    t, spec, squeeze = _leaf_args(x, "loss", tf, field, threshold, ste, ste_width, grid, origin, roi, levels, z=z)
+    return _loss(t, target, spec, squeeze, "loss", kind, rel)
 
 
 # ---------------------------------------------------------------------------------------------
 # Focal stacks: one hologram propagated to D depths (hbx_*_stack), outputs depth-major [D, B, ...]
 # ---------------------------------------------------------------------------------------------
-def _depths_arg(zs, what: str) -> Tuple[float, ...]:
-    """zs of the *_stack calls -> a tuple of 1 to 8 finite floats; anything else raises ValueError."""
-    try:
-        out = tuple(float(v) for v in zs)
-    except (TypeError, ValueError):
-        raise ValueError(f"{what}: zs is a sequence of depths (numbers), got {zs!r}") from None
-    if not 1 <= len(out) <= _lib.MAX_DEPTHS:
-        raise ValueError(f"{what}: 1 to {_lib.MAX_DEPTHS} depths, got {len(out)}")
-    if not all(np.isfinite(v) for v in out):
-        raise ValueError(f"{what}: every depth must be finite, got {out!r}")
-    return out
-
-
-class _StackSpec:
-    """What a *_stack call fixed before any GPU use: geometry, depths, the leaf kind and its parameters."""
-
-    def __init__(self, wls, dx, dy, tf_kind, zs, leaf, field_kind, ste_args, levels):
-        self.wls, self.dx, self.dy, self.tf_kind, self.zs, self.leaf = wls, dx, dy, tf_kind, zs, leaf
-        self.field_kind, self.ste_args, self.levels = field_kind, ste_args, levels
-        self.groups = len(wls)
-        self.dev = None                  # the device index, set once the input is on it (_stack_device)
-
-    def forward_plan(self, x):
-        b, c, h, w = x.shape
-        real_in = self.leaf in (_lib.LEAF_REAL, _lib.LEAF_THRESHOLD)
-        planes = (c if real_in else 2 * c) // self.groups
-        fk = self.field_kind if self.leaf == _lib.LEAF_THRESHOLD else _lib.FIELD_AMPLITUDE
-        return _plan_for(h, w, planes, self.wls, self.dx, self.dy, self.zs[0], b, self.dev, self.tf_kind, fk, self.zs)
-
-    def adjoint_plan(self, x):
-        """The plan for the negated depths, 2 C / G real planes per group (C complex ones), with the
-        leaf's field kind (its vb) for a thresholded leaf; B G D job slots, one chunk of the backward."""
-        b, c, h, w = x.shape
-        fk = self.field_kind if self.leaf == _lib.LEAF_THRESHOLD else _lib.FIELD_AMPLITUDE
-        nz = tuple(-v for v in self.zs)
-        return _plan_for(h, w, 2 * c // self.groups, self.wls, self.dx, self.dy, nz[0], b, self.dev, self.tf_kind, fk, nz,
-                         depth_slots=True)
-
-    def evaluate(self, x, target=None, want_field=True, want_intensity=True):
-        tau = self.ste_args[0] if self.ste_args is not None else 0.0
-        plan = self.forward_plan(x)
-        return (plan,) + plan.evaluate_stack(x, self.leaf, target, want_field=want_field, want_intensity=want_intensity,
-                                             levels=self.levels, threshold=tau)
-
-    def backward(self, x, values, weight=None, scale=1.0):
-        """One hbx_backward_stack: the leaf's gradient summed over the depths."""
-        kw = {}
-        if self.leaf == _lib.LEAF_THRESHOLD:
-            _, kw["surrogate"], kw["p0"], kw["p1"] = self.ste_args
-        needs = self.leaf in (_lib.LEAF_PHASE, _lib.LEAF_PHASE_LEVELS, _lib.LEAF_THRESHOLD)
-        return self.adjoint_plan(x).backward_stack(values, self.leaf, samples=x if needs else None, weight=weight,
-                                                   scale=scale, levels=self.levels, **kw)
-
-
-class _SimulateStack(torch.autograd.Function):
-    """x -> the fields A(z_d) u(x) of every depth, complex64 [D, B, C, H, W] (hbx_evaluate_stack).
-    Backward: one hbx_backward_stack of grad_output on the plan for the negated depths, whose last
-    pass sums the D adjoint propagations and writes the leaf's gradient once.  No double backward."""
-
-    @staticmethod
-    def forward(ctx, x, spec):
-        ctx.spec = spec
-        ctx.save_for_backward(x)
-        return spec.evaluate(x)[1]
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_output):
-        x, = ctx.saved_tensors
-        g = grad_output.to(torch.complex64).resolve_conj().resolve_neg().contiguous()
-        return ctx.spec.backward(x, g), None
-
-
-class _IntensityStack(torch.autograd.Function):
-    """x -> the plane-mean intensities of every depth, float32 [D, B, G, H, W], the per-depth fields
-    saved.  Backward: hbx_backward_stack of the saved fields with (2 / P) grad_output applied in the
-    first passes' loads.  No double backward."""
-
-    @staticmethod
-    def forward(ctx, x, spec):
-        ctx.spec = spec
-        _, field, inten, _ = spec.evaluate(x)
-        ctx.save_for_backward(x, field)
-        return inten
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_output):
-        x, field = ctx.saved_tensors
-        gi = grad_output.to(torch.float32).resolve_neg().contiguous()
-        return ctx.spec.backward(x, field, weight=gi, scale=2.0 / (x.shape[1] // ctx.spec.groups)), None
-
-
-class _LossStack(torch.autograd.Function):
-    """x -> the relative MSE or PSNR per env over the whole stack (hbx_evaluate_stack, hbx_loss_stack),
-    the per-depth fields, intensities and statistics saved.  Backward: hbx_loss_weight_stack (a I + c T
-    with one (a, c) per env for all depths), then one hbx_backward_stack.  No double backward."""
-
-    @staticmethod
-    def forward(ctx, x, target, spec, kind, rel):
-        ctx.spec, ctx.kind, ctx.rel = spec, kind, rel
-        plan, field, inten, stats = spec.evaluate(x, target)
-        ctx.save_for_backward(x, field, inten, stats, target)
-        return plan.loss_stack(stats, kind, rel)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_output):
-        x, field, inten, stats, target = ctx.saved_tensors
-        spec = ctx.spec
-        gl = grad_output.to(torch.float64).resolve_neg().contiguous()
-        wgt = spec.adjoint_plan(x).loss_weight_stack(inten, target, stats, gl, ctx.kind, ctx.rel)
-        grad = spec.backward(x, field, weight=wgt, scale=2.0 / (x.shape[1] // spec.groups))
-        return grad, None, None, None, None
-
-
-def _stack_args(x, zs, tf, field, threshold, ste, ste_width, levels, grid, origin, roi, what: str):
-    """The checks every *_stack call makes before any GPU use -> (t [B, C, H, W], the _StackSpec without
-    its device, whether x was 3-D)."""
-    if grid is not None or origin is not None or roi is not None:
-        raise ValueError(f"{what}: grid=, origin= and roi= are not accepted (focal stacks are not windowed)")
-    zs = _depths_arg(zs, what)
-    tf_kind = _switch(tf, _TF_NAMES, "tf")
-    field_kind = _switch(field, _FIELD_NAMES, "field")
-    ste_args = _ste_args(threshold, ste, ste_width, what)
-    meta = _meta_of(x)
-    wl = meta["wl"]
-    wls = tuple(float(v) for v in wl) if isinstance(wl, (tuple, list)) else (float(wl),)
-    groups = len(wls)
-    if not 1 <= groups <= _lib.MAX_GROUPS:
-        raise ValueError(f"{what}: 1 to {_lib.MAX_GROUPS} wavelengths, got {groups}")
-    dx, dy = meta.get("dx", (hbx.plan.PIXEL_PITCH,) * 2)
-    t = x.as_subclass(torch.Tensor) if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
-    squeeze = t.dim() == 3
-    if squeeze:
-        t = t.unsqueeze(0)
-    if t.dim() != 4:
-        raise ValueError(f"{what} expects [B, C, H, W] or [C, H, W], got {tuple(t.shape)}")
-    c = t.shape[1]
-    if c == 0 or c % groups:
-        raise ValueError(f"{what}: {c} planes do not split into {groups} colour groups")
-    if t.is_complex() and field_kind != _lib.FIELD_AMPLITUDE:
-        raise ValueError(f"{what}: a complex field is used as it is (field=\"amplitude\")")
-    if ste_args is not None and t.is_complex():
-        raise ValueError(f"{what}: threshold= needs a real leaf, got a complex field")
-    levels = _levels_arg(levels, False, t.is_complex(), field_kind, ste_args is not None, None, what)
-    if t.is_complex():
-        leaf = _lib.LEAF_COMPLEX
-    elif ste_args is not None:
-        leaf = _lib.LEAF_THRESHOLD
-    elif levels is not None:
-        leaf = _lib.LEAF_PHASE_LEVELS
-    elif field_kind == _lib.FIELD_PHASE:
-        leaf = _lib.LEAF_PHASE
-    else:
-        leaf = _lib.LEAF_REAL
-    if leaf in (_lib.LEAF_REAL, _lib.LEAF_THRESHOLD) and (c // groups) % 2:
-        raise ValueError(f"{what}: a real or thresholded leaf needs an even number of planes per colour group, "
-                         f"got {c // groups}")
-    if t.shape[2] != t.shape[3] or t.shape[2] not in _GRIDS:
-        raise ValueError(f"{what}: the hologram is one of the built grids {_GRIDS} squared, got {tuple(t.shape[2:])}")
-    return t, _StackSpec(wls, dx, dy, tf_kind, zs, leaf, field_kind, ste_args, levels), squeeze
-
-
-def _stack_device(t, spec):
-    """The device tensor the kernels read (by torch ops: autograd carries the casts back); names the
-    device in the spec."""
-    if not torch.cuda.is_available():
-        raise RuntimeError("tt.*_stack needs a ROCm GPU (libhbx.so)")
-    if t.is_cuda:
-        dev = t.device.index
-    else:
-        dev = torch.cuda.current_device()
-        t = t.to(f"cuda:{dev}")
-    spec.dev = dev
-    if spec.leaf == _lib.LEAF_COMPLEX:
-        return t.to(torch.complex64).resolve_conj().resolve_neg().contiguous()
-    return _phase_samples(t)
-
-
 def simulate_stack(x, zs, tf="asm", field="amplitude", threshold=None, ste="window", ste_width=0.5, levels=None,
                    grid=None, origin=None, roi=None) -> torch.Tensor:
     """The propagated field of one hologram at every depth of `zs` (1 to 8 distances, repeats and
@@ -1426,14 +918,9 @@ def simulate_stack(x, zs, tf="asm", field="amplitude", threshold=None, ste="wind
     the backward pass is one hbx_backward_stack on the plan for the negated depths, whose last pass
     adds the D adjoint propagations as it loads them and writes the leaf's gradient once.  grid=,
     origin= and roi= raise ValueError (focal stacks are not windowed).  No double backward."""
-    t, spec, squeeze = _stack_args(x, zs, tf, field, threshold, ste, ste_width, levels, grid, origin, roi,
-                                   "simulate_stack")
-    xs = _stack_device(t, spec)
-    if xs.requires_grad and torch.is_grad_enabled():
-        out = _SimulateStack.apply(xs, spec)
-    else:
-        out = spec.evaluate(xs)[1]
-    return out[:, 0] if squeeze else out
+    t, spec, squeeze = _leaf_args(x, "simulate_stack", tf, field, threshold, ste, ste_width, grid, origin, roi, levels,
+                                  zs=zs)
+    return _simulate(t, spec, squeeze, "simulate_stack")
 
 
 def intensity_stack(x, zs, tf="asm", field="amplitude", threshold=None, ste="window", ste_width=0.5, levels=None,
@@ -1442,14 +929,9 @@ def intensity_stack(x, zs, tf="asm", field="amplitude", threshold=None, ste="win
     arguments as simulate_stack's.  With a gradient request the per-depth fields are saved and the
     backward pass is one hbx_backward_stack with (2 / P) grad_output applied in the first passes'
     loads; without one no field is written."""
-    t, spec, squeeze = _stack_args(x, zs, tf, field, threshold, ste, ste_width, levels, grid, origin, roi,
-                                   "intensity_stack")
-    xs = _stack_device(t, spec)
-    if xs.requires_grad and torch.is_grad_enabled():
-        out = _IntensityStack.apply(xs, spec)
-    else:
-        out = spec.evaluate(xs, want_field=False)[2]
-    return out[:, 0] if squeeze else out
+    t, spec, squeeze = _leaf_args(x, "intensity_stack", tf, field, threshold, ste, ste_width, grid, origin, roi, levels,
+                                  zs=zs)
+    return _intensity(t, spec, squeeze, "intensity_stack")
 
 
 def loss_stack(x, target, zs, metric="mse", rel_scale="lsq", tf="asm", field="amplitude", threshold=None,
@@ -1466,27 +948,9 @@ def loss_stack(x, target, zs, metric="mse", rel_scale="lsq", tf="asm", field="am
     temporaries backward.  grid=, origin= and roi= raise ValueError.  No double backward."""
     kind = _switch(metric, _METRIC_NAMES, "metric")
     rel = _switch(rel_scale, _REL_NAMES, "rel_scale")
-    t, spec, squeeze = _stack_args(x, zs, tf, field, threshold, ste, ste_width, levels, grid, origin, roi,
-                                   "loss_stack")
-    tg = target.as_subclass(torch.Tensor) if isinstance(target, torch.Tensor) else torch.as_tensor(np.asarray(target))
-    if tg.dim() != (4 if squeeze else 5):
-        raise ValueError(f"loss_stack: target must be [D, B, G, H, W] ([D, G, H, W] for a 3-D x), got {tuple(tg.shape)}")
-    if squeeze:
-        tg = tg.unsqueeze(1)
-    b, _, h, w = t.shape
-    want = (len(spec.zs), b, spec.groups, h, w)
-    if tg.is_complex() or tuple(tg.shape) != want:
-        raise ValueError(f"loss_stack: target must be real {want}, got {tuple(tg.shape)} {tg.dtype}")
-    if tg.requires_grad:
-        raise ValueError("loss_stack: the target is a constant (it requires grad)")
-    xs = _stack_device(t, spec)
-    tg = tg.to(device=xs.device, dtype=torch.float32).contiguous()
-    if xs.requires_grad and torch.is_grad_enabled():
-        out = _LossStack.apply(xs, tg, spec, kind, rel)
-    else:
-        plan, _, _, stats = spec.evaluate(xs, tg, want_field=False, want_intensity=False)
-        out = plan.loss_stack(stats, kind, rel)
-    return out[0] if squeeze else out
+    t, spec, squeeze = _leaf_args(x, "loss_stack", tf, field, threshold, ste, ste_width, grid, origin, roi, levels,
+                                  zs=zs)
+    return _loss(t, target, spec, squeeze, "loss_stack", kind, rel)
 
 
 def relativeLoss(x: torch.Tensor, y, fn: Callable, rel_scale="lsq") -> torch.Tensor:
