@@ -545,6 +545,7 @@ struct FullRequest {
   int phase_levels = 0;                // (hbx_*_phase_levels) L: phase_values, or grad_samples of the phase
                                        // gradient, are quantized to L levels as they are loaded; 0: continuous
   const float* target = nullptr;       // [n][G][N][N]; null: no statistics
+  const float* pixel_weight = nullptr; // (hbx_evaluate_pw) [n][G][N][N] f32 per-pixel loss weight, with a target only
   const int32_t* env_ids = nullptr;    // absolute env ids into every buffer (mask input only); null: 0 .. n - 1
   int n = 0;
   // outputs, all nullable
@@ -639,6 +640,7 @@ int propagate_full(hbx_plan_t p, const FullRequest& r, void* stream) {
     c.phase_values = at(r.phase_values, s_cplx);
     c.phase_levels = r.phase_levels;
     c.target = at(r.target, s_img);
+    c.pixel_weight = at(r.pixel_weight, s_img);
     c.inten_out = direct ? at(r.intensity, s_img) : (r.intensity ? p->job_inten : nullptr);
     c.field_out = at(r.field, s_field);
     c.complex_field = at(r.complex_field, s_cout);
@@ -956,11 +958,17 @@ int check_stack_plan(hbx_plan_t p, bool complex_field) {
 bool leaf_kind_known(int32_t kind) { return kind >= HBX_LEAF_REAL && kind <= HBX_LEAF_PHASE_LEVELS; }
 }  // namespace
 
-int hbx_evaluate_stack(hbx_plan_t p, const void* values, const hbx_leaf_t* leaf, const float* target, int32_t n_env,
-                       float* field, float* intensity, double* chan_stats, void* stream) {
+namespace {
+// hbx_evaluate_stack, and hbx_evaluate_stack_pw with weighted = true: pixel_weight [D][B][G][N][N], depth d's
+// last pass takes depth d's block as it takes depth d's target block
+int evaluate_stack(hbx_plan_t p, const void* values, const hbx_leaf_t* leaf, const float* target,
+                   const float* pixel_weight, bool weighted, int32_t n_env, float* field, float* intensity,
+                   double* chan_stats, void* stream) {
   HBX_ENTER(p, n_env, "n_env");
   if (!leaf || !leaf_kind_known(leaf->kind)) return fail(HBX_ERR_INVALID, "leaf: a known HBX_LEAF_* kind");
   if (!values) return fail(HBX_ERR_INVALID, "null buffer");
+  if (weighted && (!target || !pixel_weight || !chan_stats))
+    return fail(HBX_ERR_INVALID, "null buffer: target, pixel_weight and chan_stats are required");
   const bool real_in = leaf->kind == HBX_LEAF_REAL || leaf->kind == HBX_LEAF_THRESHOLD;
   if (leaf->kind == HBX_LEAF_PHASE_LEVELS) {
     if (int rc = check_levels(leaf->levels)) return rc;
@@ -1002,6 +1010,7 @@ int hbx_evaluate_stack(hbx_plan_t p, const void* values, const hbx_leaf_t* leaf,
         default: c.phase_values = v; break;
       }
       c.target = at(target, s_img);
+      c.pixel_weight = at(pixel_weight, s_img);
       if (real_in) {
         c.inten_out = intensity ? p->job_inten : nullptr;
         c.field_out = at(reinterpret_cast<float2*>(field), s_fld);
@@ -1021,6 +1030,47 @@ int hbx_evaluate_stack(hbx_plan_t p, const void* values, const hbx_leaf_t* leaf,
     }
   }
   return HBX_OK;
+}
+}  // namespace
+
+int hbx_evaluate_stack(hbx_plan_t p, const void* values, const hbx_leaf_t* leaf, const float* target, int32_t n_env,
+                       float* field, float* intensity, double* chan_stats, void* stream) {
+  return evaluate_stack(p, values, leaf, target, nullptr, false, n_env, field, intensity, chan_stats, stream);
+}
+
+int hbx_evaluate_stack_pw(hbx_plan_t p, const void* values, const hbx_leaf_t* leaf, const float* target,
+                          const float* pixel_weight, int32_t n_env, float* field, float* intensity,
+                          double* chan_stats, void* stream) {
+  return evaluate_stack(p, values, leaf, target, pixel_weight, true, n_env, field, intensity, chan_stats, stream);
+}
+
+// the single-depth forward of every sample leaf kind with a per-pixel loss weight: the matching evaluate
+// call's request with the weight set
+int hbx_evaluate_pw(hbx_plan_t p, const void* values, const hbx_leaf_t* leaf, const float* target,
+                    const float* pixel_weight, int32_t n_env, float* field, float* intensity, double* chan_stats,
+                    void* stream) {
+  HBX_ENTER(p, n_env, "n_env");
+  if (!leaf || !leaf_kind_known(leaf->kind)) return fail(HBX_ERR_INVALID, "leaf: a known HBX_LEAF_* kind");
+  if (leaf->kind == HBX_LEAF_PHASE_LEVELS) {
+    if (int rc = check_levels(leaf->levels)) return rc;
+  }
+  if (!values || !target || !pixel_weight || !chan_stats)
+    return fail(HBX_ERR_INVALID, "null buffer: values, target, pixel_weight and chan_stats are required");
+  const bool real_in = leaf->kind == HBX_LEAF_REAL || leaf->kind == HBX_LEAF_THRESHOLD;
+  if (int rc = check_real_plan(p, !real_in)) return rc;
+  FullRequest r;
+  switch (leaf->kind) {
+    case HBX_LEAF_THRESHOLD: r.binarize = true; r.threshold = leaf->threshold;   // fallthrough
+    case HBX_LEAF_REAL: r.real_values = static_cast<const float*>(values); break;
+    case HBX_LEAF_COMPLEX: r.complex_values = static_cast<const float2*>(values); break;
+    case HBX_LEAF_PHASE_LEVELS: r.phase_levels = leaf->levels;   // fallthrough
+    default: r.phase_values = static_cast<const float*>(values); break;
+  }
+  r.target = target; r.pixel_weight = pixel_weight; r.n = n_env;
+  if (real_in) r.field = reinterpret_cast<float2*>(field);
+  else { r.complex_field = reinterpret_cast<float2*>(field); r.complex_stats = true; }
+  r.intensity = intensity; r.chan_stats = chan_stats;
+  return propagate_full(p, r, stream);
 }
 
 int hbx_backward_stack(hbx_plan_t p, const float* values, const float* weight, float scale, const hbx_leaf_t* leaf,
@@ -1175,6 +1225,70 @@ int hbx_loss_weight_stack(hbx_plan_t p, const float* intensity, const float* tar
   HBX_HIP(hbx::launch_loss_weight_stack(intensity, target, chan_stats, grad_loss, n_env, p->pd.G, D,
                                         (size_t)p->pd.N * p->pd.N, kind, rel_scale, (double)D * pixel_count(p), weight,
                                         (hipStream_t)stream));
+  return HBX_OK;
+}
+
+namespace {
+// the n_depths argument of the hbx_*_pw loss calls: 0 = a single depth (D = 1), else the plan's depth count
+int resolve_pw_depths(hbx_plan_t p, int32_t n_depths, int* D) {
+  if (n_depths != 0 && (p->pd.n_depths < 1 || n_depths != p->pd.n_depths))
+    return fail(HBX_ERR_INVALID, "n_depths: 0 (a single depth) or the depths set on the plan (hbx_plan_set_depths)");
+  *D = n_depths ? n_depths : 1;
+  return HBX_OK;
+}
+}  // namespace
+
+int hbx_pixel_weight_sum(hbx_plan_t p, const float* pixel_weight, int32_t n_env, int32_t n_depths, double* weight_sum,
+                         void* stream) {
+  int rc = check_plan(p);
+  if (rc) return rc;
+  int D;
+  if ((rc = resolve_pw_depths(p, n_depths, &D))) return rc;
+  if (n_env <= 0) return n_env == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "n_env");
+  if (!pixel_weight || !weight_sum) return fail(HBX_ERR_INVALID, "null buffer");
+  HBX_HIP(hipSetDevice(p->device));
+  // a chunk of envs at a time through the plan's row-block partials (stream-ordered scratch, as the passes use
+  // it): G row_blocks 3 doubles per env.  The slices per env depend on the geometry alone, so the order of the
+  // additions -- and the bits -- do not depend on max_jobs
+  const PlanDev& pd = p->pd;
+  const int per_env = pd.G * (pd.R ? pd.N / (256 / pd.R) : pd.N / 8) * 3;
+  const int K = per_env < 64 ? per_env : 64;
+  const int chunk = p->max_jobs / pd.G;
+  for (int i0 = 0; i0 < n_env; i0 += chunk)
+    HBX_HIP(hbx::launch_pixel_weight_sum(pixel_weight, i0, std::min(chunk, n_env - i0), n_env, pd.G, D,
+                                         (size_t)pd.N * pd.N, pd.partial, K, weight_sum, (hipStream_t)stream));
+  return HBX_OK;
+}
+
+int hbx_loss_pw(hbx_plan_t p, const double* chan_stats, const double* weight_sum, int32_t n_env, int32_t n_depths,
+                int32_t kind, int32_t rel_scale, double* loss, void* stream) {
+  int rc = check_plan(p);
+  if (rc) return rc;
+  if ((rc = check_loss_kind(kind, rel_scale))) return rc;
+  int D;
+  if ((rc = resolve_pw_depths(p, n_depths, &D))) return rc;
+  if (n_env <= 0) return n_env == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "n_env");
+  if (!chan_stats || !weight_sum || !loss) return fail(HBX_ERR_INVALID, "null buffer");
+  HBX_HIP(hipSetDevice(p->device));
+  HBX_HIP(hbx::launch_loss_pw(chan_stats, weight_sum, n_env, p->pd.G, D, kind, rel_scale, p->optics.peak, loss,
+                              (hipStream_t)stream));
+  return HBX_OK;
+}
+
+int hbx_loss_weight_pw(hbx_plan_t p, const float* intensity, const float* target, const float* pixel_weight,
+                       const double* chan_stats, const double* weight_sum, const double* grad_loss, int32_t n_env,
+                       int32_t n_depths, int32_t kind, int32_t rel_scale, float* weight, void* stream) {
+  int rc = check_plan(p);
+  if (rc) return rc;
+  if ((rc = check_loss_kind(kind, rel_scale))) return rc;
+  int D;
+  if ((rc = resolve_pw_depths(p, n_depths, &D))) return rc;
+  if (n_env <= 0) return n_env == 0 ? HBX_OK : fail(HBX_ERR_INVALID, "n_env");
+  if (!intensity || !target || !pixel_weight || !chan_stats || !weight_sum || !weight)
+    return fail(HBX_ERR_INVALID, "null buffer");
+  HBX_HIP(hipSetDevice(p->device));
+  HBX_HIP(hbx::launch_loss_weight_pw(intensity, target, pixel_weight, chan_stats, weight_sum, grad_loss, n_env, p->pd.G,
+                                     D, (size_t)p->pd.N * p->pd.N, kind, rel_scale, weight, (hipStream_t)stream));
   return HBX_OK;
 }
 

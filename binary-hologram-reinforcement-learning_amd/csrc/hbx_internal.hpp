@@ -378,6 +378,13 @@ struct PassCall {
   int stack_skip_first = 0;
   int stack_skip_last = 0;
   int stack_slot0 = 0;
+  // (extension, hbx_evaluate_pw / hbx_evaluate_stack_pw) a non-negative per-pixel loss weight v,
+  // [env][G][N][N] f32 addressed as target: the last pass's three sums become sum v I T, sum v I^2 and
+  // sum v T^2 (rowinv_epilogue_pw); the intensity and the field stay the unweighted ones.  Only with a
+  // target and statistics on the f32 sample paths (complex or phase in: complex_stats and no real part);
+  // never with a window, plane cache, actions, walk, reconcile or env-major output (check_pass_call).
+  // Null: the launches a call ran before
+  const float* pixel_weight = nullptr;
 };
 // whether any focal-stack field is set
 inline bool pass_stack(const PassCall& c) {
@@ -486,6 +493,15 @@ inline hipError_t check_pass_call(const PlanDev& pd, const PassCall& c) {
     ok = ok && !(c.stack_skip_first && (c.stack_skip_last || c.stack_slot0 != 0));
     ok = ok && (!c.stack_slot0 || c.stack_skip_last);
     if (c.stack_skip_last) ok = ok && c.complex_values && !complex_out && !grad_out && !c.target && !c.inten_out;
+  }
+  // a per-pixel loss weight: sample input on the f32 path, with a target and the reduced statistics (complex or
+  // phase in: the statistics form, no real part, no gradient); no window, plane cache, actions, walk or
+  // reconcile, nothing env-major, and not a piece that stops in front of the last pass
+  if (c.pixel_weight) {
+    ok = ok && !c.mask && f32 && c.target && !c.skip_reduce;
+    ok = ok && (!pass_complex(c) || (c.complex_stats && !c.real_part && !grad_out));
+    ok = ok && !c.windowed && !planes && !c.actions && !walk && !c.rc_pending && !c.inten_by_env;
+    ok = ok && !c.stack_skip_last;
   }
   return ok ? hipSuccess : hipErrorInvalidValue;
 }
@@ -744,5 +760,16 @@ hipError_t launch_loss_stack(const double* chan_stats, int n, int G, int D, int 
 hipError_t launch_loss_weight_stack(const float* inten, const float* target, const double* chan_stats,
                                     const double* grad_loss, int n, int G, int D, size_t hw, int kind, int rel_scale,
                                     double count, float* weight, hipStream_t st);
+// (extension, per-pixel loss weights) hbx_pack.hip: weight_sum[n] = the sum of pixel_weight[D][n][G][hw] over an
+// env's D G images (d outer, g inner), f64 in a fixed order, a chunk of n envs from env b0 at a time in K slices
+// per env through n K doubles of scratch; then the loss and its gradient with weight_sum[b]
+// in the place of the pixel count, weight[d][b] = pixel_weight[d][b] * (a_b I + c_b T).  D = 1: a single depth
+hipError_t launch_pixel_weight_sum(const float* pixel_weight, int b0, int n, int n_total, int G, int D, size_t hw,
+                                   double* part, int K, double* weight_sum, hipStream_t st);
+hipError_t launch_loss_pw(const double* chan_stats, const double* weight_sum, int n, int G, int D, int kind,
+                          int rel_scale, double peak, double* loss, hipStream_t st);
+hipError_t launch_loss_weight_pw(const float* inten, const float* target, const float* pixel_weight,
+                                 const double* chan_stats, const double* weight_sum, const double* grad_loss, int n,
+                                 int G, int D, size_t hw, int kind, int rel_scale, float* weight, hipStream_t st);
 
 }  // namespace hbx

@@ -459,4 +459,181 @@ hipError_t launch_rel_stats(const void* x, const void* y, int kind, int64_t n, d
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Per-pixel loss weights (hbx_pixel_weight_sum, hbx_loss_pw, hbx_loss_weight_pw; include/hbx.h)
+// ---------------------------------------------------------------------------
+// Behind every other kernel of this file.  The arrays are depth-major [D][n][..] as a focal stack's; D = 1 is the
+// single depth, where env_sums_stack runs env_sums' additions in env_sums' order.
+namespace {
+
+constexpr int kPwSumNT = 256;
+
+// hbx_pixel_weight_sum, first step: an env's D G images of pixel_weight in K slices.  Workgroup (b, k) adds slice
+// k of depth 0's G hw floats (g inner), then of depth 1's, ..: thread t its elements t, t + NT, .. of the slice in
+// f64, then the wave's lanes by xor shuffles, then the four waves in order -> part[b K + k].  A fixed order for a
+// given K, bitwise reproducible, and exact whenever every partial sum is representable (a 0 / 1 indicator: the
+// count of ones).  VEC: 16-byte pieces.  b0, n_total: the chunk's first env and the envs of the whole array
+template <bool VEC>
+__global__ __launch_bounds__(kPwSumNT) void k_pixel_weight_part(const float* __restrict__ pw, int b0, int n_total,
+                                                                int D, int64_t n1, int K, double* __restrict__ part) {
+  __shared__ double s[kPwSumNT / 64];
+  const int b = blockIdx.x / K, k = blockIdx.x % K;
+  const int64_t nv = VEC ? n1 / 4 : n1;             // pieces per depth
+  const int64_t per = (nv + K - 1) / K;
+  const int64_t lo = (int64_t)k * per, hi = lo + per < nv ? lo + per : nv;
+  double a = 0.0;
+  for (int d = 0; d < D; ++d) {
+    const float* img = pw + ((int64_t)d * n_total + b0 + b) * n1;
+    if constexpr (VEC) {
+      const float4* img4 = reinterpret_cast<const float4*>(img);
+      for (int64_t i = lo + threadIdx.x; i < hi; i += kPwSumNT) {
+        const float4 x = img4[i];
+        a += (double)x.x; a += (double)x.y; a += (double)x.z; a += (double)x.w;
+      }
+    } else {
+      for (int64_t i = lo + threadIdx.x; i < hi; i += kPwSumNT) a += (double)img[i];
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = a;
+  __syncthreads();
+  if (threadIdx.x == 0) part[(int64_t)b * K + k] = ((s[0] + s[1]) + s[2]) + s[3];
+}
+
+// second step: env b's K partials in order -> weight_sum[b0 + b]
+__global__ void k_pixel_weight_final(const double* __restrict__ part, int n, int K, double* __restrict__ weight_sum) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= n) return;
+  double w = 0.0;
+  for (int k = 0; k < K; ++k) w += part[(int64_t)b * K + k];
+  weight_sum[b] = w;
+}
+
+// dMSE/dI = v (a I + c T): loss_weight_coeffs' expressions on the sums given, with the weight sum W as the
+// count; an env with W = 0 (an all-zero weight) has nothing to differentiate: a = c = 0, never a NaN
+__device__ __forceinline__ void loss_pw_coeffs(double sxy, double sxx, double syy, double count, double up, int kind,
+                                               int rel_scale, float& af, float& cf) {
+  double a, c;
+  if (rel_scale == HBX_REL_LSQ) {
+    const double s = sxx > 0.0 ? sxy / sxx : 0.0;   // no scale to differentiate: a = c = 0
+    a = 2.0 * s * s / count;
+    c = sxx > 0.0 ? -2.0 * s / count : 0.0;
+  } else {
+    a = 2.0 / count;
+    c = -2.0 / count;
+  }
+  if (kind == HBX_LOSS_PSNR) {
+    const double mse = rel_mse_from(sxy, sxx, syy, count, rel_scale);
+    const double f = mse > 0.0 ? -(10.0 / 2.302585092994045684) / mse : 0.0;
+    a *= f;
+    c *= f;
+  }
+  if (count == 0.0) { a = 0.0; c = 0.0; }
+  af = (float)(a * up), cf = (float)(c * up);
+}
+
+// hbx_loss_pw: k_loss_stack's expressions with weight_sum[b] as the count; W = 0: MSE 0, PSNR +inf
+__global__ void k_loss_pw(const double* __restrict__ chan_stats, const double* __restrict__ weight_sum, int n, int G,
+                          int D, int kind, int rel_scale, double peak, double* __restrict__ loss) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= n) return;
+  double sxy, sxx, syy;
+  env_sums_stack(chan_stats, b, n, G, D, sxy, sxx, syy);
+  const double count = weight_sum[b];
+  if (count == 0.0) {
+    loss[b] = kind == HBX_LOSS_PSNR ? (double)INFINITY : 0.0;
+    return;
+  }
+  loss[b] = kind == HBX_LOSS_PSNR ? psnr_from(sxy, sxx, syy, count, rel_scale, peak)
+                                  : rel_mse_from(sxy, sxx, syy, count, rel_scale);
+}
+
+// hbx_loss_weight_pw: weight[d][b] = v[d][b] * fmaf(a_b, I, c_b T) -- k_loss_weight_stack's coefficients and fmaf,
+// then one more multiply -- indexed as k_loss_weight_stack indexes the images.  V4 = float4 (16-byte pieces) or
+// float (any count, any alignment)
+template <class V4>
+__global__ __launch_bounds__(256) void k_loss_weight_pw(const V4* __restrict__ inten, const V4* __restrict__ target,
+                                                        const V4* __restrict__ pw,
+                                                        const double* __restrict__ chan_stats,
+                                                        const double* __restrict__ weight_sum,
+                                                        const double* __restrict__ grad_loss, int n, int G, int D,
+                                                        int64_t nv, unsigned bx, int kind, int rel_scale,
+                                                        V4* __restrict__ weight) {
+  const int db = blockIdx.x / bx;   // d * n + b
+  const int b = db % n;
+  double sxy, sxx, syy;
+  env_sums_stack(chan_stats, b, n, G, D, sxy, sxx, syy);
+  float af, cf;
+  loss_pw_coeffs(sxy, sxx, syy, weight_sum[b], grad_loss ? grad_loss[b] : 1.0, kind, rel_scale, af, cf);
+  const int64_t base = (int64_t)db * nv;
+  const int64_t i0 = (int64_t)(blockIdx.x % bx) * (256 * kLossPer) + threadIdx.x;
+  V4 I[kLossPer], T[kLossPer], v[kLossPer];
+#pragma unroll
+  for (int k = 0; k < kLossPer; ++k) {
+    const int64_t i = i0 + 256 * k;
+    if (i < nv) {
+      I[k] = inten[base + i];
+      T[k] = target[base + i];
+      v[k] = pw[base + i];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < kLossPer; ++k) {
+    const int64_t i = i0 + 256 * k;
+    if (i < nv) {
+      if constexpr (sizeof(V4) == 16)
+        weight[base + i] = make_float4(v[k].x * fmaf(af, I[k].x, cf * T[k].x), v[k].y * fmaf(af, I[k].y, cf * T[k].y),
+                                       v[k].z * fmaf(af, I[k].z, cf * T[k].z), v[k].w * fmaf(af, I[k].w, cf * T[k].w));
+      else
+        weight[base + i] = v[k] * fmaf(af, I[k], cf * T[k]);
+    }
+  }
+}
+
+}  // namespace
+
+// n envs from env b0 of an array of n_total in K slices each; part: scratch of n K doubles
+hipError_t launch_pixel_weight_sum(const float* pixel_weight, int b0, int n, int n_total, int G, int D, size_t hw,
+                                   double* part, int K, double* weight_sum, hipStream_t st) {
+  const int64_t n1 = (int64_t)G * (int64_t)hw;
+  const bool vec = n1 % 4 == 0 && (reinterpret_cast<uintptr_t>(pixel_weight) & 15) == 0;
+  if (K < 1) return hipErrorInvalidValue;
+  if (vec)
+    hipLaunchKernelGGL(k_pixel_weight_part<true>, dim3((unsigned)n * K), dim3(kPwSumNT), 0, st, pixel_weight, b0,
+                       n_total, D, n1, K, part);
+  else
+    hipLaunchKernelGGL(k_pixel_weight_part<false>, dim3((unsigned)n * K), dim3(kPwSumNT), 0, st, pixel_weight, b0,
+                       n_total, D, n1, K, part);
+  hipLaunchKernelGGL(k_pixel_weight_final, dim3((n + 63) / 64), dim3(64), 0, st, part, n, K, weight_sum + b0);
+  return hipGetLastError();
+}
+
+hipError_t launch_loss_pw(const double* chan_stats, const double* weight_sum, int n, int G, int D, int kind,
+                          int rel_scale, double peak, double* loss, hipStream_t st) {
+  hipLaunchKernelGGL(k_loss_pw, dim3((n + 63) / 64), dim3(64), 0, st, chan_stats, weight_sum, n, G, D, kind, rel_scale,
+                     peak, loss);
+  return hipGetLastError();
+}
+
+hipError_t launch_loss_weight_pw(const float* inten, const float* target, const float* pixel_weight,
+                                 const double* chan_stats, const double* weight_sum, const double* grad_loss, int n,
+                                 int G, int D, size_t hw, int kind, int rel_scale, float* weight, hipStream_t st) {
+  const int64_t n1 = (int64_t)G * (int64_t)hw;
+  const auto misaligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) != 0; };
+  if (n1 % 4 != 0 || misaligned(inten) || misaligned(target) || misaligned(pixel_weight) || misaligned(weight)) {
+    const unsigned bx1 = (unsigned)((n1 + 256 * kLossPer - 1) / (256 * kLossPer));
+    hipLaunchKernelGGL(k_loss_weight_pw<float>, dim3(bx1 * (unsigned)n * (unsigned)D), dim3(256), 0, st, inten, target,
+                       pixel_weight, chan_stats, weight_sum, grad_loss, n, G, D, n1, bx1, kind, rel_scale, weight);
+    return hipGetLastError();
+  }
+  const int64_t n4 = n1 / 4;
+  const unsigned bx = (unsigned)((n4 + 256 * kLossPer - 1) / (256 * kLossPer));
+  hipLaunchKernelGGL(k_loss_weight_pw<float4>, dim3(bx * (unsigned)n * (unsigned)D), dim3(256), 0, st,
+                     reinterpret_cast<const float4*>(inten), reinterpret_cast<const float4*>(target),
+                     reinterpret_cast<const float4*>(pixel_weight), chan_stats, weight_sum, grad_loss, n, G, D, n4, bx,
+                     kind, rel_scale, reinterpret_cast<float4*>(weight));
+  return hipGetLastError();
+}
+
 }  // namespace hbx

@@ -1467,6 +1467,10 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_walk_anneal(const JobDesc* __
   walk_planes_arrive<true>(wk, reinterpret_cast<char*>(scratch));
 }
 
+// (pixel weights) the weighted last passes and their pick, behind every other kernel of this file
+template <int R>
+static void launch_last_pw(const PlanDev& pd, const PassCall& c, float2* ws_b, unsigned blocks, hipStream_t st);
+
 template <int R, int SK>
 static hipError_t launch_passes(const PlanDev& pd, const PassCall& c, hipStream_t st) {
   constexpr int N = R * R;
@@ -1535,7 +1539,9 @@ static hipError_t launch_passes(const PlanDev& pd, const PassCall& c, hipStream_
 
   const unsigned blocks = (unsigned)n_jobs * kRowBlocks;
   if (tm) tm->begin(2, st);
-  if (pass_complex(c)) {   // recombine each plane pair, or a leaf's gradient instead (pick_last_pass_cplx)
+  if (c.pixel_weight) {    // the weighted statistics forms, only when the pointer is set
+    launch_last_pw<R>(pd, c, ws_b, blocks, st);
+  } else if (pass_complex(c)) {   // recombine each plane pair, or a leaf's gradient instead (pick_last_pass_cplx)
     const auto k = pick_last_pass_cplx<SampleKernels<R>>(pass_grad_kind(c), c.complex_stats != 0,
                                                          c.windowed != 0);
     launch_kernel(k, blocks, NT, st, jobs, ws_b, pd.tw, P, pd.G, c.complex_field, c.real_part, tg.rows, tg.mask,
@@ -1778,6 +1784,334 @@ hipError_t run_stack_last(const PlanDev& pd, const PassCall& c, int n_depths, in
     case 16: return launch_stack_last<16>(pd, c, n_depths, slot_stride, st);
     case 8: return launch_stack_last<8>(pd, c, n_depths, slot_stride, st);
     default: return hipErrorInvalidValue;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Per-pixel loss weights (hbx_evaluate_pw / hbx_evaluate_stack_pw, EXTENSION): the weighted last passes
+// ---------------------------------------------------------------------------
+// The statistics-producing last passes of the sample paths with rowinv_epilogue_pw (hbx_rowinv.hpp) as their
+// tail: the weight row of (env, group, y) enters the three f64 sums, and everything in front of the tail -- the
+// loads, the inverse row FFTs, |U|^2, the field stores -- is the sibling's arithmetic in the sibling's order, so
+// the field and the intensity are its bits.  Each is its sibling's general form without the plane cache, walk,
+// reconcile, window, target-ahead and env-major code (check_pass_call refuses a weight with any of them), with an
+// argument list of its own, named and instantiated behind every other kernel of this file, so that none of them
+// moves (tools/isa_cmp.py).  k_rowinv_d_pw: k_rowinv_d (N = 1024 / 256), field_out nullable.
+template <int R>
+__global__ __launch_bounds__(256, 2) void k_rowinv_d_pw(const JobDesc* __restrict__ jobs,
+                                                        const float2* __restrict__ ws_b,
+                                                        const float* __restrict__ target,
+                                                        const float* __restrict__ pixel_weight,
+                                                        const float2* __restrict__ tw_glob, int P, int G,
+                                                        double* __restrict__ partial, float* __restrict__ inten_out,
+                                                        float2* __restrict__ field_out) {
+  constexpr int N = R * R, GPB = 256 / R, RB = N / GPB;
+  __shared__ float2 tw[N];
+  __shared__ float2 scratch[GPB * R * (R + 1)];
+  __shared__ double red[GPB][3];
+  for (int i = threadIdx.x; i < N; i += 256) tw[i] = tw_glob[i];
+
+  const int grp = threadIdx.x / R;
+  const int t = threadIdx.x % R;
+  const int bid = xcd_pair<RB>(blockIdx.x);
+  const int rb = bid % RB;
+  const int j = bid / RB;
+  const JobDesc jb = jobs[j];
+  if (jb.env < 0) {   // uniform per block
+    rowinv_zero_partial(partial, j, RB, rb);
+    return;
+  }
+  const int y = rb * GPB + grp;
+  constexpr int PLB = N * N;                 // float2 per B plane
+  const __amdgpu_buffer_rsrc_t rs = plane_rsrc(ws_b + (size_t)j * P * PLB, (unsigned)((size_t)P * PLB * 8));
+  const RowinvLanes<R> ln(y, t);
+  auto load_plane = [&](pk2 (&v)[R], int p) { rowinv_load_plane(v, ln, rs, p); };
+  float acc[R];
+#pragma unroll
+  for (int k = 0; k < R; ++k) acc[k] = 0.0f;
+  const PaddedScratch<R> sc{scratch + grp * R * (R + 1)};
+  auto finish_plane = [&](pk2 (&v)[R], int p) {   // plane_out without the plane cache
+    fft_group<R, true>(v, t, sc, tw);
+#pragma unroll
+    for (int k = 0; k < R; ++k) acc[k] += fmaf(v[k].x, v[k].x, v[k].y * v[k].y);
+    if (field_out) {
+      float2* frow = field_out + (((size_t)jb.env * G * P + jb.group * P + p) * N + y) * N;
+#pragma unroll
+      for (int k = 0; k < R; ++k) frow[t + R * k] = make_float2(v[k].x, v[k].y);
+    }
+  };
+  pk2 va[R];
+  load_plane(va, 0);
+  __syncthreads();  // tw visible
+  if constexpr (R == 16) {   // N = 256: the next plane in flight under this one's FFT, as k_rowinv_d
+    pk2 vb[R];
+#pragma unroll 1
+    for (int p = 0; p < P; p += 2) {         // P is even (hbx_plan_create)
+      load_plane(vb, p + 1);
+      finish_plane(va, p);
+      if (p + 2 < P) load_plane(va, p + 2);   // uniform: no plane is read twice
+      finish_plane(vb, p + 1);
+    }
+  } else {
+#pragma unroll 1
+    for (int p = 0; p < P; ++p) {
+      finish_plane(va, p);
+      if (p + 1 < P) load_plane(va, p + 1);   // uniform
+    }
+  }
+  rowinv_epilogue_pw<R, R, GPB>(acc, P, G, jb, j, y, rb, grp, t, target, pixel_weight, inten_out, partial, red);
+}
+
+// k_rowinv (N = 64) with the weighted tail
+template <int R, int NT>
+__global__ __launch_bounds__(NT, 512 / NT) void k_rowinv_pw(const JobDesc* __restrict__ jobs,
+                                                      const float2* __restrict__ ws_b,
+                                                      const float* __restrict__ target,
+                                                      const float* __restrict__ pixel_weight,
+                                                      const float2* __restrict__ tw_glob, int P, int G,
+                                                      double* __restrict__ partial, float* __restrict__ inten_out,
+                                                      float2* __restrict__ field_out) {
+  constexpr int N = R * R;
+  constexpr int GPB = NT / R;          // rows per block
+  constexpr int RB = N / GPB;
+  constexpr int CH16 = N * GPB / 2;     // 16-B chunks per plane tile
+  constexpr int PER = CH16 / NT;
+  static_assert(CH16 % NT == 0, "chunking");
+  constexpr int SCR = GPB * R * (R + 1);   // padded transpose scratch reuses the tile
+  __shared__ float2 tw[N];
+  __shared__ __attribute__((aligned(16))) float2 tile[SCR > N * GPB ? SCR : N * GPB];
+  __shared__ double red[GPB][3];
+
+  for (int i = threadIdx.x; i < N; i += NT) tw[i] = tw_glob[i];
+
+  const int grp = threadIdx.x / R;
+  const int t = threadIdx.x % R;
+  const int bid = xcd_pair<RB>(blockIdx.x);
+  const int rb = bid % RB;
+  const int j = bid / RB;
+  const JobDesc jb = jobs[j];
+  if (jb.env < 0) {   // uniform per block
+    rowinv_zero_partial(partial, j, RB, rb);
+    return;
+  }
+  const int y0 = rb * GPB;
+  const int y = y0 + grp;
+  constexpr size_t PLB = plane_b_elems(R);
+  const float2* jbase = ws_b + (size_t)j * P * PLB;
+
+  float4 pre[PER];   // this thread's share of a plane tile, one plane ahead
+#pragma unroll
+  for (int i = 0; i < PER; ++i) {
+    const TileChunk ch = tile_chunk<NT, GPB>(i);
+    pre[i] = ld_stream4(jbase + LayoutB<R>::at(ch.line, y0 + ch.r2));
+  }
+  float acc[R];
+#pragma unroll
+  for (int k = 0; k < R; ++k) acc[k] = 0.0f;
+
+#pragma unroll 1
+  for (int p = 0; p < P; ++p) {
+    lds_barrier();  // previous plane's scratch use is over (also publishes tw)
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const TileChunk ch = tile_chunk<NT, GPB>(i);
+      tile[tile_pos<R, GPB>(ch.line, ch.r2)] = make_float2(pre[i].x, pre[i].y);
+      tile[tile_pos<R, GPB>(ch.line, ch.r2 + 1)] = make_float2(pre[i].z, pre[i].w);
+    }
+    if (p + 1 < P) {  // next plane's tile in flight under this plane's FFT
+      const float2* nb = jbase + (size_t)(p + 1) * PLB;
+#pragma unroll
+      for (int i = 0; i < PER; ++i) {
+        const TileChunk ch = tile_chunk<NT, GPB>(i);
+        pre[i] = ld_stream4(nb + LayoutB<R>::at(ch.line, y0 + ch.r2));
+      }
+    }
+    lds_barrier();
+    pk2 v[R];
+#pragma unroll
+    for (int jj = 0; jj < R; ++jj) v[jj] = to_pk(tile[tile_pos<R, GPB>(t + R * jj, grp)]);
+    lds_barrier();  // tile consumed: reuse it as transpose scratch
+    fft_group<R, true>(v, t, PaddedScratch<R>{tile + grp * R * (R + 1)}, tw);
+#pragma unroll
+    for (int k = 0; k < R; ++k) acc[k] += fmaf(v[k].x, v[k].x, v[k].y * v[k].y);
+    if (field_out) {
+      float2* frow = field_out + (((size_t)jb.env * G * P + jb.group * P + p) * N + y) * N;
+#pragma unroll
+      for (int k = 0; k < R; ++k) frow[t + R * k] = from_pk(v[k]);
+    }
+  }
+  rowinv_epilogue_pw<R, R, GPB>(acc, P, G, jb, j, y, rb, grp, t, target, pixel_weight, inten_out, partial, red);
+}
+
+// k_rowinv_d_cplx's statistics form (N = 1024 / 256) with the weighted tail; field_out nullable, no real part
+template <int R>
+__global__ __launch_bounds__(256, 2) void k_rowinv_d_cplx_pw(const JobDesc* __restrict__ jobs,
+                                                             const float2* __restrict__ ws_b,
+                                                             const float2* __restrict__ tw_glob, int P, int G,
+                                                             float2* __restrict__ field_out,
+                                                             const float* __restrict__ target,
+                                                             const float* __restrict__ pixel_weight,
+                                                             double* __restrict__ partial,
+                                                             float* __restrict__ inten_out) {
+  constexpr int N = R * R, GPB = 256 / R, RB = N / GPB;
+  __shared__ float2 tw[N];
+  __shared__ float2 scratch[GPB * R * (R + 1)];
+  __shared__ double red[GPB][3];
+  for (int i = threadIdx.x; i < N; i += 256) tw[i] = tw_glob[i];
+
+  const int grp = threadIdx.x / R;
+  const int t = threadIdx.x % R;
+  const int bid = xcd_pair<RB>(blockIdx.x);
+  const int rb = bid % RB;
+  const int j = bid / RB;
+  const JobDesc jb = jobs[j];
+  if (jb.env < 0) {  // uniform per block
+    rowinv_zero_partial(partial, j, RB, rb);
+    return;
+  }
+  const int y = rb * GPB + grp;
+  const hbx_window_t win = {0, 0, 0, 0};
+  const WinRow wr(win, y, t);   // (unread: no window form)
+  const int Q = P / 2;                        // complex planes per group
+  constexpr int PLB = N * N;                 // float2 per B plane
+  const __amdgpu_buffer_rsrc_t rs = plane_rsrc(ws_b + (size_t)j * P * PLB, (unsigned)((size_t)P * PLB * 8));
+  const RowinvLanes<R> ln(y, t);
+  auto load_pair = [&](pk2 (&v)[R], int q) { rowinv_load_pair(v, ln, rs, q); };
+  const PaddedScratch<R> sc{scratch + grp * R * (R + 1)};
+  const size_t row0 = (((size_t)jb.env * G + jb.group) * Q * N + y) * N + t;   // complex plane 0, pixel x = t
+  float acc[R];
+#pragma unroll
+  for (int k = 0; k < R; ++k) acc[k] = 0.0f;
+  auto finish_plane = [&](pk2 (&v)[R], int q) {
+    fft_group<R, true>(v, t, sc, tw);
+    cplx_plane_out<R, R, true, kGradNone, false>(v, acc, jb.env, jb.group, G, Q, q, y, row0, win, wr, field_out, nullptr,
+                                                 nullptr, nullptr, 0.0f, 0.0f, 0.0f);
+  };
+  pk2 va[R];
+  load_pair(va, 0);
+  __syncthreads();  // tw visible
+  if constexpr (R == 16) {
+    pk2 vb[R];
+#pragma unroll 1
+    for (int q = 0; q < Q; q += 2) {
+      if (q + 1 < Q) load_pair(vb, q + 1);
+      finish_plane(va, q);
+      if (q + 1 < Q) {
+        if (q + 2 < Q) load_pair(va, q + 2);
+        finish_plane(vb, q + 1);
+      }
+    }
+  } else {
+#pragma unroll 1
+    for (int q = 0; q < Q; ++q) {
+      finish_plane(va, q);
+      if (q + 1 < Q) load_pair(va, q + 1);   // uniform: no pair is read twice
+    }
+  }
+  rowinv_epilogue_pw<R, R, GPB>(acc, Q, G, jb, j, y, rb, grp, t, target, pixel_weight, inten_out, partial, red);
+}
+
+// k_rowinv_cplx's statistics form (N = 64) with the weighted tail
+template <int R, int NT>
+__global__ __launch_bounds__(NT, 512 / NT) void k_rowinv_cplx_pw(const JobDesc* __restrict__ jobs,
+                                                           const float2* __restrict__ ws_b,
+                                                           const float2* __restrict__ tw_glob, int P, int G,
+                                                           float2* __restrict__ field_out,
+                                                           const float* __restrict__ target,
+                                                           const float* __restrict__ pixel_weight,
+                                                           double* __restrict__ partial,
+                                                           float* __restrict__ inten_out) {
+  constexpr int N = R * R;
+  constexpr int GPB = NT / R;          // rows per block
+  constexpr int RB = N / GPB;
+  constexpr int CH16 = N * GPB / 2;     // 16-B chunks per plane tile
+  constexpr int PER = CH16 / NT;
+  static_assert(CH16 % NT == 0, "chunking");
+  constexpr int SCR = GPB * R * (R + 1);   // padded transpose scratch reuses the tile
+  __shared__ float2 tw[N];
+  __shared__ __attribute__((aligned(16))) float2 tile[SCR > N * GPB ? SCR : N * GPB];
+  __shared__ double red[GPB][3];
+
+  for (int i = threadIdx.x; i < N; i += NT) tw[i] = tw_glob[i];
+
+  const int grp = threadIdx.x / R;
+  const int t = threadIdx.x % R;
+  const int bid = xcd_pair<RB>(blockIdx.x);
+  const int rb = bid % RB;
+  const int j = bid / RB;
+  const JobDesc jb = jobs[j];
+  if (jb.env < 0) {  // uniform per block
+    rowinv_zero_partial(partial, j, RB, rb);
+    return;
+  }
+  const int y0 = rb * GPB;
+  const int y = y0 + grp;
+  const int Q = P / 2;
+  constexpr size_t PLB = plane_b_elems(R);
+  const float2* jbase = ws_b + (size_t)j * P * PLB;
+
+  float4 pa[PER], pb[PER];   // this thread's share of the pair's two plane tiles, one pair ahead
+  auto load_pair = [&](int q) {
+    const float2* a = jbase + (size_t)(2 * q) * PLB;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const TileChunk ch = tile_chunk<NT, GPB>(i);
+      pa[i] = ld_stream4(a + LayoutB<R>::at(ch.line, y0 + ch.r2));
+      pb[i] = ld_stream4(a + PLB + LayoutB<R>::at(ch.line, y0 + ch.r2));
+    }
+  };
+  load_pair(0);
+  const size_t row0 = (((size_t)jb.env * G + jb.group) * Q * N + y) * N + t;
+  float acc[R];
+#pragma unroll
+  for (int k = 0; k < R; ++k) acc[k] = 0.0f;
+
+#pragma unroll 1
+  for (int q = 0; q < Q; ++q) {
+    lds_barrier();  // previous plane's scratch use is over (also publishes tw)
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {   // B[2q] + i B[2q + 1]
+      const TileChunk ch = tile_chunk<NT, GPB>(i);
+      tile[tile_pos<R, GPB>(ch.line, ch.r2)] = make_float2(pa[i].x - pb[i].y, pa[i].y + pb[i].x);
+      tile[tile_pos<R, GPB>(ch.line, ch.r2 + 1)] = make_float2(pa[i].z - pb[i].w, pa[i].w + pb[i].z);
+    }
+    if (q + 1 < Q) load_pair(q + 1);   // next pair's tiles in flight under this plane's FFT
+    lds_barrier();
+    pk2 v[R];
+#pragma unroll
+    for (int jj = 0; jj < R; ++jj) v[jj] = to_pk(tile[tile_pos<R, GPB>(t + R * jj, grp)]);
+    lds_barrier();  // tile consumed: reuse it as transpose scratch
+    fft_group<R, true>(v, t, PaddedScratch<R>{tile + grp * R * (R + 1)}, tw);
+#pragma unroll
+    for (int k = 0; k < R; ++k) acc[k] += fmaf(v[k].x, v[k].x, v[k].y * v[k].y);
+    if (field_out) {
+      const size_t row = row0 + (size_t)q * N * N;
+#pragma unroll
+      for (int k = 0; k < R; ++k) field_out[row + R * k] = from_pk(v[k]);
+    }
+  }
+  rowinv_epilogue_pw<R, R, GPB>(acc, Q, G, jb, j, y, rb, grp, t, target, pixel_weight, inten_out, partial, red);
+}
+
+// launch_passes' last pass of a call with PassCall::pixel_weight set (check_pass_call has passed: sample
+// input, a target, statistics; tg.rows is the caller's target)
+template <int R>
+static void launch_last_pw(const PlanDev& pd, const PassCall& c, float2* ws_b, unsigned blocks, hipStream_t st) {
+  constexpr int NT = kRowNT<R>;
+  if (pass_complex(c)) {
+    if constexpr (kTiledB<R>)
+      launch_kernel(k_rowinv_d_cplx_pw<R>, blocks, 256, st, c.jobs, ws_b, pd.tw, pd.P, pd.G, c.complex_field, c.target,
+                    c.pixel_weight, pd.partial, c.inten_out);
+    else
+      launch_kernel(k_rowinv_cplx_pw<R, NT>, blocks, NT, st, c.jobs, ws_b, pd.tw, pd.P, pd.G, c.complex_field, c.target,
+                    c.pixel_weight, pd.partial, c.inten_out);
+  } else {
+    if constexpr (kTiledB<R>)
+      launch_kernel(k_rowinv_d_pw<R>, blocks, 256, st, c.jobs, ws_b, c.target, c.pixel_weight, pd.tw, pd.P, pd.G,
+                    pd.partial, c.inten_out, c.field_out);
+    else
+      launch_kernel(k_rowinv_pw<R, NT>, blocks, NT, st, c.jobs, ws_b, c.target, c.pixel_weight, pd.tw, pd.P, pd.G,
+                    pd.partial, c.inten_out, c.field_out);
   }
 }
 

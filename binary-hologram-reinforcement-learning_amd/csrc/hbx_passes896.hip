@@ -628,6 +628,9 @@ struct SampleKernels896 {
   static auto last_cplx() { return k_rowinv896_cplx<ST, GK, WIN>; }
 };
 
+// (pixel weights) the weighted last passes and their pick, behind every other kernel of this file
+static void launch_last_pw_896(const PlanDev& pd, const PassCall& c, float2* ws_b, unsigned blocks, hipStream_t st);
+
 hipError_t run_jobs_896(const PlanDev& pd, const PassCall& c, hipStream_t st) {
   const JobDesc* jobs = c.jobs;
   const int n_jobs = c.n_jobs;
@@ -667,7 +670,9 @@ hipError_t run_jobs_896(const PlanDev& pd, const PassCall& c, hipStream_t st) {
   if (c.stack_skip_last) return hipGetLastError();
 
   if (tm) tm->begin(2, st);
-  if (pass_complex(c)) {   // recombine each plane pair, or a leaf's gradient instead (pick_last_pass_cplx)
+  if (c.pixel_weight) {    // the weighted statistics forms, only when the pointer is set
+    launch_last_pw_896(pd, c, ws_b, blocks, st);
+  } else if (pass_complex(c)) {   // recombine each plane pair, or a leaf's gradient instead (pick_last_pass_cplx)
     const auto k = pick_last_pass_cplx<SampleKernels896>(pass_grad_kind(c), c.complex_stats != 0,
                                                          c.windowed != 0);
     launch_kernel(k, blocks, 256, st, jobs, ws_b, pd.tw, P, pd.G, c.complex_field, c.real_part, tg.rows, tg.mask,
@@ -747,6 +752,118 @@ hipError_t run_stack_last_896(const PlanDev& pd, const PassCall& c, int n_depths
                 pass_grad_p0(c), pass_grad_p1(c));
   if (tm) tm->end(2, c.n_jobs, st);
   return hipGetLastError();
+}
+
+// Per-pixel loss weights (hbx_evaluate_pw / hbx_evaluate_stack_pw, EXTENSION): k_rowinv896 and the statistics
+// form of k_rowinv896_cplx with rowinv_epilogue_pw (hbx_rowinv.hpp) as their tail -- the sibling's loads, FFTs,
+// |U|^2 and field stores in the sibling's order, the weight row in the three f64 sums (hbx_passes.hip has the
+// account).  No plane cache, window or env-major form; argument lists of their own, behind every other kernel
+// of this file.
+__global__ __launch_bounds__(256, 2) void k_rowinv896_pw(const JobDesc* __restrict__ jobs,
+                                                         const float2* __restrict__ ws_b,
+                                                         const float* __restrict__ target,
+                                                         const float* __restrict__ pixel_weight,
+                                                         const float2* __restrict__ tw_glob, int P, int G,
+                                                         double* __restrict__ partial, float* __restrict__ inten_out,
+                                                         float2* __restrict__ field_out) {
+  __shared__ float2 tw[kN];
+  __shared__ float2 scratch[kSCR];
+  __shared__ double red[kGPB][3];
+  for (int i = threadIdx.x; i < kN; i += 256) tw[i] = tw_glob[i];
+
+  const int grp = threadIdx.x / kR;
+  const int t = threadIdx.x % kR;
+  const int bid = xcd_pair<kRB>(blockIdx.x);
+  const int rb = bid % kRB;
+  const int j = bid / kRB;
+  const JobDesc jb = jobs[j];
+  if (jb.env < 0) {   // uniform per block
+    rowinv_zero_partial(partial, j, kRB, rb);
+    return;
+  }
+  const int y = rb * kGPB + grp;
+  const __amdgpu_buffer_rsrc_t rs = plane_rsrc(ws_b + (size_t)j * P * kPlaneB, (unsigned)((size_t)P * kPlaneB * 8));
+  const Rowinv896Lanes ln(y, t);
+  float acc[kL];
+#pragma unroll
+  for (int k = 0; k < kL; ++k) acc[k] = 0.0f;
+  const PaddedScratch<kR> sc{scratch + grp * kR * (kR + 1)};
+  float2 v[32];
+  rowinv_load_plane(v, ln, rs, 0);
+  __syncthreads();  // tw visible
+#pragma unroll 1
+  for (int p = 0; p < P; ++p) {
+    fft896_sn<true, kInvScalar>(v, t, sc, tw);      // slot layout in, natural out: x = t + 32 k
+#pragma unroll
+    for (int k = 0; k < kL; ++k) acc[k] += fmaf(v[k].x, v[k].x, v[k].y * v[k].y);   // plane_out without the cache
+    if (field_out) {
+      float2* frow = field_out + (((size_t)jb.env * G * P + jb.group * P + p) * kN + y) * kN;
+#pragma unroll
+      for (int k = 0; k < kL; ++k) frow[t + kR * k] = make_float2(v[k].x, v[k].y);
+    }
+    if (p + 1 < P) rowinv_load_plane(v, ln, rs, p + 1);   // uniform: no plane is read twice
+  }
+  rowinv_epilogue_pw<kR, kL, kGPB>(acc, P, G, jb, j, y, rb, grp, t, target, pixel_weight, inten_out, partial, red);
+}
+
+__global__ __launch_bounds__(256, 2) void k_rowinv896_cplx_pw(const JobDesc* __restrict__ jobs,
+                                                              const float2* __restrict__ ws_b,
+                                                              const float2* __restrict__ tw_glob, int P, int G,
+                                                              float2* __restrict__ field_out,
+                                                              const float* __restrict__ target,
+                                                              const float* __restrict__ pixel_weight,
+                                                              double* __restrict__ partial,
+                                                              float* __restrict__ inten_out) {
+  __shared__ float2 tw[kN];
+  __shared__ float2 scratch[kSCR];
+  __shared__ double red[kGPB][3];
+  for (int i = threadIdx.x; i < kN; i += 256) tw[i] = tw_glob[i];
+
+  const int grp = threadIdx.x / kR;
+  const int t = threadIdx.x % kR;
+  const int bid = xcd_pair<kRB>(blockIdx.x);
+  const int rb = bid % kRB;
+  const int j = bid / kRB;
+  const JobDesc jb = jobs[j];
+  if (jb.env < 0) {  // uniform per block
+    rowinv_zero_partial(partial, j, kRB, rb);
+    return;
+  }
+  const int y = rb * kGPB + grp;
+  const int Q = P / 2;                            // complex planes per group
+  const __amdgpu_buffer_rsrc_t rs = plane_rsrc(ws_b + (size_t)j * P * kPlaneB, (unsigned)((size_t)P * kPlaneB * 8));
+  const Rowinv896Lanes ln(y, t);
+  const PaddedScratch<kR> sc{scratch + grp * kR * (kR + 1)};
+  const size_t row0 = (((size_t)jb.env * G + jb.group) * Q * kN + y) * kN + t;   // complex plane 0, pixel x = t
+  float acc[kL];
+#pragma unroll
+  for (int k = 0; k < kL; ++k) acc[k] = 0.0f;
+  float2 v[32];
+  rowinv_load_pair(v, ln, rs, 0);
+  __syncthreads();  // tw visible
+#pragma unroll 1
+  for (int q = 0; q < Q; ++q) {
+    fft896_sn<true, kInvScalar>(v, t, sc, tw);      // slot layout in, natural out: x = t + 32 k
+#pragma unroll
+    for (int k = 0; k < kL; ++k) acc[k] += fmaf(v[k].x, v[k].x, v[k].y * v[k].y);
+    if (field_out) {
+      const size_t row = row0 + (size_t)q * kN * kN;
+#pragma unroll
+      for (int k = 0; k < kL; ++k) field_out[row + kR * k] = v[k];
+    }
+    if (q + 1 < Q) rowinv_load_pair(v, ln, rs, q + 1);   // uniform: no pair is read twice
+  }
+  rowinv_epilogue_pw<kR, kL, kGPB>(acc, Q, G, jb, j, y, rb, grp, t, target, pixel_weight, inten_out, partial, red);
+}
+
+// run_jobs_896's last pass of a call with PassCall::pixel_weight set (check_pass_call has passed)
+static void launch_last_pw_896(const PlanDev& pd, const PassCall& c, float2* ws_b, unsigned blocks, hipStream_t st) {
+  if (pass_complex(c))
+    launch_kernel(k_rowinv896_cplx_pw, blocks, 256, st, c.jobs, ws_b, pd.tw, pd.P, pd.G, c.complex_field, c.target,
+                  c.pixel_weight, pd.partial, c.inten_out);
+  else
+    launch_kernel(k_rowinv896_pw, blocks, 256, st, c.jobs, ws_b, c.target, c.pixel_weight, pd.tw, pd.P, pd.G, pd.partial,
+                  c.inten_out, c.field_out);
 }
 
 }  // namespace hbx

@@ -325,6 +325,60 @@ __device__ __forceinline__ void rowinv_epilogue(float (&acc)[L], int P, int G, c
   }
 }
 
+// rowinv_epilogue with a per-pixel loss weight (hbx_evaluate_pw / hbx_evaluate_stack_pw): the
+// weight row of (env, group, y) is addressed as the target row, and the three f64 sums take it as
+//   vI = (double)v (double)I, vT = (double)v (double)T      exact: 24 + 24 bits
+//   sxy = fma(vI, T, sxy), sxx = fma(vI, I, sxx), syy = fma(vT, T, syy)
+// in rowinv_epilogue's order -- over the lane's k, the group's lanes, the block's rows.  A pixel with v = 1
+// adds rowinv_epilogue's term bit for bit, one with v = 0 leaves the running sums as they are (a finite
+// I and T: 0 times inf is NaN).  The intensity written is the unweighted plane mean.  Always a target,
+// job-major intensity rows, plain partials: no SC1, target-ahead, env-major or reconcile form.
+template <int R, int L, int GPB>
+__device__ __forceinline__ void rowinv_epilogue_pw(float (&acc)[L], int P, int G, const JobDesc& jb, int j, int y,
+                                                   int rb, int grp, int t, const float* __restrict__ target,
+                                                   const float* __restrict__ pixel_weight,
+                                                   float* __restrict__ inten_out, double* __restrict__ partial,
+                                                   double (&red)[GPB][3]) {
+  constexpr int N = R * L;
+  constexpr int RB = N / GPB;
+  const float invp = 1.0f / (float)P;
+  const size_t ro = (((size_t)jb.env * G + jb.group) * N + y) * N;
+  const float* trow = target + ro;
+  const float* vrow = pixel_weight + ro;
+  double sxy = 0.0, sxx = 0.0, syy = 0.0;
+#pragma unroll
+  for (int k = 0; k < L; ++k) {
+    const float I = acc[k] * invp;
+    const float T = trow[t + R * k];
+    const double v = (double)vrow[t + R * k];
+    const double vI = v * (double)I, vT = v * (double)T;
+    sxy = fma(vI, (double)T, sxy);
+    sxx = fma(vI, (double)I, sxx);
+    syy = fma(vT, (double)T, syy);
+    acc[k] = I;
+  }
+  if (inten_out) {
+    float* orow = inten_out + ((size_t)j * N + y) * N;
+#pragma unroll
+    for (int k = 0; k < L; ++k) orow[t + R * k] = acc[k];
+  }
+  // reduce over the R lanes of the group, fixed order -> bitwise reproducible
+#pragma unroll
+  for (int off = R / 2; off >= 1; off >>= 1) {
+    sxy += __shfl_xor(sxy, off, 64);
+    sxx += __shfl_xor(sxx, off, 64);
+    syy += __shfl_xor(syy, off, 64);
+  }
+  if (t == 0) { red[grp][0] = sxy; red[grp][1] = sxx; red[grp][2] = syy; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double a = 0.0, b = 0.0, cc = 0.0;
+    for (int g = 0; g < GPB; ++g) { a += red[g][0]; b += red[g][1]; cc += red[g][2]; }
+    double* o = partial + ((size_t)j * RB + rb) * 3;
+    o[0] = a; o[1] = b; o[2] = cc;
+  }
+}
+
 // ---------------------------------------------------------------------------
 // The last pass over an output window (hbx_*_window; WinRow, hbx_rowcol.hpp)
 // ---------------------------------------------------------------------------

@@ -53,6 +53,7 @@ EXPORTED_SYMBOLS = (
     "hbx_simulate_phase_levels", "hbx_evaluate_phase_levels", "hbx_phase_levels_backward", "hbx_quantize_phase",
     "hbx_plan_set_depths", "hbx_plan_depths", "hbx_evaluate_stack", "hbx_backward_stack",
     "hbx_loss_stack", "hbx_loss_weight_stack",
+    "hbx_evaluate_pw", "hbx_evaluate_stack_pw", "hbx_pixel_weight_sum", "hbx_loss_pw", "hbx_loss_weight_pw",
 )
 NUM_PASSES = 5
 PASS_NAMES = ("k_rowfwd", "k_col", "k_rowinv", "k_psf_eval", "k_psf_commit")
@@ -181,6 +182,11 @@ def _declare(lib):
     lib.hbx_loss_stack.argtypes = [VP, VP, I32, I32, I32, VP, VP]
     lib.hbx_loss_weight_stack.argtypes = [VP, VP, VP, VP, VP, I32, I32, I32, VP, VP]
     lib.hbx_loss_weight.argtypes = [VP, VP, VP, VP, VP, I32, I32, I32, VP, VP]
+    lib.hbx_evaluate_pw.argtypes = [VP, VP, LP, VP, VP, I32, VP, VP, VP, VP]
+    lib.hbx_evaluate_stack_pw.argtypes = [VP, VP, LP, VP, VP, I32, VP, VP, VP, VP]
+    lib.hbx_pixel_weight_sum.argtypes = [VP, VP, I32, I32, VP, VP]
+    lib.hbx_loss_pw.argtypes = [VP, VP, VP, I32, I32, I32, I32, VP, VP]
+    lib.hbx_loss_weight_pw.argtypes = [VP, VP, VP, VP, VP, VP, VP, I32, I32, I32, I32, VP, VP]
     lib.hbx_flip_map.argtypes = [VP, VP, VP, VP, VP, VP]
     lib.hbx_eval_flips_psf.argtypes = [VP, VP, VP, VP, VP, VP, VP, I32, VP, VP, VP]
     lib.hbx_commit_flip_psf.argtypes = [VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, I32, VP]

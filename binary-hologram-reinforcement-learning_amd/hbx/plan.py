@@ -769,6 +769,99 @@ class Plan:
                                                   _stream(stream)), "hbx_loss_weight_stack")
         return weight
 
+    # --- per-pixel loss weights (hbx_*_pw): a constant weight v of the target's shape in the statistics ---
+    def _evaluate_pw(self, name, values, kind, target, pixel_weight, want_field, want_intensity, levels, threshold,
+                     depths, stream):
+        leaf = self._leaf(kind, levels, threshold)
+        n = _batch(values)
+        c = self.cfg
+        real_in = kind in (_lib.LEAF_REAL, _lib.LEAF_THRESHOLD)
+        shape = (n, c.channels if real_in else c.channels // 2, c.height, c.width)
+        values = self._in(values, "values", torch.complex64 if kind == _lib.LEAF_COMPLEX else torch.float32, shape)
+        tshape = depths + tuple(self.target_shape(n))
+        _need(target, "target", torch.float32, tshape, self.device)
+        _need(pixel_weight, "pixel_weight", torch.float32, tshape, self.device)
+        field = torch.empty(depths + shape + (2,), dtype=torch.float32, device=self.device) if want_field else None
+        inten = torch.empty(tshape, dtype=torch.float32, device=self.device) if want_intensity else None
+        stats = torch.empty(depths + (n, c.groups, 3), dtype=torch.float64, device=self.device)
+        _lib.check(getattr(self.lib, name)(self._h, _ptr(values), C.byref(leaf), _ptr(target), _ptr(pixel_weight), n,
+                                           _ptr(field), _ptr(inten), _ptr(stats), _stream(stream)), name)
+        return _complex(field), inten, stats
+
+    def evaluate_pw(self, values: torch.Tensor, kind: int, target: torch.Tensor, pixel_weight: torch.Tensor,
+                    want_field: bool = True, want_intensity: bool = True, levels=None, threshold: float = 0.0,
+                    stream=None):
+        """The single-depth evaluate call of leaf kind `kind` (hbx._lib.LEAF_*; `values`, `levels` and
+        `threshold` as `evaluate_stack` takes them) with a per-pixel loss weight (hbx_evaluate_pw):
+        `pixel_weight` float32 [B, G, H, W], non-negative, enters the statistics only -- chan_stats
+        [B, G, 3] = (sum v I T, sum v I^2, sum v T^2) per group.  Returns (field | None, intensity |
+        None, chan_stats); field and intensity are the unweighted call's bit for bit, and with
+        pixel_weight = 1 so is chan_stats.  `target` is required."""
+        return self._evaluate_pw("hbx_evaluate_pw", values, kind, target, pixel_weight, want_field, want_intensity,
+                                 levels, threshold, (), stream)
+
+    def evaluate_stack_pw(self, values: torch.Tensor, kind: int, target: torch.Tensor, pixel_weight: torch.Tensor,
+                          want_field: bool = True, want_intensity: bool = True, levels=None, threshold: float = 0.0,
+                          stream=None):
+        """`evaluate_stack` with a per-pixel loss weight per depth (hbx_evaluate_stack_pw): `target` and
+        `pixel_weight` float32 [D, B, G, H, W], both required.  Returns (field | None, intensity | None,
+        chan_stats [D, B, G, 3]); depth d of each equals `evaluate_pw`'s on a plan for zs[d]."""
+        return self._evaluate_pw("hbx_evaluate_stack_pw", values, kind, target, pixel_weight, want_field,
+                                 want_intensity, levels, threshold, (self.depths,), stream)
+
+    def _pw_depths(self, stack: bool):
+        return ((self.depths,), self.depths, 1) if stack else ((), 0, 0)
+
+    def pixel_weight_sum(self, pixel_weight: torch.Tensor, stack: bool = False, stream=None) -> torch.Tensor:
+        """W[b] = the sum of env b's pixel weights, float64 [B] on the device (hbx_pixel_weight_sum):
+        over [B, G, H, W], or with stack=True over [D, B, G, H, W] (D the plan's).  A fixed-order
+        float64 reduction: bitwise reproducible, and exact for a 0 / 1 weight."""
+        depths, d, axis = self._pw_depths(stack)
+        n = _batch(pixel_weight, axis)
+        _need(pixel_weight, "pixel_weight", torch.float32, depths + tuple(self.target_shape(n)), self.device)
+        out = torch.empty((n,), dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.hbx_pixel_weight_sum(self._h, _ptr(pixel_weight), n, d, _ptr(out), _stream(stream)),
+                   "hbx_pixel_weight_sum")
+        return out
+
+    def loss_pw(self, chan_stats: torch.Tensor, weight_sum: torch.Tensor, kind: int = _lib.LOSS_MSE,
+                rel_scale: int = _lib.REL_LSQ, stack: bool = False, stream=None) -> torch.Tensor:
+        """`loss` (stack=True: `loss_stack`) on weighted statistics, with weight_sum float64 [B]
+        (`pixel_weight_sum`) in the place of the pixel count (hbx_loss_pw).  An env whose weights are
+        all zero gives MSE 0 / PSNR +inf."""
+        depths, d, axis = self._pw_depths(stack)
+        n = _batch(chan_stats, axis)
+        _need(chan_stats, "chan_stats", torch.float64, depths + (n, self.cfg.groups, 3), self.device)
+        _need(weight_sum, "weight_sum", torch.float64, (n,), self.device)
+        out = torch.empty((n,), dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.hbx_loss_pw(self._h, _ptr(chan_stats), _ptr(weight_sum), n, d, int(kind), int(rel_scale),
+                                        _ptr(out), _stream(stream)), "hbx_loss_pw")
+        return out
+
+    def loss_weight_pw(self, intensity: torch.Tensor, target: torch.Tensor, pixel_weight: torch.Tensor,
+                       chan_stats: torch.Tensor, weight_sum: torch.Tensor, grad_loss: Optional[torch.Tensor] = None,
+                       kind: int = _lib.LOSS_MSE, rel_scale: int = _lib.REL_LSQ, stack: bool = False,
+                       stream=None) -> torch.Tensor:
+        """The weighted loss's gradient with respect to the intensity (hbx_loss_weight_pw): float32 of
+        the intensity's shape, grad_loss[b] * pixel_weight * (a_b I + c_b T) with `loss_weight`'s
+        (stack=True: `loss_weight_stack`'s) coefficients, weight_sum for the pixel count.  It goes into
+        the backward calls as the unweighted loss weight does."""
+        depths, d, axis = self._pw_depths(stack)
+        n = _batch(intensity, axis)
+        tshape = depths + tuple(self.target_shape(n))
+        _need(intensity, "intensity", torch.float32, tshape, self.device)
+        _need(target, "target", torch.float32, tshape, self.device)
+        _need(pixel_weight, "pixel_weight", torch.float32, tshape, self.device)
+        _need(chan_stats, "chan_stats", torch.float64, depths + (n, self.cfg.groups, 3), self.device)
+        _need(weight_sum, "weight_sum", torch.float64, (n,), self.device)
+        if grad_loss is not None:
+            _need(grad_loss, "grad_loss", torch.float64, (n,), self.device)
+        weight = torch.empty(tshape, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.hbx_loss_weight_pw(self._h, _ptr(intensity), _ptr(target), _ptr(pixel_weight),
+                                               _ptr(chan_stats), _ptr(weight_sum), _ptr(grad_loss), n, d, int(kind),
+                                               int(rel_scale), _ptr(weight), _stream(stream)), "hbx_loss_weight_pw")
+        return weight
+
     # --- windows (hbx_*_window): holograms of any size zero-filled into the grid, outputs over a rectangle ---
     def window(self, win):
         """(y0, x0, h, w) | None -> (the _lib.Window to pass, or None for the full grid, and its

@@ -387,11 +387,17 @@ class _Leaf:
     def kept(self, x):
         return (x,) if self.keeps_leaf else ()
 
-    def evaluate(self, x, target=None, want_field=True, want_intensity=True):
+    def evaluate(self, x, target=None, want_field=True, want_intensity=True, pixel_weight=None):
         """One forward launch set -> (plan, field | None, intensity | None, chan_stats | None).  A real
         or thresholded leaf of an odd C is padded with a zero plane here: the field keeps it, and the
-        intensity is the mean over the C planes given."""
+        intensity is the mean over the C planes given.  pixel_weight (loss and loss_stack alone: a
+        target, an even C for a real leaf, no window): the weighted statistics of hbx_evaluate_pw /
+        hbx_evaluate_stack_pw."""
         plan, leaf = self.forward_plan(x), self.leaf
+        if pixel_weight is not None:
+            call = plan.evaluate_pw if self.zs is None else plan.evaluate_stack_pw
+            return (plan,) + call(x, leaf, target, pixel_weight, want_field=want_field, want_intensity=want_intensity,
+                                  levels=self.levels, threshold=self.tau)
         if self.zs is not None:
             return (plan,) + plan.evaluate_stack(x, leaf, target, want_field=want_field, want_intensity=want_intensity,
                                                  levels=self.levels, threshold=self.tau)
@@ -462,15 +468,21 @@ class _Leaf:
         grad = gf if cplx else gr
         return grad if grad.shape[1] == self.c else grad[:, :self.c]    # a padded field's zero plane
 
-    def loss(self, plan, stats, kind, rel):
+    def loss(self, plan, stats, kind, rel, weight_sum=None):
+        if weight_sum is not None:                              # a per-pixel weight: its sum for the pixel count
+            return plan.loss_pw(stats, weight_sum, kind, rel, stack=self.zs is not None)
         if self.zs is not None:
             return plan.loss_stack(stats, kind, rel)
         if self.win is not None:
             return plan.loss_window(stats, self.win[2], kind, rel)
         return plan.loss(stats, kind, rel)
 
-    def loss_weight(self, adj, inten, target, stats, gl, kind, rel):
-        """dL/dI = a I + c T per env on the adjoint plan (its G and N only)"""
+    def loss_weight(self, adj, inten, target, stats, gl, kind, rel, pixel_weight=None, weight_sum=None):
+        """dL/dI = a I + c T per env on the adjoint plan (its G and N only); with a per-pixel weight v,
+        v (a I + c T) with the weight sum for the pixel count"""
+        if pixel_weight is not None:
+            return adj.loss_weight_pw(inten, target, pixel_weight, stats, weight_sum, gl, kind, rel,
+                                      stack=self.zs is not None)
         if self.zs is not None:
             return adj.loss_weight_stack(inten, target, stats, gl, kind, rel)
         if self.win is not None:
@@ -547,25 +559,29 @@ class _Loss(torch.autograd.Function):
     the roi of a window, over all depths of a stack).  The forward pass is one launch set that leaves
     the field F, I and the statistics; with w = gL dL/dI = a I + c T (_Leaf.loss_weight: a, c per
     env from the statistics and the incoming gradient gL), dL/du = A^H((2 / P) w F): one launch set
-    of F on the adjoint plan, as _Intensity's backward pass.  No double backward."""
+    of F on the adjoint plan, as _Intensity's backward pass.  pw: a per-pixel weight v of the target's
+    shape (or None), saved with its sum per env next to the target; the statistics, the loss and
+    dL/dI = v (a I + c T) are then the weighted ones.  No double backward."""
 
     @staticmethod
-    def forward(ctx, x, target, spec, kind, rel):
-        ctx.spec, ctx.kind, ctx.rel = spec, kind, rel
-        plan, field, inten, stats = spec.evaluate(x, target)
-        ctx.save_for_backward(field, inten, stats, target, *spec.kept(x))
-        return spec.loss(plan, stats, kind, rel)
+    def forward(ctx, x, target, spec, kind, rel, pw=None):
+        ctx.spec, ctx.kind, ctx.rel, ctx.weighted = spec, kind, rel, pw is not None
+        plan, field, inten, stats = spec.evaluate(x, target, pixel_weight=pw)
+        wsum = None if pw is None else plan.pixel_weight_sum(pw, stack=spec.zs is not None)
+        ctx.save_for_backward(field, inten, stats, target, *spec.kept(x), *(() if pw is None else (pw, wsum)))
+        return spec.loss(plan, stats, kind, rel, wsum)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_output):
-        spec = ctx.spec
-        field, inten, stats, target, x = ctx.saved_tensors + (() if spec.keeps_leaf else (None,))
+        spec, saved = ctx.spec, ctx.saved_tensors
+        pw, wsum = saved[-2:] if ctx.weighted else (None, None)
+        field, inten, stats, target, x = saved[:4] + ((saved[4],) if spec.keeps_leaf else (None,))
         gl = _materialised(grad_output, torch.float64)
         adj = spec.adjoint_plan(field if x is None else x)
-        wgt = spec.loss_weight(adj, inten, target, stats, gl, ctx.kind, ctx.rel)
+        wgt = spec.loss_weight(adj, inten, target, stats, gl, ctx.kind, ctx.rel, pw, wsum)
         grad = spec.backward(x, field, weight=wgt, scale=2.0 / (spec.c // spec.groups), adj=adj)
-        return grad, None, None, None, None
+        return grad, None, None, None, None, None
 
 
 def _as_tensor(x) -> torch.Tensor:
@@ -573,13 +589,16 @@ def _as_tensor(x) -> torch.Tensor:
 
 
 def _leaf_args(x, what: str, tf, field, threshold, ste, ste_width, grid, origin, roi, levels, z=None, zs=None,
-               binary: bool = False, save_field: bool = True):
+               binary: bool = False, save_field: bool = True, pixel_weight=None):
     """The checks of every public call, all before any GPU use -> (t [B, C, H, W] as given, the _Leaf
     without its device, whether x was 3-D).  what: the public function's name; its own rules are
     `simulate`: one wavelength, any C (an odd one is padded); `intensity`: an odd C / G only for one
     group of a real or complex field or a phase; `loss`: an even C / G for a real field; the *_stack
     calls (zs given): no window, an even C / G for a real or thresholded leaf, a built grid."""
     stacked = zs is not None
+    if pixel_weight is not None and (grid is not None or origin is not None or roi is not None):
+        raise ValueError(f"{what}: pixel_weight= is not accepted with grid=, origin= or roi= (a rectangle is the "
+                         "weight that is 1 inside it)")
     if stacked:
         if grid is not None or origin is not None or roi is not None:
             raise ValueError(f"{what}: grid=, origin= and roi= are not accepted (focal stacks are not windowed)")
@@ -670,6 +689,28 @@ def _target_arg(target, want: Tuple[int, ...], squeeze: bool, what: str) -> torc
     return tg
 
 
+def _pixel_weight_arg(pixel_weight, want: Tuple[int, ...], squeeze: bool, what: str) -> torch.Tensor:
+    """pixel_weight of loss and loss_stack -> a real tensor that broadcasts to the target's shape `want`
+    (for a 3-D x: to the shape without the env axis), a constant; anything else raises ValueError.  It is
+    still as given: _loss expands it on the device."""
+    pw = _as_tensor(pixel_weight)
+    if pw.is_complex():
+        raise ValueError(f"{what}: pixel_weight must be a real tensor, got {pw.dtype}")
+    if pw.requires_grad:
+        raise ValueError(f"{what}: the pixel weight is a constant (it requires grad)")
+    axis = len(want) - 4                                        # the env axis: after a stack's depth axis
+    shape = want[:axis] + want[axis + 1:] if squeeze else want
+    try:
+        ok = pw.dim() <= len(shape) and tuple(torch.broadcast_shapes(tuple(pw.shape), shape)) == tuple(shape)
+    except RuntimeError:
+        ok = False
+    if not ok:
+        raise ValueError(f"{what}: pixel_weight {tuple(pw.shape)} does not broadcast to the target's shape {shape}")
+    if squeeze and pw.dim() == len(shape):
+        pw = pw.unsqueeze(axis)
+    return pw
+
+
 def _device_leaf(t: torch.Tensor, spec: _Leaf, what: str, cast: bool = True) -> torch.Tensor:
     """The device tensor the kernels read, cast by torch ops (autograd carries the casts of a float64
     or complex128 leaf back); names the device in the spec."""
@@ -708,19 +749,33 @@ def _intensity(t, spec, squeeze, what):
     return out.select(0 if spec.zs is None else 1, 0) if squeeze else out
 
 
-def _loss(t, target, spec, squeeze, what, kind, rel):
+def _loss(t, target, spec, squeeze, what, kind, rel, pixel_weight=None):
     """loss and loss_stack on the checked input: the target has the shape of the intensity (a window's
-    roi, a stack's depths first); without a gradient request neither field nor intensity is written"""
+    roi, a stack's depths first); without a gradient request neither field nor intensity is written.
+    pixel_weight None: the code as it was; else the weight is expanded to the target's shape and made
+    contiguous float32 on the device, once per call."""
     b, _, h, w = t.shape
     depths = () if spec.zs is None else (len(spec.zs),)
-    tg = _target_arg(target, depths + (b, spec.groups) + ((h, w) if spec.win is None else spec.win[2][2:]), squeeze, what)
+    want = depths + (b, spec.groups) + ((h, w) if spec.win is None else spec.win[2][2:])
+    tg = _target_arg(target, want, squeeze, what)
+    if pixel_weight is None:
+        xs = _device_leaf(t, spec, what)
+        tg = tg.to(device=xs.device, dtype=torch.float32).contiguous()
+        if _wants_grad(xs):
+            out = _Loss.apply(xs, tg, spec, kind, rel)
+        else:
+            plan, _, _, stats = spec.evaluate(xs, tg, want_field=False, want_intensity=False)
+            out = spec.loss(plan, stats, kind, rel)
+        return out[0] if squeeze else out
+    pw = _pixel_weight_arg(pixel_weight, want, squeeze, what)
     xs = _device_leaf(t, spec, what)
     tg = tg.to(device=xs.device, dtype=torch.float32).contiguous()
+    pw = pw.to(device=xs.device, dtype=torch.float32).expand(want).contiguous()
     if _wants_grad(xs):
-        out = _Loss.apply(xs, tg, spec, kind, rel)
+        out = _Loss.apply(xs, tg, spec, kind, rel, pw)
     else:
-        plan, _, _, stats = spec.evaluate(xs, tg, want_field=False, want_intensity=False)
-        out = spec.loss(plan, stats, kind, rel)
+        plan, _, _, stats = spec.evaluate(xs, tg, want_field=False, want_intensity=False, pixel_weight=pw)
+        out = spec.loss(plan, stats, kind, rel, plan.pixel_weight_sum(pw, stack=spec.zs is not None))
     return out[0] if squeeze else out
 
 
@@ -852,7 +907,7 @@ _METRIC_NAMES = {"mse": _lib.LOSS_MSE, "psnr": _lib.LOSS_PSNR}
 
 
 def loss(x, target, z: float, metric="mse", rel_scale="lsq", tf="asm", field="amplitude", threshold=None,
-         ste="window", ste_width=0.5, grid=None, origin=None, roi=None, levels=None) -> torch.Tensor:
+         ste="window", ste_width=0.5, grid=None, origin=None, roi=None, levels=None, pixel_weight=None) -> torch.Tensor:
     """The relative loss of a continuous hologram against a target, one value per env, without
     leaving the HIP path and without a host wait: float64 [B] on the device (0-dim for a 3-D x),
         metric="mse"   what tt.relativeLoss(I[b], target[b], F.mse_loss) gives (env.py:131),
@@ -896,11 +951,25 @@ def loss(x, target, z: float, metric="mse", rel_scale="lsq", tf="asm", field="am
     modulator displays -- hbx.quantize_phase(x, L) is its export -- quantized by the first pass of
     hbx_evaluate_phase_levels as it loads x.  If x requires grad the backward pass is the
     straight-through estimator: hbx_loss_weight, then one hbx_phase_levels_backward on the plan for -z.
-    Neither the quantized samples nor exp(i pi q) nor the complex gradient is written."""
+    Neither the quantized samples nor exp(i pi q) nor the complex gradient is written.
+
+    pixel_weight=v (None runs the code above untouched; every leaf kind): a non-negative per-pixel
+    weight -- a signal window with a don't-care region around it, or any weighting -- that the last
+    pass takes into the three sums: sum v I T, sum v I^2, sum v T^2, and W = sum v per env takes the
+    place of the pixel count n in the loss (hbx_evaluate_pw, hbx_pixel_weight_sum, hbx_loss_pw).  v is
+    a real tensor of the target's shape or one that broadcasts to it ([H, W], [G, H, W], ..), cast to
+    float32, and a constant: one that requires grad raises ValueError, as do a complex one, one that
+    does not broadcast, and pixel_weight= together with grid=, origin= or roi= (all before any GPU
+    use).  v = 1 gives the unweighted loss bit for bit, v = a rectangle's indicator roi='s statistics.
+    With a gradient request dL/dI = v (a I + c T) (hbx_loss_weight_pw) goes into the same backward
+    launch set; the energy the hologram cannot place may land where v = 0 at no cost.  Not checked
+    (a check would cost a host wait): a negative weight is used as it stands, a NaN weight poisons
+    that env's loss, an env whose weights are all zero has loss 0 (psnr: +inf) and a zero gradient."""
     kind = _switch(metric, _METRIC_NAMES, "metric")
     rel = _switch(rel_scale, _REL_NAMES, "rel_scale")
-    t, spec, squeeze = _leaf_args(x, "loss", tf, field, threshold, ste, ste_width, grid, origin, roi, levels, z=z)
-    return _loss(t, target, spec, squeeze, "loss", kind, rel)
+    t, spec, squeeze = _leaf_args(x, "loss", tf, field, threshold, ste, ste_width, grid, origin, roi, levels, z=z,
+                                  pixel_weight=pixel_weight)
+    return _loss(t, target, spec, squeeze, "loss", kind, rel, pixel_weight)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -935,7 +1004,8 @@ def intensity_stack(x, zs, tf="asm", field="amplitude", threshold=None, ste="win
 
 
 def loss_stack(x, target, zs, metric="mse", rel_scale="lsq", tf="asm", field="amplitude", threshold=None,
-               ste="window", ste_width=0.5, levels=None, grid=None, origin=None, roi=None) -> torch.Tensor:
+               ste="window", ste_width=0.5, levels=None, grid=None, origin=None, roi=None,
+               pixel_weight=None) -> torch.Tensor:
     """``tt.loss`` over a focal stack: one value per env, float64 [B] on the device (0-dim for a 3-D
     x), of the intensities at every depth of `zs` against ``target`` float32 [D, B, G, H, W]
     ([D, G, H, W] for a 3-D x), a constant.  The sums of I T, I^2 and T^2 run over an env's D G
@@ -945,12 +1015,17 @@ def loss_stack(x, target, zs, metric="mse", rel_scale="lsq", tf="asm", field="am
     per-depth fields, intensities and statistics, and the backward pass is hbx_loss_weight_stack
     followed by ONE hbx_backward_stack on the plan for the negated depths -- where D calls of
     tt.loss run D first passes forward, and D last passes and D - 1 additions of gradient-sized
-    temporaries backward.  grid=, origin= and roi= raise ValueError.  No double backward."""
+    temporaries backward.  grid=, origin= and roi= raise ValueError.  No double backward.
+
+    pixel_weight=v as in loss, of the target's shape [D, B, G, H, W] or one that broadcasts to it (e.g.
+    [D, 1, G, H, W]: one weight per depth, each depth scored where its part of the scene is in focus):
+    depth d's last pass takes depth d's weight (hbx_evaluate_stack_pw), and W = sum v over an env's
+    D G images takes the place of n = D G H W."""
     kind = _switch(metric, _METRIC_NAMES, "metric")
     rel = _switch(rel_scale, _REL_NAMES, "rel_scale")
     t, spec, squeeze = _leaf_args(x, "loss_stack", tf, field, threshold, ste, ste_width, grid, origin, roi, levels,
-                                  zs=zs)
-    return _loss(t, target, spec, squeeze, "loss_stack", kind, rel)
+                                  zs=zs, pixel_weight=pixel_weight)
+    return _loss(t, target, spec, squeeze, "loss_stack", kind, rel, pixel_weight)
 
 
 def relativeLoss(x: torch.Tensor, y, fn: Callable, rel_scale="lsq") -> torch.Tensor:

@@ -609,6 +609,63 @@ int hbx_loss_weight_stack(hbx_plan_t plan, const float* intensity, const float* 
                           const double* chan_stats, const double* grad_loss, int32_t n_env, int32_t kind,
                           int32_t rel_scale, float* weight, void* stream);
 
+/* (ABI v15, additive) EXTENSION, no reference counterpart beyond its rectangular crop before the comparison
+ * (env_1024_24_128.py:144-149): per-pixel loss weights -- a signal window plus a don't-care region, or any
+ * non-negative weighting, for every leaf kind at one depth and over a focal stack.  A constant weight v of the
+ * target's shape enters the three float64 sums the last pass leaves and everything downstream of them:
+ *     S_xy = sum v I T    S_xx = sum v I^2    S_yy = sum v T^2    W = sum v   (per env)
+ * hbx_loss's formulas hold with the pixel count n replaced by W, and dL/dI = v (a I + c T) with a and c per env
+ * as hbx_loss_weight forms them, W for n.  The intensity and the field that are written stay the unweighted
+ * ones.  Each term is formed in float64 as vI = (double)v (double)I and vT = (double)v (double)T (exact:
+ * 24 + 24 bits), sxy = fma(vI, T, sxy), sxx = fma(vI, I, sxx), syy = fma(vT, T, syy), in the unweighted last
+ * pass's order (the lane's pixels, the group's lanes, the block's rows): a pixel with v = 1 adds the unweighted
+ * term bit for bit and one with v = 0 leaves the sums unchanged, so v = 1 everywhere gives the unweighted
+ * calls' chan_stats and v = the indicator of a rectangle gives hbx_evaluate_*_window's over that out_win.
+ *
+ * hbx_evaluate_pw: the single-depth forward of every sample leaf kind, named through hbx_leaf_t as
+ *   hbx_evaluate_stack names them (HBX_LEAF_REAL: hbx_evaluate_real, _THRESHOLD: hbx_evaluate_threshold with
+ *   leaf->threshold, _COMPLEX: hbx_evaluate_complex, _PHASE: hbx_evaluate_phase, _PHASE_LEVELS:
+ *   hbx_evaluate_phase_levels with leaf->levels), `values` as that call takes them.  Every rule of that call
+ *   holds, except that target, pixel_weight [B][G][H][W] float32 and chan_stats [B][G][3] are required; field
+ *   and intensity are nullable and are the unweighted call's bit for bit.  There is no psnr output.
+ * hbx_evaluate_stack_pw: hbx_evaluate_stack with pixel_weight [D][B][G][H][W]; depth d's last pass takes depth
+ *   d's block.  target, pixel_weight and chan_stats [D][B][G][3] are required.  Depth d's outputs equal
+ *   hbx_evaluate_pw's on a plan for z[d] with that block, bit for bit.
+ * hbx_pixel_weight_sum: weight_sum [B] float64 = the sum of an env's G images of pixel_weight (n_depths = 0:
+ *   [B][G][H][W]) or of its D G images (n_depths = D >= 1, which must be the plan's: [D][B][G][H][W], d outer,
+ *   g inner), a fixed-order float64 reduction, bitwise reproducible; a sum of ones is exact, so it is G H W for
+ *   v = 1 and G h w for a rectangle's indicator.
+ * hbx_loss_pw / hbx_loss_weight_pw: hbx_loss / hbx_loss_weight (n_depths = 0) or hbx_loss_stack /
+ *   hbx_loss_weight_stack (n_depths = the plan's D) with weight_sum [B] where those calls use n, and
+ *   weight = pixel_weight * (a I + c T): the same coefficients and fmaf, one more float32 multiply.  At v = 1
+ *   both give the unweighted calls' bits.  An env with W = 0 (an all-zero weight) follows the degenerate-env
+ *   rule: its MSE is 0, its PSNR +inf and its loss weight all zero, never a NaN.
+ * The backward pass needs no new call: weight goes into hbx_simulate_complex_weighted, hbx_phase_backward,
+ * hbx_phase_levels_backward, hbx_threshold_backward and hbx_backward_stack as the unweighted loss weight does.
+ *
+ * Undefined, and not checked (a check would cost a host wait): a negative weight is the caller's business (the
+ * formulas are applied as they stand); a NaN weight poisons that env's statistics and loss; a non-finite I or T
+ * under v = 0 gives NaN.  Null required pointers, an unknown leaf kind, levels outside [2, 256] and an n_depths
+ * that is neither 0 nor the plan's: HBX_ERR_INVALID before anything is enqueued; a reduced-precision plan:
+ * HBX_ERR_UNSUPPORTED (the two evaluate calls; the other three do not look at the precision, as hbx_loss does
+ * not); n_env 0 is OK and < 0 HBX_ERR_INVALID.  Out of scope: windows together with weights; the bit path and
+ * every env, DBS, plane-cache and incremental entry point; hbx_rel_stats; a weighted intensity; a weighted psnr
+ * output of the evaluate calls; a differentiable weight. */
+int hbx_evaluate_pw(hbx_plan_t plan, const void* values, const hbx_leaf_t* leaf, const float* target,
+                    const float* pixel_weight, int32_t n_env, float* field, float* intensity,
+                    double* chan_stats, void* stream);
+int hbx_evaluate_stack_pw(hbx_plan_t plan, const void* values, const hbx_leaf_t* leaf, const float* target,
+                          const float* pixel_weight, int32_t n_env, float* field, float* intensity,
+                          double* chan_stats, void* stream);
+int hbx_pixel_weight_sum(hbx_plan_t plan, const float* pixel_weight, int32_t n_env, int32_t n_depths,
+                         double* weight_sum, void* stream);
+int hbx_loss_pw(hbx_plan_t plan, const double* chan_stats, const double* weight_sum, int32_t n_env,
+                int32_t n_depths, int32_t kind, int32_t rel_scale, double* loss, void* stream);
+int hbx_loss_weight_pw(hbx_plan_t plan, const float* intensity, const float* target, const float* pixel_weight,
+                       const double* chan_stats, const double* weight_sum, const double* grad_loss,
+                       int32_t n_env, int32_t n_depths, int32_t kind, int32_t rel_scale, float* weight,
+                       void* stream);
+
 /* PSNR from per-channel statistics (tt.relativeLoss(.., tm.get_PSNR),
  * env.py:174): chan_stats[B][G][3] -> psnr[B]. */
 int hbx_psnr(hbx_plan_t plan, const double* chan_stats, int32_t n_env, double* psnr,
