@@ -115,15 +115,16 @@ def pack_mask(values: torch.Tensor, threshold: Optional[float] = None, out: Opti
     threshold None: bit = (v != 0), and a value other than 0 / 1 stores 1 at `error_ptr`
     (an address the kernel may write: device or host-mapped memory) -- tt.simulate's binary
     check without a host sync.  threshold t: bit = (v >= t) -- env.py:120's `pre_model >= 0.5`.
-    bool / int8 / uint8 / float32 / float64 are read as they are; other dtypes are converted
-    to float32 on the device first.  `out`: a contiguous int64 tensor of the result's shape."""
+    bool / int8 / uint8 / float32 / float64 are read as they are; other dtypes, and int8 against
+    a threshold (the byte kind reads unsigned bytes), are converted to float32 on the device first.  `out`: a contiguous int64 tensor of the result's shape."""
     if not values.is_cuda:
         raise ValueError("pack_mask runs on the GPU (hbx_pack_mask); pack_bits packs host tensors")
     w = values.shape[-1]
     if w % 64:
         raise ValueError("width must be a multiple of 64")
     kind = _PACK_KIND.get(values.dtype)
-    if kind is None:
+    if kind is None or (threshold is not None and values.dtype == torch.int8):
+        # the byte kind compares the unsigned byte: a negative int8 against a threshold goes through float32 (exact)
         values, kind = values.to(torch.float32), _lib.SRC_F32
     if not values.is_contiguous() or values.data_ptr() % _PACK_ALIGN[kind]:
         values = values.contiguous() if not values.is_contiguous() else values.clone()

@@ -13,6 +13,21 @@ Parity status
   cubic, accept/rollback/termination rules) follows the reference code
   line-for-line and is pinned by the known answers the reference itself
   states (``env.py:228-229``: "1 = +300, 1/2 = +100, 1/4 = -100, 1/8 = -300").
+* The control logic (OracleEnv, OracleEnvGroup with importance_ranks at
+  K = 10,000, dbs_greedy with stop_diff, LinearGreedy, premodel_histogram) is
+  pinned to RECORDED RUNS OF THE REFERENCE'S OWN PROGRAMS: oracle/ref_run.py
+  runs env.py, env_md.py, env_group.py and the loop functions of DBS.py,
+  DBS_ratio_0.5.py and DBS_1024_24.py unmodified (stand-ins for the absent
+  packages, this module's physics behind tt / tm),
+  tests/golden/make_ref_golden.py records them (tests/golden/ref_*.npz) and
+  tests/test_ref_parity_host.py replays them here: masks, records, counters,
+  flags and accept sequences exactly, PSNR within 1e-11 dB.  Stated deviations:
+  importance_sample's RNG (the reference draws from the global np.random; the
+  recordings replay it from the seed) and the per-group RGB env step
+  (env_1024_24.py's own step raises on unassigned group means; the
+  RGB semantics pinned are DBS_1024_24.py's loop).  importance_ranks sorts
+  stably; the reference's np.argsort leaves equal changes (a pixel sampled twice)
+  in an unspecified order, so ranks agree up to a permutation within such ties.
 * The physics (``tt.simulate``, ``tt.relativeLoss``, ``tm.get_PSNR``) lives
   in the third-party package ``torchOptics`` which is absent from
   /root/reference, unpinned (not in requirements.txt, ``.gitignore:3``) and

@@ -1,10 +1,13 @@
 """Generate the committed golden fixtures from the oracle (oracle/hbx_oracle.py).
 
-The reference cannot run here (torchOptics / gymnasium / SB3 / torchvision
-absent), so these vectors are the oracle's own float64 outputs on
-seeded inputs, plus the reference's stated known answers (env.py:228-229).
-They pin (a) the oracle against silent drift and (b) the HIP path in the
--m gpu parity tests.  Run:  python tests/golden/make_golden.py
+The reference's physics cannot run here (torchOptics absent), so these
+vectors are the oracle's own float64 outputs on seeded inputs, plus the reference's
+stated known answers (env.py:228-229).  They pin (a) the oracle against silent drift
+and (b) the HIP path in the -m gpu parity tests.  The reference's CONTROL LOGIC does
+run (oracle/ref_run.py: stand-ins for the absent packages, the oracle's physics behind
+tt / tm): tests/golden/make_ref_golden.py records it into tests/golden/ref_*.npz, and
+those recordings, not this file's vectors, are what pins the oracle's env and DBS rules
+to the reference (tests/test_ref_parity_host.py, tests/test_gpu_ref_parity.py).  Run:  python tests/golden/make_golden.py
 (the headline-size DBS fixtures: python tests/golden/make_golden.py --large)
 """
 import os

@@ -64,6 +64,27 @@ def test_pack_threshold_matches_numpy(dtype):
     assert np.array_equal(_words(got), O.pack_mask((pre >= 0.5).astype(np.uint8)))
 
 
+@pytest.mark.parametrize("threshold", [0.5, 0, -1])
+@pytest.mark.parametrize("dtype", [torch.int8, torch.uint8, torch.bool])
+def test_pack_threshold_integer_kinds_match_torch(dtype, threshold):
+    """bit = (v >= t) as torch compares it, for the byte kinds: int8 is signed (-1 >= 0.5 is False, -128
+    and -1 are below 0 and -1 >= -1 holds), uint8 reaches 255 and bool is 0 / 1.  Every edge value sits
+    in every byte lane of the kernel's 4-byte load, over 7 words (not a multiple of its 4-word group)."""
+    import hbx
+    edges = {torch.int8: [-128, -1, 0, 1, 127], torch.uint8: [0, 1, 127, 128, 255], torch.bool: [0, 1]}[dtype]
+    n = 3 * 7 * 64
+    v = np.random.default_rng(23).choice(np.array(edges, np.int64), n)
+    for lane in range(4):
+        assert set(v[lane::4]) == set(edges)
+    t = torch.from_numpy(v.reshape(3, 7 * 64)).to(dtype).cuda()
+    want = (v.reshape(3, 7 * 64) >= threshold).astype(np.uint8)       # the values' own order
+    if (dtype, threshold) != (torch.uint8, -1):     # torch wraps a scalar -1 to uint8 255 before it compares
+        assert np.array_equal(want, (t >= threshold).cpu().numpy().astype(np.uint8))
+    assert 0 < want.sum() <= want.size
+    got = hbx.pack_mask(t, threshold=threshold)
+    assert got.shape == (3, 7) and np.array_equal(_words(got), O.pack_mask(want))
+
+
 def test_pack_into_env_slice_and_misaligned_view():
     """out= an env's mask row (what reset does); a view whose start is not 16-byte aligned
     is copied first, with the same bits."""
