@@ -546,6 +546,15 @@ struct FullRequest {
                                        // gradient, are quantized to L levels as they are loaded; 0: continuous
   const float* target = nullptr;       // [n][G][N][N]; null: no statistics
   const float* pixel_weight = nullptr; // (hbx_evaluate_pw) [n][G][N][N] f32 per-pixel loss weight, with a target only
+  // (hbx_evaluate_source / hbx_backward_source) the illumination [G][N][N] complex64, shared by every env; the
+  // forward multiplies on load, the adjoint (complex input) by its conjugate in the last pass.  source_real:
+  // real samples [n][G*P/2][N][N] f32 into complex plane slots (forward with a source only), binarized at
+  // source_threshold with source_binarize
+  const float2* source = nullptr;
+  bool source_adjoint = false;
+  const float* source_real = nullptr;
+  bool source_binarize = false;
+  float source_threshold = 0.0f;
   const int32_t* env_ids = nullptr;    // absolute env ids into every buffer (mask input only); null: 0 .. n - 1
   int n = 0;
   // outputs, all nullable
@@ -587,7 +596,7 @@ int propagate_full(hbx_plan_t p, const FullRequest& r, void* stream) {
   const int G = pd.G, CH = pd.G * pd.P;
   const int CHs = CH + 2 * r.spares;   // plane-cache slots per env
   const int chunk = p->max_jobs / G;
-  const bool cplx = r.complex_values || r.phase_values;
+  const bool cplx = r.complex_values || r.phase_values || r.source_real;
   HBX_HIP(hipSetDevice(p->device));
   if (r.plane_pool) {
     if (pd.R != 32 && pd.R != 16 && pd.R != 0)
@@ -641,6 +650,11 @@ int propagate_full(hbx_plan_t p, const FullRequest& r, void* stream) {
     c.phase_levels = r.phase_levels;
     c.target = at(r.target, s_img);
     c.pixel_weight = at(r.pixel_weight, s_img);
+    c.source = r.source;
+    c.source_adjoint = r.source_adjoint;
+    c.source_real = at(r.source_real, s_cplx);
+    c.source_binarize = r.source_binarize;
+    c.source_threshold = r.source_threshold;
     c.inten_out = direct ? at(r.intensity, s_img) : (r.intensity ? p->job_inten : nullptr);
     c.field_out = at(r.field, s_field);
     c.complex_field = at(r.complex_field, s_cout);
@@ -1141,6 +1155,107 @@ int hbx_backward_stack(hbx_plan_t p, const float* values, const float* weight, f
     HBX_HIP(hbx::run_stack_last(pd, o, D, nj, st));
   }
   return HBX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Illumination fields (include/hbx.h, "Illumination fields")
+// ---------------------------------------------------------------------------
+namespace {
+// what the three calls ask of their common arguments, before anything is enqueued
+int check_source_call(hbx_plan_t p, const void* values, const hbx_leaf_t* leaf, const float* source) {
+  if (!leaf || !leaf_kind_known(leaf->kind)) return fail(HBX_ERR_INVALID, "leaf: a known HBX_LEAF_* kind");
+  if (leaf->kind == HBX_LEAF_PHASE_LEVELS) {
+    if (int rc = check_levels(leaf->levels)) return rc;
+  }
+  if (!source) return fail(HBX_ERR_INVALID, "null buffer: source [G][H][W] complex64 is required");
+  if (!values) return fail(HBX_ERR_INVALID, "null buffer: values");
+  if (p->pd.store_kind != HBX_PRECISION_F32)
+    return fail(HBX_ERR_UNSUPPORTED, "illumination fields: HBX_PRECISION_F32 only (the plan stores reduced-precision intermediates)");
+  return HBX_OK;
+}
+// the leaf as the sourced first pass reads it: every kind is one complex plane per leaf plane
+void set_source_leaf(FullRequest& r, const void* values, const hbx_leaf_t* leaf) {
+  switch (leaf->kind) {
+    case HBX_LEAF_THRESHOLD: r.source_binarize = true; r.source_threshold = leaf->threshold;   // fallthrough
+    case HBX_LEAF_REAL: r.source_real = static_cast<const float*>(values); break;
+    case HBX_LEAF_COMPLEX: r.complex_values = static_cast<const float2*>(values); break;
+    case HBX_LEAF_PHASE_LEVELS: r.phase_levels = leaf->levels;   // fallthrough
+    default: r.phase_values = static_cast<const float*>(values); break;
+  }
+}
+}  // namespace
+
+int hbx_source_field(hbx_plan_t p, const void* values, const hbx_leaf_t* leaf, const float* source, int32_t n_env,
+                     float* out_field, void* stream) {
+  HBX_ENTER(p, n_env, "n_env");
+  if (int rc = check_source_call(p, values, leaf, source)) return rc;
+  if (!out_field) return fail(HBX_ERR_INVALID, "null buffer: out_field");
+  const PlanDev& pd = p->pd;
+  HBX_HIP(hipSetDevice(p->device));
+  // the first pass's kind and parameters, from the PassCall it would get
+  FullRequest r;
+  set_source_leaf(r, values, leaf);
+  PassCall c;
+  c.complex_values = r.complex_values; c.phase_values = r.phase_values; c.phase_levels = r.phase_levels;
+  c.source_real = r.source_real; c.source_binarize = r.source_binarize; c.source_threshold = r.source_threshold;
+  const hbx::SourceParams sp = hbx::pass_source_params(pd, c);
+  const int Q = pd.P / 2;
+  HBX_HIP(hbx::launch_source_field(hbx::pass_source_samples(c), reinterpret_cast<const float2*>(source),
+                                   hbx::pass_source_kind(c), (int64_t)n_env * pd.G * Q, pd.G, Q, (size_t)pd.N * pd.N,
+                                   sp.p0, sp.p1, sp.p2, reinterpret_cast<float2*>(out_field), (hipStream_t)stream));
+  return HBX_OK;
+}
+
+// hbx_evaluate_complex (pixel_weight: hbx_evaluate_pw's complex form) with the sourced first pass
+int hbx_evaluate_source(hbx_plan_t p, const void* values, const hbx_leaf_t* leaf, const float* source,
+                        const float* target, const float* pixel_weight, int32_t n_env, float* field, float* intensity,
+                        double* chan_stats, void* stream) {
+  HBX_ENTER(p, n_env, "n_env");
+  if (int rc = check_source_call(p, values, leaf, source)) return rc;
+  if (pixel_weight) {
+    if (!target || !chan_stats)
+      return fail(HBX_ERR_INVALID, "null buffer: a pixel_weight needs target and chan_stats");
+  } else if (int rc = check_eval_outputs(target, chan_stats, nullptr, intensity != nullptr, true)) {
+    return rc;
+  }
+  FullRequest r;
+  set_source_leaf(r, values, leaf);
+  r.source = reinterpret_cast<const float2*>(source);
+  r.target = target; r.pixel_weight = pixel_weight; r.n = n_env;
+  r.complex_field = reinterpret_cast<float2*>(field); r.complex_stats = true;
+  r.intensity = intensity; r.chan_stats = chan_stats;
+  return propagate_full(p, r, stream);
+}
+
+// hbx_backward_stack's outputs at one depth, on the plan for -z, with conj(source) in the last pass
+int hbx_backward_source(hbx_plan_t p, const float* values, const float* weight, float scale, const hbx_leaf_t* leaf,
+                        const float* source, const float* samples, int32_t n_env, float* grad_field, float* grad,
+                        void* stream) {
+  HBX_ENTER(p, n_env, "n_env");
+  if (int rc = check_source_call(p, values, leaf, source)) return rc;
+  if ((grad_field != nullptr) == (grad != nullptr))
+    return fail(HBX_ERR_INVALID, "exactly one of grad_field and grad is given");
+  if ((leaf->kind == HBX_LEAF_COMPLEX) != (grad_field != nullptr))
+    return fail(HBX_ERR_INVALID, "grad_field is a complex leaf's output, grad every other leaf's");
+  const bool needs_samples = leaf->kind == HBX_LEAF_PHASE || leaf->kind == HBX_LEAF_PHASE_LEVELS ||
+                             leaf->kind == HBX_LEAF_THRESHOLD;
+  if (needs_samples != (samples != nullptr))
+    return fail(HBX_ERR_INVALID, "samples: the leaf's x for a phase, L-level or thresholded leaf, null otherwise");
+  if (leaf->kind == HBX_LEAF_THRESHOLD) {
+    if (int rc = check_surrogate(leaf->surrogate, leaf->p1)) return rc;
+  }
+  FullRequest r;
+  r.complex_values = reinterpret_cast<const float2*>(values); r.weight = weight; r.n = n_env;
+  if (weight) r.scale = scale;
+  r.source = reinterpret_cast<const float2*>(source); r.source_adjoint = true;
+  switch (leaf->kind) {
+    case HBX_LEAF_COMPLEX: r.complex_field = reinterpret_cast<float2*>(grad_field); break;
+    case HBX_LEAF_REAL: r.real_part = grad; break;
+    case HBX_LEAF_PHASE_LEVELS: r.phase_levels = leaf->levels;   // fallthrough
+    case HBX_LEAF_PHASE: r.grad_samples = samples; r.grad_phase = grad; break;
+    default: set_ste(r, samples, grad, leaf->surrogate, leaf->p0, leaf->p1); break;
+  }
+  return propagate_full(p, r, stream);
 }
 
 namespace {

@@ -250,6 +250,12 @@ constexpr int kLoadComplex = 0, kLoadWeighted = 1, kLoadPhase = 2, kLoadPhaseLev
 // with the quantizer on the samples it loads
 constexpr int kGradNone = 0, kGradPhase = 1, kGradSteWindow = 2, kGradSteSigmoid = 3, kGradPhaseLevels = 4;
 
+// Illumination fields (hbx.h, "Illumination fields"): the leaf kind a sourced first pass (k_rowfwd_src,
+// k_rowfwd32_src, k_rowfwd896_src) or the materialiser (k_source_field, hbx_pack.hip) forms f from, before
+// it multiplies by the source sample s (source_leaf_field / source_mul, below).  Every kind fills one
+// complex plane per leaf plane
+constexpr int kSrcComplex = 0, kSrcPhase = 1, kSrcPhaseLevels = 2, kSrcReal = 3, kSrcThreshold = 4;
+
 // The phase quantizer (hbx.h, "Quantized phase holograms"): the float32 phase sample x, in units of pi,
 // to the nearest of L levels 2 k / L.  Every operation is float32, round-half-to-even:
 //   r = x - 2 rint(x / 2)   exact, r in [-1, 1] (so a contraction of the subtract into an fma changes nothing)
@@ -385,6 +391,23 @@ struct PassCall {
   // never with a window, plane cache, actions, walk, reconcile or env-major output (check_pass_call).
   // Null: the launches a call ran before
   const float* pixel_weight = nullptr;
+  // (extension, hbx_evaluate_source / hbx_backward_source) the illumination: [G][N][N] complex64, constant,
+  // shared by every env and plane of a colour group.  source_adjoint = 0, the forward: the first pass
+  // propagates u = s f (source_load_row), f from complex_values, phase_values (with phase_levels) or
+  // source_real below, and the last pass is the complex path's as it is.  source_adjoint = 1, the backward
+  // on the plan for -z: complex_values (with or without complex_weight) in through the existing loads, and
+  // the last pass multiplies the plane by conj(s) before its one output -- complex_field, real_part, or the
+  // gradient pair with its kind -- without statistics.  Only on the complex path of an f32 plan; never
+  // with a window, a stack piece, the plane cache, actions, a walk, the reconcile or env-major output
+  // (check_pass_call).  Null: the launches a call ran before
+  const float2* source = nullptr;
+  int source_adjoint = 0;
+  // ... and the fifth input (counted by "exactly one"): real samples [env][G*P/2][N][N] f32 into complex
+  // plane slots, u = s x, or with source_binarize u = s (va + vb [x >= source_threshold]).  Only with a
+  // source in the forward: the real kinds have one plane per leaf plane there, not a pair
+  const float* source_real = nullptr;
+  int source_binarize = 0;
+  float source_threshold = 0.0f;
 };
 // whether any focal-stack field is set
 inline bool pass_stack(const PassCall& c) {
@@ -408,7 +431,7 @@ inline bool pass_window_in(const PassCall& c, int N) {
 }
 
 // The complex path: complex or phase samples in, the pair-recombining last pass out
-inline bool pass_complex(const PassCall& c) { return c.complex_values || c.phase_values; }
+inline bool pass_complex(const PassCall& c) { return c.complex_values || c.phase_values || c.source_real; }
 
 // The quantizing forms' constants reach the kernels in arguments their load / gradient kind leaves unread, so
 // no kernel signature changes (and no existing kernel's code): the first pass reads h where the weighted load
@@ -436,6 +459,24 @@ inline float pass_grad_p1(const PassCall& c) {
   return pass_grad_kind(c) == kGradPhaseLevels ? phase_levels_of(c.phase_levels).s : c.grad_p1;
 }
 
+// the sourced first pass's leaf kind (kSrc*), its samples as floats and its three parameters (source_sample)
+inline int pass_source_kind(const PassCall& c) {
+  return c.source_real ? (c.source_binarize ? kSrcThreshold : kSrcReal)
+                       : c.phase_values ? (c.phase_levels ? kSrcPhaseLevels : kSrcPhase) : kSrcComplex;
+}
+inline const float* pass_source_samples(const PassCall& c) {
+  return c.source_real ? c.source_real : c.phase_values ? c.phase_values : reinterpret_cast<const float*>(c.complex_values);
+}
+struct SourceParams {
+  float p0, p1, p2;
+};
+inline SourceParams pass_source_params(const PlanDev& pd, const PassCall& c) {
+  const int sk = pass_source_kind(c);
+  if (sk == kSrcPhaseLevels) return {phase_levels_of(c.phase_levels).h, phase_levels_of(c.phase_levels).s, 0.0f};
+  if (sk == kSrcThreshold) return {c.source_threshold, pd.va, pd.va + pd.vb};
+  return {0.0f, 0.0f, 0.0f};
+}
+
 // Which PassCalls the pass kernels of this plan can run: every field a selected kernel would not
 // read is refused, not ignored.  run_jobs calls it before a timer slot opens or a kernel is enqueued.
 inline hipError_t check_pass_call(const PlanDev& pd, const PassCall& c) {
@@ -446,7 +487,7 @@ inline hipError_t check_pass_call(const PlanDev& pd, const PassCall& c) {
   const bool complex_out = c.complex_field || c.real_part || c.complex_stats;
   const bool grad_out = c.grad_samples || c.grad_phase;
   bool ok = (c.mask != nullptr) + (c.real_values != nullptr) + (c.complex_values != nullptr) +
-            (c.phase_values != nullptr) == 1;
+            (c.phase_values != nullptr) + (c.source_real != nullptr) == 1;
   ok = ok && (!planes || (c.plane_pool && c.plane_slot && (tiled || pd.R == 0)));
   ok = ok && (!c.walk_planes || (c.plane_mode == kPlanesStep && tiled));
   ok = ok && (!c.walk_anneal || c.walk_planes);
@@ -503,6 +544,22 @@ inline hipError_t check_pass_call(const PlanDev& pd, const PassCall& c) {
     ok = ok && !c.windowed && !planes && !c.actions && !walk && !c.rc_pending && !c.inten_by_env;
     ok = ok && !c.stack_skip_last;
   }
+  // an illumination source: the complex path of an f32 plan -- not the bit path, not the real-pair path -- and
+  // no window, stack piece, plane cache, actions, walk, reconcile or env-major output.  The forward takes any
+  // of the complex path's outputs (a pixel weight too: the last pass is the existing statistics form); the
+  // adjoint has complex samples in and one output that is no statistics form, so no target and no pixel weight.
+  // The real samples in a complex slot, and their threshold switch, only in the forward of a sourced call
+  if (c.source) {
+    ok = ok && !c.mask && !c.real_values && f32;
+    ok = ok && !c.windowed && !pass_stack(c) && !planes && !c.actions && !walk && !c.rc_pending && !c.inten_by_env;
+    if (c.source_adjoint)
+      ok = ok && c.complex_values && !c.complex_stats && !c.target && !c.inten_out && !c.pixel_weight &&
+           (c.complex_field != nullptr) + (c.real_part != nullptr) + (grad_out ? 1 : 0) == 1;
+    else
+      ok = ok && !c.complex_weight && !grad_out;
+  }
+  ok = ok && (c.source || (!c.source_adjoint && !c.source_real));
+  ok = ok && (!c.source_real || !c.source_adjoint) && (c.source_real || !c.source_binarize);
   return ok ? hipSuccess : hipErrorInvalidValue;
 }
 // The target rows the last pass reads.  No target: the plan's zero row, every row offset masked to 0
@@ -743,6 +800,10 @@ hipError_t launch_pack_mask(const void* src, int kind, int64_t n_words, int mode
 // (ABI v15, additive) hbx_pack.hip: the phase quantizer's export, level[n] uint8 and / or q[n] f32 (nullable)
 hipError_t launch_quantize_phase(const float* src, int64_t n, int levels, uint8_t* out_levels, float* out_phase,
                                  hipStream_t st);
+// (extension, illumination fields) hbx_pack.hip: out[n_planes][hw] complex64 = source[g] * f(values), leaf
+// kind sk (kSrc*) with source_sample's (p0, p1, p2); plane i belongs to group (i / Q) % G
+hipError_t launch_source_field(const float* values, const float2* source, int sk, int64_t n_planes, int G, int Q,
+                               size_t hw, float p0, float p1, float p2, float2* out, hipStream_t st);
 int rel_partial_slots();
 hipError_t launch_rel_stats(const void* x, const void* y, int kind, int64_t n, double count, int rel_scale,
                             double peak, double* part, double* out, hipStream_t st);

@@ -23,6 +23,7 @@
 
 #include "hbx.h"
 #include "hbx_internal.hpp"
+#include "hbx_rowcol.hpp"
 
 namespace hbx {
 
@@ -633,6 +634,54 @@ hipError_t launch_loss_weight_pw(const float* inten, const float* target, const 
                      reinterpret_cast<const float4*>(inten), reinterpret_cast<const float4*>(target),
                      reinterpret_cast<const float4*>(pixel_weight), chan_stats, weight_sum, grad_loss, n, G, D, n4, bx,
                      kind, rel_scale, reinterpret_cast<float4*>(weight));
+  return hipGetLastError();
+}
+
+// (extension, illumination fields) hbx_source_field: the field at the modulator, u = s f(x), one streaming
+// pass with the device functions the sourced first passes form it with (source_sample, hbx_rowcol.hpp), so
+// the materialised u is theirs bit for bit.  The leaf's [B][G Q][hw] samples -- complex64 pairs for
+// kSrcComplex, float32 otherwise, read once (non-temporal) -- times source[g][pixel].  A workgroup row
+// (blockIdx.y, strided) is a plane, so the group is found once per plane and no pixel divides; the pixels of
+// a plane go to the threads of its workgroups in a grid-stride loop.
+template <int SK>
+__global__ __launch_bounds__(256) void k_source_field(const float* __restrict__ values,
+                                                      const float2* __restrict__ source, int64_t n_planes, int G,
+                                                      int Q, int hw, float p0, float p1, float p2,
+                                                      float2* __restrict__ out) {
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  const int stride = (int)gridDim.x * 256;
+  for (int64_t plane = blockIdx.y; plane < n_planes; plane += gridDim.y) {
+    const int g = (int)((plane / Q) % G);
+    const float2* __restrict__ srow = source + (size_t)g * hw;
+    const size_t base = (size_t)plane * hw;
+    for (int pix = (int)blockIdx.x * 256 + threadIdx.x; pix < hw; pix += stride) {
+      const float2 s = srow[pix];
+      float a, b = 0.0f;
+      if constexpr (SK == kSrcComplex) {
+        const f32x2 x = __builtin_nontemporal_load(reinterpret_cast<const f32x2*>(values) + base + pix);
+        a = x.x, b = x.y;
+      } else {
+        a = __builtin_nontemporal_load(values + base + pix);
+      }
+      float ur, ui;
+      source_sample<SK>(a, b, s.x, s.y, p0, p1, p2, ur, ui);
+      out[base + pix] = make_float2(ur, ui);
+    }
+  }
+}
+
+hipError_t launch_source_field(const float* values, const float2* source, int sk, int64_t n_planes, int G, int Q,
+                               size_t hw, float p0, float p1, float p2, float2* out, hipStream_t st) {
+  if (n_planes <= 0 || hw == 0) return hipSuccess;
+  const size_t want = (hw + 1023) / 1024;   // 4 pixels per thread before the grid is capped
+  const unsigned bx = (unsigned)(want < 64 ? want : 64);
+  const unsigned by = (unsigned)(n_planes < 65535 ? n_planes : 65535);
+  auto k = k_source_field<kSrcComplex>;
+  if (sk == kSrcPhase) k = k_source_field<kSrcPhase>;
+  if (sk == kSrcPhaseLevels) k = k_source_field<kSrcPhaseLevels>;
+  if (sk == kSrcReal) k = k_source_field<kSrcReal>;
+  if (sk == kSrcThreshold) k = k_source_field<kSrcThreshold>;
+  hipLaunchKernelGGL(k, dim3(bx, by), dim3(256), 0, st, values, source, n_planes, G, Q, (int)hw, p0, p1, p2, out);
   return hipGetLastError();
 }
 

@@ -1470,6 +1470,11 @@ __global__ __launch_bounds__(256, 2) void k_rowinv_walk_anneal(const JobDesc* __
 // (pixel weights) the weighted last passes and their pick, behind every other kernel of this file
 template <int R>
 static void launch_last_pw(const PlanDev& pd, const PassCall& c, float2* ws_b, unsigned blocks, hipStream_t st);
+// (illumination fields) the sourced first and last passes and their picks, behind the weighted ones
+template <int R>
+static void launch_first_src(const PlanDev& pd, const PassCall& c, float2* ws_a, unsigned blocks, hipStream_t st);
+template <int R>
+static void launch_last_src(const PlanDev& pd, const PassCall& c, float2* ws_b, unsigned blocks, hipStream_t st);
 
 template <int R, int SK>
 static hipError_t launch_passes(const PlanDev& pd, const PassCall& c, hipStream_t st) {
@@ -1504,7 +1509,9 @@ static hipError_t launch_passes(const PlanDev& pd, const PassCall& c, hipStream_
   float2* const ws_b = pd.ws_b + (size_t)c.stack_slot0 * P * plane_b_elems(R);
   if (!c.stack_skip_first) {
     if (tm) tm->begin(0, st);
-    if (pass_complex(c)) {   // the load kind: complex samples as they are, times scale * weight, or exp(i pi phase)
+    if (c.source && !c.source_adjoint) {   // the sourced loads, only when the pointer is set
+      launch_first_src<R>(pd, c, ws_a, sample_blocks, st);
+    } else if (pass_complex(c)) {   // the load kind: complex samples as they are, times scale * weight, or exp(i pi phase)
       const int lk = c.phase_values ? (c.phase_levels ? kLoadPhaseLevels : kLoadPhase) : c.complex_weight ? kLoadWeighted : kLoadComplex;
       launch_kernel(pick_first_pass_cplx<SampleKernels<R>>(lk, pass_window_in(c, N)), sample_blocks, NT, st, jobs,
                     c.complex_values, ws_a, pd.tw, P, CH, c.complex_weight, pass_first_scale(c), c.phase_values, pass_first_window(c));
@@ -1541,6 +1548,8 @@ static hipError_t launch_passes(const PlanDev& pd, const PassCall& c, hipStream_
   if (tm) tm->begin(2, st);
   if (c.pixel_weight) {    // the weighted statistics forms, only when the pointer is set
     launch_last_pw<R>(pd, c, ws_b, blocks, st);
+  } else if (c.source && c.source_adjoint) {   // conj(source) on the plane, then the leaf's gradient
+    launch_last_src<R>(pd, c, ws_b, blocks, st);
   } else if (pass_complex(c)) {   // recombine each plane pair, or a leaf's gradient instead (pick_last_pass_cplx)
     const auto k = pick_last_pass_cplx<SampleKernels<R>>(pass_grad_kind(c), c.complex_stats != 0,
                                                          c.windowed != 0);
@@ -2113,6 +2122,304 @@ static void launch_last_pw(const PlanDev& pd, const PassCall& c, float2* ws_b, u
       launch_kernel(k_rowinv_pw<R, NT>, blocks, NT, st, c.jobs, ws_b, c.target, c.pixel_weight, pd.tw, pd.P, pd.G,
                     pd.partial, c.inten_out, c.field_out);
   }
+}
+
+// ---------------------------------------------------------------------------
+// Illumination fields (hbx_evaluate_source / hbx_backward_source, EXTENSION)
+// ---------------------------------------------------------------------------
+// The modulator is lit by source[G][N][N] complex64 instead of a unit plane wave: the forward's first pass
+// propagates u = s f(x), formed as it loads the leaf's samples and the source row (source_load_row,
+// hbx_rowcol.hpp), and the backward's last pass multiplies the back-propagated plane by conj(s) behind its
+// inverse row FFT and in front of the leaf's gradient formula (source_conj_row).  The column pass, the
+// forward's last pass and the backward's first pass are the launches that exist.  The kernels are the
+// siblings' bodies -- k_rowfwd_cplx / k_rowfwd32_cplx, k_rowinv_d_cplx / k_rowinv_cplx without their
+// statistics and window forms -- with argument lists of their own, behind every other kernel of this file,
+// so no existing instantiation's code, descriptor or place moves (tools/isa_cmp.py).
+//
+// SK (kSrc*): the leaf kind; all five fill one complex plane per leaf plane, the two real kinds included.
+// values: [env][CH / 2][N][N] complex64 (kSrcComplex) or float32; (p0, p1, p2): source_sample's.
+template <int R, int NT, int SK>
+__global__ __launch_bounds__(NT, 512 / NT) void k_rowfwd_src(const JobDesc* __restrict__ jobs,
+                                                       const float* __restrict__ values,
+                                                       const float2* __restrict__ source,
+                                                       float2* __restrict__ ws_a,
+                                                       const float2* __restrict__ tw_glob, int P, int CH,
+                                                       float p0, float p1, float p2) {
+  constexpr int N = R * R;
+  constexpr int GPB = NT / R;          // rows per row block
+  __shared__ float2 tw[N];
+  __shared__ __attribute__((aligned(16))) float2 lds[rowfwd_scratch<R, NT>()];
+
+  stage_twiddles<N, NT>(tw, tw_glob);
+
+  const int grp = threadIdx.x / R;
+  const int t = threadIdx.x % R;
+  const int lane_base = (threadIdx.x & 63) - t;
+  constexpr int RB = N / GPB;
+  const FirstPassBlock wg = first_pass_block<RB>(xcd_pair<RB>(blockIdx.x), P / 2);
+  const int j = wg.j;
+  const JobDesc jb = jobs[j];
+  if (jb.env < 0) return;  // uniform per block
+  const int y0 = wg.rbw * GPB;
+  const int y = y0 + grp;
+  pk2 v[R];
+  first_pass_load_src<R, R, SK, R>(v, values, source, jb.env, jb.group, P, CH, wg.q, y, t, p0, p1, p2);
+  __syncthreads();  // tw visible
+
+  float2* base = ws_a + ((size_t)j * P + 2 * wg.q) * plane_a_elems(R);
+  rowfwd_emit<R, NT, HBX_PRECISION_F32>(v, t, grp, lane_base, y0, lds, tw, base);
+}
+
+// N = 1024: k_rowfwd32_cplx's geometry and its three workgroups per CU.  A row is 32 samples and 32
+// source pairs per lane, and all of them are in flight at once: 142 VGPRs for the complex kind, 112-115
+// for the others, of the 168 that three workgroups leave, no scratch.  In halves (kSrc32Piece = 16) the
+// complex kind takes 128 and occupies the same, so the whole row stays (DESIGN.md;
+// profiles/source_field/resource_usage.txt)
+constexpr int kSrc32Piece = 32;
+template <int SK>
+__global__ __launch_bounds__(256, 3) void k_rowfwd32_src(const JobDesc* __restrict__ jobs,
+                                                         const float* __restrict__ values,
+                                                         const float2* __restrict__ source,
+                                                         float2* __restrict__ ws_a,
+                                                         const float2* __restrict__ tw_glob, int P, int CH,
+                                                         float p0, float p1, float p2) {
+  constexpr int R = 32, NT = 256, N = R * R;
+  constexpr int GPB = NT / R;          // 8 rows per row block
+  __shared__ float2 tw[N];
+  __shared__ __attribute__((aligned(16))) float lds[kRowfwd32Scr];
+
+  stage_twiddles<N, NT>(tw, tw_glob);
+
+  const int grp = threadIdx.x / R;
+  const int t = threadIdx.x % R;
+  const int k1 = mirror_k1(t);         // the second FFT stage in mirror-paired lane order
+  constexpr int RB = N / GPB;
+  const FirstPassBlock wg = first_pass_block<RB>(xcd_pair<RB>(blockIdx.x), P / 2);
+  const int j = wg.j;
+  const JobDesc jb = jobs[j];
+  if (jb.env < 0) return;  // uniform per block
+  const int y0 = wg.rbw * GPB;
+  const int y = y0 + grp;
+  pk2 v[R];
+  first_pass_load_src<R, R, SK, kSrc32Piece>(v, values, source, jb.env, jb.group, P, CH, wg.q, y, t, p0, p1, p2);
+  __syncthreads();  // tw visible
+
+  float2* base = ws_a + ((size_t)j * P + 2 * wg.q) * plane_a_elems(R);
+  rowfwd32_emit<HBX_PRECISION_F32>(v, t, k1, grp, y0, lds, tw, base);
+}
+
+// The sourced last passes: k_rowinv_d_cplx (N = 1024 / 256) and k_rowinv_cplx (N = 64) with g' = conj(s) g
+// between the inverse row FFT and cplx_plane_out; source row y of the job's group, loaded behind the FFT.
+// GK: kGradNone (g' to field_out, or Re g' to real_out -- one of the two), the two phase kinds, the two
+// STE kinds.  No statistics, no window.
+template <int R, int GK>
+__global__ __launch_bounds__(256, 2) void k_rowinv_d_src(const JobDesc* __restrict__ jobs,
+                                                         const float2* __restrict__ ws_b,
+                                                         const float2* __restrict__ tw_glob, int P, int G,
+                                                         const float2* __restrict__ source,
+                                                         float2* __restrict__ field_out,
+                                                         float* __restrict__ real_out,
+                                                         const float* __restrict__ phase,
+                                                         float* __restrict__ grad, float gvb, float ga,
+                                                         float gb) {
+  constexpr int N = R * R, GPB = 256 / R, RB = N / GPB;
+  __shared__ float2 tw[N];
+  __shared__ float2 scratch[GPB * R * (R + 1)];
+  for (int i = threadIdx.x; i < N; i += 256) tw[i] = tw_glob[i];
+
+  const int grp = threadIdx.x / R;
+  const int t = threadIdx.x % R;
+  const int bid = xcd_pair<RB>(blockIdx.x);
+  const int rb = bid % RB;
+  const int j = bid / RB;
+  const JobDesc jb = jobs[j];
+  if (jb.env < 0) return;  // uniform per block
+  const int y = rb * GPB + grp;
+  const hbx_window_t win = {0, 0, 0, 0};
+  const WinRow wr(win, y, t);   // (unread: no window form)
+  const int Q = P / 2;                        // complex planes per group
+  constexpr int PLB = N * N;                 // float2 per B plane
+  const __amdgpu_buffer_rsrc_t rs = plane_rsrc(ws_b + (size_t)j * P * PLB, (unsigned)((size_t)P * PLB * 8));
+  const RowinvLanes<R> ln(y, t);
+  auto load_pair = [&](pk2 (&v)[R], int q) { rowinv_load_pair(v, ln, rs, q); };
+  const PaddedScratch<R> sc{scratch + grp * R * (R + 1)};
+  const size_t row0 = (((size_t)jb.env * G + jb.group) * Q * N + y) * N + t;   // complex plane 0, pixel x = t
+  const float2* s0 = source + ((size_t)jb.group * N + y) * N + t;               // the source row, pixel x = t
+  float acc[1];
+  auto finish_plane = [&](pk2 (&v)[R], int q) {
+    fft_group<R, true>(v, t, sc, tw);
+    source_conj_row<R, R>(v, s0);
+    cplx_plane_out<R, R, false, GK, false>(v, acc, jb.env, jb.group, G, Q, q, y, row0, win, wr, field_out, real_out,
+                                           phase, grad, gvb, ga, gb);
+  };
+  pk2 va[R];
+  load_pair(va, 0);
+  __syncthreads();  // tw visible
+  if constexpr (R == 16) {
+    pk2 vb[R];
+#pragma unroll 1
+    for (int q = 0; q < Q; q += 2) {
+      if (q + 1 < Q) load_pair(vb, q + 1);
+      finish_plane(va, q);
+      if (q + 1 < Q) {
+        if (q + 2 < Q) load_pair(va, q + 2);
+        finish_plane(vb, q + 1);
+      }
+    }
+  } else {
+#pragma unroll 1
+    for (int q = 0; q < Q; ++q) {
+      finish_plane(va, q);
+      if (q + 1 < Q) load_pair(va, q + 1);   // uniform: no pair is read twice
+    }
+  }
+}
+
+// N = 64: the registers also hold the next pair's tiles (pa, pb), and the unsourced gradient forms run five
+// workgroups per CU (86-93 VGPRs).  To keep that: the launch bound asks for five, the source row is taken in
+// pieces of kSrc8Piece pixels, and kGradNone is two instantiations -- RP: the real part to real_out, else the
+// field to field_out -- so no null test sits between the product and the stores.  84-96 VGPRs, no scratch
+// (whole row and one kGradNone form under the same bound: 12-68 bytes of scratch;
+// profiles/source_field/resource_usage.txt)
+constexpr int kSrc8Piece = 2;
+template <int R, int NT, int GK, bool RP = false>
+__global__ __launch_bounds__(NT, 5) void k_rowinv_src(const JobDesc* __restrict__ jobs,
+                                                       const float2* __restrict__ ws_b,
+                                                       const float2* __restrict__ tw_glob, int P, int G,
+                                                       const float2* __restrict__ source,
+                                                       float2* __restrict__ field_out,
+                                                       float* __restrict__ real_out,
+                                                       const float* __restrict__ phase,
+                                                       float* __restrict__ grad, float gvb, float ga,
+                                                       float gb) {
+  constexpr int N = R * R;
+  constexpr int GPB = NT / R;          // rows per block
+  constexpr int RB = N / GPB;
+  constexpr int CH16 = N * GPB / 2;     // 16-B chunks per plane tile
+  constexpr int PER = CH16 / NT;
+  static_assert(CH16 % NT == 0, "chunking");
+  constexpr int SCR = GPB * R * (R + 1);   // padded transpose scratch reuses the tile
+  __shared__ float2 tw[N];
+  __shared__ __attribute__((aligned(16))) float2 tile[SCR > N * GPB ? SCR : N * GPB];
+
+  for (int i = threadIdx.x; i < N; i += NT) tw[i] = tw_glob[i];
+
+  const int grp = threadIdx.x / R;
+  const int t = threadIdx.x % R;
+  const int bid = xcd_pair<RB>(blockIdx.x);
+  const int rb = bid % RB;
+  const int j = bid / RB;
+  const JobDesc jb = jobs[j];
+  if (jb.env < 0) return;  // uniform per block
+  const int y0 = rb * GPB;
+  const int y = y0 + grp;
+  const hbx_window_t win = {0, 0, 0, 0};
+  const WinRow wr(win, y, t);   // (unread: no window form)
+  const int Q = P / 2;
+  constexpr size_t PLB = plane_b_elems(R);
+  const float2* jbase = ws_b + (size_t)j * P * PLB;
+
+  float4 pa[PER], pb[PER];   // this thread's share of the pair's two plane tiles, one pair ahead
+  auto load_pair = [&](int q) {
+    const float2* a = jbase + (size_t)(2 * q) * PLB;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const TileChunk ch = tile_chunk<NT, GPB>(i);
+      pa[i] = ld_stream4(a + LayoutB<R>::at(ch.line, y0 + ch.r2));
+      pb[i] = ld_stream4(a + PLB + LayoutB<R>::at(ch.line, y0 + ch.r2));
+    }
+  };
+  load_pair(0);
+  const size_t row0 = (((size_t)jb.env * G + jb.group) * Q * N + y) * N + t;
+  const float2* s0 = source + ((size_t)jb.group * N + y) * N + t;   // the source row, pixel x = t
+  float acc[1];
+
+#pragma unroll 1
+  for (int q = 0; q < Q; ++q) {
+    lds_barrier();  // previous plane's scratch use is over (also publishes tw)
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {   // B[2q] + i B[2q + 1]
+      const TileChunk ch = tile_chunk<NT, GPB>(i);
+      tile[tile_pos<R, GPB>(ch.line, ch.r2)] = make_float2(pa[i].x - pb[i].y, pa[i].y + pb[i].x);
+      tile[tile_pos<R, GPB>(ch.line, ch.r2 + 1)] = make_float2(pa[i].z - pb[i].w, pa[i].w + pb[i].z);
+    }
+    if (q + 1 < Q) load_pair(q + 1);   // next pair's tiles in flight under this plane's FFT
+    lds_barrier();
+    pk2 v[R];
+#pragma unroll
+    for (int jj = 0; jj < R; ++jj) v[jj] = to_pk(tile[tile_pos<R, GPB>(t + R * jj, grp)]);
+    lds_barrier();  // tile consumed: reuse it as transpose scratch
+    fft_group<R, true>(v, t, PaddedScratch<R>{tile + grp * R * (R + 1)}, tw);
+    source_conj_row<R, R, kSrc8Piece>(v, s0);
+    if constexpr (GK == kGradNone) {
+      // cplx_plane_out's full-grid form with the output chosen at compile time (check_pass_call: exactly one)
+      const size_t row = row0 + (size_t)q * N * N;
+      if constexpr (!RP) {
+#pragma unroll
+        for (int k = 0; k < R; ++k) field_out[row + R * k] = from_pk(v[k]);
+      } else {
+#pragma unroll
+        for (int k = 0; k < R; ++k) real_out[row + R * k] = v[k].x;
+      }
+    } else {
+      cplx_plane_out<R, R, false, GK, false>(v, acc, jb.env, jb.group, G, Q, q, y, row0, win, wr, field_out, real_out,
+                                             phase, grad, gvb, ga, gb);
+    }
+  }
+}
+
+// the five leaf kinds' first passes, in the order the code object gets them
+template <int R>
+static void launch_first_src(const PlanDev& pd, const PassCall& c, float2* ws_a, unsigned blocks, hipStream_t st) {
+  constexpr int NT = kRowNT<R>;
+  const auto pick = [](int sk) {
+    if constexpr (R == 32) {
+      auto k = k_rowfwd32_src<kSrcComplex>;
+      if (sk == kSrcPhase) k = k_rowfwd32_src<kSrcPhase>;
+      if (sk == kSrcPhaseLevels) k = k_rowfwd32_src<kSrcPhaseLevels>;
+      if (sk == kSrcReal) k = k_rowfwd32_src<kSrcReal>;
+      if (sk == kSrcThreshold) k = k_rowfwd32_src<kSrcThreshold>;
+      return k;
+    } else {
+      auto k = k_rowfwd_src<R, NT, kSrcComplex>;
+      if (sk == kSrcPhase) k = k_rowfwd_src<R, NT, kSrcPhase>;
+      if (sk == kSrcPhaseLevels) k = k_rowfwd_src<R, NT, kSrcPhaseLevels>;
+      if (sk == kSrcReal) k = k_rowfwd_src<R, NT, kSrcReal>;
+      if (sk == kSrcThreshold) k = k_rowfwd_src<R, NT, kSrcThreshold>;
+      return k;
+    }
+  };
+  const SourceParams sp = pass_source_params(pd, c);
+  launch_kernel(pick(pass_source_kind(c)), blocks, NT, st, c.jobs, pass_source_samples(c), c.source, ws_a, pd.tw, pd.P,
+                pd.G * pd.P, sp.p0, sp.p1, sp.p2);
+}
+
+// the sourced last pass of the call's gradient kind (check_pass_call has passed: one output, no statistics)
+template <int R>
+static void launch_last_src(const PlanDev& pd, const PassCall& c, float2* ws_b, unsigned blocks, hipStream_t st) {
+  constexpr int NT = kRowNT<R>;
+  const bool real_out = c.real_part != nullptr;   // kGradNone: the field or its real part, one of the two
+  const auto pick = [real_out](int gk) {
+    (void)real_out;   // (the tiled forms test the two pointers themselves)
+    if constexpr (kTiledB<R>) {
+      auto k = k_rowinv_d_src<R, kGradNone>;
+      if (gk == kGradPhase) k = k_rowinv_d_src<R, kGradPhase>;
+      if (gk == kGradPhaseLevels) k = k_rowinv_d_src<R, kGradPhaseLevels>;
+      if (gk == kGradSteWindow) k = k_rowinv_d_src<R, kGradSteWindow>;
+      if (gk == kGradSteSigmoid) k = k_rowinv_d_src<R, kGradSteSigmoid>;
+      return k;
+    } else {
+      auto k = k_rowinv_src<R, NT, kGradNone>;
+      if (gk == kGradNone && real_out) k = k_rowinv_src<R, NT, kGradNone, true>;
+      if (gk == kGradPhase) k = k_rowinv_src<R, NT, kGradPhase>;
+      if (gk == kGradPhaseLevels) k = k_rowinv_src<R, NT, kGradPhaseLevels>;
+      if (gk == kGradSteWindow) k = k_rowinv_src<R, NT, kGradSteWindow>;
+      if (gk == kGradSteSigmoid) k = k_rowinv_src<R, NT, kGradSteSigmoid>;
+      return k;
+    }
+  };
+  launch_kernel(pick(pass_grad_kind(c)), blocks, NT, st, c.jobs, ws_b, pd.tw, pd.P, pd.G, c.source, c.complex_field,
+                c.real_part, c.grad_samples, c.grad_phase, pd.vb, pass_grad_p0(c), pass_grad_p1(c));
 }
 
 }  // namespace hbx

@@ -630,6 +630,9 @@ struct SampleKernels896 {
 
 // (pixel weights) the weighted last passes and their pick, behind every other kernel of this file
 static void launch_last_pw_896(const PlanDev& pd, const PassCall& c, float2* ws_b, unsigned blocks, hipStream_t st);
+// (illumination fields) the sourced first and last passes and their picks, behind the weighted ones
+static void launch_first_src_896(const PlanDev& pd, const PassCall& c, float2* ws_a, unsigned blocks, hipStream_t st);
+static void launch_last_src_896(const PlanDev& pd, const PassCall& c, float2* ws_b, unsigned blocks, hipStream_t st);
 
 hipError_t run_jobs_896(const PlanDev& pd, const PassCall& c, hipStream_t st) {
   const JobDesc* jobs = c.jobs;
@@ -649,7 +652,9 @@ hipError_t run_jobs_896(const PlanDev& pd, const PassCall& c, hipStream_t st) {
   if (!c.stack_skip_first) {
     if (tm) tm->begin(0, st);
     const bool win_in = pass_window_in(c, kN);
-    if (pass_complex(c)) {   // the load kind: complex samples as they are, times scale * weight, or exp(i pi phase)
+    if (c.source && !c.source_adjoint) {   // the sourced loads, only when the pointer is set
+      launch_first_src_896(pd, c, ws_a, blocks * (P / 2), st);
+    } else if (pass_complex(c)) {   // the load kind: complex samples as they are, times scale * weight, or exp(i pi phase)
       const int lk = c.phase_values ? (c.phase_levels ? kLoadPhaseLevels : kLoadPhase) : c.complex_weight ? kLoadWeighted : kLoadComplex;
       launch_kernel(pick_first_pass_cplx<SampleKernels896>(lk, win_in), blocks * (P / 2), 256, st, jobs, c.complex_values,
                     ws_a, pd.tw, P, CH, c.complex_weight, pass_first_scale(c), c.phase_values, pass_first_window(c));
@@ -672,6 +677,8 @@ hipError_t run_jobs_896(const PlanDev& pd, const PassCall& c, hipStream_t st) {
   if (tm) tm->begin(2, st);
   if (c.pixel_weight) {    // the weighted statistics forms, only when the pointer is set
     launch_last_pw_896(pd, c, ws_b, blocks, st);
+  } else if (c.source && c.source_adjoint) {   // conj(source) on the plane, then the leaf's gradient
+    launch_last_src_896(pd, c, ws_b, blocks, st);
   } else if (pass_complex(c)) {   // recombine each plane pair, or a leaf's gradient instead (pick_last_pass_cplx)
     const auto k = pick_last_pass_cplx<SampleKernels896>(pass_grad_kind(c), c.complex_stats != 0,
                                                          c.windowed != 0);
@@ -864,6 +871,107 @@ static void launch_last_pw_896(const PlanDev& pd, const PassCall& c, float2* ws_
   else
     launch_kernel(k_rowinv896_pw, blocks, 256, st, c.jobs, ws_b, c.target, c.pixel_weight, pd.tw, pd.P, pd.G, pd.partial,
                   c.inten_out, c.field_out);
+}
+
+// Illumination fields (hbx_evaluate_source / hbx_backward_source, EXTENSION; hbx_passes.hip has the account):
+// k_rowfwd896_cplx with the sourced load on the 28 loaded samples of a lane (slots >= 28 stay zero: the
+// padding gets no light), and k_rowinv896_cplx without its statistics and window forms, g' = conj(s) g
+// between the inverse row FFT and cplx_plane_out.  Argument lists of their own, behind every other kernel
+// of this file.
+constexpr int kSrc896Piece = kL;   // all 28 pixels of a lane in flight at once (124 VGPRs at most, no scratch)
+template <int SK>
+__global__ __launch_bounds__(256, 3) void k_rowfwd896_src(const JobDesc* __restrict__ jobs,
+                                                          const float* __restrict__ values,
+                                                          const float2* __restrict__ source,
+                                                          float2* __restrict__ ws_a,
+                                                          const float2* __restrict__ tw_glob, int P, int CH,
+                                                          float p0, float p1, float p2) {
+  __shared__ float2 tw[kN];
+  __shared__ __attribute__((aligned(16))) float lds[kRowfwd896Scr];
+  stage_twiddles<kN, 256>(tw, tw_glob);
+
+  const int grp = threadIdx.x / kR;
+  const int t = threadIdx.x % kR;
+  const int lane_base = (threadIdx.x & 63) - t;
+  const FirstPassBlock wg = first_pass_block<kRB>(blockIdx.x, P / 2);
+  const int j = wg.j;
+  const JobDesc jb = jobs[j];
+  if (jb.env < 0) return;  // uniform per block
+  const int y0 = wg.rbw * kGPB;
+  const int y = y0 + grp;
+  float2 v[32];
+  first_pass_load_src<kR, kL, SK, kSrc896Piece>(v, values, source, jb.env, jb.group, P, CH, wg.q, y, t, p0, p1, p2);
+  __syncthreads();  // tw visible
+
+  float2* base = ws_a + ((size_t)j * P + 2 * wg.q) * kPlaneA;
+  rowfwd896_emit(v, t, grp, lane_base, y0, lds, tw, base);
+}
+
+template <int GK>
+__global__ __launch_bounds__(256, 2) void k_rowinv896_src(const JobDesc* __restrict__ jobs,
+                                                          const float2* __restrict__ ws_b,
+                                                          const float2* __restrict__ tw_glob, int P, int G,
+                                                          const float2* __restrict__ source,
+                                                          float2* __restrict__ field_out,
+                                                          float* __restrict__ real_out,
+                                                          const float* __restrict__ phase,
+                                                          float* __restrict__ grad, float gvb, float ga,
+                                                          float gb) {
+  __shared__ float2 tw[kN];
+  __shared__ float2 scratch[kSCR];
+  for (int i = threadIdx.x; i < kN; i += 256) tw[i] = tw_glob[i];
+
+  const int grp = threadIdx.x / kR;
+  const int t = threadIdx.x % kR;
+  const int bid = xcd_pair<kRB>(blockIdx.x);
+  const int rb = bid % kRB;
+  const int j = bid / kRB;
+  const JobDesc jb = jobs[j];
+  if (jb.env < 0) return;   // uniform per block
+  const int y = rb * kGPB + grp;
+  const hbx_window_t win = {0, 0, 0, 0};
+  const WinRow wr(win, y, t);   // (unread: no window form)
+  const int Q = P / 2;                            // complex planes per group
+  const __amdgpu_buffer_rsrc_t rs = plane_rsrc(ws_b + (size_t)j * P * kPlaneB, (unsigned)((size_t)P * kPlaneB * 8));
+  const Rowinv896Lanes ln(y, t);
+  const PaddedScratch<kR> sc{scratch + grp * kR * (kR + 1)};
+  const size_t row0 = (((size_t)jb.env * G + jb.group) * Q * kN + y) * kN + t;   // complex plane 0, pixel x = t
+  const float2* s0 = source + ((size_t)jb.group * kN + y) * kN + t;               // the source row, pixel x = t
+  float acc[1];
+  float2 v[32];
+  rowinv_load_pair(v, ln, rs, 0);
+  __syncthreads();  // tw visible
+#pragma unroll 1
+  for (int q = 0; q < Q; ++q) {
+    fft896_sn<true, kInvScalar>(v, t, sc, tw);      // slot layout in, natural out: x = t + 32 k
+    source_conj_row<kR, kL>(v, s0);
+    cplx_plane_out<kR, kL, false, GK, false>(v, acc, jb.env, jb.group, G, Q, q, y, row0, win, wr, field_out, real_out,
+                                             phase, grad, gvb, ga, gb);
+    if (q + 1 < Q) rowinv_load_pair(v, ln, rs, q + 1);   // uniform: no pair is read twice
+  }
+}
+
+static void launch_first_src_896(const PlanDev& pd, const PassCall& c, float2* ws_a, unsigned blocks, hipStream_t st) {
+  const int sk = pass_source_kind(c);
+  auto k = k_rowfwd896_src<kSrcComplex>;
+  if (sk == kSrcPhase) k = k_rowfwd896_src<kSrcPhase>;
+  if (sk == kSrcPhaseLevels) k = k_rowfwd896_src<kSrcPhaseLevels>;
+  if (sk == kSrcReal) k = k_rowfwd896_src<kSrcReal>;
+  if (sk == kSrcThreshold) k = k_rowfwd896_src<kSrcThreshold>;
+  const SourceParams sp = pass_source_params(pd, c);
+  launch_kernel(k, blocks, 256, st, c.jobs, pass_source_samples(c), c.source, ws_a, pd.tw, pd.P, pd.G * pd.P, sp.p0,
+                sp.p1, sp.p2);
+}
+
+static void launch_last_src_896(const PlanDev& pd, const PassCall& c, float2* ws_b, unsigned blocks, hipStream_t st) {
+  const int gk = pass_grad_kind(c);
+  auto k = k_rowinv896_src<kGradNone>;
+  if (gk == kGradPhase) k = k_rowinv896_src<kGradPhase>;
+  if (gk == kGradPhaseLevels) k = k_rowinv896_src<kGradPhaseLevels>;
+  if (gk == kGradSteWindow) k = k_rowinv896_src<kGradSteWindow>;
+  if (gk == kGradSteSigmoid) k = k_rowinv896_src<kGradSteSigmoid>;
+  launch_kernel(k, blocks, 256, st, c.jobs, ws_b, pd.tw, pd.P, pd.G, c.source, c.complex_field, c.real_part,
+                c.grad_samples, c.grad_phase, pd.vb, pass_grad_p0(c), pass_grad_p1(c));
 }
 
 }  // namespace hbx

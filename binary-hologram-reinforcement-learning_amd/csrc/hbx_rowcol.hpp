@@ -308,6 +308,130 @@ __device__ __forceinline__ void ste_grad_row(const V (&v)[NV], const float* __re
 }
 
 // ---------------------------------------------------------------------------
+// Illumination fields (hbx_source_field / hbx_evaluate_source / hbx_backward_source): the modulator is lit
+// by a complex source s = (sr, si), source[G][N][N] complex64, and the field is u = s f with f the leaf
+// kind's unsourced sample.  Every product is rounded on its own -- the bodies below are compiled with
+// contraction off, so the one fma each formula names is the only one, and no multiply of theirs fuses
+// with an add of the row FFT behind it: the first pass and the materialiser (k_source_field) then form
+// the same float32 u, and hbx_evaluate_source equals hbx_evaluate_complex on hbx_source_field's output
+// bit for bit.
+//   u.re = fmaf(fr, sr, -(fi * si))     u.im = fmaf(fr, si, fi * sr)
+__device__ __forceinline__ void source_mul(float fr, float fi, float sr, float si, float& ur, float& ui) {
+#pragma clang fp contract(off)
+  const float a = fi * si, b = fi * sr;
+  ur = __builtin_fmaf(fr, sr, -a);
+  ui = __builtin_fmaf(fr, si, b);
+}
+// the two real kinds: fi is absent, not 0 -- one multiply each
+__device__ __forceinline__ void source_mul_real(float fr, float sr, float si, float& ur, float& ui) {
+#pragma clang fp contract(off)
+  ur = fr * sr;
+  ui = fr * si;
+}
+// the adjoint: g' = conj(s) g,  g'.re = fmaf(g.re, sr, g.im * si)   g'.im = fmaf(g.im, sr, -(g.re * si))
+__device__ __forceinline__ void source_mul_conj(float gr, float gi, float sr, float si, float& pr, float& pi) {
+#pragma clang fp contract(off)
+  const float a = gi * si, b = gr * si;
+  pr = __builtin_fmaf(gr, sr, a);
+  pi = __builtin_fmaf(gi, sr, -b);
+}
+
+// u = s f(x) of one sample, the leaf kind's map and the product (SK: kSrc*, hbx_internal.hpp).  (a, b) =
+// the complex sample, or a = the float32 sample x and b unread.  (p0, p1, p2): kSrcPhaseLevels the
+// quantizer's (h, s) (quantize_phase_sample); kSrcThreshold (thr, lo, hi), lo = va and hi = va + vb of the
+// plan, NaN compares false and gives lo as threshold_load_row has it; unread by the other kinds
+template <int SK>
+__device__ __forceinline__ void source_sample(float a, float b, float sr, float si, float p0, float p1, float p2,
+                                              float& ur, float& ui) {
+  if constexpr (SK == kSrcComplex) {
+    source_mul(a, b, sr, si, ur, ui);
+  } else if constexpr (SK == kSrcPhase || SK == kSrcPhaseLevels) {
+    float c, s;
+    if constexpr (SK == kSrcPhaseLevels) a = quantize_phase_sample(a, p0, p1);
+    phase_sincos(a, c, s);
+    source_mul(c, s, sr, si, ur, ui);
+  } else if constexpr (SK == kSrcThreshold) {
+    source_mul_real(a >= p0 ? p2 : p1, sr, si, ur, ui);
+  } else {
+    static_assert(SK == kSrcReal, "a source leaf kind");
+    source_mul_real(a, sr, si, ur, ui);
+  }
+}
+
+// The sourced first-pass load: lane t loads the sample of pixel x = t + R jj, jj < L, of the leaf's row
+// (`row`: complex64 pairs for kSrcComplex, float32 otherwise; read once, non-temporal) and the source
+// sample of the same pixel (srow: the row of the group's source, re-read by every env and plane of the
+// group, default cache policy as the weight row of complex_load_row_weighted), and v[jj] = s f.  The
+// loads of C pixels -- samples, then source -- are all issued before the first use; C = L is the whole
+// row, C = L / 2 loads and multiplies in halves (N = 1024: DESIGN.md has the register account).
+// v[L ..] = 0 (N = 896: the padding is no sample and gets no light).
+template <int R, int L, int SK, int C, class V>
+__device__ __forceinline__ void source_load_row(V (&v)[R], const float* __restrict__ row,
+                                                const float2* __restrict__ srow, int t, float p0, float p1,
+                                                float p2) {
+  static_assert(L % C == 0, "whole pieces");
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  const f32x2* r2 = reinterpret_cast<const f32x2*>(row);
+  const f32x2* s2 = reinterpret_cast<const f32x2*>(srow);
+#pragma unroll
+  for (int j0 = 0; j0 < L; j0 += C) {
+    f32x2 a[C], s[C];
+#pragma unroll
+    for (int jj = 0; jj < C; ++jj) {
+      if constexpr (SK == kSrcComplex) a[jj] = __builtin_nontemporal_load(r2 + t + R * (j0 + jj));
+      else a[jj] = f32x2{__builtin_nontemporal_load(row + t + R * (j0 + jj)), 0.0f};
+    }
+#pragma unroll
+    for (int jj = 0; jj < C; ++jj) s[jj] = s2[t + R * (j0 + jj)];
+#pragma unroll
+    for (int jj = 0; jj < C; ++jj) {
+      float ur, ui;
+      source_sample<SK>(a[jj].x, a[jj].y, s[jj].x, s[jj].y, p0, p1, p2, ur, ui);
+      v[j0 + jj] = V{ur, ui};
+    }
+  }
+#pragma unroll
+  for (int jj = L; jj < R; ++jj) v[jj] = V{0.f, 0.f};
+}
+
+// The row load of the sourced first passes, once for every size (N = R L): complex plane q of the job's
+// group of values [env][CH / 2][N][N] -- complex64 for kSrcComplex, float32 otherwise -- times row y of
+// source[group].  The addresses are formed as first_pass_load_cplx forms them.
+template <int R, int L, int SK, int C, class V>
+__device__ __forceinline__ void first_pass_load_src(V (&v)[R], const float* values, const float2* source, int env,
+                                                    int group, int P, int CH, int q, int y, int t, float p0,
+                                                    float p1, float p2) {
+  constexpr int N = R * L;
+  const size_t row = (((size_t)env * (CH / 2) + group * (P / 2) + q) * N + y) * N;
+  const size_t srow = ((size_t)group * N + y) * N;
+  source_load_row<R, L, SK, C>(v, values + row * (SK == kSrcComplex ? 2 : 1), source + srow, t, p0, p1, p2);
+}
+
+// The sourced last passes: g' = conj(s) g on the plane in registers, behind the inverse row FFT and in
+// front of cplx_plane_out (v: natural layout, x = t + R k).  s0 = the lane's pixel x = t of the source row;
+// the source loads are issued behind the FFT, as phase_grad_row issues its samples: no source sample is live
+// across it.  C of the L pixels are in flight at a time: C = L issues the whole row's loads together; the
+// N = 64 last pass, whose registers also hold the next pair's tiles, takes them in pieces (kSrc8Piece).
+template <int R, int L, int C = L, class V, int NV>
+__device__ __forceinline__ void source_conj_row(V (&v)[NV], const float2* __restrict__ s0) {
+  static_assert(L % C == 0, "whole pieces");
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  const f32x2* s2 = reinterpret_cast<const f32x2*>(s0);
+#pragma unroll
+  for (int k0 = 0; k0 < L; k0 += C) {
+    f32x2 s[C];
+#pragma unroll
+    for (int k = 0; k < C; ++k) s[k] = s2[R * (k0 + k)];
+#pragma unroll
+    for (int k = 0; k < C; ++k) {
+      float pr, pi;
+      source_mul_conj(v[k0 + k].x, v[k0 + k].y, s[k].x, s[k].y, pr, pi);
+      v[k0 + k] = V{pr, pi};
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Windows (hbx_*_window): an array that belongs to a window of the grid is compact, [..][h][w] with
 // row pitch w, and the row passes reach it through a predicate on their per-element loads and stores.
 // WinRow is row y of such an array as lane t sees it: whether the row is inside, and for pixel

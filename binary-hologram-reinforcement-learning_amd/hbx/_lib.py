@@ -54,6 +54,7 @@ EXPORTED_SYMBOLS = (
     "hbx_plan_set_depths", "hbx_plan_depths", "hbx_evaluate_stack", "hbx_backward_stack",
     "hbx_loss_stack", "hbx_loss_weight_stack",
     "hbx_evaluate_pw", "hbx_evaluate_stack_pw", "hbx_pixel_weight_sum", "hbx_loss_pw", "hbx_loss_weight_pw",
+    "hbx_source_field", "hbx_evaluate_source", "hbx_backward_source",
 )
 NUM_PASSES = 5
 PASS_NAMES = ("k_rowfwd", "k_col", "k_rowinv", "k_psf_eval", "k_psf_commit")
@@ -187,6 +188,9 @@ def _declare(lib):
     lib.hbx_pixel_weight_sum.argtypes = [VP, VP, I32, I32, VP, VP]
     lib.hbx_loss_pw.argtypes = [VP, VP, VP, I32, I32, I32, I32, VP, VP]
     lib.hbx_loss_weight_pw.argtypes = [VP, VP, VP, VP, VP, VP, VP, I32, I32, I32, I32, VP, VP]
+    lib.hbx_source_field.argtypes = [VP, VP, LP, VP, I32, VP, VP]
+    lib.hbx_evaluate_source.argtypes = [VP, VP, LP, VP, VP, VP, I32, VP, VP, VP, VP]
+    lib.hbx_backward_source.argtypes = [VP, VP, VP, C.c_float, LP, VP, VP, I32, VP, VP, VP]
     lib.hbx_flip_map.argtypes = [VP, VP, VP, VP, VP, VP]
     lib.hbx_eval_flips_psf.argtypes = [VP, VP, VP, VP, VP, VP, VP, I32, VP, VP, VP]
     lib.hbx_commit_flip_psf.argtypes = [VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, I32, VP]

@@ -810,6 +810,85 @@ class Plan:
         return self._evaluate_pw("hbx_evaluate_stack_pw", values, kind, target, pixel_weight, want_field,
                                  want_intensity, levels, threshold, (self.depths,), stream)
 
+    # --- illumination fields (hbx_*_source): a constant complex source [G, H, W] lights the modulator ---
+    # Every leaf kind is one complex plane per leaf plane here: values [B, CH/2, H, W], the real and the
+    # thresholded kind included.  Out of scope: the bit path and every env, DBS, plane-cache and incremental
+    # entry point, windows, focal stacks, a gradient with respect to the source, reduced-precision plans, a
+    # per-env or per-plane source, grids other than the four built.
+    def _source_args(self, values, kind, source, levels, threshold, surrogate=_lib.STE_WINDOW, p0=-math.inf,
+                     p1=math.inf):
+        leaf = self._leaf(kind, levels, threshold, surrogate, p0, p1)
+        n = _batch(values)
+        shape = self.phase_shape(n)
+        c = self.cfg
+        source = self._in(source, "source", torch.complex64, (c.groups, c.height, c.width))
+        return leaf, n, shape, source
+
+    def source_field(self, values: torch.Tensor, kind: int, source: torch.Tensor, levels=None,
+                     threshold: float = 0.0, stream=None) -> torch.Tensor:
+        """The field at the modulator under the illumination `source` (hbx_source_field): u = s f(x),
+        complex64 [B, CH/2, H, W], f the map of leaf kind `kind` (hbx._lib.LEAF_*), formed by the device
+        functions `evaluate_source`'s first pass uses.  `values` [B, CH/2, H, W]: complex64 for
+        LEAF_COMPLEX, float32 otherwise; `source` complex64 [G, H, W] on the plan's device."""
+        leaf, n, shape, source = self._source_args(values, kind, source, levels, threshold)
+        values = self._in(values, "values", torch.complex64 if kind == _lib.LEAF_COMPLEX else torch.float32, shape)
+        out = torch.empty(tuple(shape) + (2,), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.hbx_source_field(self._h, _ptr(values), C.byref(leaf), _ptr(source), n, _ptr(out),
+                                             _stream(stream)), "hbx_source_field")
+        return torch.view_as_complex(out)
+
+    def evaluate_source(self, values: torch.Tensor, kind: int, source: torch.Tensor,
+                        target: Optional[torch.Tensor] = None, pixel_weight: Optional[torch.Tensor] = None,
+                        want_field: bool = True, want_intensity: bool = True, levels=None, threshold: float = 0.0,
+                        stream=None):
+        """`evaluate_complex` of the sourced field without writing it (hbx_evaluate_source): the first pass
+        forms u = s f(x) as it loads `values` and the source row.  Returns (field complex64
+        [B, CH/2, H, W] | None, intensity float32 [B, G, H, W] | None, chan_stats float64 [B, G, 3] |
+        None), each equal to `evaluate_complex`'s (with `pixel_weight`: `evaluate_pw`'s) on
+        `source_field`'s output bit for bit.  `pixel_weight` needs a `target`."""
+        leaf, n, shape, source = self._source_args(values, kind, source, levels, threshold)
+        values = self._in(values, "values", torch.complex64 if kind == _lib.LEAF_COMPLEX else torch.float32, shape)
+        tshape = tuple(self.target_shape(n))
+        if target is not None:
+            _need(target, "target", torch.float32, tshape, self.device)
+        elif pixel_weight is not None:
+            raise ValueError("evaluate_source: a pixel_weight needs a target")
+        elif not want_intensity:
+            raise ValueError("evaluate_source: without a target the intensity is the output")
+        if pixel_weight is not None:
+            _need(pixel_weight, "pixel_weight", torch.float32, tshape, self.device)
+        field = torch.empty(tuple(shape) + (2,), dtype=torch.float32, device=self.device) if want_field else None
+        inten = torch.empty(tshape, dtype=torch.float32, device=self.device) if want_intensity else None
+        stats = torch.empty((n, self.cfg.groups, 3), dtype=torch.float64, device=self.device) if target is not None else None
+        _lib.check(self.lib.hbx_evaluate_source(self._h, _ptr(values), C.byref(leaf), _ptr(source), _ptr(target),
+                                                _ptr(pixel_weight), n, _ptr(field), _ptr(inten), _ptr(stats),
+                                                _stream(stream)), "hbx_evaluate_source")
+        return _complex(field), inten, stats
+
+    def backward_source(self, values: torch.Tensor, kind: int, source: torch.Tensor,
+                        samples: Optional[torch.Tensor] = None, weight: Optional[torch.Tensor] = None,
+                        scale: float = 1.0, levels=None, surrogate: int = _lib.STE_WINDOW, p0: float = -math.inf,
+                        p1: float = math.inf, stream=None) -> torch.Tensor:
+        """The backward pass of a sourced leaf, on the plan for -z (hbx_backward_source): `values`
+        complex64 [B, CH/2, H, W] (the gradient with respect to the propagated field or, with `weight`
+        float32 [B, G, H, W], the saved field), back-propagated, times conj(source), then the leaf's
+        formula: complex64 [B, CH/2, H, W] for LEAF_COMPLEX, else float32 -- the real part
+        (LEAF_REAL), `phase_backward`'s, `phase_levels_backward`'s or `threshold_backward`'s gradient
+        from `samples` float32 [B, CH/2, H, W] (the leaf's x).  The source has no gradient."""
+        leaf, n, shape, source = self._source_args(values, kind, source, levels, 0.0, surrogate, p0, p1)
+        values = self._in(values, "values", torch.complex64, shape)
+        needs = kind in (_lib.LEAF_PHASE, _lib.LEAF_PHASE_LEVELS, _lib.LEAF_THRESHOLD)
+        if needs != (samples is not None):
+            raise ValueError("backward_source: samples are the leaf of a phase, L-level or thresholded leaf, else None")
+        samples = self._in(samples, "samples", torch.float32, shape, optional=True)
+        weight = self._in(weight, "weight", torch.float32, self.target_shape(n), optional=True)
+        cplx = kind == _lib.LEAF_COMPLEX
+        out = torch.empty(tuple(shape) + ((2,) if cplx else ()), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.hbx_backward_source(self._h, _ptr(values), _ptr(weight), float(scale), C.byref(leaf),
+                                                _ptr(source), _ptr(samples), n, _ptr(out) if cplx else None,
+                                                None if cplx else _ptr(out), _stream(stream)), "hbx_backward_source")
+        return torch.view_as_complex(out) if cplx else out
+
     def _pw_depths(self, stack: bool):
         return ((self.depths,), self.depths, 1) if stack else ((), 0, 0)
 

@@ -63,6 +63,15 @@ hbx_evaluate_complex), hbx_loss turns them into a float64 device tensor with no 
 the backward pass is hbx_loss_weight (dL/dI = a I + c T per env) followed by the same weighted
 launch set on the plan for -z.
 
+``source=`` on simulate(.., binary=False), intensity and loss lights the modulator with a constant
+complex illumination s [H, W] or [G, H, W] instead of the unit plane wave on axis, u = s f(x) for every
+leaf kind (real, thresholded, complex, phase, L-level phase): the first pass multiplies by the source
+row as it loads the leaf (hbx_evaluate_source) and the backward's last pass by conj(s) before the
+leaf's gradient formula (hbx_backward_source), so an obliquely lit DMD, a phase SLM under a Gaussian
+beam or a lit disc keep the fused loads and the fused gradients.  ``tt.sources`` builds the usual
+ones (plane_wave, gaussian, lens).  Out of scope: a source on the binary=True path or with grid= /
+the *_stack calls, a gradient with respect to the source, a per-env or per-plane source.
+
 The physics follows the assumptions documented in DESIGN.md (the original torchOptics is
 absent and unpinned): no padding; exact angular spectrum and amplitude field unless
 ``tf="fresnel"`` / ``field="phase"`` select the plan's other switches.  relativeLoss uses the
@@ -83,9 +92,10 @@ import hbx
 from hbx import _lib
 
 from . import metrics as _metrics
+from . import sources  # noqa: F401  (tt.sources: illumination fields for source=)
 
 __all__ = ["Tensor", "simulate", "intensity", "loss", "relativeLoss", "imread", "check_binary",
-           "simulate_stack", "intensity_stack", "loss_stack"]
+           "simulate_stack", "intensity_stack", "loss_stack", "sources"]
 
 
 class Tensor(torch.Tensor):
@@ -348,12 +358,16 @@ class _Leaf:
     a window's have the field kind given (the leaf's vb), every other plan FIELD_AMPLITUDE."""
 
     def __init__(self, wls, dx, dy, tf_kind, leaf, field_kind=_lib.FIELD_AMPLITUDE, ste_args=None, levels=None,
-                 c=0, z=None, win=None, zs=None, recompute=False, dev=None):
+                 c=0, z=None, win=None, zs=None, recompute=False, dev=None, source=None):
         self.wls, self.dx, self.dy, self.tf_kind, self.leaf, self.dev = wls, dx, dy, tf_kind, leaf, dev
         self.field_kind, self.ste_args, self.levels, self.c = field_kind, ste_args, levels, c
         self.z, self.win, self.zs = z, win, zs
         self.groups = len(wls)
-        self.real_in = leaf in (_lib.LEAF_REAL, _lib.LEAF_THRESHOLD)
+        # source: the illumination as given (checked, _source_arg); _device_leaf replaces it by the complex64
+        # [G, H, W] device tensor the kernels read.  Under a source every kind is one complex plane per leaf
+        # plane, the real and the thresholded one included (a single depth, no window: _leaf_args)
+        self.source = source
+        self.real_in = leaf in (_lib.LEAF_REAL, _lib.LEAF_THRESHOLD) and source is None
         self.plan_field = field_kind if leaf == _lib.LEAF_THRESHOLD or win is not None else _lib.FIELD_AMPLITUDE
         self.tau = ste_args[0] if ste_args is not None else 0.0
         self.ste = {} if ste_args is None else dict(surrogate=ste_args[1], p0=ste_args[2], p1=ste_args[3])
@@ -362,7 +376,7 @@ class _Leaf:
         self.reads_leaf = leaf in (_lib.LEAF_PHASE, _lib.LEAF_PHASE_LEVELS, _lib.LEAF_THRESHOLD)
         self.keeps_leaf = self.reads_leaf or win is not None or zs is not None
         # tt.intensity(save_field=False) of a real leaf at one depth: keep x, form the field again
-        self.recompute = recompute and leaf == _lib.LEAF_REAL and not (win or zs)
+        self.recompute = recompute and leaf == _lib.LEAF_REAL and not (win or zs) and source is None
 
     def _plan(self, b, planes, h, w, adjoint):
         if self.win is not None:
@@ -387,6 +401,15 @@ class _Leaf:
     def kept(self, x):
         return (x,) if self.keeps_leaf else ()
 
+    def kept_source(self):
+        """the device source for save_for_backward, last of what a Function saves: the backward reads it from
+        there, so a source changed in place between the two passes is an error, as it is for the target"""
+        return () if self.source is None else (self.source,)
+
+    def split_source(self, saved):
+        """saved tensors -> (those without the source, the source | None)"""
+        return (saved, None) if self.source is None else (saved[:-1], saved[-1])
+
     def evaluate(self, x, target=None, want_field=True, want_intensity=True, pixel_weight=None):
         """One forward launch set -> (plan, field | None, intensity | None, chan_stats | None).  A real
         or thresholded leaf of an odd C is padded with a zero plane here: the field keeps it, and the
@@ -394,6 +417,11 @@ class _Leaf:
         target, an even C for a real leaf, no window): the weighted statistics of hbx_evaluate_pw /
         hbx_evaluate_stack_pw."""
         plan, leaf = self.forward_plan(x), self.leaf
+        if self.source is not None:                             # without a target the intensity is the call's output
+            field, inten, stats = plan.evaluate_source(x, leaf, self.source, target, pixel_weight, want_field=want_field,
+                                                       want_intensity=want_intensity or target is None,
+                                                       levels=self.levels, threshold=self.tau)
+            return plan, field, (inten if want_intensity else None), stats
         if pixel_weight is not None:
             call = plan.evaluate_pw if self.zs is None else plan.evaluate_stack_pw
             return (plan,) + call(x, leaf, target, pixel_weight, want_field=want_field, want_intensity=want_intensity,
@@ -443,7 +471,7 @@ class _Leaf:
         field = self.evaluate(x, want_intensity=self.zs is not None)[1]
         return field if field.shape[-3] == x.shape[1] else field[:, :x.shape[1]]
 
-    def backward(self, x, values, weight=None, scale=1.0, adj=None):
+    def backward(self, x, values, weight=None, scale=1.0, adj=None, source=None):
         """One launch set on the adjoint plan (adj, where the caller has fetched it already): the
         leaf's gradient from `values` (the gradient with respect to the field, or with `weight` the
         saved field).  x: the leaf where the Functions keep it, else None.  A real leaf receives the
@@ -452,6 +480,9 @@ class _Leaf:
         if adj is None:
             adj = self.adjoint_plan(values if x is None else x)
         samples = x if self.reads_leaf else None
+        if self.source is not None:                             # source: the saved one (split_source)
+            return adj.backward_source(values, self.leaf, source, samples=samples, weight=weight, scale=scale,
+                                       levels=self.levels, **self.ste)
         if self.zs is not None:
             return adj.backward_stack(values, self.leaf, samples=samples, weight=weight, scale=scale,
                                       levels=self.levels, **self.ste)
@@ -515,14 +546,15 @@ class _Simulate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, spec):
         ctx.spec = spec
-        ctx.save_for_backward(*spec.kept(x))
+        ctx.save_for_backward(*spec.kept(x), *spec.kept_source())
         return spec.field(x)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_output):
-        x, = ctx.saved_tensors or (None,)
-        return ctx.spec.backward(x, _materialised(grad_output, torch.complex64)), None
+        saved, src = ctx.spec.split_source(ctx.saved_tensors)
+        x, = saved or (None,)
+        return ctx.spec.backward(x, _materialised(grad_output, torch.complex64), source=src), None
 
 
 class _Intensity(torch.autograd.Function):
@@ -539,19 +571,20 @@ class _Intensity(torch.autograd.Function):
             ctx.save_for_backward(x)
             return spec.evaluate(x, want_field=False)[2]
         _, field, inten, _ = spec.evaluate(x)
-        ctx.save_for_backward(field, *spec.kept(x))
+        ctx.save_for_backward(field, *spec.kept(x), *spec.kept_source())
         return inten
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_output):
-        spec, saved = ctx.spec, ctx.saved_tensors
+        spec = ctx.spec
+        saved, src = spec.split_source(ctx.saved_tensors)
         if spec.recompute:
             field, x = spec.evaluate(saved[0], want_intensity=False)[1], None
         else:
             field, x = saved[0], (saved[1] if len(saved) > 1 else None)
         gi = _materialised(grad_output, torch.float32)
-        return spec.backward(x, field, weight=gi, scale=2.0 / (spec.c // spec.groups)), None
+        return spec.backward(x, field, weight=gi, scale=2.0 / (spec.c // spec.groups), source=src), None
 
 
 class _Loss(torch.autograd.Function):
@@ -568,19 +601,21 @@ class _Loss(torch.autograd.Function):
         ctx.spec, ctx.kind, ctx.rel, ctx.weighted = spec, kind, rel, pw is not None
         plan, field, inten, stats = spec.evaluate(x, target, pixel_weight=pw)
         wsum = None if pw is None else plan.pixel_weight_sum(pw, stack=spec.zs is not None)
-        ctx.save_for_backward(field, inten, stats, target, *spec.kept(x), *(() if pw is None else (pw, wsum)))
+        ctx.save_for_backward(field, inten, stats, target, *spec.kept(x), *(() if pw is None else (pw, wsum)),
+                              *spec.kept_source())
         return spec.loss(plan, stats, kind, rel, wsum)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_output):
-        spec, saved = ctx.spec, ctx.saved_tensors
+        spec = ctx.spec
+        saved, src = spec.split_source(ctx.saved_tensors)
         pw, wsum = saved[-2:] if ctx.weighted else (None, None)
         field, inten, stats, target, x = saved[:4] + ((saved[4],) if spec.keeps_leaf else (None,))
         gl = _materialised(grad_output, torch.float64)
         adj = spec.adjoint_plan(field if x is None else x)
         wgt = spec.loss_weight(adj, inten, target, stats, gl, ctx.kind, ctx.rel, pw, wsum)
-        grad = spec.backward(x, field, weight=wgt, scale=2.0 / (spec.c // spec.groups), adj=adj)
+        grad = spec.backward(x, field, weight=wgt, scale=2.0 / (spec.c // spec.groups), adj=adj, source=src)
         return grad, None, None, None, None, None
 
 
@@ -588,8 +623,31 @@ def _as_tensor(x) -> torch.Tensor:
     return x.as_subclass(torch.Tensor) if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
 
 
+def _source_arg(source, groups: int, h: int, w: int, what: str) -> torch.Tensor:
+    """source= of simulate, intensity and loss -> a real or complex tensor that expands to [G, H, W], a
+    constant, still as given (_device_leaf casts and expands it on the device); anything else raises
+    ValueError."""
+    try:
+        src = _as_tensor(source)
+    except (TypeError, ValueError, RuntimeError) as e:
+        raise ValueError(f"{what}: source= must be a real or complex tensor or array ({e})") from None
+    if src.dtype == torch.bool or not (src.is_complex() or src.is_floating_point() or
+                                       src.dtype in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)):
+        raise ValueError(f"{what}: source= must have a numeric dtype, got {src.dtype}")
+    if src.requires_grad:
+        raise ValueError(f"{what}: the source is a constant (it requires grad); there is no gradient with respect to it")
+    want = (groups, h, w)
+    try:
+        ok = src.dim() in (2, 3) and tuple(torch.broadcast_shapes(tuple(src.shape), want)) == want
+    except RuntimeError:
+        ok = False
+    if not ok:
+        raise ValueError(f"{what}: source {tuple(src.shape)} is neither [H, W] nor [G, H, W] = {want}")
+    return src
+
+
 def _leaf_args(x, what: str, tf, field, threshold, ste, ste_width, grid, origin, roi, levels, z=None, zs=None,
-               binary: bool = False, save_field: bool = True, pixel_weight=None):
+               binary: bool = False, save_field: bool = True, pixel_weight=None, source=None):
     """The checks of every public call, all before any GPU use -> (t [B, C, H, W] as given, the _Leaf
     without its device, whether x was 3-D).  what: the public function's name; its own rules are
     `simulate`: one wavelength, any C (an odd one is padded); `intensity`: an odd C / G only for one
@@ -599,6 +657,14 @@ def _leaf_args(x, what: str, tf, field, threshold, ste, ste_width, grid, origin,
     if pixel_weight is not None and (grid is not None or origin is not None or roi is not None):
         raise ValueError(f"{what}: pixel_weight= is not accepted with grid=, origin= or roi= (a rectangle is the "
                          "weight that is 1 inside it)")
+    if source is not None:
+        if stacked:
+            raise ValueError(f"{what}: source= is not accepted (a focal stack is lit by the unit plane wave)")
+        if binary:
+            raise ValueError(f"{what}: source= lights a leaf on the continuous path (binary=False)")
+        if grid is not None or origin is not None or roi is not None:
+            raise ValueError(f"{what}: source= is not accepted with grid=, origin= or roi= (a source that is 0 "
+                             "outside a rectangle is the dark surround)")
     if stacked:
         if grid is not None or origin is not None or roi is not None:
             raise ValueError(f"{what}: grid=, origin= and roi= are not accepted (focal stacks are not windowed)")
@@ -637,12 +703,13 @@ def _leaf_args(x, what: str, tf, field, threshold, ste, ste_width, grid, origin,
         raise ValueError("tt.simulate (hbx) propagates binary {0,1} masks only, as the reference does")
     if cplx and field_kind != _lib.FIELD_AMPLITUDE:
         raise ValueError(f"{tt_what}: a complex field is used as it is (field=\"amplitude\")")
-    if what == "loss" and not cplx and field_kind == _lib.FIELD_AMPLITUDE and odd:
+    # (under a source every kind is one complex plane per leaf plane: no plane pairs, no even count asked)
+    if what == "loss" and not cplx and field_kind == _lib.FIELD_AMPLITUDE and odd and source is None:
         raise ValueError(f"loss: a real field needs an even number of planes per colour group, got {per}")
     if thresholded:
         if cplx:
             raise ValueError(f"{tt_what}: threshold= needs a real leaf, got a complex field")
-        if what in ("intensity", "loss") and odd:
+        if what in ("intensity", "loss") and odd and source is None:
             raise ValueError(f"{what}: threshold= needs an even number of planes per colour group, got {per}")
     if grid is not None and binary:
         raise ValueError("simulate: grid= places a real leaf on the continuous path (binary=False)")
@@ -668,8 +735,10 @@ def _leaf_args(x, what: str, tf, field, threshold, ste, ste_width, grid, origin,
             raise ValueError(f"{what}: the hologram is one of the built grids {_GRIDS} squared, got {tuple(t.shape[2:])}")
     # a windowed simulate pads an odd C by torch ops (the Function sees, and returns, the pair)
     c_seen = c + (c % 2) if win is not None else c
+    if source is not None:
+        source = _source_arg(source, groups, t.shape[2], t.shape[3], what)
     spec = _Leaf(wls, dx, dy, tf_kind, leaf, field_kind, ste_args, levels, c=c_seen, z=z, win=win, zs=zs,
-                 recompute=not save_field)
+                 recompute=not save_field, source=source)
     return t, spec, squeeze
 
 
@@ -721,6 +790,9 @@ def _device_leaf(t: torch.Tensor, spec: _Leaf, what: str, cast: bool = True) -> 
     else:
         spec.dev = torch.cuda.current_device()
         t = t.to(f"cuda:{spec.dev}")
+    if spec.source is not None:                                 # once per call: complex64 [G, H, W], contiguous
+        spec.source = (spec.source.to(device=t.device).to(torch.complex64).resolve_conj().resolve_neg()
+                       .expand(spec.groups, t.shape[2], t.shape[3]).contiguous())
     if not cast:
         return t
     if spec.leaf == _lib.LEAF_COMPLEX:
@@ -781,7 +853,7 @@ def _loss(t, target, spec, squeeze, what, kind, rel, pixel_weight=None):
 
 def simulate(x, z: float, strict: bool = False, binary: bool = True, tf="asm", field="amplitude",
              threshold=None, ste="window", ste_width=0.5, grid=None, origin=None, roi=None, levels=None,
-             **_) -> torch.Tensor:
+             source=None, **_) -> torch.Tensor:
     """Free-space propagation of a tensor [B, C, H, W] (or [C, H, W]) by z metres: the
     complex field of every plane, complex64, on the GPU.
 
@@ -829,9 +901,24 @@ def simulate(x, z: float, strict: bool = False, binary: bool = True, tf="asm", f
     requires grad the backward pass is the straight-through estimator dq/dx := 1, one
     hbx_phase_levels_backward on the plan for -z: the continuous gradient at the displayed phase.
     levels with binary=True, a complex x, field="amplitude", threshold=, grid=, a non-integer or a
-    value outside [2, 256] raises ValueError before any GPU use."""
+    value outside [2, 256] raises ValueError before any GPU use.
+
+    binary=False with source=s (None runs the code above untouched; every leaf kind): the modulator is
+    lit by the complex illumination s instead of a unit plane wave on axis, u = s f(x) with f the leaf
+    kind's map above -- an oblique plane wave, a Gaussian beam, a converging reference wave, a lit disc
+    (tt.sources has the usual ones; s = 0 is a dark surround for every kind).  s is a real or complex
+    tensor or array [H, W] or [G, H, W], a constant, cast to complex64 and expanded once per call.  The
+    first pass multiplies by the source row as it loads x (hbx_evaluate_source): neither s f(x) nor,
+    for a phase or thresholded leaf, f(x) is written.  If x requires grad the backward pass is one
+    hbx_backward_source on the plan for -z: its last pass multiplies the back-propagated plane by
+    conj(s) and applies the leaf's own gradient formula (the phase gradient, the straight-through
+    estimators); the source is saved for it with the other tensors.  An odd number of planes per group
+    needs no padding plane under a source, also for a real or thresholded leaf of intensity and loss.  binary=True, grid= / origin= / roi=, a source that requires grad, a shape that does
+    not expand to [G, H, W] or a non-numeric dtype raises ValueError before any GPU use; the *_stack
+    calls take no source.  Out of scope: a gradient with respect to the source, a per-env or per-plane
+    source, windows and focal stacks under a source."""
     t, spec, squeeze = _leaf_args(x, "simulate", tf, field, threshold, ste, ste_width, grid, origin, roi, levels, z=z,
-                                  binary=binary)
+                                  binary=binary, source=source)
     if not binary:
         return _simulate(t, spec, squeeze, "simulate")
     t = _device_leaf(t, spec, "simulate", cast=False)
@@ -855,7 +942,7 @@ def simulate(x, z: float, strict: bool = False, binary: bool = True, tf="asm", f
 
 
 def intensity(x, z: float, tf="asm", field="amplitude", save_field: bool = True, threshold=None, ste="window",
-              ste_width=0.5, grid=None, origin=None, roi=None, levels=None) -> torch.Tensor:
+              ste_width=0.5, grid=None, origin=None, roi=None, levels=None, source=None) -> torch.Tensor:
     """Plane-mean intensity of the propagated field, the quantity every loss of the project goes
     through: float32 [B, G, H, W] (or [G, H, W] for a 3-D x) with
         I[b, g] = mean over the planes p of group g of |IFFT2(FFT2(u[b, p]) H_g(z))|^2,
@@ -897,9 +984,13 @@ def intensity(x, z: float, tf="asm", field="amplitude", save_field: bool = True,
 
     levels=L with field="phase" (real x; as in simulate): the intensity of the hologram displayed at L
     phase levels, through hbx_evaluate_phase_levels; with a gradient request the backward pass is one
-    hbx_phase_levels_backward, the straight-through estimator.  The field is always saved."""
+    hbx_phase_levels_backward, the straight-through estimator.  The field is always saved.
+
+    source=s as in simulate (None runs the code above untouched; every leaf kind, no grid=): the
+    intensity under the illumination s, through hbx_evaluate_source; the field is always saved, and the
+    backward pass is one hbx_backward_source."""
     t, spec, squeeze = _leaf_args(x, "intensity", tf, field, threshold, ste, ste_width, grid, origin, roi, levels, z=z,
-                                  save_field=bool(save_field))
+                                  save_field=bool(save_field), source=source)
     return _intensity(t, spec, squeeze, "intensity")
 
 
@@ -907,7 +998,8 @@ _METRIC_NAMES = {"mse": _lib.LOSS_MSE, "psnr": _lib.LOSS_PSNR}
 
 
 def loss(x, target, z: float, metric="mse", rel_scale="lsq", tf="asm", field="amplitude", threshold=None,
-         ste="window", ste_width=0.5, grid=None, origin=None, roi=None, levels=None, pixel_weight=None) -> torch.Tensor:
+         ste="window", ste_width=0.5, grid=None, origin=None, roi=None, levels=None, pixel_weight=None,
+         source=None) -> torch.Tensor:
     """The relative loss of a continuous hologram against a target, one value per env, without
     leaving the HIP path and without a host wait: float64 [B] on the device (0-dim for a 3-D x),
         metric="mse"   what tt.relativeLoss(I[b], target[b], F.mse_loss) gives (env.py:131),
@@ -964,11 +1056,17 @@ def loss(x, target, z: float, metric="mse", rel_scale="lsq", tf="asm", field="am
     With a gradient request dL/dI = v (a I + c T) (hbx_loss_weight_pw) goes into the same backward
     launch set; the energy the hologram cannot place may land where v = 0 at no cost.  Not checked
     (a check would cost a host wait): a negative weight is used as it stands, a NaN weight poisons
-    that env's loss, an env whose weights are all zero has loss 0 (psnr: +inf) and a zero gradient."""
+    that env's loss, an env whose weights are all zero has loss 0 (psnr: +inf) and a zero gradient.
+
+    source=s as in simulate (None runs the code above untouched; every leaf kind, with or without
+    pixel_weight=, no grid=): the loss of the hologram under the illumination s.  The forward is one
+    hbx_evaluate_source, whose last pass and statistics are hbx_evaluate_complex's (hbx_evaluate_pw's
+    with a pixel weight); the backward pass is hbx_loss_weight (or _pw), then one hbx_backward_source
+    on the plan for -z.  The loss equals tt.loss on the complex tensor s f(x) bit for bit."""
     kind = _switch(metric, _METRIC_NAMES, "metric")
     rel = _switch(rel_scale, _REL_NAMES, "rel_scale")
     t, spec, squeeze = _leaf_args(x, "loss", tf, field, threshold, ste, ste_width, grid, origin, roi, levels, z=z,
-                                  pixel_weight=pixel_weight)
+                                  pixel_weight=pixel_weight, source=source)
     return _loss(t, target, spec, squeeze, "loss", kind, rel, pixel_weight)
 
 
@@ -976,7 +1074,7 @@ def loss(x, target, z: float, metric="mse", rel_scale="lsq", tf="asm", field="am
 # Focal stacks: one hologram propagated to D depths (hbx_*_stack), outputs depth-major [D, B, ...]
 # ---------------------------------------------------------------------------------------------
 def simulate_stack(x, zs, tf="asm", field="amplitude", threshold=None, ste="window", ste_width=0.5, levels=None,
-                   grid=None, origin=None, roi=None) -> torch.Tensor:
+                   grid=None, origin=None, roi=None, source=None) -> torch.Tensor:
     """The propagated field of one hologram at every depth of `zs` (1 to 8 distances, repeats and
     negative values allowed): complex64 [D, B, C, H, W] ([D, C, H, W] for a 3-D x), depth d what
     ``tt.simulate(x, zs[d], binary=False, ...)`` returns, from ONE first pass, D column passes and D
@@ -986,26 +1084,27 @@ def simulate_stack(x, zs, tf="asm", field="amplitude", threshold=None, ste="wind
     a real or thresholded leaf needs an even number of planes per colour group.  If x requires grad
     the backward pass is one hbx_backward_stack on the plan for the negated depths, whose last pass
     adds the D adjoint propagations as it loads them and writes the leaf's gradient once.  grid=,
-    origin= and roi= raise ValueError (focal stacks are not windowed).  No double backward."""
+    origin= and roi= raise ValueError (focal stacks are not windowed), and so does source= (a stack is
+    lit by the unit plane wave).  No double backward."""
     t, spec, squeeze = _leaf_args(x, "simulate_stack", tf, field, threshold, ste, ste_width, grid, origin, roi, levels,
-                                  zs=zs)
+                                  zs=zs, source=source)
     return _simulate(t, spec, squeeze, "simulate_stack")
 
 
 def intensity_stack(x, zs, tf="asm", field="amplitude", threshold=None, ste="window", ste_width=0.5, levels=None,
-                    grid=None, origin=None, roi=None) -> torch.Tensor:
+                    grid=None, origin=None, roi=None, source=None) -> torch.Tensor:
     """``tt.intensity`` at every depth of `zs`: float32 [D, B, G, H, W] ([D, G, H, W] for a 3-D x), the
     arguments as simulate_stack's.  With a gradient request the per-depth fields are saved and the
     backward pass is one hbx_backward_stack with (2 / P) grad_output applied in the first passes'
     loads; without one no field is written."""
     t, spec, squeeze = _leaf_args(x, "intensity_stack", tf, field, threshold, ste, ste_width, grid, origin, roi, levels,
-                                  zs=zs)
+                                  zs=zs, source=source)
     return _intensity(t, spec, squeeze, "intensity_stack")
 
 
 def loss_stack(x, target, zs, metric="mse", rel_scale="lsq", tf="asm", field="amplitude", threshold=None,
                ste="window", ste_width=0.5, levels=None, grid=None, origin=None, roi=None,
-               pixel_weight=None) -> torch.Tensor:
+               pixel_weight=None, source=None) -> torch.Tensor:
     """``tt.loss`` over a focal stack: one value per env, float64 [B] on the device (0-dim for a 3-D
     x), of the intensities at every depth of `zs` against ``target`` float32 [D, B, G, H, W]
     ([D, G, H, W] for a 3-D x), a constant.  The sums of I T, I^2 and T^2 run over an env's D G
@@ -1024,7 +1123,7 @@ def loss_stack(x, target, zs, metric="mse", rel_scale="lsq", tf="asm", field="am
     kind = _switch(metric, _METRIC_NAMES, "metric")
     rel = _switch(rel_scale, _REL_NAMES, "rel_scale")
     t, spec, squeeze = _leaf_args(x, "loss_stack", tf, field, threshold, ste, ste_width, grid, origin, roi, levels,
-                                  zs=zs, pixel_weight=pixel_weight)
+                                  zs=zs, pixel_weight=pixel_weight, source=source)
     return _loss(t, target, spec, squeeze, "loss_stack", kind, rel, pixel_weight)
 
 

@@ -666,6 +666,53 @@ int hbx_loss_weight_pw(hbx_plan_t plan, const float* intensity, const float* tar
                        int32_t n_env, int32_t n_depths, int32_t kind, int32_t rel_scale, float* weight,
                        void* stream);
 
+/* (ABI v15, additive) EXTENSION, no reference counterpart: illumination fields.  Every other entry point lights
+ * the modulator with a unit plane wave on axis, u = f(x) with f the leaf kind's map.  Here it is lit by a
+ * constant complex source, source [G][H][W] complex64, shared by all envs and all planes of a colour group:
+ * an oblique plane wave, a Gaussian beam, a converging reference wave, a lit disc (0 outside).  With
+ * s = (sr, si) the source sample and f = (fr, fi) the leaf's unsourced sample at a pixel, in float32 with every
+ * product rounded on its own (no other contraction):
+ *     forward   u.re  = fmaf(fr, sr, -(fi * si))        u.im  = fmaf(fr, si, fi * sr)
+ *               (HBX_LEAF_REAL / _THRESHOLD: fi is absent, not 0:  u = (fr * sr, fr * si), one multiply each)
+ *     backward  g'.re = fmaf(g.re, sr, g.im * si)       g'.im = fmaf(g.im, sr, -(g.re * si))      g' = conj(s) g
+ * g = the plane the complex last pass would write on the plan for -z; the leaf's gradient is the existing
+ * formula at g': complex g', real Re g', phase and L-level pi (Im g' cos pi q - Re g' sin pi q), thresholded
+ * vb ste(x) Re g' with both surrogates.  The source is a constant and has no gradient.  At N = 896 the padding
+ * slots stay 0.
+ *
+ * Layout: in these three calls every leaf kind, real and thresholded included, is ONE complex plane per leaf
+ * plane: values [B][G*P/2][H][W] (complex64 pairs for HBX_LEAF_COMPLEX, float32 otherwise) on a plan of P real
+ * planes per group -- hbx_evaluate_stack's Pc = P/2, here for all five kinds.  An odd number of leaf planes per
+ * group needs no padding plane.
+ *
+ * hbx_source_field: the field at the modulator, out_field [B][G*P/2][H][W][2] = u, one streaming kernel with the
+ *   device functions the first pass uses (no propagation).
+ * hbx_evaluate_source: the first pass forms u as it loads the leaf's samples and the source row, then the
+ *   column pass and hbx_evaluate_complex's last pass and reduction as they are.  Null-ability and the target /
+ *   chan_stats pairing are hbx_evaluate_complex's (no psnr output); pixel_weight [B][G][H][W] is nullable and
+ *   follows hbx_evaluate_pw's rules when given (target and chan_stats required).  Every output equals
+ *   hbx_evaluate_complex's (hbx_evaluate_pw's with HBX_LEAF_COMPLEX) on hbx_source_field's output, bit for bit.
+ * hbx_backward_source: on the plan for -z.  values [B][G*P/2][H][W][2], optionally times scale * weight
+ *   [B][G][H][W] (hbx_simulate_complex_weighted's load), the column pass, and a last pass that multiplies the
+ *   plane by conj(s) before the leaf's formula.  Exactly one of grad_field [B][G*P/2][H][W][2] (HBX_LEAF_COMPLEX)
+ *   and grad [B][G*P/2][H][W] float32 (every other kind) is non-null; samples [B][G*P/2][H][W] float32 is the
+ *   leaf's x for the phase, L-level and thresholded kinds and null otherwise; leaf carries levels / surrogate /
+ *   p0 / p1 as hbx_backward_stack reads them.  A closed HBX_STE_WINDOW gate stores +0.0 whatever g' holds.
+ * All three: chunked by max_jobs as their siblings; n_env 0 is OK, < 0 HBX_ERR_INVALID; the four built sizes;
+ *   the pass-timer slots are the siblings'.  A null source, values or leaf, an unknown kind or levels outside
+ *   [2, 256]: HBX_ERR_INVALID before anything is enqueued; a reduced-precision plan: HBX_ERR_UNSUPPORTED.
+ * Out of scope: a source on the bit path or on any env, DBS, plane-cache or incremental entry point; a source
+ *   with windows or focal stacks (the depth-summing last pass); a gradient with respect to the source;
+ *   reduced-precision plans; a per-env or per-plane source; grids other than the four built. */
+int hbx_source_field(hbx_plan_t plan, const void* values, const hbx_leaf_t* leaf, const float* source,
+                     int32_t n_env, float* out_field, void* stream);
+int hbx_evaluate_source(hbx_plan_t plan, const void* values, const hbx_leaf_t* leaf, const float* source,
+                        const float* target, const float* pixel_weight, int32_t n_env, float* field,
+                        float* intensity, double* chan_stats, void* stream);
+int hbx_backward_source(hbx_plan_t plan, const float* values, const float* weight, float scale,
+                        const hbx_leaf_t* leaf, const float* source, const float* samples, int32_t n_env,
+                        float* grad_field, float* grad, void* stream);
+
 /* PSNR from per-channel statistics (tt.relativeLoss(.., tm.get_PSNR),
  * env.py:174): chan_stats[B][G][3] -> psnr[B]. */
 int hbx_psnr(hbx_plan_t plan, const double* chan_stats, int32_t n_env, double* psnr,
