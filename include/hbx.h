@@ -184,7 +184,29 @@ int hbx_host_free(void* host);
 /* Plan: owns twiddles, transfer-function tables and a workspace for up to
  * `max_jobs` concurrent group propagations (P * 12 * N^2 bytes per job:
  * 96 MiB at N = 1024, P = 8; hbx_plan_workspace_bytes gives the total).
- * Replaces the per-call setup hidden inside tt.simulate (env.py:172). */
+ * Replaces the per-call setup hidden inside tt.simulate (env.py:172).
+ *
+ * Reuse contract (tests/test_gpu_plan_reuse.py): every entry point below runs in the plan's one set of
+ * workspaces, and calls on one plan, issued in stream order, are independent of the calls before them
+ * -- each call's results equal, bit for bit, those of the same call on a plan just created.  A call
+ * reads no workspace element it did not write itself; the tables built on first use (the single-pixel
+ * fields, the flip-map and walk scratch) depend on the optics alone; a refused call (a negative return
+ * code) enqueues nothing and changes nothing.  All of a call's device work, the lazy table builds
+ * included, is on the `stream` it was given; one plan serves one stream at a time.  What does persist:
+ *   hbx_plan_set_precision  the rounding of the pass intermediates of every later call, until set again;
+ *                           back at HBX_PRECISION_F32 the plan is as created
+ *   hbx_plan_set_depths     the depth tables the hbx_*_stack calls read, until set again (it
+ *                           synchronises the device); no single-depth call reads them
+ *   hbx_plan_set_timing*    whether events are recorded around the pass launches; no result changes
+ *   a walk                  nothing in the plan that a result depends on.  The walk's state is the
+ *                           caller's (hbx_dbs_walk_t, mask, statistics, the plane pool or field, the
+ *                           accept log): a walk may be split into calls at any batch, with other
+ *                           calls on the plan between them, and gives the accept sequence, PSNRs,
+ *                           mask, statistics and cached planes of the walk made in one call.  A
+ *                           call's first batch propagates every candidate in full and starts the
+ *                           spare-slot rotation of hbx_dbs_walk_planes* at 0, so WHICH spare slot of
+ *                           the pool holds a candidate's fresh pair may differ across a call boundary.
+ * A PSNR formed from statistics that are NaN is not NaN: +inf, or with sum I^2 NaN the unscaled one. */
 int hbx_plan_create(hbx_plan_t* plan, const hbx_optics_t* optics, int32_t max_jobs,
                     int32_t device);
 int hbx_plan_destroy(hbx_plan_t plan);
